@@ -42,10 +42,6 @@ import time
 
 import numpy as np
 
-# configs[4] batch: 8 stream lanes (+ the handle's own stream) map onto hardware queues only if the runtime may open that many
-# (ROCm's default is 4 per process, shared with torch's own streams); must be set before HIP initialises
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -645,6 +641,18 @@ def bench_c5_native(m, reg, scans, n_gpus, share, table_torch, lanes=8):
     return out
 
 
+def dump_outputs(out_dir: str, T, ok: bool, stats) -> None:
+    """--dump-outputs: what fls_match_resident handed its caller in the last timed step -- the (4, 4) pose, the status and every fls_stats
+    field -- one float64 .npy per array, so that two builds can be compared output for output on the same seeded inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pose": np.asarray(T, np.float64).reshape(4, 4), "converged": np.array([1.0 if ok else 0.0])}
+    for name, _ in stats._fields_:
+        if name != "reserved":
+            arrays["stats_" + name] = np.array(getattr(stats, name), np.float64).reshape(-1)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n: int) -> int:
     """Re-run this command line under torch.distributed.run with n ranks on this node (127.0.0.1 rendezvous, a free port)."""
     import socket
@@ -674,7 +682,11 @@ def main():
     ap.add_argument("--batch-jobs-total", type=int, default=0, help="configs[4]: total number of jobs (default: 512 at N = 1 and at N = 8, 64 * N otherwise)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl == RCCL; gloo + FLS_BENCH_SHARE_DEVICE=1 exercises the N > 1 code path on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pose, status, fls_stats fields) as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Called bare (`python bench.py --gpus 8`, the shape of the driver's N = 1 command): launch the ranks ourselves -- one process
@@ -824,6 +836,8 @@ def main():
     iters = m.stats.iterations
     n_valid_head = m.stats.n_valid
     T_head = np.array(T)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, T_head, ok, m.stats)
     # algorithmic-traffic counters: one extra (untimed) Match with the counting kernel variant
     m.set_profiling(False, counters=True)
     step()

@@ -31,6 +31,25 @@ if ROOT not in sys.path:
 
 SCENARIOS = ("ivox", "ivox_lru", "icp", "ndt", "ndt_dev", "loam", "icp_loc", "kd_loc", "ivox_loc", "ndt_loc")
 IVOX_LRU_CAPACITY = 9000
+# the seeded random and degenerate families tests/test_ref_pin.py runs: fuzz<seed>, fuzzL<seed>, lfuzz<seed>, ffuzz<seed> (features), deg_*
+FUZZ_SEEDS = list(range(24))
+FUZZ_LONG_SEEDS = [0, 1, 2, 3]
+FUZZ_LOC_SEEDS = list(range(12))
+FEATURE_FUZZ_SEEDS = list(range(12))
+DEGENERATE = ("deg_ivox_empty", "deg_ivox_tiny", "deg_ivox_far", "deg_icp_tiny12", "deg_icp_far", "deg_ndt_empty", "deg_ndt_tiny", "deg_ndt_far",
+              "deg_loam_nocorner", "deg_loam_tiny", "deg_loam_far", "deg_kd_tiny", "deg_kd_far")
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def pinned_scenarios() -> list:
+    """Every registration scenario whose compiled-reference output has a committed record (tests/golden/ref_<name>.npz)."""
+    return (list(SCENARIOS) + [f"fuzz{s}" for s in FUZZ_SEEDS] + [f"fuzzL{s}" for s in FUZZ_LONG_SEEDS] + [f"lfuzz{s}" for s in FUZZ_LOC_SEEDS]
+            + list(DEGENERATE))
+
+
+def pinned_feature_cases() -> list:
+    """Every feature case whose compiled-reference output has a committed record (tests/golden/ref_features_<name>.npz)."""
+    return list(FEATURE_CASES) + [f"ffuzz{s}" for s in FEATURE_FUZZ_SEEDS]
 
 
 def _sha(*arrays) -> str:
@@ -388,6 +407,79 @@ def run_ref_subprocess(name: str, env: dict = None) -> dict:
         subprocess.check_call([sys.executable, "-m", "tests.refpin", name, path], cwd=ROOT, env=dict(os.environ, **(env or {})))
         with np.load(path, allow_pickle=True) as z:
             return z["out"].item()
+
+
+# ---- the compiled reference's output: live where libref.so is available, else its committed record ----------------------
+def ref_output(name: str) -> dict:
+    """run("ref", name) in a fresh process where oracle/_ref/libref.so is available, else from tests/golden/ref_<name>.npz
+    (tests/golden/make_ref_golden.py wrote it from the same library); compare() takes either form."""
+    from oracle import ref as R
+    if R.available():
+        return run_ref_subprocess(name)
+    with np.load(os.path.join(GOLD, f"ref_{name}.npz")) as g:
+        return from_golden(g)
+
+
+def features_to_golden(out: dict) -> dict:
+    """run_features() output for np.savez: the arrays as SHA-1 digests, the scalars as they are."""
+    return {k: (np.array(_sha(v)) if isinstance(v, np.ndarray) else np.array(v)) for k, v in out.items()}
+
+
+def ref_features_output(name: str) -> dict:
+    """run_features("ref", name) in a fresh process where libref.so is available, else from tests/golden/ref_features_<name>.npz
+    (arrays as digests)."""
+    from oracle import ref as R
+    if R.available():
+        return run_features_subprocess(name)
+    with np.load(os.path.join(GOLD, f"ref_features_{name}.npz")) as g:
+        return {k: (str(g[k]) if g[k].dtype.kind in "US" else g[k].item()) for k in g.files}
+
+
+def assert_features_equal(ref: dict, ora: dict, name: str) -> None:
+    """Feature front-end outputs equal bit for bit; `ref` may hold digests in place of arrays (golden form)."""
+    assert ref["digest"] == ora["digest"], f"{name}: scenario inputs differ"
+    assert ref["n_ordered"] == ora["n_ordered"] and ref["extracted"] == ora["extracted"], name
+    for f in FEATURE_FIELDS:
+        if isinstance(ref[f], str):
+            assert ref[f] == _sha(ora[f]), (name, f)
+        else:
+            assert ref[f].shape == ora[f].shape and np.array_equal(ref[f], ora[f]), (name, f)
+
+
+def small_function_cases():
+    """Seeded inputs of the small-function pin: 200 rotation vectors over eight decades, 2,000 float32 (x, y) pairs."""
+    rng = np.random.default_rng(5)
+    vs = np.array([rng.normal(size=3) * rng.choice([1e-9, 1e-3, 0.3, 2.5]) for _ in range(200)])
+    xy = rng.normal(size=(2000, 2)).astype(np.float32) * 30
+    return vs, xy
+
+
+def run_small_functions_ref(vs: np.ndarray, xy: np.ndarray) -> dict:
+    """The reference's SO3Exp (column-major 3 x 3 per row), RotationMatrixToRPY of that matrix, FastAtan2 -- through libref.so."""
+    import ctypes as C
+
+    from oracle import ref as R
+    L = R.lib()
+    dp = C.POINTER(C.c_double)
+    so3, rpy = np.zeros((len(vs), 9)), np.zeros((len(vs), 3))
+    for i, v in enumerate(vs):
+        v = np.ascontiguousarray(v)
+        L.ref_so3_exp(v.ctypes.data_as(dp), so3[i].ctypes.data_as(dp))
+        L.ref_rpy(so3[i].ctypes.data_as(dp), rpy[i].ctypes.data_as(dp))
+    atan2 = np.array([L.ref_fast_atan2f(float(y), float(x)) for x, y in xy], np.float64)  # float32 results, exact in float64
+    return dict(digest=_sha(vs, xy), so3=so3, rpy=rpy, atan2=atan2)
+
+
+def ref_small_functions(vs: np.ndarray, xy: np.ndarray) -> dict:
+    """run_small_functions_ref() where libref.so is available, else tests/golden/ref_small_functions.npz."""
+    from oracle import ref as R
+    if R.available():
+        return run_small_functions_ref(vs, xy)
+    with np.load(os.path.join(GOLD, "ref_small_functions.npz")) as g:
+        out = {k: g[k] for k in g.files}
+    out["digest"] = str(out["digest"])
+    assert out["digest"] == _sha(vs, xy), "small-function inputs differ from the ones the record was made from"
+    return out
 
 
 if __name__ == "__main__":

@@ -3,6 +3,9 @@
 import json
 import os
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,3 +68,38 @@ def test_launcher_rank_count_must_match_gpus_flag():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--no-batch", "--no-extras", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 2 and "refusing to run" in p.stderr, (p.returncode, p.stderr[-1000:])
+
+
+def test_steps_below_one_is_refused():
+    """--steps is the number of timed steps and ms_per_step divides by it: zero or fewer is an argument error, before anything touches a GPU."""
+    import subprocess
+    import sys
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--no-batch", "--no-extras", "--no-cpu-baseline"],
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr, (p.returncode, p.stderr[-1000:])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the pose, status and fls_stats fields of the last timed step as float64 .npy files; the line's steps / ms_per_step
+    describe exactly the K timed steps asked for, and the dumped result is the one the line compares with the CPU oracle."""
+    import subprocess
+    import sys
+
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-batch", "--no-extras",
+                        "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert {"pose.npy", "converged.npy", "stats_iterations.npy", "stats_n_valid.npy", "stats_sum_res.npy", "stats_last_dx.npy"} <= set(files)
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    T = files["pose.npy"]
+    assert T.shape == (4, 4) and np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]) and np.allclose(T[:3, :3].T @ T[:3, :3], np.eye(3), atol=1e-9)
+    assert files["stats_iterations.npy"][0] == line["config"]["gn_iterations"] and bool(files["converged.npy"][0]) == line["config"]["converged"]
+    same = line["pose_err_vs_oracle"]["timed_step_vs_oracle_same_call_index"]
+    assert same["dt_m"] < 1e-4 and same["dR_rad"] < 1e-4 and same["same_n_valid"]

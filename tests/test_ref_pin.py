@@ -8,8 +8,11 @@ neighbour lists (Q15), the iVox insert rule + LRU, std::nth_element slot order, 
 NDT voxel statistics, the feature walk -- and leave Eigen's association order as the one unpinned thing
 (FP64 fields are compared to 1e-9, observed <= 2e-14; everything integer or float-only is compared exactly).
 
-  * live tests: need libref.so (built here whenever /root/reference exists; the .so also travels with a gpurun snapshot)
-  * golden tests: tests/golden/ref_*.npz (made by tests/golden/make_ref_golden.py from libref.so) -- run anywhere.
+  * the oracle-vs-reference tests run the compiled reference live where libref.so is available (built by build() whenever the
+    reference checkout exists) and compare with its committed record otherwise: tests/golden/ref_*.npz, written by
+    tests/golden/make_ref_golden.py from the same library -- so they run anywhere (refpin.ref_output / ref_features_output)
+  * need_ref tests check the compiled reference itself (its parallel build, its abort) and need libref.so
+  * golden tests: tests/golden/ref_*.npz on their own -- run anywhere.
 """
 import os
 
@@ -23,12 +26,11 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 need_ref = pytest.mark.skipif(not R.available(), reason="oracle/_ref/libref.so absent and /root/reference not present to build it")
 
 
-@need_ref
 @pytest.mark.parametrize("name", refpin.SCENARIOS)
 def test_oracle_equals_compiled_reference(name):
     """Multi-scan replay (mapping mode: ivox, ivox_lru, icp, ndt, loam) / localization mode (+ GetFitnessScore) through the compiled
     reference in a fresh process vs the oracle, every frame, every field (tests/refpin.py lists them)."""
-    ref_out = refpin.run_ref_subprocess(name)
+    ref_out = refpin.ref_output(name)
     ora_out = refpin.run("oracle", name)
     worst = refpin.compare(ora_out, ref_out, name)
     assert worst["T"] < 1e-12, worst
@@ -46,30 +48,24 @@ def test_compiled_reference_parallel_pstl_equals_serial(name):
     assert all(v == 0.0 for v in worst.values()), worst
 
 
-@need_ref
-@pytest.mark.parametrize("seed", list(range(24)))
+@pytest.mark.parametrize("seed", refpin.FUZZ_SEEDS)
 def test_oracle_equals_compiled_reference_fuzz(seed):
     """Seeded random variations of the mapping-mode replays (tests/refpin.py::make_fuzz_scenario: kind by seed % 4; iteration budgets of two,
     gates far tighter / looser than the YAML's, deques of one or two frames, an effective-point floor the scan cannot meet, iVox LRU capacities
     of a few hundred voxels, start poses anywhere in the room): the oracle follows the compiled reference through every frame and field.
     (120 seeds were run once: profiles/r05_ref_pin_fuzz_200_scenarios.log; what the draw had to avoid is a reference crash, see the generator.)"""
     name = f"fuzz{seed}"
-    ref_out = refpin.run_ref_subprocess(name)
+    ref_out = refpin.ref_output(name)
     ora_out = refpin.run("oracle", name)
     worst = refpin.compare(ora_out, ref_out, name)
     assert worst["T"] < 1e-12, worst
 
 
-DEGENERATE = ("deg_ivox_empty", "deg_ivox_tiny", "deg_ivox_far", "deg_icp_tiny12", "deg_icp_far", "deg_ndt_empty", "deg_ndt_tiny", "deg_ndt_far",
-              "deg_loam_nocorner", "deg_loam_tiny", "deg_loam_far", "deg_kd_tiny", "deg_kd_far")
-
-
-@need_ref
-@pytest.mark.parametrize("name", DEGENERATE)
+@pytest.mark.parametrize("name", refpin.DEGENERATE)
 def test_oracle_equals_compiled_reference_degenerate_inputs(name):
     """Empty source clouds, sources with fewer points than any gate needs, scans that see nothing of the map (every query without candidates),
     LoamFull without corner features: return value, pose, counts and map state of the oracle are the compiled reference's."""
-    worst = refpin.compare(refpin.run("oracle", name), refpin.run_ref_subprocess(name), name)
+    worst = refpin.compare(refpin.run("oracle", name), refpin.ref_output(name), name)
     assert worst["T"] < 1e-10, worst  # (thirty iterations on a rank-deficient 6 x 6 system, deg_loam_tiny, amplify the last bits to 4e-12)
 
 
@@ -82,40 +78,32 @@ def test_compiled_reference_aborts_on_ten_or_fewer_icp_points():
         refpin.run_ref_subprocess("deg_icp_le10")
 
 
-@need_ref
-@pytest.mark.parametrize("seed", [0, 1, 2, 3])
+@pytest.mark.parametrize("seed", refpin.FUZZ_LONG_SEEDS)
 def test_oracle_equals_compiled_reference_fuzz_long_runs(seed):
     """8-14 frames per scenario (one seed per kind here, 60 run once): deques past the length at which the reference VoxelGrids them, LRU lists at
     capacity for many frames, keyframe gates passing and failing in turn."""
     name = f"fuzzL{seed}"
-    worst = refpin.compare(refpin.run("oracle", name), refpin.run_ref_subprocess(name), name)
+    worst = refpin.compare(refpin.run("oracle", name), refpin.ref_output(name), name)
     assert worst["T"] < 1e-12, worst
 
 
-@need_ref
-@pytest.mark.parametrize("seed", list(range(12)))
+@pytest.mark.parametrize("seed", refpin.FUZZ_LOC_SEEDS)
 def test_oracle_equals_compiled_reference_fuzz_localization(seed):
     """The same for localization mode (kind by seed % 4: IcpOptimized, LoamPointToPlaneKdtree, LoamPointToPlaneIVOX, IncrementalNDT): prior maps of
     random size, random thresholds / budgets, GetFitnessScore after every Match (40 seeds run once, all equal: the same log file)."""
     name = f"lfuzz{seed}"
-    ref_out = refpin.run_ref_subprocess(name)
+    ref_out = refpin.ref_output(name)
     ora_out = refpin.run("oracle", name)
     worst = refpin.compare(ora_out, ref_out, name)
     assert worst["T"] < 1e-12, worst
 
 
-@need_ref
-@pytest.mark.parametrize("seed", list(range(12)))
+@pytest.mark.parametrize("seed", refpin.FEATURE_FUZZ_SEEDS)
 def test_feature_oracle_equals_compiled_reference_fuzz(seed):
     """PointcloudProjector + FeatureExtractor on seeded random frames (either lidar model, tilted poses, thresholds and range gates away from the
     YAML's, up to 90 % of the returns dropped, driver order shuffled or not): every array bit for bit (40 seeds run once, all equal)."""
     name = f"ffuzz{seed}"
-    ref_out = refpin.run_features_subprocess(name)
-    ora = refpin.run_features("oracle", name, sort_mode=1)
-    assert ref_out["digest"] == ora["digest"]
-    assert ref_out["n_ordered"] == ora["n_ordered"] and ref_out["extracted"] == ora["extracted"]
-    for f in refpin.FEATURE_FIELDS:
-        assert ref_out[f].shape == ora[f].shape and np.array_equal(ref_out[f], ora[f]), (name, f)
+    refpin.assert_features_equal(refpin.ref_features_output(name), refpin.run_features("oracle", name, sort_mode=1), name)
 
 
 @pytest.mark.parametrize("name", refpin.SCENARIOS)
@@ -127,16 +115,11 @@ def test_oracle_equals_reference_golden(name):
     refpin.compare(ora_out, g, name)
 
 
-@need_ref
 @pytest.mark.parametrize("name", list(refpin.FEATURE_CASES))
 def test_feature_oracle_equals_compiled_reference(name):
     """PointcloudProjector::Project + FeatureExtractor::ExtractFeatures, every array bit for bit -- including the order of
     equal-roughness points, which is libstdc++'s std::sort permutation in the reference (oracle sort_mode 1)."""
-    ref_out = refpin.run_features_subprocess(name)
-    ora = refpin.run_features("oracle", name, sort_mode=1)
-    assert ref_out["n_ordered"] == ora["n_ordered"] and ref_out["extracted"] == ora["extracted"]
-    for f in refpin.FEATURE_FIELDS:
-        assert ref_out[f].shape == ora[f].shape and np.array_equal(ref_out[f], ora[f]), (name, f)
+    refpin.assert_features_equal(refpin.ref_features_output(name), refpin.run_features("oracle", name, sort_mode=1), name)
 
 
 @pytest.mark.parametrize("name", list(refpin.FEATURE_CASES))
@@ -160,32 +143,29 @@ def test_feature_oracle_equals_reference_golden_and_tie_order_is_the_only_freedo
     assert moved <= 2 * o.tie_pairs() + 2, (moved, o.tie_pairs())
 
 
-@need_ref
 def test_small_functions_against_compiled_reference():
-    """SO3Exp / RotationMatrixToRPY (math_function.h), FastAtan2, LidarModel::ColIndex: oracle vs the reference's compiled code."""
-    rng = np.random.default_rng(5)
-    L = R.lib()
-    for _ in range(200):
-        v = rng.normal(size=3) * rng.choice([1e-9, 1e-3, 0.3, 2.5])
-        a = np.zeros(9); b = np.zeros(9)
-        L.ref_so3_exp(v.ctypes.data_as(O.C.POINTER(O.C.c_double)), a.ctypes.data_as(O.C.POINTER(O.C.c_double)))
-        Rm = O.so3_exp(v)
-        assert np.allclose(a.reshape(3, 3, order="F"), Rm, rtol=0, atol=1e-15)
-        rr = np.zeros(3)
-        L.ref_rpy(a.ctypes.data_as(O.C.POINTER(O.C.c_double)), rr.ctypes.data_as(O.C.POINTER(O.C.c_double)))
+    """SO3Exp / RotationMatrixToRPY (math_function.h), FastAtan2, LidarModel::ColIndex: oracle vs the reference's compiled code
+    (live, or its committed record tests/golden/ref_small_functions.npz)."""
+    vs, xy = refpin.small_function_cases()
+    ref = refpin.ref_small_functions(vs, xy)
+    for v, a, rr in zip(vs, ref["so3"], ref["rpy"]):
+        assert np.allclose(a.reshape(3, 3, order="F"), O.so3_exp(v), rtol=0, atol=1e-15)
         assert np.allclose(rr, O.rpy(a.reshape(3, 3, order="F")), rtol=0, atol=1e-15)
-    xy = rng.normal(size=(2000, 2)).astype(np.float32) * 30
-    for x, y in xy:
-        assert L.ref_fast_atan2f(float(y), float(x)) == O.lib().flo_fast_atan2f(float(y), float(x))
+    for (x, y), r in zip(xy, ref["atan2"]):
+        assert r == O.lib().flo_fast_atan2f(float(y), float(x))
 
 
-@need_ref
 def test_ivox_eviction_and_recreation_inside_one_batch_against_compiled_reference():
     """IVoxMap::AddPoints evicts inside its insert loop (ivox_map.cpp:133-136): one 3,000-point batch at capacity 60 with 722 evictions, 641 of them of
     voxels a later point of the same batch re-creates -- the corner the device-side eviction walk resolves (kernels_ivox_update.hpp).  The reference's own
     code (fresh process), a sequential Python model and the oracle agree on the LRU order, every voxel's points and the surviving points (tests/evict_pin.py)."""
     from tests import evict_pin as E
-    n_evict, n_recreate = E.check(E.run_ref_subprocess(), E.run_oracle())
+    if R.available():
+        ref = E.run_ref_subprocess()
+    else:  # the committed record of the same run (tests/golden/ref_ivox_recreate.npz)
+        with np.load(E.GOLDEN) as z:
+            ref = {k: z[k] for k in z.files}
+    n_evict, n_recreate = E.check(ref, E.run_oracle())
     assert (n_evict, n_recreate) == (722, 641)
 
 
