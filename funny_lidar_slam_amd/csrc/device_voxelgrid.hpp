@@ -489,9 +489,8 @@ struct DeviceVoxelGrid {
         const float inv = 1.0f / leaf;
         // (the reference sorts the FINITE points only: a cloud with a non-finite point is the host's, refuse_bad = 1)
         // (blocks: 48 in rounds 2-4 -- "few blocks: six header atomics each" -- left a 115,200-point scan to 12 k threads, 11-12 us in the trace
-        // of the call; 160 blocks = three points per thread and < 1,000 atomics: FLS_VG_MINMAX_BLOCKS for A/B)
-        static const int mm_env = [] { const char* e = std::getenv("FLS_VG_MINMAX_BLOCKS"); return e ? std::min(kVgMinmaxMaxBlocks, std::max(1, std::atoi(e))) : 0; }();
-        const int mm_blocks = mm_env ? mm_env : int(std::min<size_t>(kVgMinmaxMaxBlocks, std::max<size_t>(160, n / 4096)));  // (one row per block, no atomics but the ticket: more blocks for the keyframe deques)
+        // of the call; 160 blocks = three points per thread and < 1,000 atomics)
+        const int mm_blocks = int(std::min<size_t>(kVgMinmaxMaxBlocks, std::max<size_t>(160, n / 4096)));  // (one row per block, no atomics but the ticket: more blocks for the keyframe deques)
         hipLaunchKernelGGL(vg_minmax_plan, dim3(unsigned(std::min(nb1, mm_blocks))), dim3(kVgBlock), 0, s, x, y, z, ni, inv, 1, d_acc.p, d_plan.p, es);
         hipLaunchKernelGGL(vg_index_plan, dim3(unsigned(nb1)), dim3(kVgBlock), 0, s, x, y, z, ni, (const VgPlan*)d_plan.p, sort.k0, sort.v0);
         exact.fused_launch(sort.k0, sort.v0, n, &d_plan.p->status, s);
@@ -686,20 +685,20 @@ struct KdMapDevice {
         vg_on_device = device_voxelgrid_mode() != 0;
     }
     // grid over a HOST cloud (the exact host filter's output, or an unfiltered cloud)
-    fls_status build_from_host(CellGridImage& grid, const std::vector<PtI>& cloud, float cell, hipStream_t s, int rings = 1, bool by_id = false) {
+    fls_status build_from_host(CellGridImage& grid, const std::vector<PtI>& cloud, float cell, hipStream_t s, int rings = 1) {
         const size_t n = cloud.size();
         if (grid_on_device && n != 0) {
             stage.reserve(3 * n);
             xyz.reserve(3 * n);
             for (size_t i = 0; i < n; ++i) { stage.p[i] = cloud[i].x; stage.p[n + i] = cloud[i].y; stage.p[2 * n + i] = cloud[i].z; }
             FLS_HIP(hipMemcpyAsync(xyz.p, stage.p, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-            if (builder.run(grid, xyz.p, xyz.p + n, xyz.p + 2 * n, n, cell, rings, by_id, s)) return FLS_OK;  // (run() synchronises: the staging is free)
+            if (builder.run(grid, xyz.p, xyz.p + n, xyz.p + 2 * n, n, cell, rings, false, s)) return FLS_OK;  // (run() synchronises: the staging is free)
             FLS_HIP(hipStreamSynchronize(s));
         }
-        return grid.build(cloud, cell, s, rings, by_id);
+        return grid.build(cloud, cell, s, rings);
     }
     // local map = [VoxelGrid of] the concatenated deque, then the grid: all on the device.  false: declined, nothing changed.
-    bool filter_and_build(CellGridImage& grid, const DeviceCloudRing& ring, bool filter, float leaf, float cell, int rings, bool by_id, size_t& n_map,
+    bool filter_and_build(CellGridImage& grid, const DeviceCloudRing& ring, bool filter, float leaf, float cell, int rings, size_t& n_map,
                           hipStream_t s) {
         if (!vg_on_device || !grid_on_device) return false;
         size_t n = ring.size();
@@ -711,7 +710,7 @@ struct KdMapDevice {
             n = vg.n_out;
             if (n == 0) return false;
         }
-        if (!builder.run(grid, x, y, z, n, cell, rings, by_id, s)) return false;
+        if (!builder.run(grid, x, y, z, n, cell, rings, false, s)) return false;
         n_map = n;
         ++device_filters;
         return true;

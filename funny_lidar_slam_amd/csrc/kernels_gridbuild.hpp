@@ -12,7 +12,7 @@
 //   (vg_hist / vg_scan_rows / vg_scatter: ceil(bits / 8) radix passes)
 //   cg_fill     points gathered into sorted order; the head of every run writes its cell's `begin`
 //   cg_count    the tail of every run writes its cell's `count`
-//   cg_by_id    optional: the cloud in its own order as float4 (grid_knn27_kernel gathers its winners there)
+//   cg_by_id    optional: the cloud in its own order as float4 (the loop-closure GICP kernels read their targets there)
 //   soa_append  AoS {x, y, z, i} rows -> four SoA planes at an offset (the device-side cloud deque)
 #pragma once
 #include "kernels_voxelgrid.hpp"

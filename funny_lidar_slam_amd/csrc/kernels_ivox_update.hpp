@@ -198,22 +198,6 @@ ivox_upd_scan1(const IvoxUpdBatch b, const int nblocks, IvoxUpdState* __restrict
     if (threadIdx.x == 0) { st->n1 = tot[0]; st->n2 = tot[1]; st->status = kUpdOk; st->apply = 0u; }
 }
 
-// loads of words other threads of the SAME launch may have changed with atomics (the fused one-workgroup form below runs all phases
-// in one launch: an L2 atomic does not update a line the CU's L1 already holds)
-// COH = true only there (an agent-scope load is served from memory, ~3x the latency of an L2 hit: the multi-launch forms, whose phases
-// are separated by kernel boundaries, use plain loads)
-template <bool COH>
-__device__ __forceinline__ unsigned upd_ld(const unsigned* p) {
-    if (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
-}
-template <bool COH>
-__device__ __forceinline__ uint2 upd_ld_cell(const uint2* p) {
-    if (!COH) return *p;
-    const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_uint2((unsigned)(v & 0xffffffffull), (unsigned)(v >> 32));
-}
-
 // sequence rank r = source point i: its cell (bricks created on demand), the sequence arrays, the per-cell scratch (count, first rank)
 __device__ __forceinline__ void upd_seq_rank(const IvoxUpdBatch& b, const IvoxUpdArrays& a, IvoxUpdState* __restrict__ st, const unsigned r, const unsigned i) {
     const float4 p = b.pw[i];
@@ -266,13 +250,12 @@ __device__ __forceinline__ void upd_seq_rank(const IvoxUpdBatch& b, const IvoxUp
 // counts it as a creation with nothing to keep
 constexpr unsigned kUpdRecreate = 0x80000000u;
 // what the batch does to the voxel whose first point has rank r: {new region slots, creation, touched, capacity left behind}
-template <bool COH = false>
 __device__ __forceinline__ bool upd_plan_rank(const IvoxUpdBatch& b, const IvoxUpdArrays& a, const unsigned r, unsigned (&v)[4]) {
     v[0] = v[1] = v[2] = v[3] = 0u;
     const unsigned cell = b.seq_cell[r];
-    if (cell == kUpdInvalidCell || upd_ld<COH>(&a.rank_mm[cell]) != r) return false;
-    uint2 old = upd_ld_cell<COH>(&a.cells[cell]);
-    const unsigned pe = upd_ld<COH>(&a.pend[cell]);
+    if (cell == kUpdInvalidCell || a.rank_mm[cell] != r) return false;
+    uint2 old = a.cells[cell];
+    const unsigned pe = a.pend[cell];
     const bool recreate = (pe & kUpdRecreate) != 0u;
     if (recreate) old = make_uint2(0u, 0u);  // (its old points and region are accounted for by the eviction)
     const unsigned total = old.y + (pe & ~kUpdRecreate);
@@ -317,12 +300,11 @@ __device__ __forceinline__ void upd_decide_totals(IvoxUpdState* __restrict__ st,
     if (!evict_ready) st->apply = status == kUpdOk ? 1u : 0u;  // no eviction selection follows: this is the verdict (ivox_upd_decide otherwise)
 }
 // the slot region of the voxel first touched by rank r: relocated when it outgrows its capacity; cell + halo copies; touched list
-template <bool COH = false>
 __device__ __forceinline__ void upd_region_rank(const IvoxUpdBatch& b, const IvoxUpdArrays& a, const IvoxUpdState* __restrict__ st, const unsigned r,
                                                 const unsigned alloc_before, const unsigned touched_before) {
     const unsigned cell = b.seq_cell[r];
-    const uint2 old = upd_ld_cell<COH>(&a.cells[cell]);
-    const unsigned total = old.y + upd_ld<COH>(&a.pend[cell]);
+    const uint2 old = a.cells[cell];
+    const unsigned total = old.y + a.pend[cell];
     const unsigned cl = a.cap_log2[cell];
     const unsigned cap = cl ? (1u << cl) : 0u;
     unsigned begin = old.x;
@@ -337,12 +319,11 @@ __device__ __forceinline__ void upd_region_rank(const IvoxUpdBatch& b, const Ivo
     brick_write_mirrors(a, cell, make_uint2(begin, total));
     b.tlist[touched_before] = cell;
 }
-template <bool COH = false>
 __device__ __forceinline__ void upd_point_rank(const IvoxUpdBatch& b, const IvoxUpdArrays& a, const IvoxUpdState* __restrict__ st, const unsigned r) {
     const unsigned cell = b.seq_cell[r];
-    const uint2 e = upd_ld_cell<COH>(&a.cells[cell]);
+    const uint2 e = a.cells[cell];
     const float4 p = b.pw[b.seq_src[r]];
-    a.pts[e.x + (e.y - upd_ld<COH>(&a.pend[cell])) + b.jj[r]] = make_float4(p.x, p.y, p.z, __int_as_float(st->next_id + (int)r));
+    a.pts[e.x + (e.y - a.pend[cell]) + b.jj[r]] = make_float4(p.x, p.y, p.z, __int_as_float(st->next_id + (int)r));
 }
 
 // rank of every inserted point, its window cell, the sequence arrays, and the per-cell scratch (count, first rank)
@@ -596,12 +577,12 @@ ivox_upd_points(const IvoxUpdBatch b, const IvoxUpdArrays a, const IvoxUpdState*
 // per voxel with an insertion sort in global memory, took up to 1.2 ms.)
 constexpr int kUpdFinishMaxK = 1024;  // new points of one voxel staged per wave; more than that: serial fallback by lane 0
 // one wave: the new points of touched voxel number t into id order (s_row: MAXK float4 of LDS owned by this wave), stamp, scratch reset
-template <int MAXK, bool COH = false>
+template <int MAXK>
 __device__ __forceinline__ void upd_finish_voxel(const IvoxUpdBatch& b, const IvoxUpdArrays& a, const IvoxUpdState* __restrict__ st, const unsigned t,
                                                  float4* __restrict__ s_row, const int lane) {
     const unsigned cell = b.tlist[t];
-    const uint2 e = upd_ld_cell<COH>(&a.cells[cell]);
-    const unsigned k = upd_ld<COH>(&a.pend[cell]);
+    const uint2 e = a.cells[cell];
+    const unsigned k = a.pend[cell];
     float4* const q = a.pts + e.x + (e.y - k);
     if (k > 1u && k <= (unsigned)MAXK) {
         for (unsigned i = lane; i < k; i += 64) s_row[i] = q[i];
@@ -616,7 +597,7 @@ __device__ __forceinline__ void upd_finish_voxel(const IvoxUpdBatch& b, const Iv
             q[pos] = x;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // (the row is reused by the wave's next voxel in the fused form)
+        __builtin_amdgcn_wave_barrier();
     } else if (k > (unsigned)MAXK && lane == 0) {
         for (unsigned i = 1; i < k; ++i) {  // (rare: more new points in one 0.5 m voxel than the wave stages)
             const float4 x = q[i];
@@ -627,7 +608,7 @@ __device__ __forceinline__ void upd_finish_voxel(const IvoxUpdBatch& b, const Iv
         }
     }
     if (lane == 0) {
-        a.stamp[cell] = st->stamp_base + upd_ld<COH>(&a.rank_mm[cell]) + 1ull;
+        a.stamp[cell] = st->stamp_base + a.rank_mm[cell] + 1ull;
         a.pend[cell] = 0u;
         a.rank_mm[cell] = kUpdNoRank;
     }
@@ -679,8 +660,8 @@ __global__ void ivox_upd_commit(IvoxUpdState* __restrict__ st, IvoxUpdMailbox* _
 // few hundred block totals, flipped first -> last ranks or published the result are folded into their neighbours:
 //   ivox_add_decide_kernel (+ count)  ->  ivox_upd_seq_nb (every block sums the block totals before it: no scan1)  ->  ivox_upd_plan
 //   ->  ivox_upd_last_regions (every block sums the plan totals and evaluates the verdict itself: no scan2, no separate `last`)
-//   ->  ivox_upd_points  ->  ivox_upd_finish  ->  ivox_upd_commit   (ivox_upd_finish_commit, where the last block to finish publishes, is
-//   the FLS_IVOX_FUSED_COMMIT=1 variant: measured slower, 15-26 us against 4.6 + 4.1 us).
+//   ->  ivox_upd_points  ->  ivox_upd_finish  ->  ivox_upd_commit   (a last-arriving finish block that publishes instead of the commit
+//   launch measured slower: 15-26 us against 4.6 + 4.1 us).
 // Same device functions, same arithmetic.  Batches that may evict keep the long chain (the selection needs grid-wide steps of its own).
 __global__ void __launch_bounds__(kUpdBlock)
 ivox_upd_seq_nb(const IvoxUpdBatch b, const IvoxUpdArrays a, IvoxUpdState* __restrict__ st, const int nblocks) {
@@ -721,110 +702,6 @@ ivox_upd_last_regions(const IvoxUpdBatch b, const IvoxUpdArrays a, IvoxUpdState*
     // and the status it stores is the one they computed
     if (blockIdx.x == 0 && threadIdx.x == 0) upd_decide_totals(st, tot, 0u, 0u, status_in);
 }
-// points of rank r in the short chain: the block offsets of ivox_upd_plan were never scanned in place, nothing else differs
-// (ivox_upd_points serves both chains)
-constexpr int kFinishBlocks = 256;
-__global__ void __launch_bounds__(kUpdBlock)
-ivox_upd_finish_commit(const IvoxUpdBatch b, const IvoxUpdArrays a, IvoxUpdState* __restrict__ st, IvoxUpdMailbox* __restrict__ mb, const unsigned seq,
-                       unsigned* __restrict__ ticket) {
-    __shared__ float4 s_pts[kUpdBlock / 64][kUpdFinishMaxK];
-    __shared__ unsigned s_last;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (st->apply) {
-        const unsigned touched = st->touched;
-        for (unsigned t = blockIdx.x * (kUpdBlock / 64) + w; t < touched; t += gridDim.x * (kUpdBlock / 64)) upd_finish_voxel<kUpdFinishMaxK>(b, a, st, t, &s_pts[w][0], lane);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = fanin_last_arriver(ticket, 8);
-    __syncthreads();
-    if (s_last && threadIdx.x == 0) upd_commit(st, mb, seq, a.n_bricks_cap);  // every other block is done with the words this changes
-}
-
-// ---- the whole batch in ONE launch of ONE workgroup (small batches: the 0.5 m-filtered planar cloud the pipeline feeds, ~10 k points) ----
-// The ten launches above are 2-5 us of work each with ~4 us of dispatch latency between dependent launches: ~90 us for microseconds of
-// work.  Up to kFusedMaxN source points the same phases run inside one 1024-thread workgroup, separated by
-// __syncthreads() instead of kernel boundaries: the two block scans happen once (16 consecutive codes per thread; a contiguous slice of
-// the ranks per thread), the per-rank phases stride over the ranks.  Same device functions, same arithmetic, same result -- ranks,
-// regions in first-touch order, ids, stamps.  Batches that may evict (the selection sorts the alive cells: a grid-wide job) and larger
-// batches keep the multi-launch form.
-constexpr int kFusedThreads = 1024, kFusedItems = 16, kFusedMaxN = kFusedThreads * kFusedItems, kFusedFinishK = 256;
-__global__ void __launch_bounds__(kFusedThreads)
-ivox_upd_fused_kernel(const IvoxUpdBatch b, const IvoxUpdArrays a, IvoxUpdState* __restrict__ st, IvoxUpdMailbox* __restrict__ mb, const unsigned seq) {
-    __shared__ unsigned wsum2[kFusedThreads / 64][2];
-    __shared__ unsigned wsum4[kFusedThreads / 64][4];
-    __shared__ uint4 s_base[kFusedThreads];
-    __shared__ float4 s_pts[kFusedThreads / 64][kFusedFinishK];
-    __shared__ unsigned s_apply;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) { st->status = kUpdOk; st->apply = 0u; }
-    // ---- count + rank: 16 consecutive decision codes per thread ----
-    unsigned char cd[kFusedItems];
-    unsigned v2[2] = {0u, 0u}, tot2[2];
-#pragma unroll
-    for (int k = 0; k < kFusedItems; ++k) {
-        const int i = t * kFusedItems + k;
-        cd[k] = i < b.n ? b.code[i] : (unsigned char)0;
-        v2[0] += cd[k] == 1 ? 1u : 0u;
-        v2[1] += cd[k] == 2 ? 1u : 0u;
-    }
-    block_excl_scan<2>(v2, tot2, wsum2);  // (its barriers also order the status reset above before any atomicOr below)
-    const unsigned n1 = tot2[0], A = tot2[0] + tot2[1];
-    {
-        unsigned r1 = v2[0], r2 = n1 + v2[1];
-#pragma unroll
-        for (int k = 0; k < kFusedItems; ++k) {
-            const unsigned i = (unsigned)(t * kFusedItems + k);
-            if (cd[k] == 1) b.seq_src[r1++] = i;
-            else if (cd[k] == 2) b.seq_src[r2++] = i;
-        }
-    }
-    if (t == 0) { st->n1 = n1; st->n2 = tot2[1]; }
-    __syncthreads();
-    // ---- seq: cell of every rank (bricks on demand), arrival number, first rank per cell ----
-    for (unsigned r = t; r < A; r += kFusedThreads) upd_seq_rank(b, a, st, r, b.seq_src[r]);
-    __syncthreads();
-    // ---- plan: a contiguous slice of the ranks per thread; exclusive {alloc, creations, touched, relocated} of the first-touchers ----
-    const unsigned per = (A + kFusedThreads - 1) / kFusedThreads, r_lo = min(A, (unsigned)t * per), r_hi = min(A, r_lo + per);
-    unsigned v4[4] = {0u, 0u, 0u, 0u}, tot4[4];
-    for (unsigned r = r_lo; r < r_hi; ++r) {
-        unsigned inc[4];
-        const bool first = upd_plan_rank<true>(b, a, r, inc);
-        b.fbit[r] = first ? 1 : 0;
-        b.px[r] = make_uint4(v4[0], v4[1], v4[2], v4[3]);  // exclusive inside the slice
-        v4[0] += inc[0]; v4[1] += inc[1]; v4[2] += inc[2]; v4[3] += inc[3];
-    }
-    block_excl_scan<4>(v4, tot4, wsum4);
-    s_base[t] = make_uint4(v4[0], v4[1], v4[2], v4[3]);
-    if (t == 0) {
-        upd_decide_totals(st, tot4, 0u, 0u, __hip_atomic_load(&st->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));  // (no eviction selection in this form: a batch that reaches the capacity is sent to the multi-launch form by the host)
-        s_apply = st->apply;
-    }
-    __syncthreads();
-    const bool apply = s_apply != 0u;
-    // ---- last: first rank -> last rank per cell, or scratch reset when the batch is refused ----
-    for (unsigned r = t; r < A; r += kFusedThreads) {
-        const unsigned cell = b.seq_cell[r];
-        if (cell == kUpdInvalidCell) continue;
-        if (apply) atomicMax(&a.rank_mm[cell], r);
-        else { a.pend[cell] = 0u; a.rank_mm[cell] = kUpdNoRank; }
-    }
-    if (apply) {
-        __syncthreads();
-        // ---- regions (slice order = first-touch order), points, per-voxel id order ----
-        const uint4 base = s_base[t];
-        for (unsigned r = r_lo; r < r_hi; ++r)
-            if (b.fbit[r]) { const uint4 loc = b.px[r]; upd_region_rank<true>(b, a, st, r, base.x + loc.x, base.z + loc.z); }
-        __syncthreads();
-        for (unsigned r = t; r < A; r += kFusedThreads) upd_point_rank<true>(b, a, st, r);
-        __syncthreads();
-        const unsigned touched = tot4[2];
-        for (unsigned tv = w; tv < touched; tv += kFusedThreads / 64) upd_finish_voxel<kFusedFinishK, true>(b, a, st, tv, &s_pts[w][0], lane);
-    }
-    __syncthreads();
-    if (t == 0) upd_commit(st, mb, seq, a.n_bricks_cap);
-}
-
 // ---- image <-> host mirror ---------------------------------------------------------------------------------------------------------
 // every alive voxel of the image as a record (sync_host_from_device: the device image back into the host mirror), in any order
 struct IvoxAliveRec { unsigned long long key; unsigned begin, count, cap_log2, pad; unsigned long long stamp; };

@@ -30,7 +30,7 @@ struct CellGridDev {
     double cell;
     int rings;  // 1: the gate fits into one cell (27-cell block suffices); 2: half-size cells, 125-cell block in two stages
     DenseWindow win;  // cells == nullptr: no dense window (extent too large), hash table only
-    const float4* by_id;  // the map cloud in its own order {x, y, z, id bits} (grid_knn27_kernel gathers its winners here), may be null
+    const float4* by_id;  // the map cloud in its own order {x, y, z, id bits} (grids built with by_id only), may be null
 };
 
 template <int K>
@@ -449,7 +449,7 @@ __device__ __forceinline__ void lu_tail(GnState* __restrict__ st, LuTailSmem& sm
     const bool early_fail = (mode == 1 && effective < min_effective);  // incremental_ndt.h:306-309: T = pose; return false
     double det = 1.0;
     if (!early_fail) {
-        // SPD fast path (kernels_p2plane.hpp::ldlt_solve6_lane): positive pivots imply det(H) > 0, so the reference's exact
+        // SPD fast path (kernels_p2plane.hpp::ldlt_fast_path): positive pivots imply det(H) > 0, so the reference's exact
         // det == 0 test (icp_optimized.h:129, Q14) cannot fire; anything else goes through the restated LU inverse
         const int fast = ldlt_fast_path(Hs, gs, xs, match_id);
         if (!fast) det = lu6_solve_wave(Hs, inv, gs, xs, tr);
@@ -500,25 +500,27 @@ __device__ __forceinline__ void lu_tail(GnState* __restrict__ st, LuTailSmem& sm
 // and the launch has eight times the waves of ndt_kernel (which runs 29k points as 457 single-wave workgroups, under one wave
 // per SIMD).  512 threads = 64 points per workgroup: the number of partial rows stays what gn_solve_lu_kernel reads in one pass.
 // Per point the seven contributions are now added by the wave reduction tree instead of sequentially (last-bit differences in H, g;
-// counts and flags are integers).
+// counts and flags are integers).  The Gauss-Newton tail runs in the last workgroup to arrive (see matcher_ndt.hpp::match_resident for
+// why the pose is parked in LDS).
 constexpr int kNdtLanesBlock = 512;
-// FUSED = the Gauss-Newton tail in the last workgroup (default since round 6, FLS_FUSED_TAIL=0 for the separate gn_solve_lu_kernel launch; see
-// matcher_ndt.hpp::fused_tail for why it was slower until the pose moved to LDS).  A template parameter, not a run-time branch.
+// (FUSED is always true.  The parameter stays so that the kernel keeps its symbol: the LDS layout the compiler picks for the kernel's
+// __shared__ variables follows their mangled names, and a renamed kernel gets different LDS offsets and register allocation.)
 template <bool FUSED>
 __global__ void __launch_bounds__(kNdtLanesBlock)
 ndt_lanes_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
                  GnState* __restrict__ st, const int first, const Pose16 T0, const NdtGridDev ng, const double outlier_thr,
                  int* __restrict__ hit_vid /* [n][7] */, unsigned char* __restrict__ eff7 /* [n][7] */, double* __restrict__ partials,
-                 unsigned* __restrict__ ticket /* nullptr: the tail runs as its own launch */, const int shards, const LuTailArgs tail) {
+                 unsigned* __restrict__ ticket, const int shards, const LuTailArgs tail) {
+    static_assert(FUSED, "the Gauss-Newton tail always runs in the last workgroup");
     const int done = first ? 0 : st->done;
     double P[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) P[k] = first ? T0.m[k] : st->T[k];
-    const int it = (FUSED && !first) ? st->iter : 0;
+    const int it = first ? 0 : st->iter;
     if (done) return;
     __shared__ double wsum[kNdtLanesBlock / 64][32];
     __shared__ double s_pose[16];
-    if (FUSED && threadIdx.x == 0) {
+    if (threadIdx.x == 0) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) s_pose[q] = P[q];
     }
@@ -604,18 +606,15 @@ ndt_lanes_kernel(const float* __restrict__ sx, const float* __restrict__ sy, con
     if (threadIdx.x < 29) {
 #pragma unroll
         for (int w = 0; w < kNdtLanesBlock / 64; ++w) v += wsum[w][threadIdx.x];
-        if (!FUSED) partials[(size_t)blockIdx.x * kPartialStride + threadIdx.x] = v;
     }
-    if constexpr (FUSED) {
-        // fused Gauss-Newton tail (round 3): the row goes out write-through, the last workgroup to arrive solves and publishes
-        __shared__ unsigned s_ticket;
-        __shared__ LuTailSmem sm;
-        if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, s_ticket)) return;
-        double Tl[16];  // (the pose parked in LDS at the start: sixteen doubles kept in registers across the per-point part cost the kernel its fourth wave per SIMD)
+    // fused Gauss-Newton tail (round 3): the row goes out write-through, the last workgroup to arrive solves and publishes
+    __shared__ unsigned s_ticket;
+    __shared__ LuTailSmem sm;
+    if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, s_ticket)) return;
+    double Tl[16];  // (the pose parked in LDS at the start: sixteen doubles kept in registers across the per-point part cost the kernel its fourth wave per SIMD)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) Tl[q] = s_pose[q];
-        lu_tail<kNdtLanesBlock, true>(st, sm, partials, (int)gridDim.x, tail, Tl, it);
-    }
+    for (int q = 0; q < 16; ++q) Tl[q] = s_pose[q];
+    lu_tail<kNdtLanesBlock, true>(st, sm, partials, (int)gridDim.x, tail, Tl, it);
 }
 
 __global__ void __launch_bounds__(1024)

@@ -13,8 +13,7 @@
 //   gicp_fdf_kernel        OptimizationFunctorWithIndices f / df: sum of res^T M res, translation gradient, sum of p (M res)^T
 //   loop_fitness_kernel    getFitnessScore: squared distance to the nearest target point
 //   loop_block_reduce      (tail of the three summing kernels) the last workgroup to arrive adds the partial rows in index order and
-//                          publishes them to the host-mapped result block + sequence word; loop_reduce_kernel = the same as a launch of
-//                          its own (FLS_LOOP_FUSED_REDUCE=0, A/B)
+//                          publishes them to the host-mapped result block + sequence word
 // Every sum has a fixed tree (DPP wave sum -> LDS -> rows in index order): results are bit-reproducible run to run.
 #pragma once
 #include "kernels_knn.hpp"
@@ -68,7 +67,7 @@ __device__ __forceinline__ void loop_block_reduce(const double (&acc)[NV], const
         __hip_atomic_store((unsigned long long*)out.rows + (size_t)blockIdx.x * kLoopMaxV + threadIdx.x, (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!out.ticket) return;  // FLS_LOOP_FUSED_REDUCE=0: loop_reduce_kernel follows
+    if (!out.ticket) return;  // (no ticket: the rows only)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) s_last = fanin_last_arriver(out.ticket, 8);
@@ -92,27 +91,6 @@ __device__ __forceinline__ void loop_block_reduce(const double (&acc)[NV], const
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     if (c == 0) __hip_atomic_store(&out.mail->seq, out.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ void __launch_bounds__(64)
-loop_reduce_kernel(const double* __restrict__ rows, const int nrows, const int nv, LoopMail* __restrict__ mail, const unsigned seq) {
-    const int c = threadIdx.x;
-    if (c < nv) {
-        double s = 0.0;
-        int r = 0;
-        for (; r + 8 <= nrows; r += 8) {  // eight loads in flight, adds in row order
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = rows[(size_t)(r + u) * kLoopMaxV + c];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; r < nrows; ++r) s += rows[(size_t)r * kLoopMaxV + c];  // fixed order
-        __hip_atomic_store((unsigned long long*)&mail->v[c], (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    if (c == 0) __hip_atomic_store(&mail->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---- P2D-NDT -----------------------------------------------------------------------------------------------------------------

@@ -213,9 +213,6 @@ constexpr int kSolveThreads = 1024;
 // order: bit-identical sums (tools/gpu_ab_libs.py: equal pose bits on every kind).  Measured (profiles/r06_aw_reduce_uniform_rounds_ab.log): IcpOptimized
 // 229.8 -> 225.9 us per Match (rows read + reduced 3,932 -> 3,480 ticks), LoamFull 236.8 -> 235.6; the 512-thread kernels (two waves per SIMD in the tail
 // workgroup: iVox, IncrementalNDT) measured 0.4-0.7 us per Match SLOWER with it and keep the guarded form, as do the 1,024-thread solve launches.
-#ifndef FLS_REDUCE_UNIFORM_ROUNDS
-#define FLS_REDUCE_UNIFORM_ROUNDS 1  // 0: every load guarded per lane everywhere (A/B builds)
-#endif
 template <int NT, bool SC1, int U, int F /* rounds without a row test */>
 __device__ __forceinline__ void reduce_partials_trip(const double* __restrict__ partials, const int r, const int nrows, const int col, double& acc) {
     constexpr int NG = NT / 32;
@@ -242,7 +239,7 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ parti
     constexpr int NG = NT / 32;
     const int col = threadIdx.x & 31, grp = threadIdx.x >> 5;
     double acc = 0.0;
-    if constexpr (FLS_REDUCE_UNIFORM_ROUNDS && NT <= 256) {
+    if constexpr (NT <= 256) {
         for (int r = grp; r < nrows; r += U * NG) {
             const int rounds = (nrows - (r - grp)) / NG;  // uniform: rounds of this trip whose row is in range for every row group
             if (rounds >= U) reduce_partials_trip<NT, SC1, U, U>(partials, r, nrows, col, acc);
@@ -284,6 +281,7 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ parti
 // moves on to the top counter, the last of those is THE last.  Counters sit 128 bytes apart and are reset by their last arriver, so
 // they are zero at every launch.  Call with one thread after the workgroup's row is published and drained; kTicketWords words.
 constexpr int kTicketWords = 32 * 10;  // [0] single counter (shards <= 1) | [32 (1 + s)] shard s | [32 * 9] top counter
+constexpr int kTicketShards = 8;       // the shard count every host launch passes
 __device__ __forceinline__ unsigned fanin_last_arriver(unsigned* __restrict__ ticket, const int shards) {
     if (shards <= 1) {
         const unsigned last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
@@ -319,31 +317,16 @@ __device__ __forceinline__ bool publish_row_and_arrive(const double v, const boo
 #endif
 
 // Fast path of the Gauss-Newton tails.  The 6x6 normal equations H = sum J J^T are symmetric positive definite whenever the
-// scene constrains all six degrees of freedom; one lane then solves H x = g by an unpivoted LDL^T in registers (static
-// indices only, ~0.8 us) instead of the wave-cooperative restatement of Eigen's FullPivHouseholderQR (6.2 us) / partial-pivot LU
+// scene constrains all six degrees of freedom; wave 0 then solves H x = g by an unpivoted LDL^T (hm::ldlt_solve6 restated with
+// the matrix rows in lanes 0..5: wave_solve.hpp::ldlt_solve6_wave) instead of the wave-cooperative restatement of Eigen's FullPivHouseholderQR (6.2 us) / partial-pivot LU
 // inverse.  Same linear system, so the same x up to rounding (observed 1e-13 relative; the pose the Match returns agrees
 // with the oracle's to <= 1e-12 instead of <= 1e-14, every per-iteration n_valid / flag / id comparison of the test-suite is
 // unchanged).  The Eigen-arithmetic solvers remain the fallback whenever a pivot is not safely positive (rank-deficient or
 // badly conditioned systems: there Eigen's rank-revealing behaviour IS the semantics) and can be forced for every system
-// with FLS_TAIL_EXACT=1 (launch word bit 23).  Returns false when the caller must run the exact solver.
-__device__ __forceinline__ bool ldlt_solve6_lane(const double* __restrict__ H /* 6x6 column-major, LDS */, const double* __restrict__ g, double* __restrict__ x) {
-    return hm::ldlt_solve6(H, g, x);  // host_math.hpp (__host__ __device__: tests/host/host_logic_test.cpp checks it on the CPU)
-}
-// The fast path as the tails call it (whole wave 0, uniform result; launch word bit 23 = FLS_TAIL_EXACT: no fast path).  Default since the end of
-// round 6: the factorisation with the matrix rows in lanes 0..5 (wave_solve.hpp::ldlt_solve6_wave); -DFLS_TAIL_LDLT_WAVE=0 builds the one-lane
-// form it replaced (A/B: tools/gpu_ab_libs.py).
-#ifndef FLS_TAIL_LDLT_WAVE
-#define FLS_TAIL_LDLT_WAVE 1
-#endif
+// with FLS_TAIL_EXACT=1 (launch word bit 23).  Called by the whole wave 0, uniform result; 0 when the caller must run the exact solver.
 __device__ __forceinline__ int ldlt_fast_path(const double* __restrict__ H, const double* __restrict__ g, double* __restrict__ x, const unsigned launch_word) {
     if ((launch_word >> 23) & 1u) return 0;
-#if FLS_TAIL_LDLT_WAVE
     return ldlt_solve6_wave(H, g, x) ? 1 : 0;
-#else
-    int fast = 0;
-    if ((threadIdx.x & 63) == 0) fast = ldlt_solve6_lane(H, g, x) ? 1 : 0;
-    return __shfl(fast, 0, 64);
-#endif
 }
 
 // shared memory of the LOAM-family Gauss-Newton tail

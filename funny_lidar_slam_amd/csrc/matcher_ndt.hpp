@@ -3,8 +3,8 @@
 //   AddCloudToLocalMap :182-227  voxel insert with LRU eviction + UpdateVoxel (:130-179) on the host;
 //                                the estimated voxels are flattened into a device hash table
 //                                {key -> slot} with mu[slot], info[slot] in FP64.
-//   Match              :229-337  device-resident loop: ndt_kernel (7-voxel Mahalanobis scoring,
-//                                FP64) + gn_solve_lu_kernel (mode 1).
+//   Match              :229-337  device-resident loop: ndt_lanes_kernel (7-voxel Mahalanobis scoring,
+//                                FP64, the Gauss-Newton tail in its last workgroup; mode 1).
 #pragma once
 #include "matcher_base.hpp"
 #include "host_math.hpp"
@@ -69,12 +69,6 @@ struct NdtMatcher final : fls_matcher {
     std::vector<PtI> source;
     SourceFilter src_filter;
     bool host_timing = false;  // FLS_HOST_TIMING=1: print the host-side split of every map update
-    bool lanes_kernel = true;  // FLS_NDT_LANES=0: one lane per point (ndt_kernel) instead of one lane per neighbour voxel
-    bool fused_tail = true;    // the Gauss-Newton tail in the correspondence kernel's last workgroup instead of its own launch (gn_solve_lu_kernel); FLS_FUSED_TAIL=0: separate launch.
-                               // Rounds 3-5 measured the fused form SLOWER on configs[2] (83.9 vs 76-80 us per Match) and kept it off: ndt_lanes_kernel<true> held the pose
-                               // (sixteen doubles) in registers across the per-point part for the tail -- 144 VGPRs = 3 waves per SIMD = ONE 512-thread workgroup per CU, so
-                               // its 457 workgroups ran in two rounds.  Round 6 parks the pose in LDS: 118 VGPRs like the plain kernel, one round, and the launch the tail
-                               // no longer needs is a gain: 73.5-74.1 vs 78.3-79.6 us per Match, same pose to the last bit (tools/gpu_ab_ndt.py, profiles/r06_ai_*).
     DevBuf<unsigned> d_ticket;
     DevBuf<int> d_hit_vid;
     DevBuf<unsigned char> d_eff7;
@@ -92,8 +86,6 @@ struct NdtMatcher final : fls_matcher {
         init_common();
         src_filter.init();
         if (const char* e = std::getenv("FLS_HOST_TIMING")) host_timing = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_NDT_LANES")) lanes_kernel = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_FUSED_TAIL")) fused_tail = std::atoi(e) != 0;
         d_ticket.reserve(kTicketWords);
         FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
         if (const char* e = std::getenv("FLS_NDT_DEVICE_UPDATE")) allow_device_update = std::atoi(e) != 0;
@@ -649,26 +641,21 @@ struct NdtMatcher final : fls_matcher {
         std::memcpy(T0.m, T, sizeof(T0.m));
         const unsigned word = run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it], stream));
-            if (nblk > 0 && lanes_kernel && !count_traffic) {  // one lane per neighbour voxel (64 points per workgroup: same row count)
+            if (nblk > 0 && !count_traffic) {
+                // one lane per neighbour voxel (64 points per workgroup: same row count) and the Gauss-Newton tail in the last workgroup: one launch
+                // per iteration.  Rounds 3-5 measured the fused tail SLOWER on configs[2] (83.9 vs 76-80 us per Match): the kernel held the pose
+                // (sixteen doubles) in registers across the per-point part for the tail -- 144 VGPRs = 3 waves per SIMD = ONE 512-thread workgroup per
+                // CU, so its 457 workgroups ran in two rounds.  Round 6 parks the pose in LDS: 118 VGPRs like the plain kernel, one round, and the
+                // launch the tail no longer needs is a gain: 73.5-74.1 vs 78.3-79.6 us per Match, same pose to the last bit (profiles/r06_ai_*).
                 const LuTailArgs tail{1, p.rotation_converge_thres, p.position_converge_thres, p.ndt_min_effective_pts, mb_dev, launch_word()};
-                if (fused_tail)
-                    hipLaunchKernelGGL(ndt_lanes_kernel<true>, dim3(nblk), dim3(kNdtLanesBlock), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first,
-                                       T0, ng, p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, d_ticket.p, 8, tail);
-                else
-                    hipLaunchKernelGGL(ndt_lanes_kernel<false>, dim3(nblk), dim3(kNdtLanesBlock), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first,
-                                       T0, ng, p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, (unsigned*)nullptr, 8, tail);
-                if (fused_tail) {  // the last workgroup ran the Gauss-Newton tail: one launch per iteration
-                    if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
-                    return;
-                }
-            } else if (nblk > 0) {
-                if (count_traffic)
-                    hipLaunchKernelGGL(ndt_kernel<true>, dim3(nblk), dim3(64), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first, T0, ng,
-                                       p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, d_tc.p);
-                else
-                    hipLaunchKernelGGL(ndt_kernel<false>, dim3(nblk), dim3(64), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first, T0, ng,
-                                       p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, d_tc.p);
+                hipLaunchKernelGGL(ndt_lanes_kernel<true>, dim3(nblk), dim3(kNdtLanesBlock), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first,
+                                   T0, ng, p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, d_ticket.p, kTicketShards, tail);
+                if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
+                return;
             }
+            if (nblk > 0)  // traffic counting: one lane per point, then the tail as its own launch
+                hipLaunchKernelGGL(ndt_kernel<true>, dim3(nblk), dim3(64), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first, T0, ng,
+                                   p.ndt_res_outlier_threshold, d_hit_vid.p, d_eff7.p, d_partials_b.p, d_tc.p);
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
             hipLaunchKernelGGL(gn_solve_lu_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_b.p, nblk, 1,
                                p.rotation_converge_thres, p.position_converge_thres, p.ndt_min_effective_pts, mb_dev, launch_word());

@@ -21,6 +21,8 @@
 
 namespace fls {
 
+constexpr int kIvoxXcdChunk = 8;  // workgroups per XCD chunk of the kNN block re-map (ivox_knn_kernel's `chunk`)
+
 struct P2PlaneIvoxMatcher final : fls_matcher {
     HostIvox ivox;
     IvoxImage image;
@@ -39,15 +41,12 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     bool allow_device_map = true;  // FLS_IVOX_DEVICE_UPDATE=0: always the host path (A/B)
     size_t device_margin = 4096;   // voxels of head-room below the LRU capacity required to (re-)enter device mode (FLS_IVOX_DEVICE_MARGIN: test hook)
     size_t n_device_updates = 0, n_host_fallbacks = 0, n_device_evictions = 0, n_device_recreated = 0, n_refused_conflict = 0, n_refused_full = 0, n_refused_outside = 0;
-    bool fused_update = false;     // FLS_IVOX_FUSED_UPDATE=1 (A/B): small batches as ONE launch of one workgroup
     bool short_chain_update = true;  // FLS_IVOX_SHORT_CHAIN=0 (A/B): the round-3 chain of eleven launches for every batch
-    size_t n_fused_updates = 0, n_short_updates = 0;
+    size_t n_short_updates = 0;
     // the decision + update chain queued behind the iterations the Match is expected to need, gated on the device (ivox_add_decide_kernel):
     // removes the host's mailbox turnaround + first-launch latency (~14 us) in front of the map update.  FLS_IVOX_SPECULATIVE=0: wait first.
     bool speculative_update = true, spec_pending = false, last_chain_skipped = false;
     size_t n_speculative = 0, n_speculative_skipped = 0;
-    bool fused_commit = false;     // FLS_IVOX_FUSED_COMMIT=1 (A/B): the last finishing block publishes instead of a commit launch (measured slower: 15-26 us against 4.6 + 4.1 us)
-    int finish_blocks = kFinishBlocks;  // FLS_IVOX_FINISH_BLOCKS (A/B)
     bool device_evict = true;      // FLS_IVOX_DEVICE_EVICT=0: a batch that reaches the LRU capacity is refused (round-2 behaviour, with the margin rule)
     DevicePairSort ev_sort;
     DevBuf<unsigned> d_ev_bt, d_crank, d_evict_list;
@@ -68,13 +67,6 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     std::vector<Pt4> h_pw;
     DevBuf<unsigned> d_ticket;
     bool use_dense = true; // dense voxel window instead of the hash table when the map extent allows (FLS_IVOX_DENSE=0 disables)
-    int xcd_chunk = 8;     // workgroups per XCD chunk of the kNN block re-map (FLS_IVOX_XCD_CHUNK)
-    bool balanced = true;  // equal candidate ranges per lane through an LDS voxel table (FLS_IVOX_BALANCED=0: whole voxels per lane)
-    int variant = 4;       // lanes cooperating on one query in ivox_knn_kernel: 4 or 8 (FLS_IVOX_VARIANT)
-    int ticket_shards = 8; // fan-in of the fit kernel's workgroups: 8 per-XCD counters + a top counter (FLS_TICKET_SHARDS=1: one counter)
-    int fit_threads_env = 0;    // FLS_FIT_THREADS = 512 | 256 (A/B): workgroup size of the fit kernel; 0 = by scan size
-    bool plain_launch = false;  // FLS_PLAIN_LAUNCH=1 (A/B): hipLaunchKernelGGL instead of hipExtLaunchKernelGGL with null events
-    bool prof_fit = false; // FLS_PROF_FIT=1 (diagnosis): the profiling events bracket the fit+solve kernel instead of the kNN kernel
     bool is_first = true;  // the reference's function-static flag (:62), per handle here
     const double filter_size_map_min = 0.5;  // :351
 
@@ -82,8 +74,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // per-point state that outlives an iteration (Q1) or a Match (nearest_points_, :257)
     DevBuf<float4> d_nn;          // [n][5]
     DevBuf<unsigned char> d_nn_cnt;   // neighbour count (bits 0-2) | 0x80 when the point's list is in rows form
-    DevBuf<unsigned> d_nn_ids;        // [n][8] map slots of the neighbours (ids form: what the kNN kernel writes by default)
-    bool nn_ids_mode = true;          // FLS_IVOX_NN_IDS=0: the kNN kernel writes gathered rows (round-2 behaviour)
+    DevBuf<unsigned> d_nn_ids;        // [n][8] map slots of the neighbours (ids form: what the kNN kernel writes)
     bool nn_rows_current = true;      // every list is in rows form
     size_t nn_n = 0;              // logical size of nearest_points_
     int nn_prev = 0;              // its size before the Match in flight
@@ -106,31 +97,19 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         if (unset_d(p.point_to_planar_thres) || unset_d(p.position_converge_thres) || unset_d(p.rotation_converge_thres))
             return FLS_ERR_INVALID;  // CHECK_NE(..., max()) at :45-48
         init_common();
-        if (const char* e = std::getenv("FLS_IVOX_VARIANT")) { const int v = std::atoi(e); if (v == 4 || v == 8) variant = v; }
         if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_PROF_FIT")) prof_fit = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_PLAIN_LAUNCH")) plain_launch = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_FIT_THREADS")) { const int v = std::atoi(e); fit_threads_env = (v == 256 || v == 512) ? v : 0; }
-        if (const char* e = std::getenv("FLS_IVOX_NN_IDS")) nn_ids_mode = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_BALANCED")) balanced = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_HOST_TIMING")) host_timing = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_MARGIN")) { const long c = std::atol(e); if (c >= 0) device_margin = size_t(c); }
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_EVICT")) device_evict = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_FUSED_UPDATE")) fused_update = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_SHORT_CHAIN")) short_chain_update = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_HOST_SRC")) host_src = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_SPECULATIVE")) speculative_update = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_FUSED_COMMIT")) fused_commit = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_FINISH_BLOCKS")) { const int v = std::atoi(e); if (v >= 1 && v <= 4096) finish_blocks = v; }
         d_upd_state.reserve(1);
         FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
         std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
         FLS_HIP(hipHostGetDevicePointer((void**)&upd_mb_dev, upd_mb_host, 0));
-        if (const char* e = std::getenv("FLS_IVOX_XCD_CHUNK")) { const int c = std::atoi(e); if (c >= 1 && c <= 4096) xcd_chunk = c; }
         d_ticket.reserve(kTicketWords);
         FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
-        if (const char* e = std::getenv("FLS_TICKET_SHARDS")) ticket_shards = std::atoi(e) > 1 ? 8 : 1;
         ivox.resolution = 0.5f;       // InitIVox :53-58
         ivox.inv_resolution = 1.0f / 0.5f;
         ivox.capacity = 1000000;
@@ -232,27 +211,16 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         upd_seq = (upd_seq + 1u) & 0x7fffffffu;
         if (upd_seq == 0u) upd_seq = 1u;
         const dim3 g{unsigned(nb), 1u, 1u}, t{unsigned(kUpdBlock), 1u, 1u};
-        // three forms of the same phases (kernels_ivox_update.hpp): the SHORT chain (default: five launches behind the decision), the
-        // one-workgroup single launch (FLS_IVOX_FUSED_UPDATE=1, small batches; measured slower: one CU's latency chains), and the LONG
-        // chain, which batches that may reach the LRU capacity need (the eviction selection has grid-wide steps of its own)
-        const bool cannot_evict = dev_n_alive + n < ivox.capacity;
-        const bool fused = fused_update && n <= size_t(kFusedMaxN) && cannot_evict;
-        const bool short_chain = !fused && short_chain_update && cannot_evict && counted_by_decide;
-        if (fused) {
-            hipLaunchKernelGGL(ivox_upd_fused_kernel, dim3(1), dim3(kFusedThreads), 0, stream, b, a, d_upd_state.p, upd_mb_dev, upd_seq);
-            ++n_fused_updates;
-        } else if (short_chain) {
+        // two forms of the same phases (kernels_ivox_update.hpp): the SHORT chain (default: five launches behind the decision) and the
+        // LONG chain, which batches that may reach the LRU capacity need (the eviction selection has grid-wide steps of its own)
+        const bool short_chain = short_chain_update && dev_n_alive + n < ivox.capacity && counted_by_decide;
+        if (short_chain) {
             hipLaunchKernelGGL(ivox_upd_seq_nb, g, t, 0, stream, b, a, d_upd_state.p, nb);
             hipLaunchKernelGGL(ivox_upd_plan, g, t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
             hipLaunchKernelGGL(ivox_upd_last_regions, g, t, 0, stream, b, a, d_upd_state.p);
             hipLaunchKernelGGL(ivox_upd_points, g, t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
-            if (fused_commit) {
-                const unsigned fb = unsigned(std::min<size_t>(size_t(finish_blocks), (n + kUpdBlock / 64 - 1) / (kUpdBlock / 64)));
-                hipLaunchKernelGGL(ivox_upd_finish_commit, dim3(fb), t, 0, stream, b, a, d_upd_state.p, upd_mb_dev, upd_seq, d_ticket.p);
-            } else {
-                hipLaunchKernelGGL(ivox_upd_finish, dim3(unsigned((n + kUpdBlock / 64 - 1) / (kUpdBlock / 64))), t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
-                hipLaunchKernelGGL(ivox_upd_commit, dim3(1), dim3(64), 0, stream, d_upd_state.p, upd_mb_dev, upd_seq, unsigned(image.n_bricks_cap));
-            }
+            hipLaunchKernelGGL(ivox_upd_finish, dim3(unsigned((n + kUpdBlock / 64 - 1) / (kUpdBlock / 64))), t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
+            hipLaunchKernelGGL(ivox_upd_commit, dim3(1), dim3(64), 0, stream, d_upd_state.p, upd_mb_dev, upd_seq, unsigned(image.n_bricks_cap));
             ++n_short_updates;
         } else {
         hipLaunchKernelGGL(ivox_upd_count, g, t, 0, stream, b);
@@ -386,7 +354,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         unsigned* const st_status = count_here ? &d_upd_state.p->status : nullptr;
         unsigned* const st_apply = count_here ? &d_upd_state.p->apply : nullptr;
         // (the update moves map slots: lists still in ids form become rows in the same launch)
-        if (nn_ids_mode && (speculative || !nn_rows_current) && nn_n > 0) {
+        if ((speculative || !nn_rows_current) && nn_n > 0) {
             const size_t m = std::max(n, nn_n);
             hipLaunchKernelGGL(ivox_add_decide_kernel<true>, dim3(unsigned((m + 255) / 256)), dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p,
                                int(n), Tw, d_nn.p, d_nn_cnt.p, int(nn_n), filter_size_map_min,
@@ -395,7 +363,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         } else {
             hipLaunchKernelGGL(ivox_add_decide_kernel<false>, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p,
                                int(n), Tw, d_nn.p, d_nn_cnt.p, int(nn_n), filter_size_map_min,
-                               d_code.p, d_pw.p, (const unsigned*)(nn_ids_mode ? d_nn_ids.p : nullptr), (const float4*)image.d_pts.p, unsigned(image.d_pts.cap), lx_arg, bt_arg,
+                               d_code.p, d_pw.p, (const unsigned*)d_nn_ids.p, (const float4*)image.d_pts.p, unsigned(image.d_pts.cap), lx_arg, bt_arg,
                                st_status, st_apply, gn, max_it);
         }
         FLS_HIP(hipGetLastError());
@@ -436,7 +404,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
                     if (last_chain_skipped) {
                         // a speculative chain that judged "no update here" although the host wants one (cannot happen while host and device
                         // read the same words; kept as a safe path): decide + apply the ordinary way
-                        if (nn_ids_mode) nn_rows_current = false;  // (the skipped launch materialised nothing)
+                        nn_rows_current = false;  // (the skipped launch materialised nothing)
                         counted = launch_decide(n, false);
                         ensure_nn_rows();
                         if (enqueue_update_chain(n, counted) && await_update_chain(n)) return FLS_OK;
@@ -524,10 +492,10 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // fls_match from host buffers: the scan stays in the pinned staging buffer; the first iteration's correspondence launch reads it
     // from there over PCIe (the kernel is latency bound: the reads hide behind its probe / candidate chains) and leaves the device copy
     // the later launches use.  No SDMA copy, no copy-engine -> compute-queue hand-off in front of the first kernel (8 us + 8 us for the
-    // 10 k-point planar cloud the pipeline feeds; FLS_IVOX_HOST_SRC=0 restores the copy).
-    bool host_src = true, scan_in_staging = false;
+    // 10 k-point planar cloud the pipeline feeds).
+    bool scan_in_staging = false;
     fls_status scan_upload_for_match(const float* s0, size_t n0, const float* s1, size_t n1, int stride) override {
-        if (!host_src || borrowed) return scan_upload(s0, n0, s1, n1, stride);
+        if (borrowed) return scan_upload(s0, n0, s1, n1, stride);
         (void)s1; (void)n1;
         scan.stage_raw(s0, n0, stride);
         scan_in_staging = n0 != 0;
@@ -545,10 +513,9 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // e0 / e1 (profiling only): start / stop events attached to the kernel's own dispatch packet (hipExtLaunchKernelGGL),
     // i.e. the kernel's execution time as a kernel trace sees it -- a hipEventRecord bracket also times the dispatch of
     // the kernel between its two marker packets (about 3 us more on an 18 us kernel)
-    template <int G>
-    void launch_knn(const size_t n, const int first, const Pose16& T0, const DevGrid& g, const BrickDir& win, hipEvent_t e0 = nullptr,
-                    hipEvent_t e1 = nullptr) {
-        unsigned* const ids_arg = nn_ids_mode ? d_nn_ids.p : nullptr;
+    // (4 lanes per query with the balanced candidate split: ivox_knn_kernel<4, ..., true>)
+    void launch_knn(const size_t n, const int first, const Pose16& T0, const DevGrid& g, const BrickDir& win, hipEvent_t e0, hipEvent_t e1) {
+        constexpr int G = 4;
         // first launch of a Match whose scan is still in the staging buffer: read it there, write the device copy
         const bool from_host = first && scan_in_staging;
         const float* const hx = from_host ? scan.stage_dev() : nullptr;
@@ -556,24 +523,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         const float* const src_y = from_host ? hx + n : (const float*)scan.y.p;
         const float* const src_z = from_host ? hx + 2 * n : (const float*)scan.z.p;
         float* const dev_copy = from_host ? scan.xyz.p : nullptr;
-        const size_t nblk = (n * G + 255) / 256, gran = size_t(8) * size_t(xcd_chunk);
+        const size_t nblk = (n * G + 255) / 256, gran = size_t(8) * size_t(kIvoxXcdChunk);
         const dim3 grid(unsigned((nblk + gran - 1) / gran * gran));  // multiple of 8 * chunk: the XCD re-map is a bijection
-#define FLS_KNN_L(C, D, F, B)                                                                                                        \
-    do {                                                                                                                             \
-        if (e0 || !plain_launch)                                                                                                     \
-            hipExtLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, B>), grid, dim3(256), 0, stream, e0, e1, 0, src_x,                    \
-                                  src_y, src_z, int(n), (const GnState*)d_state.p, T0, g, win,                                      \
-                                  ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, xcd_chunk, ids_arg, nn_prev, dev_copy); \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, B>), grid, dim3(256), 0, stream, src_x,                                  \
-                               src_y, src_z, int(n), (const GnState*)d_state.p, T0, g, win,                                         \
-                               ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, xcd_chunk, ids_arg, nn_prev, dev_copy);   \
-    } while (0)
-#define FLS_KNN(C, D)                                                                                                                \
-    do {                                                                                                                             \
-        if (balanced && G == 4) { if (first) FLS_KNN_L(C, D, true, true); else FLS_KNN_L(C, D, false, true); }                        \
-        else { if (first) FLS_KNN_L(C, D, true, false); else FLS_KNN_L(C, D, false, false); }                                         \
-    } while (0)
+#define FLS_KNN_L(C, D, F)                                                                                                           \
+    hipExtLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, true>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n),      \
+                          (const GnState*)d_state.p, T0, g, win, ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, kIvoxXcdChunk, \
+                          d_nn_ids.p, nn_prev, dev_copy)
+#define FLS_KNN(C, D) do { if (first) FLS_KNN_L(C, D, true); else FLS_KNN_L(C, D, false); } while (0)
         if (win.cells) { if (count_traffic) FLS_KNN(true, true); else FLS_KNN(false, true); }
         else { if (count_traffic) FLS_KNN(true, false); else FLS_KNN(false, false); }
 #undef FLS_KNN_L
@@ -605,7 +561,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         // nearest_points_.resize(n) semantics (:257): grown tail is empty, shrink forgets
         d_nn.reserve(n * 5, /*keep=*/true, stream);
         d_nn_cnt.reserve(n, /*keep=*/true, stream);
-        if (nn_ids_mode) d_nn_ids.reserve(n * 8, /*keep=*/true, stream);
+        d_nn_ids.reserve(n * 8, /*keep=*/true, stream);
         nn_prev = int(std::min(nn_n, n));  // the first iteration's kNN launch clears the counts of the grown tail [nn_prev, n)
         nn_n = n;
         d_J.reserve(7 * n);
@@ -613,7 +569,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         // workgroup size of the fit kernel: 512 threads (two waves per SIMD of a CU) when the scan fills the machine anyway; 256 (one wave per
         // SIMD) up to 65,536 points, where 256 workgroups spread the same waves over every CU -- the 9.8k-point planar cloud the pipeline feeds
         // ran its 2,500-instruction fit phase two waves deep on 20 CUs with 236 CUs idle
-        const int fit_threads = (fit_threads_env > 0) ? fit_threads_env : (n <= 65536 ? 256 : kFitThreads);
+        const int fit_threads = n <= 65536 ? 256 : kFitThreads;
         const int nwg = int((n + size_t(fit_threads) - 1) / size_t(fit_threads));
         d_partials_b.reserve(size_t(nwg) * kPartialStride);
         const int iters = int(p.max_iterations);
@@ -622,7 +578,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
         // speculative map update (see speculative_update): only where the short chain applies and the call would update the map if it converges
-        const bool spec = speculative_update && update_map && !p.is_localization_mode && !borrowed && !is_first && device_map && short_chain_update && !fused_update &&
+        const bool spec = speculative_update && update_map && !p.is_localization_mode && !borrowed && !is_first && device_map && short_chain_update &&
                           dev_n_alive + n < ivox.capacity && int((n + kUpdBlock - 1) / kUpdBlock) <= kUpdMaxBlocks;
         spec_pending = false;
         auto after_chunk = [&](int) {
@@ -633,30 +589,19 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             ++n_speculative;
         };
         const unsigned word = run_mailbox_loop(iters, n, [&](int it, int first) {
-            hipEvent_t e0 = profiling ? ev[2 * it] : nullptr, e1 = profiling ? ev[2 * it + 1] : nullptr;
-            hipEvent_t f0 = nullptr, f1 = nullptr;
-            if (prof_fit) { f0 = e0; f1 = e1; e0 = e1 = nullptr; }
-            if (variant == 4) launch_knn<4>(n, first, T0, g, win, e0, e1); else launch_knn<8>(n, first, T0, g, win, e0, e1);
+            launch_knn(n, first, T0, g, win, profiling ? ev[2 * it] : nullptr, profiling ? ev[2 * it + 1] : nullptr);
 #define FLS_FIT_NT(F, NT)                                                                                                            \
-    do {                                                                                                                             \
-        if (f0 || !plain_launch)                                                                                                     \
-            hipExtLaunchKernelGGL((p2plane_fit_solve_kernel<F, NT>), dim3(nwg), dim3(NT), 0, stream, f0, f1, 0, scan.x.p, scan.y.p, scan.z.p, int(n),  \
+    hipExtLaunchKernelGGL((p2plane_fit_solve_kernel<F, NT>), dim3(nwg), dim3(NT), 0, stream, nullptr, nullptr, 0, scan.x.p, scan.y.p, scan.z.p, int(n), \
                        d_state.p, T0, (const float4*)d_nn.p, (const unsigned char*)d_nn_cnt.p, d_J.p, d_flag.p, d_partials_b.p,     \
-                       d_ticket.p, mb_dev, launch_word(), p.point_to_planar_thres, p.rotation_converge_thres, p.position_converge_thres, ticket_shards,  \
-                       (const unsigned*)(nn_ids_mode ? d_nn_ids.p : nullptr), (const float4*)g.pts, unsigned(im.d_pts.cap));  \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((p2plane_fit_solve_kernel<F, NT>), dim3(nwg), dim3(NT), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n),  \
-                       d_state.p, T0, (const float4*)d_nn.p, (const unsigned char*)d_nn_cnt.p, d_J.p, d_flag.p, d_partials_b.p,     \
-                       d_ticket.p, mb_dev, launch_word(), p.point_to_planar_thres, p.rotation_converge_thres, p.position_converge_thres, ticket_shards,  \
-                       (const unsigned*)(nn_ids_mode ? d_nn_ids.p : nullptr), (const float4*)g.pts, unsigned(im.d_pts.cap));  \
-    } while (0)
+                       d_ticket.p, mb_dev, launch_word(), p.point_to_planar_thres, p.rotation_converge_thres, p.position_converge_thres, \
+                       kTicketShards, (const unsigned*)d_nn_ids.p, (const float4*)g.pts, unsigned(im.d_pts.cap))
 #define FLS_FIT(F) do { if (fit_threads == 256) FLS_FIT_NT(F, 256); else FLS_FIT_NT(F, kFitThreads); } while (0)
             if (first) FLS_FIT(true); else FLS_FIT(false);
 #undef FLS_FIT_NT
 #undef FLS_FIT
         }, after_chunk);
         scan_in_staging = false;  // (the first launch left the device copy)
-        if (nn_ids_mode) nn_rows_current = false;  // the lists of every point with candidates are slots of the current image now
+        nn_rows_current = false;  // the lists of every point with candidates are slots of the current image now
         const Mailbox& mb = *mb_host;
         const int used = int(word & 0xffu);
         std::memcpy(T, mb.T, sizeof(double) * 16);
@@ -672,7 +617,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (has_converge && !p.is_localization_mode && update_map && !borrowed) {  // :205-206
-            if (spec_pending && nn_ids_mode) nn_rows_current = true;  // (the speculative decision launch turned the lists into rows)
+            if (spec_pending) nn_rows_current = true;  // (the speculative decision launch turned the lists into rows)
             const fls_status arc = add_cloud_impl(scan.host, /*from_resident_scan=*/true, /*pre_enqueued=*/spec_pending);
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
         } else if (spec_pending) {
@@ -866,7 +811,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     }
     void tune_lane(fls_matcher& l) override {
         auto& q = static_cast<P2PlaneIvoxMatcher&>(l);
-        q.use_dense = use_dense; q.variant = variant; q.balanced = balanced; q.xcd_chunk = xcd_chunk; q.prof_fit = prof_fit; q.ticket_shards = ticket_shards; q.plain_launch = plain_launch; q.nn_ids_mode = nn_ids_mode;
+        q.use_dense = use_dense;
     }
 
     fls_status fitness(float max_range, float* score) override {
@@ -895,7 +840,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         if (slot == 101) return n_full_rebuilds;  //                ... as full re-flatten + upload
         if (slot == 103) return n_device_updates;  //                ... by the device-side AddPoints
         if (slot == 104) return n_host_fallbacks;  //                batches the device refused (replayed on the host)
-        if (slot == 122) return n_fused_updates;    //                ... of which in the one-launch form
+        if (slot == 122) return 0;                  //                (the former one-launch form: the slot keeps its number)
         if (slot == 124) return n_speculative;      //                chains queued speculatively behind the iterations
         if (slot == 125) return n_speculative_skipped;  //            ... that the device skipped (the Match needed more iterations / did not converge)
         if (slot == 123) return n_short_updates;    //                ... of which in the short chain (five launches behind the decision)

@@ -33,8 +33,6 @@ struct IcpMatcher final : fls_matcher {
     DeviceCloudRing ring;    // the deque's clouds back to back on the device (opt-in path only)
     size_t local_map_n = 0;  // points of the local map (the host vector is not produced on the device path)
     bool have_map = false;
-    bool fused = true;  // FLS_ICP_FUSED=0: separate correspondence and fit launches
-    bool fused_tail = true;  // FLS_FUSED_TAIL=0: gn_solve_lu_kernel as its own launch
     DevBuf<unsigned> d_ticket;
     const IcpMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
     DevScan scan;
@@ -43,9 +41,7 @@ struct IcpMatcher final : fls_matcher {
     double final_T[16]{};
     bool have_final = false;
     DevBuf<int> d_nn_id;
-    DevBuf<unsigned char> d_eff, d_nn_cnt;
-    DevBuf<float4> d_nn_pts;
-    DevBuf<float> d_kth;
+    DevBuf<unsigned char> d_eff;
 
     fls_status init() {
         if (unset_f(p.map_cloud_filter_size) || unset_f(p.source_cloud_filter_size) || unset_d(p.point_search_thres) ||
@@ -56,8 +52,6 @@ struct IcpMatcher final : fls_matcher {
         init_common();
         src_filter.init();
         mapdev.init();
-        if (const char* e = std::getenv("FLS_ICP_FUSED")) fused = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_FUSED_TAIL")) fused_tail = std::atoi(e) != 0;
         d_ticket.reserve(kTicketWords);
         FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
         return FLS_OK;
@@ -77,7 +71,7 @@ struct IcpMatcher final : fls_matcher {
         // iterations), the two-stage search would run its second stage for most queries (measured 25 vs 13.5 us / launch)
         const float cell = cell_for_gate(p.point_search_thres);
         // opt-in device path: the deque is resident, VoxelGrid (Q13: always) + grid build never leave the device
-        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, false, local_map_n, stream)) {
+        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, local_map_n, stream)) {
             local_map.clear();
             have_map = true;
             return FLS_OK;
@@ -111,40 +105,24 @@ struct IcpMatcher final : fls_matcher {
         if (src_filter.raw_pending) src_filter.refilter(stream, scan, source);  // :57, on the resident raw scan
         if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
         const size_t n = scan.n;
-        const int nwg = int((n + 255) / 256);
         stats = fls_stats{};
         stats.n_source = int(n);
-        d_nn_pts.reserve(std::max<size_t>(n, 1));
-        d_nn_cnt.reserve(std::max<size_t>(n, 1));
-        d_kth.reserve(std::max<size_t>(n, 1));
         d_nn_id.reserve(std::max<size_t>(n, 1));
         d_eff.reserve(std::max<size_t>(n, 1));
         const CellGridDev cg = cell_dev(owner ? owner->grid : grid);
         const dim3 knn_grid_dim(unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64));  // multiple of 64: the XCD chunk re-map is a bijection
-        d_partials_b.reserve(size_t(std::max<unsigned>(knn_grid_dim.x, unsigned(std::max(nwg, 1)))) * kPartialStride);
+        d_partials_b.reserve(size_t(std::max(knn_grid_dim.x, 1u)) * kPartialStride);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
         const unsigned word = run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it], stream));
-            if (fused) {  // search + fit in one launch: one partial row per workgroup of the search grid
-                const LuTailArgs tail{0, p.rotation_converge_thres, p.position_converge_thres, 0, mb_dev, launch_word()};
-                hipLaunchKernelGGL(icp_knn_fit_kernel, knn_grid_dim, dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first,
-                                   T0, cg, float(p.point_search_thres), p.point_search_thres, d_nn_id.p, d_eff.p, d_partials_b.p,
-                                   fused_tail ? d_ticket.p : (unsigned*)nullptr, 8, tail);
-                if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
-                if (fused_tail) return;  // ... and the Gauss-Newton tail in its last workgroup: one launch per iteration
-                hipLaunchKernelGGL(gn_solve_lu_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_b.p,
-                                   int(knn_grid_dim.x), 0, p.rotation_converge_thres, p.position_converge_thres, 0, mb_dev, launch_word());
-                return;
-            }
-            hipLaunchKernelGGL((grid_knn_kernel<1, true>), knn_grid_dim, dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p,
-                               first, T0, cg, float(p.point_search_thres), d_nn_pts.p, d_nn_cnt.p, d_kth.p, (unsigned char*)nullptr);
+            // search + fit in one launch (one partial row per workgroup of the search grid) and the Gauss-Newton tail in its last
+            // workgroup: one launch per iteration
+            const LuTailArgs tail{0, p.rotation_converge_thres, p.position_converge_thres, 0, mb_dev, launch_word()};
+            hipLaunchKernelGGL(icp_knn_fit_kernel, knn_grid_dim, dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first,
+                               T0, cg, float(p.point_search_thres), p.point_search_thres, d_nn_id.p, d_eff.p, d_partials_b.p, d_ticket.p,
+                               kTicketShards, tail);
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
-            hipLaunchKernelGGL(icp_fit_kernel, dim3(nwg), dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p, int(n), d_state.p, first, T0,
-                               (const float4*)d_nn_pts.p, (const unsigned char*)d_nn_cnt.p, (const float*)d_kth.p, p.point_search_thres,
-                               d_nn_id.p, d_eff.p, d_partials_b.p);
-            hipLaunchKernelGGL(gn_solve_lu_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_b.p,
-                               nwg, 0, p.rotation_converge_thres, p.position_converge_thres, 0, mb_dev, launch_word());
         });
         const Mailbox& mb = *mb_host;
         std::memcpy(T, mb.T, sizeof(double) * 16);
@@ -235,19 +213,13 @@ struct FeatureDev {
     void launch(hipStream_t s, GnState* st, int first, const Pose16& T0, const CellGridDev& cg, float gate, double thres, double* partials) {
         const size_t n = scan.n;
         if (n == 0) return;
-        if (cg.rings == 1 && cg.by_id != nullptr) {  // gate-sized cells + the cloud by index: the one-stage 27-cell kernel
-            const dim3 g27(unsigned((((n * 4 + 255) / 256) + 63) / 64 * 64));
-            hipLaunchKernelGGL((grid_knn27_kernel<false>), g27, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, nn_pts.p, nn_cnt.p,
-                               kth.p, flag.p);
-        } else {
-            const dim3 knn_grid_dim(unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64));  // multiple of 64: the XCD chunk re-map is a bijection
-            if (std::isinf(gate))  // un-gated search (LoamPointToPlaneKdtree): the instantiation with the ring walk
-                hipLaunchKernelGGL((grid_knn_kernel<5, false, true>), knn_grid_dim, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, gate,
-                                   nn_pts.p, nn_cnt.p, kth.p, flag.p);
-            else
-                hipLaunchKernelGGL((grid_knn_kernel<5, false>), knn_grid_dim, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, gate,
-                                   nn_pts.p, nn_cnt.p, kth.p, flag.p);
-        }
+        const dim3 knn_grid_dim(unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64));  // multiple of 64: the XCD chunk re-map is a bijection
+        if (std::isinf(gate))  // un-gated search (LoamPointToPlaneKdtree): the instantiation with the ring walk
+            hipLaunchKernelGGL((grid_knn_kernel<5, false, true>), knn_grid_dim, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, gate,
+                               nn_pts.p, nn_cnt.p, kth.p, flag.p);
+        else
+            hipLaunchKernelGGL((grid_knn_kernel<5, false>), knn_grid_dim, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, gate,
+                               nn_pts.p, nn_cnt.p, kth.p, flag.p);
         hipLaunchKernelGGL((feature_fit_kernel<LINE>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st,
                            first, T0, (const float4*)nn_pts.p, (const unsigned char*)nn_cnt.p, (const float*)kth.p, gate, thres, nn_id.p,
                            cnt_out.p, J.p, flag.p, partials);
@@ -265,15 +237,9 @@ struct LoamFullMatcher final : fls_matcher {
     const LoamFullMatcher* owner = nullptr;  // batch lane: reads the owner's two map grids
     FeatureDev corner, planar;
     hm::KeyframeGate gate;
-    bool grid27 = false;     // FLS_GRID27=1: gate-sized cells + the one-stage 27-cell kernel (measured slower: A/B switch)
-    bool dual_launch = true;  // FLS_LOAM_DUAL=0: one correspondence + one fit launch per feature class
-    bool loam_fused_tail = true;  // FLS_FUSED_TAIL=0: gn_solve_loam_kernel as a launch of its own after the dual fit launch
     DevBuf<unsigned> d_loam_ticket;
 
     fls_status init() {
-        if (const char* e = std::getenv("FLS_GRID27")) grid27 = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_LOAM_DUAL")) dual_launch = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_FUSED_TAIL")) loam_fused_tail = std::atoi(e) != 0;
         if (unset_d(p.point_to_planar_thres) || unset_d(p.point_search_thres) || unset_d(p.line_ratio_thres) ||
             unset_d(p.position_converge_thres) || unset_d(p.rotation_converge_thres) || unset_d(p.rot_thre_add_cloud) ||
             unset_d(p.dist_thre_add_cloud))
@@ -294,20 +260,18 @@ struct LoamFullMatcher final : fls_matcher {
         if (dev) { ring_corner.push_back(corner_cloud, stream); ring_planar.push_back(planar_cloud, stream); }
         if (planar_deque.size() > p.local_planar_size) { planar_deque.pop_front(); if (dev) ring_planar.pop_front(); }
         if (corner_deque.size() > p.local_corner_size) { corner_deque.pop_front(); if (dev) ring_corner.pop_front(); }
-        // FLS_GRID27=1: gate-sized cells + the one-stage 27-cell kernel; default: half-gate cells + the two-stage kernel
-        const bool g27 = grid27;
-        const float cs = (g27 ? 1.0f : 0.5f) * cell_for_gate(p.point_search_thres);
-        const int rings = g27 ? 1 : kGridRings;
+        // half-gate cells + the two-stage kernel
+        const float cs = 0.5f * cell_for_gate(p.point_search_thres);
         // one feature class: [VoxelGrid of] the concatenated deque (the filter only once the deque holds more than 5 frames, :92-100)
         auto rebuild = [&](std::deque<std::vector<PtI>>& dq, DeviceCloudRing& ring, KdMapDevice& md, CellGridImage& grid, std::vector<PtI>& local, size_t& n_local,
                            float leaf) -> fls_status {
             const bool filter = dq.size() > 5;
-            if (dev && md.filter_and_build(grid, ring, filter, leaf, cs, rings, g27, n_local, stream)) { local.clear(); return FLS_OK; }
+            if (dev && md.filter_and_build(grid, ring, filter, leaf, cs, kGridRings, n_local, stream)) { local.clear(); return FLS_OK; }
             local.clear();
             for (const auto& c : dq) local.insert(local.end(), c.begin(), c.end());
             if (filter) { local = voxel_grid(local, leaf); ++md.host_filters; }
             n_local = local.size();
-            return md.build_from_host(grid, local, cs, stream, rings, g27);
+            return md.build_from_host(grid, local, cs, stream, kGridRings);
         };
         fls_status rc = rebuild(planar_deque, ring_planar, mapdev_planar, planar_grid, local_planar, local_planar_n, p.planar_voxel_filter_size);
         if (rc != FLS_OK) return rc;
@@ -341,28 +305,22 @@ struct LoamFullMatcher final : fls_matcher {
         std::memcpy(T0.m, T, sizeof(T0.m));
         const unsigned word = run_mailbox_loop(int(p.max_iterations), np + nc, [&](int it, int first) {
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it], stream));
-            if (dual_launch && nc != 0 && np != 0 && !(cgc.rings == 1 && cgc.by_id != nullptr)) {
-                // both classes in one correspondence launch and one fit launch (they are independent until the solve)
+            if (nc != 0 && np != 0) {
+                // both classes in one correspondence launch and one fit launch (they are independent until the solve), the Gauss-Newton
+                // tail in the fit launch's last workgroup
                 const int kc = int((((nc * 8 + 255) / 256) + 63) / 64 * 64), kp = int((((np * 8 + 255) / 256) + 63) / 64 * 64);
                 hipLaunchKernelGGL((grid_knn_dual_kernel<5, false>), dim3(unsigned(kc + kp)), dim3(256), 0, stream, (const GnState*)d_state.p, first, T0,
                                    corner.knn_args(cgc, gate_f), planar.knn_args(cgp, gate_f), kc);
-                const bool fuse = loam_fused_tail;
                 const LoamFusedTail tail{(const double*)d_partials_a.p, (const double*)d_partials_b.p, nbc, nbp, p.rotation_converge_thres, p.position_converge_thres,
-                                         fuse ? d_loam_ticket.p : nullptr, 8, mb_dev, launch_word()};
-                if (fuse)
-                    hipLaunchKernelGGL(feature_fit_dual_kernel<true>, dim3(unsigned(nbc + nbp)), dim3(256), 0, stream, (const GnState*)d_state.p, first, T0,
-                                       corner.fit_args(gate_f, p.line_ratio_thres, d_partials_a.p), planar.fit_args(gate_f, p.point_to_planar_thres, d_partials_b.p), nbc, tail);
-                else
-                    hipLaunchKernelGGL(feature_fit_dual_kernel<false>, dim3(unsigned(nbc + nbp)), dim3(256), 0, stream, (const GnState*)d_state.p, first, T0,
-                                       corner.fit_args(gate_f, p.line_ratio_thres, d_partials_a.p), planar.fit_args(gate_f, p.point_to_planar_thres, d_partials_b.p), nbc, tail);
-                if (fuse) {
-                    if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
-                    return;
-                }
-            } else {
-                corner.launch<true>(stream, d_state.p, first, T0, cgc, gate_f, p.line_ratio_thres, d_partials_a.p);
-                planar.launch<false>(stream, d_state.p, first, T0, cgp, gate_f, p.point_to_planar_thres, d_partials_b.p);
+                                         d_loam_ticket.p, kTicketShards, mb_dev, launch_word()};
+                hipLaunchKernelGGL(feature_fit_dual_kernel, dim3(unsigned(nbc + nbp)), dim3(256), 0, stream, (const GnState*)d_state.p, first, T0,
+                                   corner.fit_args(gate_f, p.line_ratio_thres, d_partials_a.p), planar.fit_args(gate_f, p.point_to_planar_thres, d_partials_b.p), nbc, tail);
+                if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
+                return;
             }
+            // one feature class is empty: one correspondence + one fit launch per class, then the tail
+            corner.launch<true>(stream, d_state.p, first, T0, cgc, gate_f, p.line_ratio_thres, d_partials_a.p);
+            planar.launch<false>(stream, d_state.p, first, T0, cgp, gate_f, p.point_to_planar_thres, d_partials_b.p);
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
             hipLaunchKernelGGL(gn_solve_loam_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_a.p,
                                nbc, (const double*)d_partials_b.p, nbp, p.rotation_converge_thres, p.position_converge_thres, mb_dev, launch_word());
@@ -444,7 +402,7 @@ struct P2PlaneKdMatcher final : fls_matcher {
         }
         // un-gated 5-NN: ring search with a cell of two map leaves (>= 1 point per leaf after VoxelGrid)
         const float cell = std::max(2.0f * p.map_cloud_filter_size, 0.5f);
-        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, false, local_map_n, stream)) {
+        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, local_map_n, stream)) {
             local_map.clear();
             have_map = true;
             return FLS_OK;
