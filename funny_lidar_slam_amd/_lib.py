@@ -23,6 +23,11 @@ EXPORTED_SYMBOLS = [
     # include/fls_features.h
     "fls_features_create", "fls_features_destroy", "fls_features_project", "fls_features_extract", "fls_features_get", "fls_features_get_time",
 ]
+# every symbol include/fls_preprocess.h declares (revision 8)
+PREPROCESS_SYMBOLS = [
+    "fls_preprocess_create", "fls_preprocess_destroy", "fls_preprocess_scan", "fls_preprocess_get", "fls_preprocess_get_time",
+    "fls_features_project_deskew",
+]
 
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
@@ -105,6 +110,31 @@ class PointLayout(C.Structure):
     """fls_point_layout (include/fls_features.h)."""
 
     _fields_ = [("stride_bytes", C.c_uint32), ("xyz_offset", C.c_uint32), ("intensity_offset", C.c_uint32), ("ring_offset", C.c_uint32)]
+
+
+class RawLayout(C.Structure):
+    """fls_raw_layout (include/fls_preprocess.h)."""
+
+    _fields_ = [("stride_bytes", C.c_uint32), ("xyz_offset", C.c_uint32), ("intensity_offset", C.c_uint32), ("ring_offset", C.c_uint32),
+                ("ring_bytes", C.c_uint32), ("time_offset", C.c_uint32)]
+
+
+class PreprocessParams(C.Structure):
+    """fls_preprocess_params (include/fls_preprocess.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("lidar_point_jump_span", C.c_int32), ("min_distance", C.c_float), ("max_distance", C.c_float),
+                ("planar_voxel_filter_size", C.c_float), ("reserved", C.c_float), ("T_lidar_to_imu", C.c_double * 16)]
+
+
+class PreprocessResult(C.Structure):
+    """fls_preprocess_result (include/fls_preprocess.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("imu_status", C.c_int32), ("cloud_start_us", C.c_uint64), ("cloud_end_us", C.c_uint64),
+                ("n_raw", C.c_uint64), ("n_ordered", C.c_uint64), ("n_planar", C.c_uint64), ("n_planar_filtered", C.c_uint64),
+                ("n_segment", C.c_uint64), ("filter_on_device", C.c_int32), ("reserved", C.c_int32)]
+
+
+FLS_IMU_OK, FLS_IMU_DROP, FLS_IMU_WAIT, FLS_IMU_EMPTY_SEGMENT, FLS_IMU_EMPTY_CLOUD = range(5)
 
 
 def build(force: bool = False) -> str:
@@ -213,6 +243,20 @@ def lib():
         L.fls_features_get.argtypes = [hp, C.c_int, C.c_void_p, C.c_size_t]
         L.fls_features_get_time.restype = C.c_int
         L.fls_features_get_time.argtypes = [hp, dp, dp]
+        u64p = C.POINTER(C.c_uint64)
+        L.fls_preprocess_create.restype = C.c_int
+        L.fls_preprocess_create.argtypes = [C.POINTER(PreprocessParams), C.c_int, C.POINTER(hp)]
+        L.fls_preprocess_destroy.restype = None
+        L.fls_preprocess_destroy.argtypes = [hp]
+        L.fls_preprocess_scan.restype = C.c_int
+        L.fls_preprocess_scan.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(RawLayout), C.c_uint64, u64p, dp, C.c_size_t, C.POINTER(PreprocessResult)]
+        L.fls_preprocess_get.restype = C.c_size_t
+        L.fls_preprocess_get.argtypes = [hp, C.c_int, C.c_void_p, C.c_size_t]
+        L.fls_preprocess_get_time.restype = C.c_int
+        L.fls_preprocess_get_time.argtypes = [hp, dp, dp]
+        L.fls_features_project_deskew.restype = C.c_int
+        L.fls_features_project_deskew.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(RawLayout), C.c_uint64, u64p, dp, C.c_size_t, dp,
+                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

@@ -5,6 +5,9 @@
 #include "kernels_features.hpp"
 #include "../../include/fls_features.h"
 #include <limits>
+#include <memory>
+
+namespace fls { struct DeskewScratch; }  // preprocess_host.hpp: the buffers of fls_features_project_deskew
 
 struct fls_features {
     fls_feature_params p{};
@@ -32,6 +35,7 @@ struct fls_features {
     std::vector<unsigned char> valid_pre, valid_post, is_corner;
     std::vector<fls::PtI> corner, planar, corner_f, planar_f;
     std::vector<int> h_cidx, h_ccnt, h_pidx, h_pcnt;
+    std::shared_ptr<fls::DeskewScratch> deskew;  // created by the first fls_features_project_deskew
 
     ~fls_features() {
         for (auto e : ev) if (e) (void)hipEventDestroy(e);

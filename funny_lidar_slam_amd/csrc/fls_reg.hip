@@ -7,6 +7,7 @@
 #include "matchers_kd.hpp"
 #include "matcher_ndt.hpp"
 #include "features_host.hpp"
+#include "preprocess_host.hpp"
 #include "loop_closure.hpp"
 #include "replicas.hpp"
 #include <new>
@@ -546,6 +547,64 @@ fls_status fls_features_get_time(fls_features_handle h, double* project_ms, doub
     if (project_ms) *project_ms = h->project_ms;
     if (extract_ms) *extract_ms = h->extract_ms;
     return FLS_OK;
+}
+
+// ---- per-scan preprocessing: IMU de-skew, range gate, subsample, planar VoxelGrid (include/fls_preprocess.h) --------------------
+fls_status fls_preprocess_create(const fls_preprocess_params* params, int device_id, fls_preprocess_handle* out) {
+    if (!out) return FLS_ERR_INVALID;
+    *out = nullptr;
+    if (!params || fls_preprocess::check(*params) != FLS_OK) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device_id < 0 || device_id >= n) return FLS_ERR_DEVICE;
+        hipDeviceProp_t prop;
+        FLS_HIP(hipGetDeviceProperties(&prop, device_id));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLS_ERR_DEVICE;
+        std::unique_ptr<fls_preprocess> f(new fls_preprocess());
+        f->p = *params;
+        f->device = device_id;
+        const fls_status rc = f->init();
+        if (rc != FLS_OK) return rc;
+        *out = f.release();
+        return FLS_OK;
+    });
+}
+
+void fls_preprocess_destroy(fls_preprocess_handle h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+fls_status fls_preprocess_scan(fls_preprocess_handle h, const void* raw, size_t n, const fls_raw_layout* layout, uint64_t stamp_us, const uint64_t* imu_t_us,
+                               const double* imu_q_xyzw, size_t n_imu, fls_preprocess_result* result) {
+    if (!h || !layout || (!raw && n) || (result && result->struct_size != sizeof(fls_preprocess_result))) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->scan(raw, n, *layout, stamp_us, imu_t_us, imu_q_xyzw, n_imu, result);
+    });
+}
+
+size_t fls_preprocess_get(fls_preprocess_handle h, int what, void* out, size_t cap_elems) {
+    if (!h) return 0;
+    return h->get(what, out, cap_elems);
+}
+
+fls_status fls_preprocess_get_time(fls_preprocess_handle h, double* deskew_ms, double* filter_ms) {
+    if (!h) return FLS_ERR_INVALID;
+    if (deskew_ms) *deskew_ms = h->deskew_ms;
+    if (filter_ms) *filter_ms = h->filter_ms;
+    return FLS_OK;
+}
+
+fls_status fls_features_project_deskew(fls_features_handle h, const void* raw, size_t n, const fls_raw_layout* layout, uint64_t stamp_us,
+                                       const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, const double T_lidar_to_imu[16], size_t* n_ordered,
+                                       int* imu_status) {
+    if (!h || !layout || (!raw && n) || !T_lidar_to_imu) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return features_project_deskew(*h, raw, n, *layout, stamp_us, imu_t_us, imu_q_xyzw, n_imu, T_lidar_to_imu, n_ordered, imu_status);
+    });
 }
 
 }  // extern "C"

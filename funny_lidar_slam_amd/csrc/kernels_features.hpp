@@ -128,7 +128,7 @@ feat_compact_kernel(const unsigned char* __restrict__ raw, const RawLayoutDev L,
             int ring;
             raw_point(raw, L, own, x, y, z, ring);
             const float it = *(const float*)(raw + (size_t)own * L.stride + L.off_i);
-            ordered[i] = make_float4(x, y, z, it);  // identity de-skew (:101-111)
+            ordered[i] = make_float4(x, y, z, it);  // identity de-skew (:101-111); the IMU de-skew: kernels_deskew.hpp
             depth[i] = depth_of(x, y, z);
             colv[i] = col;
             raw_index[i] = (int)own;

@@ -1,0 +1,351 @@
+// preprocess_host.hpp -- host side of include/fls_preprocess.h: the per-scan IMU segment (GetDataSegment, slerp), SetRefTime, the
+// staging of the raw cloud, the launches of kernels_deskew.hpp, the planar VoxelGrid; and fls_features_project_deskew.
+#pragma once
+#include "features_host.hpp"
+#include "device_voxelgrid.hpp"
+#include "kernels_deskew.hpp"
+#include "../../include/fls_preprocess.h"
+#include <cmath>
+#include <limits>
+
+namespace fls {
+
+// MotionInterpolator::InterpolateQuaternionSlerp(q0, q1, t0, t1, t) (motion_interpolator.h:108-147), C library acos / sin
+inline void deskew_slerp_host(const double* a, const double* b, const uint64_t t0, const uint64_t t1, const uint64_t t, double* q) {
+    const double tt = (double)(t - t0) / (double)(t1 - t0);
+    const double one = 1.0 - std::numeric_limits<double>::epsilon();
+    const double d = (a[0] * b[0] + a[2] * b[2]) + (a[1] * b[1] + a[3] * b[3]);
+    const double ad = std::fabs(d);
+    double s0, s1;
+    if (ad >= one) {
+        s0 = 1.0 - tt;
+        s1 = tt;
+    } else {
+        const double th = std::acos(ad), st = std::sin(th);
+        s0 = std::sin((1.0 - tt) * th) / st;
+        s1 = std::sin(tt * th) / st;
+    }
+    if (d < 0.0) s1 = -s1;
+    for (int c = 0; c < 4; ++c) q[c] = s0 * a[c] + s1 * b[c];
+}
+
+// rightmost sample with ts <= t (the reference's backward scan; the caller guarantees ts[0] <= t)
+inline size_t deskew_rightmost_le(const uint64_t* ts, const size_t n, const uint64_t t) {
+    return size_t(std::upper_bound(ts, ts + n, t) - ts) - 1;
+}
+
+// IMUDataSearcher::GetDataSegment(start, end) on t_us[n] (strictly increasing, ts[0] <= start, end <= ts[n-1]).  start >= end: empty.
+// Where start and end share one bracket sample the reference's middle loop runs past the deque's end; here the segment is the two ends.
+inline void deskew_segment(const uint64_t* ts, const double* qs, const size_t n, const uint64_t start, const uint64_t end, std::vector<uint64_t>& st,
+                           std::vector<double>& sq) {
+    st.clear();
+    sq.clear();
+    if (start >= end) return;
+    double ql[4], qr[4];
+    size_t lb, rb;
+    if (ts[0] == start) { lb = 0; std::memcpy(ql, qs, sizeof ql); }
+    else { lb = deskew_rightmost_le(ts, n, start); deskew_slerp_host(qs + 4 * lb, qs + 4 * (lb + 1), ts[lb], ts[lb + 1], start, ql); }
+    if (ts[n - 1] == end) { rb = n - 1; std::memcpy(qr, qs + 4 * (n - 1), sizeof qr); }
+    else { rb = deskew_rightmost_le(ts, n, end); deskew_slerp_host(qs + 4 * rb, qs + 4 * (rb + 1), ts[rb], ts[rb + 1], end, qr); }
+    st.push_back(start);
+    sq.insert(sq.end(), ql, ql + 4);
+    for (size_t k = lb + 1; k < rb; ++k) { st.push_back(ts[k]); sq.insert(sq.end(), qs + 4 * k, qs + 4 * k + 4); }  // strictly between the brackets
+    st.push_back(end);
+    sq.insert(sq.end(), qr, qr + 4);
+}
+
+// one scan's preparation, shared by fls_preprocess_scan and fls_features_project_deskew: validation, time range, IMU status, segment,
+// q_ref_inv, and the raw cloud + segment staged in pinned memory for ONE host-to-device copy
+struct DeskewScratch {
+    PinnedBuf<unsigned char> stage;
+    DevBuf<unsigned char> d_in;  // raw bytes | segment t (u64) | segment q (4 doubles)
+    DevBuf<float4> d_corr;
+    DevBuf<unsigned char> d_flag;
+    DevBuf<uint2> d_blk, d_off;
+    std::vector<uint64_t> seg_t;
+    std::vector<double> seg_q;
+    DeskewRawDev L{};
+    DeskewParamsDev P{};
+    uint64_t start = 0, end = 0;
+    int imu_status = FLS_IMU_EMPTY_CLOUD;
+    size_t n = 0, raw_bytes = 0, seg_off = 0;
+
+    static bool layout_ok(const fls_raw_layout& l, bool need_ring) {
+        if (l.stride_bytes < 16 || (l.stride_bytes & 3u) || (l.xyz_offset & 3u) || (l.intensity_offset & 3u) || (l.time_offset & 3u)) return false;
+        if (l.xyz_offset + 12 > l.stride_bytes || l.intensity_offset + 4 > l.stride_bytes || l.time_offset + 4 > l.stride_bytes) return false;
+        if (l.ring_bytes > 2 || (need_ring && l.ring_bytes == 0)) return false;
+        if (l.ring_bytes && (l.ring_offset + l.ring_bytes > l.stride_bytes || (l.ring_bytes == 2 && (l.ring_offset & 1u)))) return false;
+        return true;
+    }
+
+    // FLS_OK: imu_status set; with FLS_IMU_OK the stage holds raw + segment and P / L are ready
+    fls_status prepare(const void* raw, size_t n_, const fls_raw_layout& l, uint64_t stamp, const uint64_t* it, const double* iq, size_t n_imu,
+                       const double* T, bool need_ring) {
+        if (!layout_ok(l, need_ring) || (!raw && n_) || !it || !iq || !T || n_imu < 2 || n_ > 0x7FFFFFF0ull) return FLS_ERR_INVALID;
+        for (size_t k = 1; k < n_imu; ++k)
+            if (!(it[k] > it[k - 1])) return FLS_ERR_INVALID;  // the searcher's deque is in time order (CHECKs of the reference)
+        n = n_;
+        L = DeskewRawDev{l.stride_bytes, l.xyz_offset, l.intensity_offset, l.ring_offset, l.ring_bytes, l.time_offset};
+        seg_t.clear();
+        seg_q.clear();
+        start = end = 0;
+        if (n == 0) { imu_status = FLS_IMU_EMPTY_CLOUD; return FLS_OK; }
+        raw_bytes = n * l.stride_bytes;
+        seg_off = (raw_bytes + 15) & ~size_t(15);
+        stage.reserve(seg_off + size_t(kDeskewMaxSeg) * 40);
+        std::memcpy(stage.p, raw, raw_bytes);
+        // GetLidarPointMinMaxOffsetTime (:554-570)
+        const unsigned char* s = stage.p + l.time_offset;
+        float mn, mx;
+        std::memcpy(&mn, s, 4);
+        mx = mn;
+        for (size_t k = 0; k < n; ++k) {
+            float v;
+            std::memcpy(&v, s + k * l.stride_bytes, 4);
+            if (!std::isfinite(v)) return FLS_ERR_INVALID;
+            if (v < mn) mn = v;
+            if (v > mx) mx = v;
+        }
+        start = (uint64_t)((int64_t)stamp + deskew_trunc_i64((double)mn * 1.0e6));  // (:89-96)
+        end = (uint64_t)((int64_t)stamp + deskew_trunc_i64((double)mx * 1.0e6));
+        if (stamp < start) start = stamp;  // (:100-104)
+        else if (stamp > end) end = stamp;
+        if (it[0] > start) { imu_status = FLS_IMU_DROP; return FLS_OK; }        // (:124-133)
+        if (it[n_imu - 1] < end) { imu_status = FLS_IMU_WAIT; return FLS_OK; }  // (:136-141)
+        deskew_segment(it, iq, n_imu, start, end, seg_t, seg_q);
+        if (seg_t.empty()) { imu_status = FLS_IMU_EMPTY_SEGMENT; return FLS_OK; }
+        if (seg_t.size() > size_t(kDeskewMaxSeg)) return FLS_ERR_INVALID;
+        imu_status = FLS_IMU_OK;
+        std::memcpy(stage.p + seg_off, seg_t.data(), seg_t.size() * 8);
+        std::memcpy(stage.p + seg_off + seg_t.size() * 8, seg_q.data(), seg_q.size() * 8);
+        // SetRefTime(stamp): the stamp lies inside [start, end], so the bracket exists
+        P = DeskewParamsDev{};
+        P.n = unsigned(n);
+        P.n_seg = int(seg_t.size());
+        P.ref_us = stamp;
+        const int lr = deskew_bracket((const unsigned long long*)seg_t.data(), P.n_seg, stamp);
+        const uint64_t tl = seg_t[size_t(lr)], tr = seg_t[size_t(lr) + 1];
+        double qref[4];
+        deskew_nlerp(seg_q.data() + 4 * lr, seg_q.data() + 4 * (lr + 1), (double)(stamp - tl) / (double)(tr - tl), qref);
+        deskew_inverse(qref, P.qri);
+        for (int i = 0; i < 3; ++i) {
+            for (int k = 0; k < 3; ++k) P.R[3 * i + k] = T[4 * k + i];
+            P.t[i] = T[12 + i];
+        }
+        return FLS_OK;
+    }
+
+    // H2D of the stage, pass 1 (gate + de-skew of every point); returns the block count
+    unsigned upload_and_deskew(hipStream_t s, bool gate, float min_d, float max_d, unsigned span) {
+        P.gate = gate ? 1 : 0;
+        P.min_dist = min_d;
+        P.max_dist = max_d;
+        P.jump_span = span;
+        const size_t bytes = seg_off + seg_t.size() * 40;
+        const unsigned nb = unsigned((n + kDeskewThreads - 1) / kDeskewThreads);
+        d_in.reserve(bytes);
+        d_corr.reserve(n);
+        d_flag.reserve(n);
+        d_blk.reserve(nb);
+        d_off.reserve(nb);
+        FLS_HIP(hipMemcpyAsync(d_in.p, stage.p, bytes, hipMemcpyHostToDevice, s));
+        const auto* st = (const unsigned long long*)(d_in.p + seg_off);
+        const auto* sq = (const double*)(d_in.p + seg_off + seg_t.size() * 8);
+        hipLaunchKernelGGL(deskew_point_kernel, dim3(nb), dim3(kDeskewThreads), seg_t.size() * 40, s, d_in.p, L, P, st, sq, d_corr.p, d_flag.p, d_blk.p);
+        FLS_HIP(hipGetLastError());
+        return nb;
+    }
+};
+
+}  // namespace fls
+
+struct fls_preprocess {
+    fls_preprocess_params p{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    fls::DeskewScratch ds;
+    fls::DeviceVoxelGrid vg;
+    fls::DevBuf<float4> d_ordered;
+    fls::DevBuf<int> d_ordered_idx;
+    fls::DevBuf<float> d_planar;  // x | y | z | i, row stride = capacity
+    fls::DevBuf<unsigned> d_tot;
+    fls::PinnedBuf<unsigned> h_tot;
+    std::vector<fls::PtI> ordered, planar, planar_f;
+    std::vector<int> ordered_idx;
+    std::vector<float> tmp;
+    double deskew_ms = 0.0, filter_ms = 0.0;
+    bool filter_on_device = false;
+
+    ~fls_preprocess() {
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    }
+
+    static fls_status check(const fls_preprocess_params& q) {
+        if (q.struct_size != sizeof(fls_preprocess_params) || q.lidar_point_jump_span < 1 || !(q.planar_voxel_filter_size >= 0.f)) return FLS_ERR_INVALID;
+        for (double v : q.T_lidar_to_imu) if (!std::isfinite(v)) return FLS_ERR_INVALID;
+        return FLS_OK;
+    }
+
+    fls_status init() {
+        if (check(p) != FLS_OK) return FLS_ERR_INVALID;
+        FLS_HIP(hipSetDevice(device));
+        FLS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (auto& e : ev) FLS_HIP(hipEventCreate(&e));
+        d_tot.reserve(2);
+        h_tot.reserve(2);
+        return FLS_OK;
+    }
+
+    void clear() {
+        ordered.clear(); planar.clear(); planar_f.clear(); ordered_idx.clear();
+        deskew_ms = filter_ms = 0.0;
+        filter_on_device = false;
+    }
+
+    fls_status scan(const void* raw, size_t n, const fls_raw_layout& L, uint64_t stamp, const uint64_t* it, const double* iq, size_t n_imu,
+                    fls_preprocess_result* r) {
+        clear();
+        const fls_status rc = ds.prepare(raw, n, L, stamp, it, iq, n_imu, p.T_lidar_to_imu, false);
+        if (rc != FLS_OK) return rc;
+        auto report = [&](fls_status s) {
+            if (r) {
+                r->imu_status = ds.imu_status;
+                r->cloud_start_us = ds.start; r->cloud_end_us = ds.end;
+                r->n_raw = n; r->n_ordered = ordered.size(); r->n_planar = planar.size(); r->n_planar_filtered = planar_f.size();
+                r->n_segment = ds.seg_t.size();
+                r->filter_on_device = filter_on_device ? 1 : 0;
+                r->reserved = 0;
+            }
+            return s;
+        };
+        if (ds.imu_status == FLS_IMU_DROP || ds.imu_status == FLS_IMU_WAIT) return report(FLS_ERR_STATE);
+        if (ds.imu_status != FLS_IMU_OK) return report(FLS_OK);
+        const size_t cap = n;
+        d_ordered.reserve(n); d_ordered_idx.reserve(n); d_planar.reserve(4 * cap);
+        FLS_HIP(hipEventRecord(ev[0], stream));
+        const unsigned nb = ds.upload_and_deskew(stream, true, p.min_distance, p.max_distance, unsigned(p.lidar_point_jump_span));
+        hipLaunchKernelGGL(fls::deskew_scan_kernel, dim3(1), dim3(1024), 0, stream, ds.d_blk.p, nb, ds.d_off.p, d_tot.p);
+        hipLaunchKernelGGL(fls::deskew_write_kernel, dim3(nb), dim3(fls::kDeskewThreads), 0, stream, ds.d_flag.p, ds.d_corr.p, unsigned(n), ds.d_off.p,
+                           d_ordered.p, d_ordered_idx.p, d_planar.p, cap);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipEventRecord(ev[1], stream));
+        FLS_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        const size_t no = h_tot.p[0], np = h_tot.p[1];
+        ordered.resize(no); ordered_idx.resize(no); planar.resize(np);
+        if (no) {
+            FLS_HIP(hipMemcpyAsync(ordered.data(), d_ordered.p, no * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipMemcpyAsync(ordered_idx.data(), d_ordered_idx.p, no * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (np) {
+            tmp.resize(4 * np);
+            for (int a = 0; a < 4; ++a)
+                FLS_HIP(hipMemcpyAsync(tmp.data() + size_t(a) * np, d_planar.p + size_t(a) * cap, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        bool vg_ok = false;
+        if (np && p.planar_voxel_filter_size > 0.f) {
+            FLS_HIP(hipEventRecord(ev[2], stream));
+            vg_ok = fls::device_voxelgrid_mode() != 0 &&
+                    vg.run(d_planar.p, d_planar.p + cap, d_planar.p + 2 * cap, d_planar.p + 3 * cap, np, p.planar_voxel_filter_size, stream);
+            FLS_HIP(hipEventRecord(ev[3], stream));
+        }
+        FLS_HIP(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < np; ++i) planar[i] = fls::PtI{tmp[i], tmp[np + i], tmp[2 * np + i], tmp[3 * np + i]};
+        float ms = 0.f;
+        FLS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        deskew_ms = ms;
+        if (np && p.planar_voxel_filter_size > 0.f) {
+            FLS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+            filter_ms = ms;
+            if (vg_ok) {
+                std::vector<float> t2;
+                planar_f = vg.download(stream, t2);
+                filter_on_device = true;
+            } else {
+                planar_f = fls::voxel_grid_strided(&planar[0].x, np, 4, p.planar_voxel_filter_size);  // the exact host filter (SourceFilter's fallback)
+            }
+        }
+        return report(FLS_OK);
+    }
+
+    template <class T>
+    static size_t copy_out(const T* v, size_t n, void* out, size_t cap) {
+        if (out && n) std::memcpy(out, v, std::min(cap, n) * sizeof(T));
+        return n;
+    }
+    size_t get(int what, void* out, size_t cap) {
+        switch (what) {
+            case FLS_PRE_ORDERED: return copy_out(ordered.data(), ordered.size(), out, cap);
+            case FLS_PRE_ORDERED_INDEX: return copy_out(ordered_idx.data(), ordered_idx.size(), out, cap);
+            case FLS_PRE_PLANAR: return copy_out(planar.data(), planar.size(), out, cap);
+            case FLS_PRE_PLANAR_FILTERED: return copy_out(planar_f.data(), planar_f.size(), out, cap);
+            case FLS_PRE_SEGMENT_T: return copy_out(ds.seg_t.data(), ds.seg_t.size(), out, cap);
+            case FLS_PRE_SEGMENT_Q: {
+                const size_t m = ds.seg_t.size();
+                if (out && m) std::memcpy(out, ds.seg_q.data(), std::min(cap, m) * 4 * sizeof(double));
+                return m;
+            }
+            default: return 0;
+        }
+    }
+};
+
+// fls_features_project_deskew: pass 1 without the gate (every point's ProcessPoint), then the projection where only points whose
+// de-skew succeeded compete for their cell, the usual ring compaction, and the corrected xyz into the ordered cloud
+inline fls_status features_project_deskew(fls_features& f, const void* raw, size_t n, const fls_raw_layout& L, uint64_t stamp, const uint64_t* it,
+                                          const double* iq, size_t n_imu, const double* T, size_t* n_ordered, int* imu_status) {
+    if (!f.deskew) f.deskew = std::make_shared<fls::DeskewScratch>();
+    fls::DeskewScratch& ds = *f.deskew;
+    const fls_status rc = ds.prepare(raw, n, L, stamp, it, iq, n_imu, T, true);
+    if (rc != FLS_OK) return rc;
+    if (imu_status) *imu_status = ds.imu_status;
+    f.projected = f.extracted = false;
+    f.have_raw_index = f.have_intro = false;
+    f.N = 0;
+    f.ordered.clear(); f.depth.clear(); f.col.clear();
+    if (n_ordered) *n_ordered = 0;
+    if (ds.imu_status == FLS_IMU_DROP || ds.imu_status == FLS_IMU_WAIT) return FLS_ERR_STATE;
+    f.n_raw = n;
+    const fls::FeatParamsDev& pd = f.pd;
+    const size_t cells = size_t(pd.rows) * size_t(pd.cols);
+    // feat_compact_kernel reads the ring field as a uint16 it does not use: point it at the xyz (in bounds for any ring width)
+    f.layout = fls::RawLayoutDev{L.stride_bytes, L.xyz_offset, L.intensity_offset, L.xyz_offset};
+    FLS_HIP(hipEventRecord(f.ev[0], f.stream));
+    FLS_HIP(hipMemsetAsync(f.d_owner.p, 0xFF, cells * sizeof(unsigned), f.stream));
+    if (ds.imu_status == FLS_IMU_OK) {
+        ds.upload_and_deskew(f.stream, false, pd.min_dist, pd.max_dist, 1u);
+        hipLaunchKernelGGL(fls::feat_project_deskew_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, f.stream, ds.d_in.p, unsigned(n), ds.L, pd,
+                           ds.d_flag.p, f.d_owner.p);
+    }
+    // (EMPTY_SEGMENT / EMPTY_CLOUD: every ProcessPoint fails, no cell is claimed; the compaction runs on the empty image)
+    const unsigned char* raw_dev = ds.imu_status == FLS_IMU_OK ? ds.d_in.p : nullptr;
+    hipLaunchKernelGGL(fls::feat_count_kernel, dim3(unsigned(pd.rows)), dim3(256), 0, f.stream, f.d_owner.p, pd, f.d_row_count.p);
+    hipLaunchKernelGGL(fls::feat_compact_kernel, dim3(unsigned(pd.rows)), dim3(256), 0, f.stream, raw_dev, f.layout, f.d_owner.p, pd, f.d_row_count.p,
+                       f.d_ordered.p, f.d_depth.p, f.d_col.p, f.d_raw_index.p, f.d_valid.p, f.d_row_start.p, f.d_row_end.p, f.d_n.p);
+    if (ds.imu_status == FLS_IMU_OK)
+        hipLaunchKernelGGL(fls::deskew_apply_kernel, dim3(unsigned((cells + 255) / 256)), dim3(256), 0, f.stream, f.d_n.p, f.d_raw_index.p, ds.d_corr.p,
+                           f.d_ordered.p);
+    FLS_HIP(hipGetLastError());
+    FLS_HIP(hipEventRecord(f.ev[1], f.stream));
+    FLS_HIP(hipMemcpyAsync(&f.N, f.d_n.p, sizeof(int), hipMemcpyDeviceToHost, f.stream));
+    f.row_start.resize(size_t(pd.rows)); f.row_end.resize(size_t(pd.rows));
+    FLS_HIP(hipMemcpyAsync(f.row_start.data(), f.d_row_start.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, f.stream));
+    FLS_HIP(hipMemcpyAsync(f.row_end.data(), f.d_row_end.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, f.stream));
+    FLS_HIP(hipStreamSynchronize(f.stream));
+    const size_t m = size_t(f.N);
+    f.ordered.resize(m); f.depth.resize(m); f.col.resize(m);
+    if (m) {
+        FLS_HIP(hipMemcpyAsync(f.ordered.data(), f.d_ordered.p, m * sizeof(float4), hipMemcpyDeviceToHost, f.stream));
+        FLS_HIP(hipMemcpyAsync(f.depth.data(), f.d_depth.p, m * sizeof(float), hipMemcpyDeviceToHost, f.stream));
+        FLS_HIP(hipMemcpyAsync(f.col.data(), f.d_col.p, m * sizeof(int), hipMemcpyDeviceToHost, f.stream));
+        FLS_HIP(hipStreamSynchronize(f.stream));
+    }
+    float ms = 0.f;
+    FLS_HIP(hipEventElapsedTime(&ms, f.ev[0], f.ev[1]));
+    f.project_ms = ms;
+    f.projected = true;
+    if (n_ordered) *n_ordered = m;
+    return FLS_OK;
+}

@@ -5,7 +5,8 @@ same PointcloudCluster fields), bound to include/fls_features.h through ctypes.
     loam::FeatureExtractor      include/loam/feature_extractor.h:15-45,    src/loam/feature_extractor.cpp:36-222
 
 The projection stays resident on the device between `Project` and `ExtractFeatures` (the cluster carries the handle).
-De-skew is outside this library (pass corrected points).  No CPU fallback.
+`project` takes corrected points (or raw ones from a static sensor); `project_deskew` de-skews with an IMU trace on the device
+(include/fls_preprocess.h).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -49,6 +50,26 @@ class FeatureFrontEnd:
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_features_project")
         return int(n.value)
+
+    def project_deskew(self, raw: np.ndarray, stamp_us: int, imu_t_us, imu_q_xyzw, T_lidar_to_imu=None):
+        """PointcloudProjector::Project with the IMU de-skew (pointcloud_projector.cpp:58-112): a point claims its cell only when its
+        ProcessPoint succeeds and the ordered cloud stores the corrected xyz.  Returns (n_ordered, imu_status); drop / wait raise FlsError
+        (FLS_ERR_STATE) with the status in its `imu_status` attribute."""
+        from .preprocess import IMU_STATUS, imu_arrays, raw_layout
+        raw = np.ascontiguousarray(raw)
+        lay = raw_layout(raw.dtype, need_ring=True)
+        t, q = imu_arrays(imu_t_us, imu_q_xyzw)
+        T = np.eye(4) if T_lidar_to_imu is None else np.asarray(T_lidar_to_imu, dtype=np.float64)
+        Tc = np.ascontiguousarray(T.reshape(4, 4).T.reshape(-1))  # column-major
+        n, st = C.c_size_t(), C.c_int(-1)
+        rc = _lib.lib().fls_features_project_deskew(self._h, raw.ctypes.data, raw.shape[0], C.byref(lay), int(stamp_us),
+                                                    t.ctypes.data_as(C.POINTER(C.c_uint64)), q.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0],
+                                                    Tc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), C.byref(st))
+        if rc != _lib.FLS_OK:
+            e = FlsError(rc, "fls_features_project_deskew")
+            e.imu_status = IMU_STATUS.get(st.value)
+            raise e
+        return int(n.value), IMU_STATUS[st.value]
 
     def extract(self):
         nc, npl = C.c_size_t(), C.c_size_t()

@@ -349,3 +349,55 @@ def make_config(config_id: int, job: int = 0, scale: float = 1.0, with_map: bool
             out["corner_map"] = sample_edges(scene, max(2000, int(100000 * scale)), rng_for(config_id, 0, salt=2))
         out["scan"] = out["scan"][::2].copy()  # 57,600 surf points
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# IMU traces and sweep motion (IMU de-skew, include/fls_preprocess.h)
+# ---------------------------------------------------------------------------------------------
+def _qmul_xyzw(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    ax, ay, az, aw = np.moveaxis(a, -1, 0)
+    bx, by, bz, bw = np.moveaxis(b, -1, 0)
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+
+def imu_orientation(t_s, yaw_rate: float = np.deg2rad(60.0), wobble: float = np.deg2rad(1.5), wobble_hz: float = 3.0) -> np.ndarray:
+    """world <- IMU orientation (xyzw unit quaternions) at times t_s [s]: yaw at a constant rate, roll / pitch a sinusoidal wobble."""
+    t = np.asarray(t_s, dtype=np.float64)
+    yaw, pitch, roll = yaw_rate * t, wobble * np.sin(2 * np.pi * wobble_hz * t), 0.7 * wobble * np.cos(2 * np.pi * wobble_hz * 1.3 * t)
+    z = np.zeros_like(t)
+    qz = np.stack([z, z, np.sin(yaw / 2), np.cos(yaw / 2)], -1)
+    qy = np.stack([z, np.sin(pitch / 2), z, np.cos(pitch / 2)], -1)
+    qx = np.stack([np.sin(roll / 2), z, z, np.cos(roll / 2)], -1)
+    q = _qmul_xyzw(_qmul_xyzw(qz, qy), qx)
+    return np.where(q[..., 3:4] < 0, -q, q)  # w >= 0
+
+
+def quat_to_rot(q: np.ndarray) -> np.ndarray:
+    """(..., 4) xyzw unit quaternions -> (..., 3, 3) rotation matrices."""
+    x, y, z, w = np.moveaxis(np.asarray(q, dtype=np.float64), -1, 0)
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
+                     np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
+                     np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], -2)
+
+
+def imu_trace(t0_us: int, t1_us: int, origin_us: int, rate_hz: float = 200.0, **motion):
+    """IMU samples (t_us uint64, q_xyzw (n, 4)) covering [t0_us, t1_us] at rate_hz; the motion (imu_orientation) is a function of the time
+    since origin_us."""
+    step = int(round(1e6 / rate_hz))
+    t_us = np.arange(int(t0_us), int(t1_us) + step, step, dtype=np.int64)
+    q = imu_orientation((t_us - int(origin_us)) * 1e-6, **motion)
+    return t_us.astype(np.uint64), q
+
+
+def sweep_distort(raw: np.ndarray, stamp_us: int, origin_us: int, **motion) -> np.ndarray:
+    """The raw cloud as a sensor rotating during the sweep measures it: a point p that the sensor would see at the header stamp is
+    measured, at its own time stamp_us + time * 1e6, as R(t)^T R(stamp) p (static translation, identity extrinsic)."""
+    out = raw.copy()
+    p = np.stack([raw["x"], raw["y"], raw["z"]], -1).astype(np.float64)
+    t_pt = (int(stamp_us) - int(origin_us)) * 1e-6 + raw["time"].astype(np.float64)
+    R_pt = quat_to_rot(imu_orientation(t_pt, **motion))
+    R_ref = quat_to_rot(imu_orientation(np.array([(int(stamp_us) - int(origin_us)) * 1e-6]), **motion))[0]
+    m = np.einsum("nji,jk,nk->ni", R_pt, R_ref, p)
+    out["x"], out["y"], out["z"] = m[:, 0].astype(np.float32), m[:, 1].astype(np.float32), m[:, 2].astype(np.float32)
+    return out

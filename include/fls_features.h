@@ -10,8 +10,9 @@
  *   the two pcl::VoxelGrid filters preprocessing.cpp:234-237 applies to the feature clouds
  *       -> FLS_FEAT_CORNER_FILTERED / FLS_FEAT_PLANAR_FILTERED (host VoxelGrid, leaf sizes from the parameters)
  *
- * Constructor arguments = the reference's (preprocessing.cpp:21-36).  De-skew (LidarDistortionCorrector, IMU driven)
- * is not part of this library: hand over corrected points, or raw points when the sensor did not move.
+ * Constructor arguments = the reference's (preprocessing.cpp:21-36).  fls_features_project takes corrected points (or raw points when
+ * the sensor did not move); the IMU de-skew (LidarDistortionCorrector) runs on the device through fls_features_project_deskew
+ * (include/fls_preprocess.h).
  * Plain C; no exception crosses the boundary; a handle is not thread-safe.  No CPU fallback.
  * ==========================================================================*/
 #ifndef FLS_FEATURES_H

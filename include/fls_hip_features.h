@@ -5,8 +5,9 @@
 //     loam::FeatureExtractor::ExtractFeatures(PointcloudCluster&)   src/loam/feature_extractor.cpp:36-222
 //
 // One object replaces both (the projection stays on the device between the two calls).  Constructor arguments are
-// the union of the two reference constructors (preprocessing.cpp:21-36).  De-skew is not done here: run
-// LidarDistortionCorrector over raw_cloud_ first, or hand over the raw points when it is disabled.
+// the union of the two reference constructors (preprocessing.cpp:21-36).  Project() does not de-skew: hand over
+// corrected points, or raw points when the sensor did not move; the de-skewing projection is fls_features_project_deskew
+// (include/fls_preprocess.h).
 // Needs only <lidar/pointcloud_cluster.h> of the reference (for PointcloudCluster) and fls_features.h.
 #pragma once
 #include "fls_features.h"
