@@ -1,8 +1,8 @@
 // device_voxelgrid.hpp -- host driver of the device VoxelGrid (kernels_voxelgrid.hpp; contract there).
 //
 // Input: x | y | z | intensity of n points, resident on the device.  Output: the filtered cloud as x | y | z | intensity
-// on the device (ascending leaf index), its size on the host.  Two short host waits per call: the bounds (the leaf box
-// decides the number of radix passes and the "leaf size too small" refusal, voxel_grid.hpp:69-74) and the output size.
+// on the device (ascending leaf index), its size on the host.  The default (exact order) is one stream of launches with ONE host
+// wait, on the output size (DeviceVoxelGrid::run_fused, kernels_voxelgrid_plan.hpp); the index-order A/B form waits twice.
 #pragma once
 #include "kernels_voxelgrid.hpp"
 #include "kernels_exactsort.hpp"
@@ -59,70 +59,44 @@ struct DevicePairSort {
     }
 };
 
-// std::sort's permutation of {key, value} records on the device (kernels_exactsort.hpp), in place.  Clouds up to kEsTaskMax records
-// (every source scan) are ONE begin launch + ONE persistent task launch; beyond that the host steers the level-synchronous top of the
-// recursion: it enqueues the expected number of levels, polls a host-mapped word (no stream synchronisation) and tops up two levels
-// at a time while ranges longer than kEsTaskMax remain.
+// std::sort's permutation of {key, value} records on the device (kernels_exactsort.hpp), in place: ONE stream of launches without a host
+// round trip -- the level-synchronous top of the recursion pre-enqueued (ranges longer than kBig records), then the persistent task kernel.
+// A preceding kernel initialises the state and the queue (vg_minmax_plan, EsInitArgs); run_sync() does that from the host.
 // the host-mapped words of the last sort started with FLS_ES_DEBUG set (diagnostics: fls_debug_exact_sort_marks reads them from another host thread
 // while a sort is in flight, so the pointer is atomic and published only in debug runs; the owner withdraws it before freeing the memory)
 inline std::atomic<EsMailbox*>& es_debug_mailbox() { static std::atomic<EsMailbox*> p{nullptr}; return p; }
 struct DeviceExactSort {
+    // more records are declined (= kVgMaxBlocks * kVgTile, the VoxelGrid's own limit).  The pre-enqueued levels serve every size up to it (round 6;
+    // until then the host steered the top of clouds beyond kEsTaskMax through a mailbox, one round trip per top-up of two levels)
+    static constexpr size_t kMaxN = size_t(1) << 22;
+    // Ranges longer than kBig records are partitioned LEVEL-SYNCHRONOUSLY by the whole device -- three launches per level (es_level_begin /
+    // count_scatter / swap, the regime-1 kernels): one workgroup needs 3 us + 0.38 us per thousand records for a partition
+    // (profiles/r05_d_ndt_global_levels.log: 47 us at 115,200), a level of launches ~16 us whatever the size.  kEsTaskMax until round 6; the deepest
+    // chain of one-workgroup partitions below a 131,072-record range (~290 us at 13/16 splits) was the task kernel's critical path.  Measured with
+    // the ticket queue, 32,768 / 65,536 / 131,072: planar deque 0.80 / 0.75 / 0.93 ms, IcpOptimized deque 0.48 / 0.53 / 0.65 ms, corner deque
+    // 0.37 / 0.42 / 0.44 ms (profiles/r06_h_*)
+    static constexpr unsigned kBig = 32768;
     DevBuf<EsSeg> seg_a, seg_b;
     DevBuf<EsWork> work;
-    DevBuf<uint2> tile_cnt;
     DevBuf<unsigned long long> tile_pub;  // es_count_scatter_kernel: a tile's published counts + the launch's epoch
     unsigned pub_epoch = 0;
     DevBuf<unsigned> tile_seg, Lp, Rl;
     DevBuf<EsState> st;
     DevBuf<EsQueue> queue;
     DevBuf<unsigned> ready;
-    PinnedBuf<EsState> h_st;
-    PinnedBuf<EsQueue> h_queue;
     EsMailbox* mb_host = nullptr;
     EsMailbox* mb_dev = nullptr;
-    unsigned seq = 0;
-    unsigned long long runs = 0, failures = 0, levels = 0;
-    int last_levels = 0;   // host-steered path: levels queued by the previous sort, and its size
-    size_t last_n = 0;
+    unsigned work_cap = 0, tile_cap = 0;
     ~DeviceExactSort() {
         EsMailbox* mine = mb_host;
         es_debug_mailbox().compare_exchange_strong(mine, nullptr);
         if (mb_host) (void)hipHostFree(mb_host);
     }
-    unsigned wait(const unsigned want, hipStream_t s) {
-        for (unsigned long long spin = 1;; ++spin) {
-            if (__atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE) == want) return want;
-            if ((spin & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) return __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);
-                if (q != hipErrorNotReady) FLS_HIP(q);
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-    }
-    unsigned work_cap = 0, tile_cap = 0;
-    // records a workgroup of the task kernel sorts in LDS, by cloud size (kernels_exactsort.hpp, FLS_ES_LDS): FLS_ES_LDS_SMALL / FLS_ES_LDS_BIG override (A/B)
-    static unsigned lds_cap_for(const size_t n) {
-        static const unsigned small = [] { const char* e = std::getenv("FLS_ES_LDS_SMALL"); const int v = e ? std::atoi(e) : kEsLdsSmall; return unsigned(std::min(std::max(v, 64), kEsLds)); }();
-        static const unsigned big = [] { const char* e = std::getenv("FLS_ES_LDS_BIG"); const int v = e ? std::atoi(e) : kEsLds; return unsigned(std::min(std::max(v, 64), kEsLds)); }();
-        return n <= size_t(kEsTaskMax) ? small : big;
-    }
+    // records a workgroup of the task kernel sorts in LDS, by cloud size (kernels_exactsort.hpp, kEsLds)
+    static unsigned lds_cap_for(const size_t n) { return n <= size_t(kEsTaskMax) ? unsigned(kEsLdsSmall) : unsigned(kEsLds); }
     // one workgroup per CU at most; as many as there are 2,048-record pieces -- NOT n / lds_cap: with 8,192-record LDS ranges that left the 475,200-record
     // deque of IcpOptimized to 62 workgroups, five ranges of ~76 us each in a row on the busiest one (profiles/r06_vg_large_cloud_filters.txt)
-    static unsigned task_grid(const size_t n) {
-        static const size_t cap = [] { const char* e = std::getenv("FLS_ES_GRID"); const int v = e ? std::atoi(e) : 256; return size_t(std::min(std::max(v, 8), 256)); }();  // (A/B)
-        return unsigned(std::min<size_t>(cap, std::max<size_t>(8, n / kEsLdsSmall + 4)));
-    }
-    // clouds beyond kEsTaskMax records: ranges longer than this stay with the level-synchronous launches (the host steers them), shorter ones are tasks.
-    // kEsTaskMax itself until round 6; the deepest chain of one-workgroup partitions below a 131,072-record range (~290 us at 3 us + 0.38 us per thousand
-    // records and 13/16 splits) was the task kernel's critical path.  Measured with the ticket queue, 32,768 / 65,536 / 131,072: planar deque 0.80 / 0.75 /
-    // 0.93 ms, IcpOptimized deque 0.48 / 0.53 / 0.65 ms, corner deque 0.37 / 0.42 / 0.44 ms (profiles/r06_h_*) -- FLS_ES_HANDOVER for A/B
-    static unsigned handover_threshold() {
-        static const unsigned v = [] { const char* e = std::getenv("FLS_ES_HANDOVER"); const int x = e ? std::atoi(e) : 32768; return unsigned(std::min(std::max(x, 4096), kEsTaskMax)); }();
-        return v;
-    }
+    static unsigned task_grid(const size_t n) { return unsigned(std::min<size_t>(256, std::max<size_t>(8, n / kEsLdsSmall + 4))); }
     void allocate(const size_t n) {
         if (!mb_host) {
             FLS_HIP(hipHostMalloc((void**)&mb_host, sizeof(EsMailbox), hipHostMallocMapped));
@@ -136,7 +110,7 @@ struct DeviceExactSort {
         seg_a.reserve(kEsMaxSeg); seg_b.reserve(kEsMaxSeg);
         work.reserve(work_cap);
         ready.reserve(work_cap);
-        tile_cnt.reserve(tile_cap); tile_seg.reserve(tile_cap);
+        tile_seg.reserve(tile_cap);
         if (tile_pub.cap < tile_cap) {  // a fresh buffer holds epoch 0, which no launch uses (growth is rare: filled and waited for here)
             tile_pub.reserve(tile_cap);
             FLS_HIP(hipMemset(tile_pub.p, 0, tile_pub.cap * sizeof(unsigned long long)));
@@ -145,153 +119,65 @@ struct DeviceExactSort {
         Lp.reserve(n); Rl.reserve(n);
         st.reserve(1);
         queue.reserve(1);
-        h_st.reserve(1);
-        h_queue.reserve(1);
     }
-    // The one-launch form for clouds up to kEsTaskMax records whose queue a preceding kernel initialises (vg_minmax_plan, EsInitArgs):
-    // fused_prepare() before that kernel is queued, fused_launch() behind the kernel that writes the records.  `skip`: device word, non-zero
-    // = nothing to sort.  The verdict (EsState::fail) stays on the device: the caller's last kernel forwards it.
-    // (kEsTaskMax until round 6: beyond it the host steered the level-synchronous top through a mailbox, two stream synchronisations and a round trip per
-    // top-up.  The pre-enqueued guess serves any size: levels that find nothing left are three ~2 us launches, ranges the guess leaves too long become
-    // tasks.  FLS_VG_FUSED_MAX for A/B)
-    bool fused_ok(const size_t n) const {
-        static const size_t lim = [] { const char* e = std::getenv("FLS_VG_FUSED_MAX"); return e ? size_t(std::atoll(e)) : (size_t(1) << 22); }();
-        return n >= 2 && n <= lim;
-    }
+    // fused_prepare() before the kernel that initialises the queue is queued, fused_launch() behind the kernel that writes the records.  `skip`:
+    // device word, non-zero = nothing to sort.  The verdict (EsState::fail) stays on the device: the caller's last kernel forwards it.
     EsInitArgs fused_prepare(const size_t n) {
         allocate(n);
         return EsInitArgs{st.p, queue.p, ready.p, work_cap};
     }
-    // Ranges longer than `big` records are partitioned LEVEL-SYNCHRONOUSLY by the whole device -- three launches per level (es_level_begin / count_scatter /
-    // swap, the regime-1 kernels), pre-enqueued without a host round trip: one workgroup needs 3 us + 0.38 us per thousand records
-    // for a partition (profiles/r05_d_ndt_global_levels.log: 47 us at 115,200), a level of launches ~16 us whatever the size.  The number of
-    // levels is a guess (the larger child keeps ~13/16 of a LiDAR range); levels that find nothing left are empty launches, ranges still longer
-    // than `big` after the last one are the task kernel's (one workgroup each, as in round 4).  FLS_ES_BIG = 0 switches the top levels off.
-    static unsigned big_threshold() {
-        static const unsigned v = [] { const char* e = std::getenv("FLS_ES_BIG"); return e ? unsigned(std::atoi(e)) : 32768u; }();
-        return v;
-    }
+    // The number of level-synchronous levels is a guess (the larger child keeps ~13/16 of a LiDAR range); levels that find nothing left are empty
+    // launches, ranges still longer than kBig after the last one are the task kernel's (one workgroup each).
     void fused_launch(unsigned* key, unsigned* val, const size_t n, const unsigned* skip, hipStream_t s) {
-        ++runs;
         const unsigned grid = task_grid(n);
         static const bool dbg_marks = std::getenv("FLS_ES_DEBUG") != nullptr;
         if (dbg_marks) std::memset(mb_host->mark, 0, sizeof(mb_host->mark));
-        const unsigned big = big_threshold();
+        EsMailbox* const dbg = dbg_marks ? mb_dev : nullptr;
+        // (a single scan keeps ~13/16 of a range in the larger child; the keyframe deques beyond kEsTaskMax records -- the same surfaces many times
+        // over -- split more evenly: ~0.7 measured, 15 levels for 1.55 M records where 13/16 all the way guesses 19, each empty level three launches)
         int top = 0;
-        if (big != 0u && n > size_t(big)) {
-            // (a single scan keeps ~13/16 of a range in the larger child; the keyframe deques beyond kEsTaskMax records -- the same surfaces many times
-            // over -- split more evenly: ~0.7 measured, 15 levels for 1.55 M records where 13/16 all the way guesses 19, each empty level three launches)
-            size_t m = n;
-            for (; m > size_t(kEsTaskMax) && m > size_t(big); m = m * 7 / 10) ++top;
-            for (; m > size_t(big); m = m * 13 / 16) ++top;
-            static const int extra = [] { const char* e = std::getenv("FLS_ES_TOP_EXTRA"); return e ? std::atoi(e) : 0; }();
-            top = std::max(1, top + extra);
-        }
+        size_t m = n;
+        for (; m > size_t(kEsTaskMax); m = m * 7 / 10) ++top;
+        for (; m > size_t(kBig); m = m * 13 / 16) ++top;
         if (top == 0) {
-            hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p,
-                               dbg_marks ? mb_dev : (EsMailbox*)nullptr, unsigned(n), skip, lds_cap_for(n));
+            hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p, dbg,
+                               unsigned(n), skip, lds_cap_for(n));
             return;
         }
-        auto next_seq = [&]() { seq = (seq + 1u) & 0x7fffffffu; if (!seq) seq = 1u; return seq; };
         EsSeg* prev = seg_a.p;
         EsSeg* cur = seg_b.p;
         hipLaunchKernelGGL(es_level_begin, dim3(1), dim3(256), 0, s, key, val, unsigned(n), (const EsSeg*)prev, cur, work.p, work_cap, (const unsigned*)Lp.p,
-                           (const unsigned*)Rl.p, st.p, (EsMailbox*)nullptr, next_seq(), 1, tile_seg.p, tile_cap, big, 0, queue.p, skip);
+                           (const unsigned*)Rl.p, st.p, 1, tile_seg.p, tile_cap, kBig, 0, queue.p, skip);
         for (int l = 0; l < top; ++l) {
-            launch_lists(key, cur, s);
+            if (++pub_epoch == 0u) ++pub_epoch;  // (0 is what a fresh buffer holds)
+            hipLaunchKernelGGL(es_count_scatter_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, (const unsigned*)key, cur, st.p, (const unsigned*)tile_seg.p,
+                               tile_pub.p, pub_epoch, Lp.p, Rl.p);
             hipLaunchKernelGGL(es_swap_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, key, val, cur, (const EsState*)st.p, (const unsigned*)tile_seg.p,
                                (const unsigned*)Lp.p, (const unsigned*)Rl.p);
             std::swap(prev, cur);
             hipLaunchKernelGGL(es_level_begin, dim3(1), dim3(256), 0, s, key, val, unsigned(n), (const EsSeg*)prev, cur, work.p, work_cap, (const unsigned*)Lp.p,
-                               (const unsigned*)Rl.p, st.p, (EsMailbox*)nullptr, next_seq(), 0, tile_seg.p, tile_cap, big, l == top - 1 ? 1 : 0, queue.p, skip);
-            ++levels;
+                               (const unsigned*)Rl.p, st.p, 0, tile_seg.p, tile_cap, kBig, l == top - 1 ? 1 : 0, queue.p, skip);
         }
-        hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p,
-                           dbg_marks ? mb_dev : (EsMailbox*)nullptr, 0u, skip, lds_cap_for(n));
+        hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p, dbg, 0u,
+                           skip, lds_cap_for(n));
     }
-    // the stop lists of a level: one launch (es_count_scatter_kernel: tiles look back at their predecessors' published counts), or the two
-    // launches it replaces (FLS_ES_LOOKBACK=0: counts, launch boundary, lists)
-    void launch_lists(const unsigned* key, EsSeg* cur, hipStream_t s) {
-        static const bool lookback = [] { const char* e = std::getenv("FLS_ES_LOOKBACK"); return e ? std::atoi(e) != 0 : true; }();
-        if (lookback) {
-            if (++pub_epoch == 0u) ++pub_epoch;  // (0 is what a fresh buffer holds)
-            hipLaunchKernelGGL(es_count_scatter_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, key, cur, st.p, (const unsigned*)tile_seg.p, tile_pub.p, pub_epoch,
-                               Lp.p, Rl.p);
-            return;
-        }
-        hipLaunchKernelGGL(es_count_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, key, (const EsSeg*)cur, (const EsState*)st.p, (const unsigned*)tile_seg.p,
-                           tile_cnt.p);
-        hipLaunchKernelGGL(es_scatter_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, key, cur, (const EsState*)st.p, (const unsigned*)tile_seg.p,
-                           (const uint2*)tile_cnt.p, Lp.p, Rl.p);
-    }
-    // queues the whole sort on `s`; false: refused before anything ran (sizes).  The verdict of the sort itself (introsort's heap-sort
-    // case) is only known once the stream has drained: failed_after_sync().
-    bool run(unsigned* key, unsigned* val, const size_t n, hipStream_t s) {
-        if (n > (size_t(1) << 22)) return false;
+    // the standalone form (test hook fls_debug_exact_sort): the initialisation vg_minmax_plan's last block does, written from the host, then the
+    // same launches on the null stream and a device synchronisation.  false: declined (more than kMaxN records, or EsState::fail: introsort's
+    // depth limit on a range longer than lds_cap, a table overflow)
+    bool run_sync(unsigned* key, unsigned* val, const size_t n) {
         if (n < 2) return true;
-        allocate(n);
-        ++runs;
-        FLS_HIP(hipMemsetAsync(ready.p, 0, work_cap * sizeof(unsigned), s));
-        if (n <= size_t(kEsTaskMax)) {
-            // every source scan: no begin launch, no host wait -- the array itself is workgroup 0's first task (open = 1 stands for it)
-            FLS_HIP(hipMemsetAsync(st.p, 0, sizeof(EsState), s));
-            *h_queue.p = EsQueue{0u, 0u, 1u, 0u};
-            FLS_HIP(hipMemcpyAsync(queue.p, h_queue.p, sizeof(EsQueue), hipMemcpyHostToDevice, s));
-            const unsigned grid = task_grid(n);
-            static const bool dbg_marks = std::getenv("FLS_ES_DEBUG") != nullptr;
-            if (dbg_marks) std::memset(mb_host->mark, 0, sizeof(mb_host->mark));
-            hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p,
-                               dbg_marks ? mb_dev : (EsMailbox*)nullptr, unsigned(n), (const unsigned*)nullptr, lds_cap_for(n));
-            FLS_HIP(hipMemcpyAsync(h_st.p, st.p, sizeof(EsState), hipMemcpyDeviceToHost, s));
-            FLS_HIP(hipGetLastError());
-            return true;
-        }
-        auto next_seq = [&]() { seq = (seq + 1u) & 0x7fffffffu; if (!seq) seq = 1u; return seq; };
-        EsSeg* prev = seg_a.p;
-        EsSeg* cur = seg_b.p;
-        hipLaunchKernelGGL(es_level_begin, dim3(1), dim3(256), 0, s, key, val, unsigned(n), (const EsSeg*)prev, cur, work.p, work_cap, (const unsigned*)Lp.p,
-                           (const unsigned*)Rl.p, st.p, mb_dev, next_seq(), 1, tile_seg.p, tile_cap, handover_threshold(), 0, (EsQueue*)nullptr, (const unsigned*)nullptr);
-        // regime 1 (ranges longer than the hand-over threshold: only clouds beyond 131 k points get here)
-        // how many levels to queue before the first look at the mailbox: what the previous sort of this object needed (a keyframe deque changes by one
-        // frame in twenty-five between two calls), else a guess from halving splits -- LiDAR leaf indices split ~13/16, so the guess is short and the
-        // loop below tops up two levels at a time, one host round trip (~10 us of idle device) each
-        int expected = 0;
-        for (size_t m = n; m > size_t(handover_threshold()); m = (m + 1) / 2) ++expected;
-        int chunk = expected ? expected + 1 : 0;
-        if (expected && last_levels > 0 && last_n != 0 && n >= last_n / 2 && n <= last_n * 2) chunk = std::max(1, last_levels);
-        int queued_levels = 0;
-        for (;;) {
-            queued_levels += chunk;
-            for (int c = 0; c < chunk; ++c) {
-                launch_lists(key, cur, s);
-                hipLaunchKernelGGL(es_swap_kernel, dim3(tile_cap), dim3(kEsBlock), 0, s, key, val, cur, (const EsState*)st.p, (const unsigned*)tile_seg.p,
-                                   (const unsigned*)Lp.p, (const unsigned*)Rl.p);
-                std::swap(prev, cur);
-                hipLaunchKernelGGL(es_level_begin, dim3(1), dim3(256), 0, s, key, val, unsigned(n), (const EsSeg*)prev, cur, work.p, work_cap, (const unsigned*)Lp.p,
-                                   (const unsigned*)Rl.p, st.p, mb_dev, next_seq(), 0, tile_seg.p, tile_cap, handover_threshold(), 0, (EsQueue*)nullptr, (const unsigned*)nullptr);
-                ++levels;
-            }
-            FLS_HIP(hipGetLastError());
-            wait(seq, s);
-            if (mb_host->fail) { ++failures; return false; }
-            if (mb_host->n_cur == 0u) break;
-            chunk = 2;
-        }
-        last_levels = queued_levels; last_n = n;  // (an over-estimate by at most one top-up: empty levels cost three ~2 us launches)
-        // regimes 2 + 3: one persistent launch over the task queue (the ranges regime 1 handed over are its first tasks)
-        const unsigned n_work = mb_host->n_work;
-        if (n_work) {
-            *h_queue.p = EsQueue{0u, n_work, n_work, n_work};
-            FLS_HIP(hipMemcpyAsync(queue.p, h_queue.p, sizeof(EsQueue), hipMemcpyHostToDevice, s));
-            const unsigned grid = task_grid(n);
-            static const bool skip = std::getenv("FLS_ES_SKIP_TASKS") != nullptr;  // (bisecting aid)
-            if (!skip) hipLaunchKernelGGL(es_task_kernel, dim3(grid), dim3(kEsTaskThreads), 0, s, key, val, work.p, ready.p, work_cap, queue.p, Lp.p, Rl.p, st.p,
-                                          std::getenv("FLS_ES_DEBUG") ? mb_dev : (EsMailbox*)nullptr, 0u, (const unsigned*)nullptr, lds_cap_for(n));
-            FLS_HIP(hipMemcpyAsync(h_queue.p, queue.p, sizeof(EsQueue), hipMemcpyDeviceToHost, s));
-        }
-        FLS_HIP(hipMemcpyAsync(h_st.p, st.p, sizeof(EsState), hipMemcpyDeviceToHost, s));
-        FLS_HIP(hipGetLastError());
-        return true;
+        if (n > kMaxN) return false;
+        const EsInitArgs ia = fused_prepare(n);
+        FLS_HIP(hipMemset(ia.st, 0, sizeof(EsState)));
+        FLS_HIP(hipMemset(ia.ready, 0, ia.work_cap * sizeof(unsigned)));
+        const EsQueue q0{0u, 0u, 1u, 0u};
+        FLS_HIP(hipMemcpy(ia.q, &q0, sizeof(EsQueue), hipMemcpyHostToDevice));
+        fused_launch(key, val, n, nullptr, nullptr);
+        FLS_HIP(hipDeviceSynchronize());
+        print_debug_stamps();
+        EsState hs;
+        FLS_HIP(hipMemcpy(&hs, ia.st, sizeof(EsState), hipMemcpyDeviceToHost));
+        return hs.fail == 0u;
     }
     void print_wg_profile() {
         if (!mb_host) return;
@@ -318,8 +204,8 @@ struct DeviceExactSort {
             std::memset(mb_host->wg, 0, sizeof(mb_host->wg));
         }
     }
-    // FLS_ES_DEBUG: stage stamps of the last sort (the fused form never copies EsState back)
-    bool failed_after_sync_debug_only() {
+    // FLS_ES_DEBUG: stage stamps of the last sort
+    void print_debug_stamps() {
         static const bool dbg = std::getenv("FLS_ES_DEBUG") && std::atoi(std::getenv("FLS_ES_DEBUG")) != 0;
         if (dbg && mb_host) {
             const unsigned* mk = mb_host->mark;
@@ -335,23 +221,6 @@ struct DeviceExactSort {
             std::memset(mb_host->lvl, 0, sizeof(mb_host->lvl));
             print_wg_profile();
         }
-        return false;
-    }
-    // after the caller's stream synchronisation: did a range hit introsort's depth limit inside es_lds_kernel?
-    bool failed_after_sync() {
-        static const bool dbg = std::getenv("FLS_ES_DEBUG") && std::atoi(std::getenv("FLS_ES_DEBUG")) != 0;
-        if (dbg && mb_host) {
-            const unsigned* mk = mb_host->mark;
-            auto us = [&](int a, int b) { return mk[a] && mk[b] ? 0.01 * double(int(mk[b] - mk[a])) : -1.0; };
-            std::fprintf(stderr, "[fls exact sort] workgroup 0, first task [us]: pop->start %.1f, global partitions %.1f, LDS load %.1f, phase A (workgroup partitions) %.1f, phase B (wave tasks) %.1f, "
-                         "ranks + write-back %.1f\n", us(0, 2), us(2, 9), us(9, 10), us(10, 3), us(3, 4), us(5, 6));
-        }
-        if (dbg) print_wg_profile();
-        if (dbg && h_st.p)
-            std::fprintf(stderr, "[fls exact sort] regime-1 levels %u, hand-over ranges %u, fail %u; task kernel: %u partitions from global memory, %u ranges (%u records) sorted in LDS\n",
-                         h_st.p->level, h_st.p->n_work, h_st.p->fail, h_st.p->pad[0], h_st.p->pad[1], h_st.p->pad[2]);
-        if (h_st.p && h_st.p->fail) { ++failures; return true; }
-        return false;
     }
 };
 
@@ -367,11 +236,10 @@ struct DeviceVoxelGrid {
     DevicePairSort sort;
     DeviceExactSort exact;
     bool exact_order = device_voxelgrid_mode() != 2;  // centroids summed in std::sort's order; false: ascending point index
-    unsigned long long exact_runs = 0, exact_declined = 0;
     DevBuf<unsigned> lx, bt;        // bt: block totals | scanned
     DevBuf<float4> sorted;          // the points in sorted order
     DevBuf<float> out;            // x | y | z | i, capacity n each
-    DevBuf<VgHeader> d_hdr;
+    DevBuf<VgHeader> d_hdr;       // run_index_order
     PinnedBuf<VgHeader> h_hdr;    // [0] = init template, [1] = read-back
     // the uninterrupted form (kernels_voxelgrid_plan.hpp): plan + accumulators on the device, the verdict in a host-mapped mailbox
     DevBuf<VgPlan> d_plan;
@@ -379,13 +247,9 @@ struct DeviceVoxelGrid {
     VgMailbox* vmb_host = nullptr;
     VgMailbox* vmb_dev = nullptr;
     unsigned vseq = 0;
-    bool fused = true;            // FLS_VG_FUSED=0: the round-4 sequence (two stream synchronisations), A/B
-    unsigned last_status = 0;
-    unsigned long long fused_runs = 0;
     size_t n_in = 0, n_out = 0;
-    int last_passes = 0;
     ~DeviceVoxelGrid() { if (vmb_host) (void)hipHostFree(vmb_host); }
-    DeviceVoxelGrid() { if (const char* e = std::getenv("FLS_VG_FUSED")) fused = std::atoi(e) != 0; }
+    DeviceVoxelGrid() = default;
     DeviceVoxelGrid(const DeviceVoxelGrid&) = delete;
     DeviceVoxelGrid& operator=(const DeviceVoxelGrid&) = delete;
     const float* ox() const { return out.p; }
@@ -397,8 +261,14 @@ struct DeviceVoxelGrid {
     bool run(const float* x, const float* y, const float* z, const float* in, size_t n, float leaf, hipStream_t s) {
         n_in = n;
         n_out = 0;
-        if (n == 0 || n > size_t(kVgMaxBlocks) * kVgTile) return false;
-        if (fused && exact_order && exact.fused_ok(n)) return run_fused(x, y, z, in, n, leaf, s);
+        if (n == 0 || n > size_t(kVgMaxBlocks) * kVgTile) return false;  // (= DeviceExactSort::kMaxN)
+        return exact_order ? run_fused(x, y, z, in, n, leaf, s) : run_index_order(x, y, z, in, n, leaf, s);
+    }
+
+    // FLS_DEVICE_VOXELGRID=2 only (A/B): the round-2/3 form -- stable radix sort, leaf sums in ascending point index (kernels_voxelgrid.hpp
+    // CONTRACT) -- with two short host waits: the bounds (they decide the number of radix passes and the "leaf size too small" refusal,
+    // voxel_grid.hpp:69-74) and the output size
+    bool run_index_order(const float* x, const float* y, const float* z, const float* in, size_t n, float leaf, hipStream_t s) {
         h_hdr.reserve(2);
         d_hdr.reserve(1);
         for (int a = 0; a < 3; ++a) { h_hdr.p[0].mn[a] = 0xffffffffu; h_hdr.p[0].mx[a] = 0u; }
@@ -431,7 +301,6 @@ struct DeviceVoxelGrid {
         g.m2 = int(div_b[0] * div_b[1]);
         g.total = unsigned(total);
         const int passes = DevicePairSort::passes_for((unsigned long long)total);  // the sentinel `total` itself must sort
-        last_passes = passes;
 
         sort.prepare(n);
         lx.reserve(n);
@@ -439,13 +308,7 @@ struct DeviceVoxelGrid {
         sorted.reserve(n);
         out.reserve(4 * n);
         hipLaunchKernelGGL(vg_index, dim3(unsigned(nb1)), dim3(kVgBlock), 0, s, x, y, z, ni, g, sort.k0, sort.v0);
-        if (exact_order) {
-            // the reference sorts the FINITE points only (non-finite ones never enter its index vector): a cloud with any is the host's
-            if (hh.n_bad != 0u || !exact.run(sort.k0, sort.v0, n, s)) { ++exact_declined; return false; }
-            ++exact_runs;
-        } else {
-            sort.run(passes, s);
-        }
+        sort.run(passes, s);
         unsigned* const k0 = sort.k0;
         unsigned* const v0 = sort.v0;
         hipLaunchKernelGGL(vg_heads, dim3(unsigned(nb2)), dim3(kVgScanBlock), 0, s, (const unsigned*)k0, (const unsigned*)v0, ni, g.total, x, y, z, in,
@@ -456,14 +319,14 @@ struct DeviceVoxelGrid {
         FLS_HIP(hipMemcpyAsync(&h_hdr.p[1], d_hdr.p, sizeof(VgHeader), hipMemcpyDeviceToHost, s));
         FLS_HIP(hipStreamSynchronize(s));
         FLS_HIP(hipGetLastError());
-        if (exact_order && exact.failed_after_sync()) { ++exact_declined; return false; }  // (introsort's heap-sort case: the host path sorts)
         n_out = h_hdr.p[1].n_out;
         return true;
     }
 
     // One uninterrupted stream of launches (kernels_voxelgrid_plan.hpp): bounds + plan + sort-queue initialisation, leaf indices, the exact
     // sort, run heads, offsets + verdict to the mailbox, centroids.  The host waits ONCE, on a host-mapped word the offsets kernel writes --
-    // before the centroid kernel has finished; whatever the caller queues next on `s` is ordered behind it.
+    // before the centroid kernel has finished; whatever the caller queues next on `s` is ordered behind it.  Every exact-order call, n = 1
+    // included: a single point needs no sort, and the EsState vg_minmax_plan zeroes tells the later kernels that none failed.
     bool run_fused(const float* x, const float* y, const float* z, const float* in, size_t n, float leaf, hipStream_t s) {
         if (!vmb_host) {
             FLS_HIP(hipHostMalloc((void**)&vmb_host, sizeof(VgMailbox), hipHostMallocMapped));
@@ -493,7 +356,7 @@ struct DeviceVoxelGrid {
         const int mm_blocks = int(std::min<size_t>(kVgMinmaxMaxBlocks, std::max<size_t>(160, n / 4096)));  // (one row per block, no atomics but the ticket: more blocks for the keyframe deques)
         hipLaunchKernelGGL(vg_minmax_plan, dim3(unsigned(std::min(nb1, mm_blocks))), dim3(kVgBlock), 0, s, x, y, z, ni, inv, 1, d_acc.p, d_plan.p, es);
         hipLaunchKernelGGL(vg_index_plan, dim3(unsigned(nb1)), dim3(kVgBlock), 0, s, x, y, z, ni, (const VgPlan*)d_plan.p, sort.k0, sort.v0);
-        exact.fused_launch(sort.k0, sort.v0, n, &d_plan.p->status, s);
+        if (n >= 2) exact.fused_launch(sort.k0, sort.v0, n, &d_plan.p->status, s);
         hipLaunchKernelGGL(vg_heads_plan, dim3(unsigned(nb2)), dim3(kVgScanBlock), 0, s, (const unsigned*)sort.k0, (const unsigned*)sort.v0, ni, (const VgPlan*)d_plan.p,
                            (const EsState*)exact.st.p, x, y, z, in, sorted.p, lx.p, bt.p);
         hipLaunchKernelGGL(vg_scan_publish, dim3(1), dim3(kVgScanBlock), 0, s, (const unsigned*)bt.p, bt.p + nb2, nb2, (const VgPlan*)d_plan.p, (const EsState*)exact.st.p,
@@ -512,16 +375,11 @@ struct DeviceVoxelGrid {
             __builtin_ia32_pause();
 #endif
         }
-        ++fused_runs;
-        last_status = vmb_host->status;
-        if (exact.failed_after_sync_debug_only()) {}
+        exact.print_debug_stamps();
         if (vmb_host->status != kVgOk || vmb_host->sort_fail != 0u) {
-            if (vmb_host->sort_fail != 0u) ++exact.failures;
-            ++exact_declined;
             FLS_HIP(hipStreamSynchronize(s));  // (the staging the caller reuses; the refused call is rare)
             return false;
         }
-        ++exact_runs;
         n_out = vmb_host->n_out;
         return true;
     }

@@ -17,13 +17,11 @@
 //   positions no other swap touches;   cut = min(L_{K*+1}, R_{K*})  (terms that do not exist count as +inf).
 // So one level = flag two predicates, rank them (prefix sums), scatter the two stop lists, swap K* disjoint pairs.  All ranges of one
 // recursion depth are independent and processed together (level-synchronous); values ride along with their keys.
-//   regime 1  ranges longer than a threshold: three launches per level over all such ranges (es_level_begin: cuts + children of the previous
-//             level, medians of this one; es_count_scatter: stop lists through per-tile counts, a tile looks back at its predecessors'
-//             published counts -- es_count / es_scatter are the two-launch form it replaced; es_swap).  Round 5: for clouds up to
-//             kEsTaskMax records the levels above 32,768 records (FLS_ES_BIG) are PRE-ENQUEUED without a host round trip (device_voxelgrid.hpp
-//             fused_launch: a level of launches costs ~16 us whatever the size, one workgroup 3 us + 0.38 us per thousand records); beyond
-//             kEsTaskMax the host steers the levels through a mailbox as in round 4;
-//   regime 2  shorter ranges are TASKS of the persistent es_task_kernel: a workgroup partitions a range longer than lds_cap (2,048 / 8,192 by cloud size) records out
+//   regime 1  ranges longer than 32,768 records (DeviceExactSort::kBig): three launches per level over all such ranges (es_level_begin: cuts +
+//             children of the previous level, medians of this one; es_count_scatter: stop lists through per-tile counts, a tile looks back at its
+//             predecessors' published counts; es_swap), PRE-ENQUEUED without a host round trip (device_voxelgrid.hpp fused_launch: a level of
+//             launches costs ~16 us whatever the size, one workgroup 3 us + 0.38 us per thousand records).  Clouds up to kBig records skip it;
+//   regime 2  shorter ranges are TASKS of the persistent es_task_kernel: a workgroup partitions a range longer than lds_cap (2,048 / 4,096 by cloud size) records out
 //             of global memory and hands one child to the queue, takes a range of <= lds_cap records into LDS, runs ALL its remaining levels
 //             there (sub-ranges above kEsCoop by the whole workgroup, the rest as wave tasks through a ticket queue: es_phase_b), then
 //             ranks the records of every final <= 16 block (= the insertion sort) and writes them back.
@@ -41,18 +39,15 @@ namespace fls {
 // Round 6: the range a workgroup takes into LDS is a RUN-TIME parameter of es_task_kernel (`lds_cap`), chosen by the size of the cloud
 // (DeviceExactSort::lds_cap_for): 2,048 records for clouds up to kEsTaskMax (every source scan: more CUs busy), 4,096 beyond (the map-side filters
 // of the kd-tree kinds, 0.2-1.6 M records; measured 2,048 / 4,096 / 8,192: planar deque 0.83 / 0.80 / 0.80 ms, IcpOptimized deque 0.48 / 0.48 / 0.52 ms,
-// profiles/r06_g_*).  FLS_ES_LDS = the capacity the LDS arrays are sized for.
+// profiles/r06_g_*).  kEsLds = the capacity the LDS arrays are sized for.
 // (The regression between BENCH_r04 and BENCH_r05 -- LoamFull keyframe update 2.25 -> 5.54 ms -- showed up as "2,048-record ranges are 3.6x slower than
 // 8,192-record ranges on 1.55 M records"; the cause was not the range size but the task queue's pop, see es_task_kernel: the ticket queue.)
-#ifndef FLS_ES_LDS
-#define FLS_ES_LDS 4096
-#endif
-constexpr int kEsLds = FLS_ES_LDS;  // records the LDS arrays hold (the largest lds_cap)
-constexpr int kEsLdsSmall = 2048;   // default lds_cap for clouds up to kEsTaskMax records
-constexpr int kEsTaskMax = 131072;  // ranges up to here are tasks of the persistent kernel; longer ones go through the level-synchronous launches
+constexpr int kEsLds = 4096;        // records the LDS arrays hold (the largest lds_cap)
+constexpr int kEsLdsSmall = 2048;   // lds_cap for clouds up to kEsTaskMax records
+constexpr int kEsTaskMax = 131072;  // clouds up to here are every source scan (lds_cap 2,048); larger ones are the keyframe deques of the map-side filters
 constexpr int kEsThreshold = 16;    // _S_threshold
 constexpr int kEsTile = 2048, kEsBlock = 256, kEsItems = kEsTile / kEsBlock;
-constexpr int kEsMaxSeg = 192;      // regime-1 ranges of one level (n / hand-over threshold: 128 for 4 Mi records at 32,768, with room)
+constexpr int kEsMaxSeg = 192;      // regime-1 ranges of one level (n / kBig: 128 for 4 Mi records at 32,768, with room)
 
 struct EsSeg { unsigned first, last; int depth; unsigned pivot, nL, nR, K, tile0; };
 struct EsWork { unsigned first, last; int depth, pad; };
@@ -65,8 +60,8 @@ struct EsState {
     unsigned level;     // regime-1 levels run
     unsigned pad[3];
 };
-// what the host polls (host-mapped): written by every es_level_begin
-struct EsMailbox { unsigned seq, n_cur, n_work, fail; unsigned mark[12]; unsigned lvl[32][8]; unsigned wg[256][8]; };  // wg[b] (FLS_ES_DEBUG): workgroup b's 100 MHz ticks waiting for a task | in partitions out of global memory | in LDS ranges, its task count, its longest LDS range (ticks, records), its longest chain of partitions out of global memory (ticks, first range's records)  // mark / lvl: stage stamps of es_task_kernel (diagnostics, FLS_ES_DEBUG): lvl[i] = {range size, 100 MHz stamps of the phases of workgroup 0's i-th partition out of global memory}
+// host-mapped diagnostics of es_task_kernel (FLS_ES_DEBUG; fls_debug_exact_sort_marks reads `mark` while a sort is in flight)
+struct EsMailbox { unsigned mark[12]; unsigned lvl[32][8]; unsigned wg[256][8]; };  // wg[b]: workgroup b's 100 MHz ticks waiting for a task | in partitions out of global memory | in LDS ranges, its task count, its longest LDS range (ticks, records), its longest chain of partitions out of global memory (ticks, first range's records)  // mark / lvl: stage stamps of es_task_kernel (diagnostics, FLS_ES_DEBUG): lvl[i] = {range size, 100 MHz stamps of the phases of workgroup 0's i-th partition out of global memory}
 
 // (Round 6, built and REMOVED: "write-through records" -- every key[] / val[] access of the task kernel as an agent-scope relaxed atomic (sc1), the
 // hand-over between workgroups without release / acquire fences.  Times equal to the fenced form within 2 % (profiles/r06_vg_large_cloud_filters.txt), and
@@ -94,14 +89,13 @@ __device__ __forceinline__ unsigned es_median_to_first(unsigned* __restrict__ ke
 
 // ---- regime 1 ----------------------------------------------------------------------------------------------------------------------
 // One workgroup: finish the previous level (cut of every range from its K*, children -> next level or the LDS work list), then open
-// the new level (median of three, pivot, tile map).  `prev` / `cur` are the two range tables, swapped by the host every level.
+// the new level (median of three, pivot, tile map).  `prev` / `cur` are the two range tables, swapped by the host every level it enqueues.
 __global__ void __launch_bounds__(256)
 es_level_begin(unsigned* __restrict__ key, unsigned* __restrict__ val, const unsigned n, const EsSeg* __restrict__ prev, EsSeg* __restrict__ cur,
                EsWork* __restrict__ work, const unsigned work_cap, const unsigned* __restrict__ Lp, const unsigned* __restrict__ Rl,
-               EsState* __restrict__ st, EsMailbox* __restrict__ mb, const unsigned seq, const int first_level, unsigned* __restrict__ tile_seg,
-               const unsigned tile_cap,
-               // round 5 (the pre-enqueued top levels of the one-stream VoxelGrid, DeviceExactSort::fused_launch): ranges longer than `big` stay
-               // level-synchronous; final_level: every child becomes a task and the task kernel's queue is written here; *skip != 0: nothing to sort
+               EsState* __restrict__ st, const int first_level, unsigned* __restrict__ tile_seg, const unsigned tile_cap,
+               // ranges longer than `big` stay level-synchronous; final_level: every child becomes a task and the task kernel's queue is written
+               // here; *skip != 0: nothing to sort
                const unsigned big, const int final_level, EsQueue* __restrict__ q_out, const unsigned* __restrict__ skip) {
     __shared__ unsigned s_ncur, s_nwork, s_fail, s_tiles[kEsMaxSeg], s_total;
     __shared__ EsSeg s_cur[kEsMaxSeg];  // the new level's ranges: completed here (pivot, tile map), written out once
@@ -186,13 +180,6 @@ es_level_begin(unsigned* __restrict__ key, unsigned* __restrict__ val, const uns
         st->fail = s_fail;
         st->level = first_level ? 0u : st->level + 1u;
         if (q_out != nullptr && final_level) { const unsigned nw = st->n_work; *q_out = EsQueue{0u, nw, nw, nw}; }
-        if (mb != nullptr) {  // (the host steers the levels only beyond kEsTaskMax records; the pre-enqueued levels of the one-stream form pass nullptr)
-            __hip_atomic_store(&mb->n_cur, st->n_cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&mb->n_work, st->n_work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(&mb->fail, s_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&mb->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 // workgroup -> (range, tile)
@@ -203,67 +190,10 @@ __device__ __forceinline__ bool es_locate(const EsSeg* __restrict__ cur, const E
     tile = blockIdx.x - cur[seg].tile0;
     return true;
 }
-// per-tile counts of the two predicates
-__global__ void __launch_bounds__(kEsBlock)
-es_count_kernel(const unsigned* __restrict__ key, const EsSeg* __restrict__ cur, const EsState* __restrict__ st, const unsigned* __restrict__ tile_seg,
-                uint2* __restrict__ tile_cnt) {
-    __shared__ unsigned wsum[kEsBlock / 64][2];
-    unsigned seg, tile;
-    if (!es_locate(cur, st, tile_seg, seg, tile)) return;
-    const EsSeg g = cur[seg];
-    const unsigned base = g.first + 1u + tile * (unsigned)kEsTile;
-    unsigned cl = 0u, cr = 0u;
-#pragma unroll
-    for (int q = 0; q < kEsItems; ++q) {
-        const unsigned i = base + q * (unsigned)kEsBlock + threadIdx.x;
-        if (i < g.last) { const unsigned k = key[i]; cl += k >= g.pivot ? 1u : 0u; cr += k <= g.pivot ? 1u : 0u; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cl += __shfl_xor(cl, o, 64); cr += __shfl_xor(cr, o, 64); }
-    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6][0] = cl; wsum[threadIdx.x >> 6][1] = cr; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned a = 0u, b = 0u;
-        for (int w = 0; w < kEsBlock / 64; ++w) { a += wsum[w][0]; b += wsum[w][1]; }
-        tile_cnt[blockIdx.x] = make_uint2(a, b);
-    }
-}
-// stop lists: L-stops ascending at Lp[first + rank], R-stops ascending at Rl[first + rank] (the k-th from the right is Rl[first + nR - 1 - k])
-__global__ void __launch_bounds__(kEsBlock)
-es_scatter_kernel(const unsigned* __restrict__ key, EsSeg* __restrict__ cur, const EsState* __restrict__ st, const unsigned* __restrict__ tile_seg,
-                  const uint2* __restrict__ tile_cnt, unsigned* __restrict__ Lp, unsigned* __restrict__ Rl) {
-    __shared__ unsigned wsum4[kEsBlock / 64][4], wsum2[kEsBlock / 64][2];
-    unsigned seg, tile;
-    if (!es_locate(cur, st, tile_seg, seg, tile)) return;
-    const EsSeg g = cur[seg];
-    const unsigned ntile = (g.last - g.first - 1u + (unsigned)kEsTile - 1u) / (unsigned)kEsTile;
-    unsigned pre[2], all[2];
-    block_prefix_total<2>(tile_cnt + g.tile0, (int)ntile, (int)tile, pre, all, wsum4);
-    if (tile == 0u && threadIdx.x == 0) { cur[seg].nL = all[0]; cur[seg].nR = all[1]; cur[seg].K = 0u; }
-    // a thread owns kEsItems CONSECUTIVE positions (ranks follow positions)
-    const unsigned base = g.first + 1u + tile * (unsigned)kEsTile + threadIdx.x * (unsigned)kEsItems;
-    unsigned kk[kEsItems];
-    unsigned v[2] = {0u, 0u}, tot[2];
-#pragma unroll
-    for (int q = 0; q < kEsItems; ++q) {
-        const unsigned i = base + q;
-        kk[q] = i < g.last ? key[i] : 0u;
-        if (i < g.last) { v[0] += kk[q] >= g.pivot ? 1u : 0u; v[1] += kk[q] <= g.pivot ? 1u : 0u; }
-    }
-    block_excl_scan<2>(v, tot, wsum2);
-    unsigned rl = g.first + pre[0] + v[0], rr = g.first + pre[1] + v[1];
-#pragma unroll
-    for (int q = 0; q < kEsItems; ++q) {
-        const unsigned i = base + q;
-        if (i < g.last) {
-            if (kk[q] >= g.pivot) Lp[rl++] = i;
-            if (kk[q] <= g.pivot) Rl[rr++] = i;
-        }
-    }
-}
-// es_count_kernel + es_scatter_kernel in ONE launch (round 5): a tile counts its two predicates, publishes the pair write-through together
-// with the launch's epoch, and looks BACK at the tiles of its range in front of it -- one predecessor per thread, polled with loads that
-// are served from memory -- instead of waiting for a launch boundary (a dependent launch costs ~4.7 us here, the look-back ~1 us).
+// stop lists: L-stops ascending at Lp[first + rank], R-stops ascending at Rl[first + rank] (the k-th from the right is Rl[first + nR - 1 - k]),
+// in ONE launch: a tile counts its two predicates, publishes the pair write-through together with the launch's epoch, and looks BACK at the
+// tiles of its range in front of it -- one predecessor per thread, polled with loads that are served from memory -- instead of waiting for a
+// launch boundary (a dependent launch costs ~4.7 us here, the look-back ~1 us).
 // A tile only ever waits for LOWER workgroup ids of the same launch, and the hardware starts workgroups in id order: no tile waits for
 // one that cannot run.  pub[t] = epoch << 32 | n_R-stops << 16 | n_L-stops (a tile holds 2,048 records); the epoch never repeats, so a
 // word of an earlier level / sort is never taken for this launch's.  "The hardware starts workgroups in id order" is what dispatch does, not a guarantee
@@ -374,7 +304,7 @@ es_swap_kernel(unsigned* __restrict__ key, unsigned* __restrict__ val, EsSeg* __
 // ---- regimes 2 + 3: ONE persistent launch, a task queue of ranges -------------------------------------------------------------------
 // A level-synchronous sweep pays for the DEEPEST branch at every level, and introsort on LiDAR leaf indices is deep and lopsided
 // (median-of-three on piecewise-monotone keys: 16 levels before the last range of a 115 k-point scan fell below 4,096 records, 23 more
-// inside it).  From kEsTaskMax records down, ranges are therefore TASKS: a workgroup pops a range from a global queue and
+// inside it).  From DeviceExactSort::kBig records down, ranges are therefore TASKS: a workgroup pops a range from a global queue and
 //   * partitions it itself out of global memory (16 waves, each over a contiguous slice in coalesced rounds of 64 with ballot ranks:
 //     counts -> wave bases -> stop lists -> K* disjoint swaps) and pushes the two children, or
 //   * (range <= lds_cap) takes it into LDS, where its WAVES run the same partition on sub-ranges from a local queue -- no workgroup
@@ -382,19 +312,13 @@ es_swap_kernel(unsigned* __restrict__ key, unsigned* __restrict__ val, EsSeg* __
 //     sort) and writes the range back.
 // Hand-off between workgroups (possibly on different XCDs): the producer writes back its L2 (agent-scope release) before it publishes a
 // child, the consumer invalidates (agent-scope acquire) after it pops one.  Termination: a counter of open tasks.
-#ifndef FLS_ES_UNROLL
-#define FLS_ES_UNROLL 8  // independent key loads a lane keeps in flight in the passes of a partition out of global memory (A/B at the end of round 4,
-                         // NDT fls_match from host buffers: 8 -> 0.682 ms, 16 -> 0.676, 24 -> 0.691, 40 -> 0.934 (spills): not what bounds the stage)
-#endif
+constexpr int kEsUnroll = 8;  // independent key loads a lane keeps in flight in the passes of a partition out of global memory (A/B at the end of round 4,
+                              // NDT fls_match from host buffers: 8 -> 0.682 ms, 16 -> 0.676, 24 -> 0.691, 40 -> 0.934 (spills): not what bounds the stage)
 constexpr int kEsTaskThreads = 1024, kEsTaskWaves = kEsTaskThreads / 64;
-#ifndef FLS_ES_COOP
-#define FLS_ES_COOP 4096  // (A/B r05: 1024 / 2048 / 4096 / 8192 -> ICP call 0.466 / 0.449 / 0.444 / 0.478 ms)
-#endif
-#ifndef FLS_ES_SHARE
-#define FLS_ES_SHARE 64    // (A/B r05: 384 / 192 / 96 / 64 / 48 / 32 -> 0.497 / 0.451 / 0.444 / 0.445 / 0.445 / 0.475 ms)
-#endif
-constexpr int kEsCoop = FLS_ES_COOP < FLS_ES_LDS ? FLS_ES_COOP : FLS_ES_LDS;    // sub-ranges of an LDS range longer than this are partitioned by the whole workgroup, shorter ones by single waves (never more than lds_cap: such ranges do not exist)
-constexpr int kEsShare = FLS_ES_SHARE;  // a wave hands children longer than this to the workgroup's queue (another wave takes them), shorter ones stay on its own stack
+// (A/B r05, kEsCoop: 1024 / 2048 / 4096 / 8192 -> ICP call 0.466 / 0.449 / 0.444 / 0.478 ms;
+//  kEsShare: 384 / 192 / 96 / 64 / 48 / 32 -> 0.497 / 0.451 / 0.444 / 0.445 / 0.445 / 0.475 ms)
+constexpr int kEsCoop = 4096;    // sub-ranges of an LDS range longer than this are partitioned by the whole workgroup, shorter ones by single waves (never more than lds_cap: such ranges do not exist)
+constexpr int kEsShare = 64;     // a wave hands children longer than this to the workgroup's queue (another wave takes them), shorter ones stay on its own stack
 constexpr int kEsStack = 64;     // pending workgroup-level sub-ranges (disjoint, each > kEsCoop records: at most kEsLds / kEsCoop)
 constexpr int kEsWaveStack = 48; // a wave's depth-first stack (smaller child first: <= log2(kEsCoop) + 1 pending ranges)
 constexpr int kEsLocalQ = 1024;  // sub-range tasks of one LDS range (<= 2 per partition, <= kEsLds / 17 partitions)
@@ -718,7 +642,7 @@ es_task_kernel(unsigned* __restrict__ key, unsigned* __restrict__ val, EsWork* _
                 const unsigned w0 = first + 1u + (unsigned)w * per, w1 = w0 + per < last ? w0 + per : last;
                 // (every loop below keeps U independent loads in flight: a global round trip costs ~1 us on a freshly invalidated cache, and a
                 // 115 k-record range is 113 rounds of 64 per wave)
-                constexpr int U = FLS_ES_UNROLL;  // (8 until the end of round 4: the passes are latency bound, the workgroup is alone on its CU and has registers to spare)
+                constexpr int U = kEsUnroll;  // (8 until the end of round 4: the passes are latency bound, the workgroup is alone on its CU and has registers to spare)
                 // (round 6, tried and dropped: the whole slice -- 16 / 32 rounds -- read once and kept in registers from the counts to the stop lists.  16 rounds
                 // fit (128 VGPRs, no scratch) and changed nothing (NDT call 0.474-0.479 vs 0.467-0.469 ms), 32 rounds spill: 0.58 ms.  profiles/r06_j_*)
                 unsigned cl = 0u, cr = 0u;

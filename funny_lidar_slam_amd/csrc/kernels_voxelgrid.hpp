@@ -4,14 +4,15 @@
 // finite bounds, leaf index i + j*dx + k*dx*dy per finite point, std::sort of (index, point) records by index, one
 // centroid per run of equal indices, runs in ascending index order.
 //
-// CONTRACT (why this path is opt-in, FLS_DEVICE_VOXELGRID=1):
+// CONTRACT of the index-order form (FLS_DEVICE_VOXELGRID=2, A/B only):
 //   * the SET of leaves, their ORDER and every integer in the pipeline are the reference's (bit-exact);
 //   * a centroid is the float sum of the leaf's points divided by their count.  The reference sums in the order
-//     libstdc++'s std::sort (introsort, unstable) leaves equal keys in; that order is not a function of the leaf alone, so
-//     no parallel algorithm reproduces it.  Here a leaf is summed in ASCENDING POINT INDEX (a stable radix sort): leaves
-//     holding one or two points are bit-identical (float addition commutes), larger leaves differ in the last bits of the
-//     float sum (|delta| <= (count - 2) ulp of the running sum per component; tests/test_gpu_voxelgrid.py measures it).
-//   The host path (host_maps.hpp voxel_grid, the exact std::sort order) stays the default.
+//     libstdc++'s std::sort (introsort, unstable) leaves equal keys in; that order is not a function of the leaf alone.
+//     Here a leaf is summed in ASCENDING POINT INDEX (a stable radix sort): leaves holding one or two points are
+//     bit-identical (float addition commutes), larger leaves differ in the last bits of the float sum (|delta| <= (count - 2)
+//     ulp of the running sum per component; tests/test_gpu_voxelgrid.py measures it).
+//   The default sorts with std::sort's own permutation instead (kernels_exactsort.hpp) and runs the same bodies through the
+//   kernels of kernels_voxelgrid_plan.hpp: bit-identical to the reference.
 //
 // Kernels (n points, 256-thread blocks, tiles of 1024 keys):
 //   vg_minmax      finite bounds (ordered-uint atomics, one set per block)

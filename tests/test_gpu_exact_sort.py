@@ -16,12 +16,12 @@ def _need_gpu(built):
     assert _lib.device_count() >= 1, "gpu tests need an MI355X (gfx950): the HIP path has no CPU fallback"
 
 
-# device modes of the test hook: 0 = the host-steered sequence (DeviceExactSort::run), 2 = what the one-stream VoxelGrid queues (fused_launch: the
-# pre-enqueued levels above 32,768 records, then the task kernel -- no host round trip)
-DEV_MODES = (0, 2)
+# device mode of the test hook: 2 = what the one-stream VoxelGrid queues (fused_launch: the pre-enqueued levels above 32,768 records, then the
+# task kernel -- no host round trip); mode 0 is an alias of it (test_leaf_indices_of_a_real_scan)
+DEV_MODES = (2,)
 
 
-def sort_both(key, dev_mode=0):
+def sort_both(key, dev_mode=2):
     L = _lib.lib()
     val = np.arange(key.size, dtype=np.uint32)
     out = []
@@ -84,7 +84,8 @@ def test_depth_limit_ranges_are_heap_sorted_like_libstdcxx():
 
 
 def test_leaf_indices_of_a_real_scan():
-    """the keys the VoxelGrid actually sorts: leaf indices of a ring-major 64 x 1800 scan at the NDT / ICP leaf sizes"""
+    """the keys the VoxelGrid actually sorts: leaf indices of a ring-major 64 x 1800 scan at the NDT / ICP leaf sizes.  On the first one,
+    on_host = 0 (the C ABI's former host-steered mode) is still accepted and returns exactly mode 2's records."""
     cfg = synth.make_config(2)
     for leaf in (0.5, 0.1, 1.0):
         p = cfg["scan"].astype(np.float32)
@@ -92,7 +93,14 @@ def test_leaf_indices_of_a_real_scan():
         q = np.floor(p * inv).astype(np.int64)
         q -= q.min(0)
         d = q.max(0) + 1
-        check(q[:, 0] + q[:, 1] * d[0] + q[:, 2] * d[0] * d[1], f"scan leaf={leaf}")
+        key = q[:, 0] + q[:, 1] * d[0] + q[:, 2] * d[0] * d[1]
+        check(key, f"scan leaf={leaf}")
+        if leaf == 0.5:
+            assert key.size == 115200
+            (_, _, _), (r0, k0, v0) = sort_both(key, 0)
+            (_, _, _), (r2, k2, v2) = sort_both(key, 2)
+            assert r0 == 0 and r2 == 0, (r0, r2)
+            assert np.array_equal(k0, k2) and np.array_equal(v0, v2)
 
 
 def test_large_cloud_many_levels():

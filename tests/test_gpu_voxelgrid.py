@@ -139,7 +139,7 @@ def test_random_clouds_edge_cases():
 @pytest.mark.parametrize("copies,leaf", [(3, 0.4), (5, 1.0), (13, 0.4)])
 def test_keyframe_deque_clouds_dense_leaves_bit_identical(copies, leaf):
     """The map-side filter of the kd-tree kinds (icp_optimized.h:187, loam_full_kdtree.h:92-100): the concatenated keyframe deque -- clouds beyond 131,072
-    points (the host-steered levels of the exact sort, 8,192-record LDS ranges, round 6), the same surfaces seen from neighbouring poses, leaves of
+    points (the pre-enqueued levels of the exact sort, 4,096-record LDS ranges), the same surfaces seen from neighbouring poses, leaves of
     hundreds to thousands of points (summed by the head's wave: vg_centroid_body's long-run path, incl. partial last rounds).  Every leaf bit-identical."""
     cfg = synth.make_config(2, with_map=False)
     base = cfg["scan"][::2, :3] if copies > 5 else cfg["scan"][:, :3]
@@ -248,20 +248,18 @@ def test_scan_upload_raw_filters_inside_every_resident_match(mode, y, cid, loc):
     a.close(); b.close()
 
 
-def test_fused_launch_sequence_equals_the_round4_sequence(monkeypatch):
-    """FLS_VG_FUSED=0 restores the round-4 host-steered sequence (bounds read back, queue initialised by the runtime, two stream
-    synchronisations); the default derives the plan on the device and publishes the verdict to a mailbox.  Same bits either way,
-    including what both decline."""
+def test_one_stream_sequence_accepts_and_declines_like_the_reference():
+    """The one stream of launches (plan derived on the device, verdict published to a mailbox) serves every exact-order cloud, a single
+    point included (no sort launch: n < 2).  Every cloud it accepts is the oracle's, bit for bit; a NaN point and PCL's "leaf size too
+    small" case are declined (the host filter takes them)."""
     cfg = synth.make_config(2, scale=0.3)
     cloud = np.concatenate([cfg["scan"], np.linspace(0, 1, len(cfg["scan"]), dtype=np.float32)[:, None]], axis=1)
     bad = cloud.copy(); bad[5, 1] = np.nan
     far = np.array([[0, 0, 0, 1], [1e6, 1e6, 1e6, 2]], np.float32)
-    res = {}
-    for fused in ("1", "0"):
-        monkeypatch.setenv("FLS_VG_FUSED", fused)
-        res[fused] = [device_voxel_grid(c, leaf) for c, leaf in ((cloud, 0.2), (cloud[:1], 0.2), (cloud[:700], 1.0), (bad, 0.2), (far, 0.1))]
-    for (rc1, o1), (rc0, o0) in zip(res["1"], res["0"]):
-        assert rc1 == rc0 and np.array_equal(o1.view(np.uint32), o0.view(np.uint32))
-    assert [r[0] for r in res["1"]] == [0, 0, 0, _lib.FLS_ERR_STATE, _lib.FLS_ERR_STATE]
-    ref = O.voxel_grid(cloud, 0.2)
-    assert np.array_equal(res["1"][0][1].view(np.uint32), ref.view(np.uint32))
+    cases = ((cloud, 0.2), (cloud[:1], 0.2), (cloud[:700], 1.0), (bad, 0.2), (far, 0.1))
+    res = [device_voxel_grid(c, leaf) for c, leaf in cases]
+    assert [r[0] for r in res] == [0, 0, 0, _lib.FLS_ERR_STATE, _lib.FLS_ERR_STATE]
+    for (c, leaf), (rc, out) in zip(cases, res):
+        if rc == 0:
+            ref = O.voxel_grid(c, leaf)
+            assert out.shape == ref.shape and np.array_equal(out.view(np.uint32), ref.view(np.uint32)), (len(c), leaf)

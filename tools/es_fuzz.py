@@ -1,6 +1,6 @@
 """Fuzz of the device exact sort against libstdc++'s std::sort (same C entry point, on_host = 1): random sizes around every regime boundary
 (16 / 64 / 2,048 / 4,096 / 32,768 / 131,072 records), key distributions from all-equal to all-distinct, and LiDAR-like piecewise-monotone
-leaf indices (what drives introsort into its lopsided recursion and its heap-sort fallback).  usage: python tools/es_fuzz.py [n_cases] [seed] [device mode: 0 = host-steered sequence, 2 = the one-stream VoxelGrid's pre-enqueued sequence] [max n]"""
+leaf indices (what drives introsort into its lopsided recursion and its heap-sort fallback).  usage: python tools/es_fuzz.py [n_cases] [seed] [device mode: 2 = the one-stream VoxelGrid's pre-enqueued sequence, 0 = an alias of 2] [max n]"""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,7 +1,7 @@
 """The map-side pcl::VoxelGrid of the kd-tree kinds on the clouds bench.py's mapping_mode legs filter (the concatenated keyframe deque of
 IcpOptimized: 31 x 14,400 points, leaf 0.4 m; LoamFull planar: 25 x 57,600, leaf 0.4 m; LoamFull corner: 25 x 7,680, leaf 0.2 m), timed on
 its own through fls_debug_voxel_grid_timed: wall-clock per call with the buffers allocated, for whatever build / switches the environment
-selects (FLS_REG_LIB, FLS_ES_*).  `python tools/gpu_vg_large.py [reps] [which,...]`; FLS_ES_DEBUG=1 adds the exact sort's stage stamps."""
+selects (FLS_REG_LIB, FLS_ES_DEBUG).  `python tools/gpu_vg_large.py [reps] [which,...]`; FLS_ES_DEBUG=1 adds the exact sort's stage stamps."""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
