@@ -3,6 +3,9 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line.
 For N > 1 the driver launches it through ``torch.distributed.run`` (one rank per GPU, RCCL).
+Such a plain run does only what the headline needs: set-up, the untimed pre-warm Matches and W warm-up steps, the K timed steps,
+--dump-outputs if asked, and the line (metric, value, unit, ms_per_step, protocol, config, legs).  ``--full`` adds everything else
+listed below; the --no-* options leave out parts of that.
 
 A "step" is one full ``Match`` (all Gauss-Newton iterations until the reference's own stop
 rule, map update excluded) of one synthetic Velodyne-64 scan (64 x 1800 = 115,200 points)
@@ -14,7 +17,7 @@ that value(N) / N is comparable with value(1); independent jobs, no data-path co
 the other ranks; the only other collectives are the start/stop barriers, the MAX
 of the per-rank times and the gather of the poses.
 
-Extra objects on the line:
+Extra objects on the line with --full:
   roofline      the correspondence kernel of the headline path: algorithmic bytes per launch (8d formula, counters
                 counted on the device and checked against the oracle's) / average launch duration measured with
                 hipEvents attached to the kernel's own dispatch packet during the timed region; `traffic` = HBM
@@ -674,10 +677,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batch", action="store_true", help="skip the configs[4] batch measurement")
-    ap.add_argument("--no-native-batch", action="store_true", help="skip c5_batch_native (configs[4] through fls_replicas_match_batch, one process / N devices)")
-    ap.add_argument("--no-extras", action="store_true", help="skip configs[0,2,3], mapping_mode, inclusive_h2d (N = 1 extras)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline too: roofline, oracle comparison, configs[0,2,3], mapping_mode, "
+                         "loop_closure, inclusive_h2d, the configs[4] batch legs, the CPU baselines (the --no-* options leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and cpu_baseline_ref")
+    ap.add_argument("--no-batch", action="store_true", help="with --full: skip the configs[4] batch measurement")
+    ap.add_argument("--no-native-batch", action="store_true", help="with --full: skip c5_batch_native (configs[4] through fls_replicas_match_batch, one process / N devices)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip configs[0,2,3], mapping_mode, loop_closure, inclusive_h2d (N = 1 extras)")
     ap.add_argument("--batch-jobs", type=int, default=512, help="configs[4] jobs in total at 8 GPUs (64 per GPU); scaled by n_gpus / 8 below 8 GPUs unless --batch-jobs-total")
     ap.add_argument("--batch-jobs-total", type=int, default=0, help="configs[4]: total number of jobs (default: 512 at N = 1 and at N = 8, 64 * N otherwise)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -701,13 +707,16 @@ def main():
     # 1-GPU box (tests/test_gpu_batch_ranks.py::test_rccl_path_at_world_size_1; VERDICT r4 missing #1)
     distributed = world > 1 or ("RANK" in os.environ and "WORLD_SIZE" in os.environ and "MASTER_PORT" in os.environ)
     n_gpus = world if distributed else 1
+    full = args.full
+    batch_legs = full and not args.no_batch
+    native_leg = batch_legs and not args.no_native_batch
 
     from funny_lidar_slam_amd import batch, synth
 
     # configs[4] inputs first (host cores, forked workers: nothing GPU-side may be initialised yet)
     n_jobs = args.batch_jobs_total or (512 if n_gpus in (1, 8) else 64 * n_gpus)
     my_scans, all_scans, job_range = [], [], (0, 0)
-    if not args.no_batch:
+    if batch_legs:
         job_range = batch.partition(n_jobs, n_gpus, rank)
         t_gen = time.perf_counter()
         # every rank casts ITS block only; rank 0, which also drives the native one-process form over ALL jobs (c5_batch_native), collects
@@ -729,12 +738,12 @@ def main():
         else:
             dist.init_process_group(backend="gloo")
     host_group = None  # CPU-side group: the scan gather below, and the idle barrier of the native-batch leg
-    if distributed and not args.no_batch and not args.no_native_batch:
+    if distributed and native_leg:
         host_group = dist.new_group(backend="gloo")
         t_g = time.perf_counter()
         all_scans = batch.gather_scans(my_scans, n_jobs, dst=0, group=host_group)
         t_gather = time.perf_counter() - t_g
-    elif not args.no_batch and not args.no_native_batch:
+    elif native_leg:
         all_scans, t_gather = my_scans, 0.0
     if args.gpus != n_gpus:
         # a launcher that started a different number of ranks than --gpus says: refuse rather than report a line for the wrong N
@@ -838,24 +847,26 @@ def main():
     T_head = np.array(T)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, T_head, ok, m.stats)
-    # algorithmic-traffic counters: one extra (untimed) Match with the counting kernel variant
-    m.set_profiling(False, counters=True)
-    step()
-    probes, hits, cand = m.traffic_counters()
-    m.set_profiling(False, counters=False)
-    assert m.stats.iterations == iters
+    if full:
+        # algorithmic-traffic counters: one extra (untimed) Match with the counting kernel variant
+        m.set_profiling(False, counters=True)
+        step()
+        probes, hits, cand = m.traffic_counters()
+        m.set_profiling(False, counters=False)
+        assert m.stats.iterations == iters
 
     if distributed:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if distributed and full:
         row = batch.pack_result(T_head, ok, m.stats.iterations, m.stats.n_valid, m.stats.sum_res)
         table = batch.gather_results(row[None, :], world, batch.RESULT_WIDTH, device=coll_dev)  # one job per rank per step
         assert table.shape == (world, batch.RESULT_WIDTH)
         assert bool(np.all(table == table[0])), "identical jobs on identical GPUs (imported map image) must give bit-identical results"
 
     c5 = None
-    if not args.no_batch:
+    if batch_legs:
         # configs[4]: job ids block-partitioned (batch.partition), every job its own scan, 8 stream lanes per GPU
         # (tools/gpu_batch.py, 256 jobs: 1 lane 3.8k, 2: 7.0k, 4: 7.7k, 8: 10.2k, 16: 10.8k scans/s)
         lanes = 8
@@ -901,7 +912,7 @@ def main():
     # block-partitioned like batch.partition and run through fls_match_batch per device; results land in the caller's arrays, no collective.
     # The other ranks idle on a CPU-side (gloo) barrier meanwhile -- an RCCL barrier would spin a kernel on the GPUs being measured.
     c5n = None
-    if not args.no_batch and not args.no_native_batch:
+    if native_leg:
         idle = host_group
         if rank == 0:
             try:
@@ -913,27 +924,9 @@ def main():
     del all_scans
 
     if rank == 0:
-        from oracle import oracle as O
-        from tests import util
         total_scans = args.steps * n_gpus
         value = total_scans / elapsed
-        per_launch_bytes = algorithmic_bytes(point_iters=cfg["scan"].shape[0] * iters, probes=probes, hits=hits, cand=cand) / max(iters, 1)
-        avg_launch_s = (ms_kernel / 1e3) / max(launches, 1)
-        achieved = per_launch_bytes / avg_launch_s / 1e9 if launches else 0.0
         dt, dr = synth.pose_error(T_head, cfg["T_gt"])
-        # HBM bytes per launch / what limits the kernel, from the committed PMC passes (rocprofv3 cannot collect counters from
-        # inside this process; gpurun keeps --pmc runs separate from everything else): profiles/traffic_ivox_knn.json
-        traffic, detail = None, None
-        try:
-            with open(os.path.join(ROOT, "profiles", "traffic_ivox_knn.json")) as f:
-                tj = json.load(f)
-            traffic = float(tj["hbm_bytes_per_launch"])
-            detail = {k: tj[k] for k in ("l2_read_bytes_per_launch", "valu_busy_pct", "wave_wait_pct", "valu_wave_instructions_per_launch",
-                                         "instruction_floor_us", "source") if k in tj}
-            if traffic and avg_launch_s:
-                detail["measured_hbm_GBs"] = traffic / avg_launch_s / 1e9
-        except (OSError, KeyError, ValueError):
-            traffic = None
         line = {
             "metric": baseline_metric(),
             "value": value, "unit": "scans/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -948,38 +941,57 @@ def main():
                        "scan_points": int(cfg["scan"].shape[0]), "map_points": int(m.map_size()),
                        "gn_iterations": int(iters), "converged": bool(ok), "pose_err_vs_gt_m_rad": [dt, dr],
                        "pre_warm_matches": PRE_WARM_MATCHES},
-            "roofline": {"bound": "hbm", "kernel": "ivox_knn_kernel<4>", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": "profiles/traffic_ivox_knn.json (separate rocprofv3 --pmc passes, bytes per launch)",
-                         "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_us": 1e6 * avg_launch_s,
-                         "launches_timed": int(launches), "device_counters": {"probes": int(probes), "hit_voxels": int(hits), "cand_points": int(cand)}},
         }
-        if detail:
-            line["roofline"]["detail"] = detail
-        # the OTHER kernel of an iteration: per-point plane fit + Jacobian + the 29 normal-equation sums + the Gauss-Newton tail in the last
-        # workgroup.  Not a streaming kernel: ~600 FP64 flop and 112 B of gathered rows per point, then a serial fan-in + one-wave tail.
-        try:
-            with open(os.path.join(ROOT, "profiles", "traffic_p2plane_fit_solve.json")) as f:
-                fj = json.load(f)
-            n_pts = int(cfg["scan"].shape[0])
-            fit_bytes = n_pts * (12 + 32 + 5 * 16 + 7 * 8 + 1)  # xyz + id row + five gathered map points + J s | |d| row (Q1 state) + flag, per point
-            fit_flop = n_pts * 600
-            lus = float(fj["trace_avg_launch_us"])
-            line["roofline_fit_kernel"] = {
-                "kernel": "p2plane_fit_solve_kernel", "avg_launch_us": lus, "launch_geometry": "225 workgroups x 512 threads = 1.76 waves / SIMD, 127 VGPRs",
-                "algorithmic_bytes_per_launch": fit_bytes, "achieved_GBs_by_algorithmic_bytes": fit_bytes / (lus * 1e-6) / 1e9, "frac_of_hbm_peak": fit_bytes / (lus * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                "fp64_flop_per_launch": fit_flop, "achieved_fp64_TFLOPs": fit_flop / (lus * 1e-6) / 1e12,
-                "traffic": fj.get("hbm_bytes_per_launch"), "measured_hbm_GBs": fj.get("measured_hbm_GBs"), "valu_busy_pct": fj.get("valu_busy_pct"),
-                "wave_wait_pct": fj.get("wave_wait_pct"), "l2_hit_rate": fj.get("l2_hit_rate"),
-                "bound": "latency: ~8 us of parallel per-point work, then the fan-in of 225 partial rows and a single-wave Gauss-Newton tail (serial)",
-                "source": "profiles/traffic_p2plane_fit_solve.json (tools/prof_round5.sh kinds: kernel trace + four PMC passes)"}
-        except (OSError, KeyError, ValueError):
-            pass
+        if full:
+            from oracle import oracle as O
+            from tests import util
+            per_launch_bytes = algorithmic_bytes(point_iters=cfg["scan"].shape[0] * iters, probes=probes, hits=hits, cand=cand) / max(iters, 1)
+            avg_launch_s = (ms_kernel / 1e3) / max(launches, 1)
+            achieved = per_launch_bytes / avg_launch_s / 1e9 if launches else 0.0
+            # HBM bytes per launch / what limits the kernel, from the committed PMC passes (rocprofv3 cannot collect counters from
+            # inside this process, and --pmc passes run on their own): profiles/traffic_ivox_knn.json
+            traffic, detail = None, None
+            try:
+                with open(os.path.join(ROOT, "profiles", "traffic_ivox_knn.json")) as f:
+                    tj = json.load(f)
+                traffic = float(tj["hbm_bytes_per_launch"])
+                detail = {k: tj[k] for k in ("l2_read_bytes_per_launch", "valu_busy_pct", "wave_wait_pct", "valu_wave_instructions_per_launch",
+                                             "instruction_floor_us", "source") if k in tj}
+                if traffic and avg_launch_s:
+                    detail["measured_hbm_GBs"] = traffic / avg_launch_s / 1e9
+            except (OSError, KeyError, ValueError):
+                traffic = None
+            line["roofline"] = {"bound": "hbm", "kernel": "ivox_knn_kernel<4>", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                                "traffic_source": "profiles/traffic_ivox_knn.json (separate rocprofv3 --pmc passes, bytes per launch)",
+                                "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_us": 1e6 * avg_launch_s,
+                                "launches_timed": int(launches), "device_counters": {"probes": int(probes), "hit_voxels": int(hits), "cand_points": int(cand)}}
+            if detail:
+                line["roofline"]["detail"] = detail
+            # the OTHER kernel of an iteration: per-point plane fit + Jacobian + the 29 normal-equation sums + the Gauss-Newton tail in the last
+            # workgroup.  Not a streaming kernel: ~600 FP64 flop and 112 B of gathered rows per point, then a serial fan-in + one-wave tail.
+            try:
+                with open(os.path.join(ROOT, "profiles", "traffic_p2plane_fit_solve.json")) as f:
+                    fj = json.load(f)
+                n_pts = int(cfg["scan"].shape[0])
+                fit_bytes = n_pts * (12 + 32 + 5 * 16 + 7 * 8 + 1)  # xyz + id row + five gathered map points + J s | |d| row (Q1 state) + flag, per point
+                fit_flop = n_pts * 600
+                lus = float(fj["trace_avg_launch_us"])
+                line["roofline_fit_kernel"] = {
+                    "kernel": "p2plane_fit_solve_kernel", "avg_launch_us": lus, "launch_geometry": "225 workgroups x 512 threads = 1.76 waves / SIMD, 127 VGPRs",
+                    "algorithmic_bytes_per_launch": fit_bytes, "achieved_GBs_by_algorithmic_bytes": fit_bytes / (lus * 1e-6) / 1e9, "frac_of_hbm_peak": fit_bytes / (lus * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                    "fp64_flop_per_launch": fit_flop, "achieved_fp64_TFLOPs": fit_flop / (lus * 1e-6) / 1e12,
+                    "traffic": fj.get("hbm_bytes_per_launch"), "measured_hbm_GBs": fj.get("measured_hbm_GBs"), "valu_busy_pct": fj.get("valu_busy_pct"),
+                    "wave_wait_pct": fj.get("wave_wait_pct"), "l2_hit_rate": fj.get("l2_hit_rate"),
+                    "bound": "latency: ~8 us of parallel per-point work, then the fan-in of 225 partial rows and a single-wave Gauss-Newton tail (serial)",
+                    "source": "profiles/traffic_p2plane_fit_solve.json (tools/prof_round5.sh kinds: kernel trace + four PMC passes)"}
+            except (OSError, KeyError, ValueError):
+                pass
         if c5 is not None:
             line["c5_batch"] = c5
         if c5n is not None:
             line["c5_batch_native"] = c5n
-        if n_gpus == 1:
+        if full and n_gpus == 1:
             # the CPU oracle on the same inputs: pose error of the headline result, and the device counters against the oracle's
             # (the timed steps re-register the same scan on ONE handle, and nearest_points_ persists from Match to Match in the
             # reference -- Q15: a point without candidates keeps its previous list -- so the steady-state step equals the oracle's

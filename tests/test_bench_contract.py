@@ -88,7 +88,7 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     import sys
 
     out = tmp_path / "dump"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-batch", "--no-extras",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-batch", "--no-extras",
                         "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
@@ -103,3 +103,34 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert files["stats_iterations.npy"][0] == line["config"]["gn_iterations"] and bool(files["converged.npy"][0]) == line["config"]["converged"]
     same = line["pose_err_vs_oracle"]["timed_step_vs_oracle_same_call_index"]
     assert same["dt_m"] < 1e-4 and same["dR_rad"] < 1e-4 and same["same_n_valid"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_computes_what_full_computes(tmp_path):
+    """Without --full the line carries the headline only (no roofline, oracle comparison, configs, batch legs or CPU baselines), and the
+    last timed step returns bit for bit what it returns in a --full run: the legs --full adds run after the timed steps."""
+    import subprocess
+    import sys
+
+    lines, dumps = [], []
+    for extra in ([], ["--full", "--no-batch", "--no-extras", "--no-cpu-baseline"]):
+        out = tmp_path / ("full" if extra else "plain")
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", *extra,
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        got = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+        assert len(got) == 1, p.stdout[-2000:]
+        lines.append(json.loads(got[0]))
+        dumps.append({f.name: np.load(f) for f in out.iterdir()})
+    plain, full = lines
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "legs"):
+        assert k in plain, k
+    assert plain["steps"] == 3 and plain["higher_is_better"] is True and plain["dtype"] == "f64" and plain["unit"] == "scans/s"
+    assert abs(plain["value"] - 1e3 / plain["ms_per_step"]) < 1e-6 * plain["value"]
+    assert list(plain)[-1] == "legs" and "headline_us" in plain["legs"]
+    for k in ("roofline", "roofline_fit_kernel", "pose_err_vs_oracle", "configs", "mapping_mode", "loop_closure", "inclusive_h2d", "c5_batch",
+              "c5_batch_native", "cpu_baseline", "cpu_baseline_ref"):
+        assert k not in plain, k
+    assert "roofline" in full and "pose_err_vs_oracle" in full
+    assert set(dumps[0]) == set(dumps[1]) and all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
+    assert plain["config"]["gn_iterations"] == full["config"]["gn_iterations"]

@@ -3,7 +3,7 @@ print every leg that moved by more than a threshold (default 10 %).
 
     python tools/bench_diff.py NEW [OLD] [--threshold 0.10] [--all]
 
-NEW / OLD: a file holding one bench.py JSON line (profiles/rNN_*_bench_full.json, gpurun_out/.../bench.json) or a driver record (BENCH_rNN.json:
+NEW / OLD: a file holding one `bench.py --full` JSON line (profiles/rNN_*_bench_full.json, or a new run's output) or a driver record (BENCH_rNN.json:
 `parsed` + the last 2,000 characters of the line in `tail`).  OLD defaults to the newest BENCH_r*.json at the repository root, completed -- for the
 legs its truncated tail no longer holds -- from the newest builder-kept full line of that round under profiles/ (named in the output).
 The legs are bench.py's LEGS table: since round 6 the line ends with them (`legs`, flat), so the driver's tail always carries all of them; lines of

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $OUT/bench_full.json 2> $OUT/bench_full.err
+timeout 600 python $R/bench.py --full --steps 20 --warmup 5 > $OUT/bench_full.json 2> $OUT/bench_full.err
 BENCH="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-extras"
 rm -rf /tmp/p_trace; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- $BENCH > $OUT/bench_under_trace.json 2> $OUT/trace.log
 cp $(find /tmp/p_trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null
