@@ -89,8 +89,6 @@ struct NdtMatcher final : fls_matcher {
         d_ticket.reserve(kTicketWords);
         FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
         if (const char* e = std::getenv("FLS_NDT_DEVICE_UPDATE")) allow_device_update = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_NDT_DEVICE_MARGIN")) { const long c = std::atol(e); if (c >= 0) device_margin = size_t(c); }
-        if (const char* e = std::getenv("FLS_NDT_DEVICE_EVICT")) device_evict = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_NDT_DEVICE_SLACK")) { const long c = std::atol(e); if (c >= 0) device_slack = size_t(c); }
         inv_voxel = 1.0 / p.ndt_voxel_size;
         return FLS_OK;
@@ -258,10 +256,8 @@ struct NdtMatcher final : fls_matcher {
     // per-voxel bookkeeping lives in device rows, the host mirror (pool / LRU list / key map) is stale until
     // sync_host_from_device().  Entered after a host-path update in mapping mode, left for good by the first refused batch.
     bool allow_device_update = true;  // FLS_NDT_DEVICE_UPDATE
-    size_t device_margin = 4096;      // FLS_NDT_DEVICE_MARGIN: voxels below the LRU capacity at which device mode is not entered
     size_t device_slack = 65536;      // FLS_NDT_DEVICE_SLACK: spare table entries / rows allocated ahead (test hook: small values force growth)
     bool device_mode = false, device_left = false;
-    bool device_evict = true;         // FLS_NDT_DEVICE_EVICT=0: a batch that reaches the LRU capacity is refused (round-2 behaviour; with it the margin rule applies)
     unsigned host_updates_since_left = 0;  // device mode is re-entered after a refusal once eight host-path updates went by (hysteresis)
     unsigned upd_seq = 0;
     size_t dev_entries = 0;           // table entries in use (alive voxels + tombstones since the last re-hash)
@@ -297,9 +293,8 @@ struct NdtMatcher final : fls_matcher {
         // after a refusal (device_left) the handle comes back once eight host-path updates went by: a scan that left the key range or
         // an eviction the device could not order exactly is an episode, not a reason to stay on the 2 ms host path for good
         const bool left = device_left && host_updates_since_left < 8;
-        const bool room = device_evict ? true : n_alive + device_margin < size_t(p.ndt_capacity);  // (without device evictions: stay clear of the capacity)
         return allow_device_update && !left && !device_mode && !owner && !p.is_localization_mode && !flag_first_scan &&
-               p.ndt_min_points_in_voxel <= kNdtCarry && p.ndt_min_points_in_voxel >= 0 && room && p.ndt_capacity > 2;
+               p.ndt_min_points_in_voxel <= kNdtCarry && p.ndt_min_points_in_voxel >= 0 && p.ndt_capacity > 2;
     }
     // uploads the whole host mirror as rows (LRU order: row 0 = least recently touched) + a table holding every alive voxel
     void enter_device_mode(size_t batch_hint) {
@@ -387,7 +382,7 @@ struct NdtMatcher final : fls_matcher {
             upd_seq = 1u;
             FLS_HIP(hipMemsetAsync(r_touch.p, 0, r_touch.cap * sizeof(unsigned long long), stream));
         }
-        const bool may_evict = device_evict && dev_alive + n >= size_t(p.ndt_capacity);  // every point a new voxel: the worst case
+        const bool may_evict = dev_alive + n >= size_t(p.ndt_capacity);  // every point a new voxel: the worst case
         NdtUpdState& hs = h_upd.p[0];
         hs = NdtUpdState{};
         hs.n_rows = unsigned(dev_rows); hs.n_alive = unsigned(dev_alive); hs.next_vid = dev_next_vid; hs.epoch = dev_epoch;
@@ -539,7 +534,7 @@ struct NdtMatcher final : fls_matcher {
                 }
                 return FLS_OK;
             }
-            sync_host_from_device();  // refused (a batch that would evict, a key out of range): exact sequential replay below
+            sync_host_from_device();  // refused (evictions that would reach voxels of the batch itself): exact sequential replay below
         }
         ++epoch;
         std::vector<int> touched;

@@ -39,15 +39,12 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // (points, voxel table, LRU stamps, counters) and the host mirror `ivox` is stale; sync_host_from_device() brings it back.
     bool device_map = false;
     bool allow_device_map = true;  // FLS_IVOX_DEVICE_UPDATE=0: always the host path (A/B)
-    size_t device_margin = 4096;   // voxels of head-room below the LRU capacity required to (re-)enter device mode (FLS_IVOX_DEVICE_MARGIN: test hook)
     size_t n_device_updates = 0, n_host_fallbacks = 0, n_device_evictions = 0, n_device_recreated = 0, n_refused_conflict = 0, n_refused_full = 0, n_refused_outside = 0;
-    bool short_chain_update = true;  // FLS_IVOX_SHORT_CHAIN=0 (A/B): the round-3 chain of eleven launches for every batch
     size_t n_short_updates = 0;
     // the decision + update chain queued behind the iterations the Match is expected to need, gated on the device (ivox_add_decide_kernel):
-    // removes the host's mailbox turnaround + first-launch latency (~14 us) in front of the map update.  FLS_IVOX_SPECULATIVE=0: wait first.
-    bool speculative_update = true, spec_pending = false, last_chain_skipped = false;
+    // removes the host's mailbox turnaround + first-launch latency (~14 us) in front of the map update
+    bool spec_pending = false, last_chain_skipped = false;
     size_t n_speculative = 0, n_speculative_skipped = 0;
-    bool device_evict = true;      // FLS_IVOX_DEVICE_EVICT=0: a batch that reaches the LRU capacity is refused (round-2 behaviour, with the margin rule)
     DevicePairSort ev_sort;
     DevBuf<unsigned> d_ev_bt, d_crank, d_evict_list;
     DevBuf<IvoxUpdState> d_upd_state;
@@ -100,10 +97,6 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_HOST_TIMING")) host_timing = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_DEVICE_MARGIN")) { const long c = std::atol(e); if (c >= 0) device_margin = size_t(c); }
-        if (const char* e = std::getenv("FLS_IVOX_DEVICE_EVICT")) device_evict = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_SHORT_CHAIN")) short_chain_update = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_IVOX_SPECULATIVE")) speculative_update = std::atoi(e) != 0;
         d_upd_state.reserve(1);
         FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
         std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
@@ -137,11 +130,10 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     }
 
     // Hand the map over to the device-side AddPoints: the brick image has no extent limit, so the only conditions left are the A/B
-    // switches (and, without device evictions, a margin below the LRU capacity).
+    // switch, a brick image and mapping mode.
     void enter_device_mode() {
         device_map = false;
         if (!allow_device_map || borrowed || !use_dense || !image.have_bricks || image.want_hash || p.is_localization_mode) return;
-        if (!device_evict && ivox.n_alive + device_margin >= ivox.capacity) return;  // without device evictions: stay clear of the capacity
         if (ivox.capacity < 4) return;
         const unsigned long long stamp_base = image.upload_update_meta(ivox, stream, upd_stage);
         IvoxUpdState st{};
@@ -211,9 +203,9 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         upd_seq = (upd_seq + 1u) & 0x7fffffffu;
         if (upd_seq == 0u) upd_seq = 1u;
         const dim3 g{unsigned(nb), 1u, 1u}, t{unsigned(kUpdBlock), 1u, 1u};
-        // two forms of the same phases (kernels_ivox_update.hpp): the SHORT chain (default: five launches behind the decision) and the
-        // LONG chain, which batches that may reach the LRU capacity need (the eviction selection has grid-wide steps of its own)
-        const bool short_chain = short_chain_update && dev_n_alive + n < ivox.capacity && counted_by_decide;
+        // two forms of the same phases (kernels_ivox_update.hpp): the SHORT chain (five launches behind the decision) and the LONG
+        // chain, which batches that may reach the LRU capacity need (the eviction selection has grid-wide steps of its own)
+        const bool short_chain = dev_n_alive + n < ivox.capacity && counted_by_decide;
         if (short_chain) {
             hipLaunchKernelGGL(ivox_upd_seq_nb, g, t, 0, stream, b, a, d_upd_state.p, nb);
             hipLaunchKernelGGL(ivox_upd_plan, g, t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
@@ -229,7 +221,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         hipLaunchKernelGGL(ivox_upd_plan, g, t, 0, stream, b, a, (const IvoxUpdState*)d_upd_state.p);
         // LRU evictions inside the batch: whenever the batch COULD reach the capacity (every point a new voxel), the alive cells are
         // listed and sorted by their 64-bit stamp (two stable 32-bit radix rounds) so that scan2 / ivox_evict_check can pick the tail
-        const bool may_evict = device_evict && dev_n_alive + n >= ivox.capacity && dev_n_alive > 0;
+        const bool may_evict = dev_n_alive + n >= ivox.capacity && dev_n_alive > 0;
         unsigned n_list = 0;
         if (may_evict) {
             const unsigned ncell = unsigned(dev_n_bricks * kBrickStride), nbe = (ncell + kEvBlock - 1) / kEvBlock;  // (bricks this batch creates hold no candidate)
@@ -577,8 +569,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         const BrickDir win = use_dense ? im.bricks() : BrickDir{nullptr, 0u, nullptr, 0u};
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
-        // speculative map update (see speculative_update): only where the short chain applies and the call would update the map if it converges
-        const bool spec = speculative_update && update_map && !p.is_localization_mode && !borrowed && !is_first && device_map && short_chain_update &&
+        // speculative map update (see spec_pending): only where the short chain applies and the call would update the map if it converges
+        const bool spec = update_map && !p.is_localization_mode && !borrowed && !is_first && device_map &&
                           dev_n_alive + n < ivox.capacity && int((n + kUpdBlock - 1) / kUpdBlock) <= kUpdMaxBlocks;
         spec_pending = false;
         auto after_chunk = [&](int) {

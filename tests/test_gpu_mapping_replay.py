@@ -64,11 +64,11 @@ def test_icp_mapping_replay():
     assert all(x["upd"] == 0 for x in h if not x["ok"]), "Q10: no map update without convergence"
 
 
-def test_ndt_mapping_replay(monkeypatch):
+def test_ndt_mapping_replay_host_evictions(monkeypatch):
     """IncrementalNDT in mapping mode: non-first-scan UpdateVoxel (min / max points, pooled mean + covariance, SVD clamp),
     LRU eviction at the (shrunk) capacity, Q11 (map update with the input pose -- every guess differs from the result).
-    HOST path of the evictions (FLS_NDT_DEVICE_EVICT=0: the margin rule keeps a handle this close to its capacity off the device)."""
-    monkeypatch.setenv("FLS_NDT_DEVICE_EVICT", "0")
+    HOST path of the evictions (FLS_NDT_DEVICE_UPDATE=0; the device evictions of the same frames: ..._with_conflicts below)."""
+    monkeypatch.setenv("FLS_NDT_DEVICE_UPDATE", "0")
     r, h = run_replay("ndt")
     cap = r["y"]["ndt_capacity"]
     assert all(x["upd"] == 1 for x in h)
@@ -98,16 +98,20 @@ def test_ndt_mapping_replay_device_update_growing_arrays(monkeypatch):
     assert r["device_growths"][0] >= 1 or r["device_growths"][1] >= 1, r["device_growths"]
 
 
-def test_ndt_mapping_replay_device_refusal(monkeypatch):
-    """Capacity 2,600 with no safety margin: device mode is entered below the capacity, the first batch that would evict is
-    refused without side effects, the device state comes back to the host mirror (LRU order from the stamps, pending points
-    from the carry buffers) and the exact sequential path takes over -- including the evictions."""
-    monkeypatch.setenv("FLS_NDT_DEVICE_MARGIN", "0")
-    monkeypatch.setenv("FLS_NDT_DEVICE_EVICT", "0")  # (with device evictions the batch would simply be applied: next test)
-    r, h = run_replay("ndt")
+def test_ndt_mapping_replay_device_refusal_when_the_batch_evicts_its_own_voxels():
+    """Capacity 700: four 12 m scans (about 380 voxels each) run on the device; then the sensor range jumps to 40 m and the batch
+    creates about 1,000 voxels, so the sequential loop would evict voxels this batch itself created (incremental_ndt.h:202-206).  The
+    device refuses that batch without side effects, the device state comes back to the host mirror (LRU order from the stamps, pending
+    points from the carry buffers) and the exact sequential path takes over -- including the evictions."""
+    r = replay.make_replay("ndt_dev", max_range=12.0, y_over=dict(ndt_capacity=700))
+    scene = synth.make_scene()
+    rng = synth.rng_for(5, 99)
+    for f in r["frames"][4:]:
+        f["scan"] = synth.cast_scan(scene, f["T_gt"], rng=rng, max_range=40.0, **dict(synth.VELODYNE_64, n_az=100))
+    r, h = run_replay("ndt_dev", r=r)
     applied, refused = r["device_updates"]
     cap = r["y"]["ndt_capacity"]
-    assert refused == 1 and applied >= 1, (applied, refused)
+    assert refused == 1 and applied >= 1, (applied, refused)  # (eight host-path updates go by before device mode is entered again)
     assert h[-1]["size"] == cap - 1
 
 

@@ -173,19 +173,14 @@ def test_pcl_layout_stride8_equals_packed():
     assert np.array_equal(res[0], res[1])
 
 
-def _replay(n_scans, capacity=None, monkeypatch=None, capacity_over_initial=None):
-    """Mapping-mode replay along a short trajectory: Match -> AddCloudToLocalMap rule -> next Match."""
+def _replay(n_scans, capacity=None, monkeypatch=None, radius=30.0, max_range=None):
+    """Mapping-mode replay along a short trajectory: Match -> AddCloudToLocalMap rule -> next Match.  radius: of the prior map;
+    max_range: of the sensor (default: 8 m beyond the mapped disc, so the map grows)."""
     scene = synth.make_scene()
     rng = synth.rng_for(1, 11)
-    radius = 30.0
     mp = synth.sample_map(scene, 60000, synth.rng_for(1, 0, 5), radius=radius)
     lid = dict(synth.VELODYNE_64, n_az=60)
     o = util.oracle_for("PointToPlane_IVOX", reg.YAML_NCLT_IVOX)
-    if capacity_over_initial is not None:  # LRU capacity = voxels of the initial map + this many (the reference hard-codes 1e6)
-        probe = util.oracle_for("PointToPlane_IVOX", reg.YAML_NCLT_IVOX)
-        probe.AddCloudToLocalMap(mp)
-        capacity = probe.map_voxels() + capacity_over_initial
-        probe.close()
     if capacity is not None:
         monkeypatch.setenv("FLS_IVOX_CAPACITY", str(capacity))
         o.set_ivox_capacity(capacity)
@@ -197,7 +192,7 @@ def _replay(n_scans, capacity=None, monkeypatch=None, capacity_over_initial=None
     guess = np.eye(4)
     for k in range(n_scans):
         Tgt = Tgt @ synth.random_pose(rng, 1.0, 0.6)
-        scan = synth.cast_scan(scene, Tgt, rng=rng, max_range=radius + 8.0, **lid)  # sees beyond the mapped disc: the map grows
+        scan = synth.cast_scan(scene, Tgt, rng=rng, max_range=radius + 8.0 if max_range is None else max_range, **lid)
         T = guess.copy()
         ok = m.Match(reg.PointcloudCluster(planar_cloud_=scan), T, update_map=True)
         ok_ref, T_ref = o.Match(scan, guess, update_map=True)
@@ -226,15 +221,14 @@ def test_mapping_replay_host_path_ab(monkeypatch):
     assert m.map_size(103) == 0 and m.map_size(100) >= 3
 
 
-def test_mapping_replay_device_refuses_batch_that_would_evict(monkeypatch):
-    """LRU capacity a little above the initial map: the first scans are applied by the device; the batch whose voxel creations
-    would reach the capacity is refused BEFORE any state changes, the device image (points, voxel table, LRU stamps) is read back
-    into the host mirror and the exact sequential path -- with evictions -- takes over.  Parity with the oracle throughout."""
-    monkeypatch.setenv("FLS_IVOX_DEVICE_MARGIN", "64")  # (head-room below the capacity needed to run on the device; default 4096)
-    monkeypatch.setenv("FLS_IVOX_DEVICE_EVICT", "0")    # round-2 behaviour: evictions only on the host (the next tests run them on the device)
-    m, o = _replay(8, monkeypatch=monkeypatch, capacity_over_initial=64 + 250)  # the scenario creates 86, 145, 190, ... 473 voxels
+def test_mapping_replay_device_refuses_batch_when_the_brick_pool_is_full():
+    """A prior map of 6 m radius (the smallest brick pool: 256 bricks) and a sensor that reaches 60 m: the first batch needs about 400
+    bricks, the device refuses it for lack of room (kUpdArrayFull) BEFORE any voxel changes, the device image (points, voxel table, LRU
+    stamps) is read back into the host mirror, the exact sequential path replays the batch and the image is rebuilt with a larger pool;
+    the later batches run on the device again.  Parity with the oracle throughout."""
+    m, o = _replay(6, radius=6.0, max_range=60.0)
     assert m.map_size(103) >= 1, "some batches must have run on the device"
-    assert m.map_size(104) >= 1, "a batch must have been refused and replayed on the host"
+    assert m.map_size(104) >= 1 and m.map_size(120) >= 1, "a batch must have been refused for a full brick pool and replayed on the host"
     assert m.map_size(102) == o.map_voxels()
 
 

@@ -171,19 +171,15 @@ def test_ndt_on_a_multi_site_map():
     m.close(); o.close()
 
 
-@pytest.mark.parametrize("form", ["short", "long"])
-def test_device_addpoints_three_forms(form, monkeypatch):
-    """The device AddPoints runs the same device functions in two launch structures: the SHORT chain (default: the decision launch
-    counts, every block derives its offsets and the verdict itself, the last block to finish publishes -- five launches behind the
-    decision instead of ten) and the round-3 LONG chain (FLS_IVOX_SHORT_CHAIN=0; what batches that may evict still use).  The 8-scan
-    mapping replay equals the oracle in both."""
-    if form == "long":
-        monkeypatch.setenv("FLS_IVOX_SHORT_CHAIN", "0")
+def test_device_addpoints_short_chain():
+    """Batches that cannot reach the LRU capacity take the SHORT chain of the device AddPoints (the decision launch counts, every block
+    derives its offsets and the verdict itself, the last block to finish publishes -- five launches behind the decision instead of the
+    ten of the LONG chain, which batches that may evict use).  The 8-scan mapping replay equals the oracle."""
     m, o = _replay(8)
     assert m.map_size(103) >= 7 and m.map_size(104) == 0
     short, one = m.map_size(123), m.map_size(122)
     # (short-chain launches include the speculative ones the device skipped: map_size(125))
-    assert (short - m.map_size(125), one) == ((m.map_size(103), 0) if form == "short" else (0, 0)), (form, short, one)
+    assert (short - m.map_size(125), one) == (m.map_size(103), 0), (short, one)
     m.close(); o.close()
 
 
@@ -214,18 +210,16 @@ def test_device_addpoints_large_and_small_batches_alternate_short_chain():
     m.close(); o.close()
 
 
-@pytest.mark.parametrize("spec", ["1", "0"])
-def test_speculative_update_chain(spec, monkeypatch):
+def test_speculative_update_chain():
     """The decision + update chain is queued behind the iterations the Match is expected to need and gates itself on the device
     (Gauss-Newton loop ended and n_valid >= 50: what LoamPointToPlaneIVOX::Match checks before AddCloudToLocalMap, :197-206); a chain that
-    finds the Match unfinished skips itself and the host queues another one behind the added iterations.  FLS_IVOX_SPECULATIVE=0 waits for
-    the result first.  Same poses, ids, map sizes as the oracle either way (the 8-scan replay + the 24-scan multi-site run)."""
-    monkeypatch.setenv("FLS_IVOX_SPECULATIVE", spec)
+    finds the Match unfinished skips itself and the host queues another one behind the added iterations.  Same poses, ids, map sizes as
+    the oracle (the 8-scan replay + the 24-scan multi-site run)."""
     m, o = _replay(8)
     assert m.map_size(103) >= 7 and m.map_size(104) == 0
     queued, skipped = m.map_size(124), m.map_size(125)
-    print(f"speculative = {spec}: {queued} chains queued, {skipped} skipped on the device, {m.map_size(103)} batches applied")
-    assert (queued >= 7 and queued - skipped == m.map_size(103)) if spec == "1" else (queued == 0 and skipped == 0), (queued, skipped, m.map_size(103))
+    print(f"{queued} chains queued, {skipped} skipped on the device, {m.map_size(103)} batches applied")
+    assert queued >= 7 and queued - skipped == m.map_size(103), (queued, skipped, m.map_size(103))
     m.close(); o.close()
     m, o = multi_site_replay(3, 9)
     assert m.map_size(104) == 0

@@ -1,5 +1,5 @@
-"""What an at-capacity map update costs with the evictions on the device (default) and with the round-2 rule (every batch that would
-evict goes to the exact host code: FLS_IVOX_DEVICE_EVICT=0 / FLS_NDT_DEVICE_EVICT=0).  The scenarios are the ones of the eviction tests
+"""What an at-capacity map update costs with the evictions on the device (default) and on the exact host path (every map update on the
+host: FLS_IVOX_DEVICE_UPDATE=0 / FLS_NDT_DEVICE_UPDATE=0).  The scenarios are the ones of the eviction tests
 (tests/test_gpu_parity.py::test_mapping_replay_device_evictions_straight_run, tests/test_gpu_mapping_replay.py::..._with_conflicts):
 this tool only times them, the tests hold the parity assertions.  Usage: python tools/gpu_evict_timing.py  (one GPU, ~40 s)."""
 import json
@@ -70,7 +70,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 1:
         print(json.dumps(run_ivox() if sys.argv[1] == "ivox" else run_ndt()))
         sys.exit(0)
-    for kind, var in (("ivox", "FLS_IVOX_DEVICE_EVICT"), ("ndt", "FLS_NDT_DEVICE_EVICT")):
+    for kind, var in (("ivox", "FLS_IVOX_DEVICE_UPDATE"), ("ndt", "FLS_NDT_DEVICE_UPDATE")):
         for val in ("1", "0"):
             env = dict(os.environ, **{var: val, "FLS_IVOX_CAPACITY": "5000"})
             p = subprocess.run([sys.executable, os.path.abspath(__file__), kind], env=env, capture_output=True, text=True, timeout=200)
