@@ -23,11 +23,12 @@ EXPORTED_SYMBOLS = [
     # include/fls_features.h
     "fls_features_create", "fls_features_destroy", "fls_features_project", "fls_features_extract", "fls_features_get", "fls_features_get_time",
 ]
-# every symbol include/fls_preprocess.h declares (revision 8)
+# every symbol include/fls_preprocess.h declares (revision 8; revision 9 = HANDOFF_SYMBOLS)
+HANDOFF_SYMBOLS = ["fls_preprocess_scan_device", "fls_scan_attach_preprocessed", "fls_preprocess_get_host_bytes"]
 PREPROCESS_SYMBOLS = [
     "fls_preprocess_create", "fls_preprocess_destroy", "fls_preprocess_scan", "fls_preprocess_get", "fls_preprocess_get_time",
     "fls_features_project_deskew",
-]
+] + HANDOFF_SYMBOLS
 
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
@@ -250,6 +251,12 @@ def lib():
         L.fls_preprocess_destroy.argtypes = [hp]
         L.fls_preprocess_scan.restype = C.c_int
         L.fls_preprocess_scan.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(RawLayout), C.c_uint64, u64p, dp, C.c_size_t, C.POINTER(PreprocessResult)]
+        L.fls_preprocess_scan_device.restype = C.c_int
+        L.fls_preprocess_scan_device.argtypes = L.fls_preprocess_scan.argtypes
+        L.fls_scan_attach_preprocessed.restype = C.c_int
+        L.fls_scan_attach_preprocessed.argtypes = [hp, hp, C.c_int]
+        L.fls_preprocess_get_host_bytes.restype = C.c_int
+        L.fls_preprocess_get_host_bytes.argtypes = [hp, u64p]
         L.fls_preprocess_get.restype = C.c_size_t
         L.fls_preprocess_get.argtypes = [hp, C.c_int, C.c_void_p, C.c_size_t]
         L.fls_preprocess_get_time.restype = C.c_int

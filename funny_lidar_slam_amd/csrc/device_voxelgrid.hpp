@@ -634,6 +634,31 @@ struct SourceFilter {
         }
         if (n0) { raw.upload_raw(s0, n0, stride, s, true); FLS_HIP(hipStreamSynchronize(s)); }
     }
+    // the same state from a cloud that is already on this device (fls_scan_attach_preprocessed): the copy kernel fills `raw`, nothing
+    // is synchronised, and raw_host is fetched only if the device filter declines
+    void attach_raw_only(const HandoffCloud& c, float leaf, hipStream_t s, DevScan& scan, std::vector<PtI>& source) {
+        resident = false;
+        scan.n = 0;
+        scan.host.clear();
+        source.clear();
+        withdrawn = true;
+        raw_pending = true;
+        raw_n = c.n;
+        raw_leaf = leaf;
+        raw_host.clear();
+        raw.attach_device(c, s, /*want_host=*/false);
+    }
+    const float* raw_rows(hipStream_t s) {
+        if (raw.stage_stale) {
+            raw.fetch_stage(s);
+            raw_host.resize(4 * raw_n);
+            const float* st = raw.stage.p;
+            for (size_t i = 0; i < raw_n; ++i) {
+                raw_host[4 * i] = st[i]; raw_host[4 * i + 1] = st[raw_n + i]; raw_host[4 * i + 2] = st[2 * raw_n + i]; raw_host[4 * i + 3] = st[3 * raw_n + i];
+            }
+        }
+        return raw_host.data();
+    }
     void refilter(hipStream_t s, DevScan& scan, std::vector<PtI>& source) {
         resident = false;
         withdrawn = false;
@@ -648,7 +673,7 @@ struct SourceFilter {
             ++device_runs;
             return;
         }
-        source = voxel_grid_strided(raw_host.data(), raw_n, 4, raw_leaf);
+        source = voxel_grid_strided(raw_rows(s), raw_n, 4, raw_leaf);
         scan.upload(source, s);
         ++host_runs;
     }

@@ -564,9 +564,50 @@ fls_status fls_preprocess_scan(fls_preprocess_handle h, const void* raw, size_t 
     });
 }
 
+fls_status fls_preprocess_scan_device(fls_preprocess_handle h, const void* raw, size_t n, const fls_raw_layout* layout, uint64_t stamp_us,
+                                      const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, fls_preprocess_result* result) {
+    if (!h || !layout || (!raw && n) || (result && result->struct_size != sizeof(fls_preprocess_result))) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->scan(raw, n, *layout, stamp_us, imu_t_us, imu_q_xyzw, n_imu, result, /*on_device=*/true);
+    });
+}
+
 size_t fls_preprocess_get(fls_preprocess_handle h, int what, void* out, size_t cap_elems) {
     if (!h) return 0;
-    return h->get(what, out, cap_elems);
+    size_t n = 0;
+    (void)guarded([&]() -> fls_status {  // (after a device scan the first request of an array downloads it)
+        FLS_HIP(hipSetDevice(h->device));
+        n = h->get(what, out, cap_elems);
+        return FLS_OK;
+    });
+    return n;
+}
+
+fls_status fls_preprocess_get_host_bytes(fls_preprocess_handle h, uint64_t* d2h_bytes) {
+    if (!h || !d2h_bytes) return FLS_ERR_INVALID;
+    *d2h_bytes = h->d2h_bytes;
+    return FLS_OK;
+}
+
+fls_status fls_scan_attach_preprocessed(fls_handle m, fls_preprocess_handle pre, int what) {
+    if (!m || !pre || (what != FLS_PRE_ORDERED && what != FLS_PRE_PLANAR && what != FLS_PRE_PLANAR_FILTERED) || m->device != pre->device)
+        return FLS_ERR_INVALID;
+    if (m->kind == FLS_LOAM_FULL || m->is_lane || !pre->scan_done) return FLS_ERR_STATE;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(m->device));
+        HandoffCloud c;
+        const std::vector<PtI>* rows = nullptr;
+        if (!pre->device_cloud(what, c, rows))  // the cloud the exact host filter made: the ordinary upload
+            return m->scan_upload_raw(rows->empty() ? nullptr : &(*rows)[0].x, rows->size(), nullptr, 0, 4);
+        if (c.n == 0) return m->scan_attach_device(c);
+        // the copy waits for the scan (and anything else queued on its stream); the next scan's writes wait for the copy
+        FLS_HIP(hipEventRecord(pre->ev_ready, pre->stream));
+        FLS_HIP(hipStreamWaitEvent(m->stream, pre->ev_ready, 0));
+        const fls_status rc = m->scan_attach_device(c);
+        FLS_HIP(hipEventRecord(pre->next_consumed_event(), m->stream));
+        return rc;
+    });
 }
 
 fls_status fls_preprocess_get_time(fls_preprocess_handle h, double* deskew_ms, double* filter_ms) {

@@ -2,6 +2,7 @@
 // Gauss-Newton state, wave partials, profiling events) and the scan upload helper.
 #pragma once
 #include "host_maps.hpp"
+#include "kernels_handoff.hpp"
 #include <memory>
 #include <thread>
 #if defined(__SSE__)
@@ -63,6 +64,9 @@ struct fls_matcher {
     virtual fls_status scan_upload_for_match(const float* s0, size_t n0, const float* s1, size_t n1, int stride) { return scan_upload(s0, n0, s1, n1, stride); }
     // fls_scan_upload_raw: kinds whose Match filters its source (ICP, NDT) keep the RAW scan resident and filter inside match_resident
     virtual fls_status scan_upload_raw(const float* s0, size_t n0, const float* s1, size_t n1, int stride) { return scan_upload(s0, n0, s1, n1, stride); }
+    // fls_scan_attach_preprocessed: what fls_scan_upload_raw(rows of `c`) would leave, from a cloud that already lies on this device.  The
+    // copy kernel is queued on this handle's stream (the caller has ordered it behind the producer); host copies are fetched on demand.
+    virtual fls_status scan_attach_device(const fls::HandoffCloud&) { return FLS_ERR_STATE; }
     virtual fls_status match_resident(double* T, int update_map, fls_stats* out) = 0;
     virtual fls_status fitness(float max_range, float* score) = 0;
     virtual int correspondences(int slot, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) = 0;
@@ -270,6 +274,34 @@ struct DevScan {
     PinnedBuf<float> stage;
     size_t n = 0;
     std::vector<PtI> host;  // kept for map updates / fitness
+    // attach_device: the scan was written on the device (x | y | z | intensity); the pinned staging copy / `host` are fetched only
+    // when a map update or a declined device path reads them
+    bool stage_stale = false, host_stale = false;
+    void attach_device(const HandoffCloud& c, hipStream_t s, bool want_host) {
+        n = c.n;
+        host.clear();
+        stage_stale = n != 0;
+        host_stale = want_host && n != 0;
+        if (n == 0) return;
+        xyz.reserve(4 * n);
+        x.p = xyz.p; y.p = xyz.p + n; z.p = xyz.p + 2 * n;
+        handoff_launch(c, xyz.p, s);
+        FLS_HIP(hipGetLastError());
+    }
+    void fetch_stage(hipStream_t s) {
+        if (!stage_stale) return;
+        stage.reserve(4 * n);
+        FLS_HIP(hipMemcpyAsync(stage.p, xyz.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost, s));
+        FLS_HIP(hipStreamSynchronize(s));
+        stage_stale = false;
+    }
+    void fetch_host(hipStream_t s) {
+        if (!host_stale) return;
+        fetch_stage(s);
+        host.resize(n);
+        for (size_t i = 0; i < n; ++i) host[i] = PtI{stage.p[i], stage.p[n + i], stage.p[2 * n + i], stage.p[3 * n + i]};
+        host_stale = false;
+    }
     void push(hipStream_t s, int fields = 3) {
         xyz.reserve(size_t(fields) * n);
         x.p = xyz.p; y.p = xyz.p + n; z.p = xyz.p + 2 * n;
@@ -297,6 +329,7 @@ struct DevScan {
     void stage_raw(const float* p, size_t count, int stride) {
         n = count;
         host.clear();
+        stage_stale = host_stale = false;
         if (n == 0) return;
         stage.reserve(4 * n);
         float* sx = stage.p; float* sy = stage.p + n; float* sz = stage.p + 2 * n; float* si = stage.p + 3 * n;
@@ -337,6 +370,7 @@ struct DevScan {
     void upload(const std::vector<PtI>& c, hipStream_t s) {
         host = c;
         n = c.size();
+        stage_stale = host_stale = false;
         if (n == 0) return;
         stage.reserve(3 * n);
         for (size_t i = 0; i < n; ++i) { stage.p[i] = c[i].x; stage.p[n + i] = c[i].y; stage.p[2 * n + i] = c[i].z; }

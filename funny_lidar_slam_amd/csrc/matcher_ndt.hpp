@@ -618,6 +618,10 @@ struct NdtMatcher final : fls_matcher {
         src_filter.upload_raw_only(s0, n0, stride, p.source_cloud_filter_size, stream, scan, source);  // (no filtered scan is resident until the next Match: fitness answers FLS_ERR_STATE)
         return FLS_OK;
     }
+    fls_status scan_attach_device(const HandoffCloud& c) override {
+        src_filter.attach_raw_only(c, p.source_cloud_filter_size, stream, scan, source);
+        return FLS_OK;
+    }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         const NdtMatcher& M = owner ? *owner : *this;  // a batch lane reads its owner's voxel tables
         if (M.alive() == 0 || !M.have_map) return FLS_ERR_STATE;  // CHECK(!grids_.empty()) :230

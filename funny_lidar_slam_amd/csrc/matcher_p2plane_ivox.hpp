@@ -411,6 +411,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
                 FLS_HIP(hipMemcpyAsync(h_code.data(), d_code.p, n, hipMemcpyDeviceToHost, stream));
                 FLS_HIP(hipMemcpyAsync(h_pw.data(), d_pw.p, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
                 FLS_HIP(hipStreamSynchronize(stream));
+                scan.fetch_stage(stream);  // (an attached scan's intensities are still on the device)
                 for (size_t i = 0; i < n; ++i) {
                     if (h_code[i] == 0) continue;
                     const PtI pw{h_pw[i].x, h_pw[i].y, h_pw[i].z, scan.staged_intensity(i)};
@@ -499,6 +500,11 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         (void)s1; (void)n1;
         // (the pinned staging buffer is free again: fls_scan_upload synchronises, a Match ends after its copies)
         scan.upload_raw(s0, n0, stride, stream);
+        return FLS_OK;
+    }
+    fls_status scan_attach_device(const HandoffCloud& c) override {
+        scan_in_staging = false;
+        scan.attach_device(c, stream, /*want_host=*/false);  // (scan.host stays empty, as after upload_raw)
         return FLS_OK;
     }
 

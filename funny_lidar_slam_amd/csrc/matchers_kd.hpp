@@ -100,6 +100,12 @@ struct IcpMatcher final : fls_matcher {
         have_final = false;  // (no filtered scan is resident until the next Match: fls_get_fitness_score answers FLS_ERR_STATE)
         return FLS_OK;
     }
+    fls_status scan_attach_device(const HandoffCloud& c) override {
+        raw_n = c.n;
+        src_filter.attach_raw_only(c, p.source_cloud_filter_size, stream, scan, source);
+        have_final = false;
+        return FLS_OK;
+    }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         if (raw_n <= 10) return FLS_ERR_INVALID;  // CHECK_GT(ordered_cloud_.size(), 10u) :55
         if (src_filter.raw_pending) src_filter.refilter(stream, scan, source);  // :57, on the resident raw scan
@@ -424,6 +430,10 @@ struct P2PlaneKdMatcher final : fls_matcher {
         planar.scan.upload(cloud_from(s0, n0, stride), stream);
         return FLS_OK;
     }
+    fls_status scan_attach_device(const HandoffCloud& c) override {
+        planar.scan.attach_device(c, stream, /*want_host=*/true);
+        return FLS_OK;
+    }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
         const size_t n = planar.scan.n;
@@ -455,6 +465,7 @@ struct P2PlaneKdMatcher final : fls_matcher {
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {  // :145-149
+            planar.scan.fetch_host(stream);  // (an attached scan is fetched only here)
             const fls_status arc = add_cloud_impl(hm::xform_cloud_f(planar.scan.host, final_T));
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
         }

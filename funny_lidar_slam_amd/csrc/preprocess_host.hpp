@@ -176,8 +176,22 @@ struct fls_preprocess {
     std::vector<float> tmp;
     double deskew_ms = 0.0, filter_ms = 0.0;
     bool filter_on_device = false;
+    // the last scan: counts (all the host learns from fls_preprocess_scan_device), the row stride of d_planar, and which host arrays
+    // have not been downloaded yet (fls_preprocess_get fetches them on first request)
+    size_t n_ordered = 0, n_planar = 0, n_planar_f = 0, planar_cap = 0;
+    bool stale_ordered = false, stale_idx = false, stale_planar = false, stale_planar_f = false;
+    bool scan_done = false;      // a scan has completed with clouds (not DROP / WAIT, not an invalid call)
+    uint64_t d2h_bytes = 0;      // device -> host copies on behalf of the last scan so far
+    // hand-off (fls_scan_attach_preprocessed): ready = "everything queued on this stream so far", recorded per attach and waited for
+    // by the matcher's stream; consumed[k] = a matcher's copy kernel has read this handle's buffers, waited for by the next scan
+    hipEvent_t ev_ready = nullptr;
+    std::vector<hipEvent_t> consumed;
+    size_t n_consumed = 0;
 
     ~fls_preprocess() {
+        for (size_t k = 0; k < n_consumed; ++k) (void)hipEventSynchronize(consumed[k]);  // (the buffers below are still being read)
+        for (auto e : consumed) if (e) (void)hipEventDestroy(e);
+        if (ev_ready) (void)hipEventDestroy(ev_ready);
         for (auto e : ev) if (e) (void)hipEventDestroy(e);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     }
@@ -193,6 +207,7 @@ struct fls_preprocess {
         FLS_HIP(hipSetDevice(device));
         FLS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         for (auto& e : ev) FLS_HIP(hipEventCreate(&e));
+        FLS_HIP(hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming));
         d_tot.reserve(2);
         h_tot.reserve(2);
         return FLS_OK;
@@ -202,10 +217,50 @@ struct fls_preprocess {
         ordered.clear(); planar.clear(); planar_f.clear(); ordered_idx.clear();
         deskew_ms = filter_ms = 0.0;
         filter_on_device = false;
+        n_ordered = n_planar = n_planar_f = 0;
+        stale_ordered = stale_idx = stale_planar = stale_planar_f = false;
+        scan_done = false;
+        d2h_bytes = 0;
     }
 
+    // the device -> host copies of the clouds: queued by fls_preprocess_scan, or by the first fls_preprocess_get after a device scan
+    void enqueue_ordered() {
+        ordered.resize(n_ordered);
+        if (n_ordered) FLS_HIP(hipMemcpyAsync(ordered.data(), d_ordered.p, n_ordered * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        d2h_bytes += n_ordered * sizeof(float4);
+        stale_ordered = false;
+    }
+    void enqueue_ordered_idx() {
+        ordered_idx.resize(n_ordered);
+        if (n_ordered) FLS_HIP(hipMemcpyAsync(ordered_idx.data(), d_ordered_idx.p, n_ordered * sizeof(int), hipMemcpyDeviceToHost, stream));
+        d2h_bytes += n_ordered * sizeof(int);
+        stale_idx = false;
+    }
+    void enqueue_planar() {
+        const size_t np = n_planar;
+        planar.resize(np);
+        if (np) {
+            tmp.resize(4 * np);
+            for (int a = 0; a < 4; ++a)
+                FLS_HIP(hipMemcpyAsync(tmp.data() + size_t(a) * np, d_planar.p + size_t(a) * planar_cap, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        d2h_bytes += 4 * np * sizeof(float);
+    }
+    void finish_planar() {  // after the stream has drained
+        const size_t np = n_planar;
+        for (size_t i = 0; i < np; ++i) planar[i] = fls::PtI{tmp[i], tmp[np + i], tmp[2 * np + i], tmp[3 * np + i]};
+        stale_planar = false;
+    }
+    void fetch_planar_f() {
+        std::vector<float> t2;
+        planar_f = vg.download(stream, t2);
+        d2h_bytes += planar_f.size() * sizeof(fls::PtI);
+        stale_planar_f = false;
+    }
+
+    // on_device: fls_preprocess_scan_device -- the clouds stay in d_ordered / d_ordered_idx / d_planar / the VoxelGrid's output
     fls_status scan(const void* raw, size_t n, const fls_raw_layout& L, uint64_t stamp, const uint64_t* it, const double* iq, size_t n_imu,
-                    fls_preprocess_result* r) {
+                    fls_preprocess_result* r, const bool on_device = false) {
         clear();
         const fls_status rc = ds.prepare(raw, n, L, stamp, it, iq, n_imu, p.T_lidar_to_imu, false);
         if (rc != FLS_OK) return rc;
@@ -213,7 +268,7 @@ struct fls_preprocess {
             if (r) {
                 r->imu_status = ds.imu_status;
                 r->cloud_start_us = ds.start; r->cloud_end_us = ds.end;
-                r->n_raw = n; r->n_ordered = ordered.size(); r->n_planar = planar.size(); r->n_planar_filtered = planar_f.size();
+                r->n_raw = n; r->n_ordered = n_ordered; r->n_planar = n_planar; r->n_planar_filtered = n_planar_f;
                 r->n_segment = ds.seg_t.size();
                 r->filter_on_device = filter_on_device ? 1 : 0;
                 r->reserved = 0;
@@ -221,9 +276,14 @@ struct fls_preprocess {
             return s;
         };
         if (ds.imu_status == FLS_IMU_DROP || ds.imu_status == FLS_IMU_WAIT) return report(FLS_ERR_STATE);
+        scan_done = true;
         if (ds.imu_status != FLS_IMU_OK) return report(FLS_OK);
         const size_t cap = n;
         d_ordered.reserve(n); d_ordered_idx.reserve(n); d_planar.reserve(4 * cap);
+        planar_cap = cap;
+        // a matcher may still be copying the previous scan out of these buffers (and out of the VoxelGrid's): this scan's writes wait
+        for (size_t k = 0; k < n_consumed; ++k) FLS_HIP(hipStreamWaitEvent(stream, consumed[k], 0));
+        n_consumed = 0;
         FLS_HIP(hipEventRecord(ev[0], stream));
         const unsigned nb = ds.upload_and_deskew(stream, true, p.min_distance, p.max_distance, unsigned(p.lidar_point_jump_span));
         hipLaunchKernelGGL(fls::deskew_scan_kernel, dim3(1), dim3(1024), 0, stream, ds.d_blk.p, nb, ds.d_off.p, d_tot.p);
@@ -233,16 +293,16 @@ struct fls_preprocess {
         FLS_HIP(hipEventRecord(ev[1], stream));
         FLS_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
         FLS_HIP(hipStreamSynchronize(stream));
-        const size_t no = h_tot.p[0], np = h_tot.p[1];
-        ordered.resize(no); ordered_idx.resize(no); planar.resize(np);
-        if (no) {
-            FLS_HIP(hipMemcpyAsync(ordered.data(), d_ordered.p, no * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipMemcpyAsync(ordered_idx.data(), d_ordered_idx.p, no * sizeof(int), hipMemcpyDeviceToHost, stream));
-        }
-        if (np) {
-            tmp.resize(4 * np);
-            for (int a = 0; a < 4; ++a)
-                FLS_HIP(hipMemcpyAsync(tmp.data() + size_t(a) * np, d_planar.p + size_t(a) * cap, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+        d2h_bytes += 2 * sizeof(unsigned);
+        n_ordered = h_tot.p[0];
+        n_planar = h_tot.p[1];
+        const size_t np = n_planar;
+        if (on_device) {
+            stale_ordered = stale_idx = stale_planar = true;
+        } else {
+            enqueue_ordered();
+            enqueue_ordered_idx();
+            enqueue_planar();
         }
         bool vg_ok = false;
         if (np && p.planar_voxel_filter_size > 0.f) {
@@ -252,7 +312,7 @@ struct fls_preprocess {
             FLS_HIP(hipEventRecord(ev[3], stream));
         }
         FLS_HIP(hipStreamSynchronize(stream));
-        for (size_t i = 0; i < np; ++i) planar[i] = fls::PtI{tmp[i], tmp[np + i], tmp[2 * np + i], tmp[3 * np + i]};
+        if (!on_device) finish_planar();
         float ms = 0.f;
         FLS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
         deskew_ms = ms;
@@ -260,14 +320,50 @@ struct fls_preprocess {
             FLS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
             filter_ms = ms;
             if (vg_ok) {
-                std::vector<float> t2;
-                planar_f = vg.download(stream, t2);
                 filter_on_device = true;
+                n_planar_f = vg.n_out;
+                if (on_device) stale_planar_f = true; else fetch_planar_f();
             } else {
+                fetch(FLS_PRE_PLANAR);  // (a device scan the VoxelGrid declined: the exact host filter needs the cloud here)
                 planar_f = fls::voxel_grid_strided(&planar[0].x, np, 4, p.planar_voxel_filter_size);  // the exact host filter (SourceFilter's fallback)
+                n_planar_f = planar_f.size();
             }
         }
         return report(FLS_OK);
+    }
+
+    // make the host copy of one array current (no-op unless the last scan left it on the device)
+    void fetch(int what) {
+        switch (what) {
+            case FLS_PRE_ORDERED: if (stale_ordered) { enqueue_ordered(); FLS_HIP(hipStreamSynchronize(stream)); } break;
+            case FLS_PRE_ORDERED_INDEX: if (stale_idx) { enqueue_ordered_idx(); FLS_HIP(hipStreamSynchronize(stream)); } break;
+            case FLS_PRE_PLANAR: if (stale_planar) { enqueue_planar(); FLS_HIP(hipStreamSynchronize(stream)); finish_planar(); } break;
+            case FLS_PRE_PLANAR_FILTERED: if (stale_planar_f) fetch_planar_f(); break;
+            default: break;
+        }
+    }
+
+    // where a cloud of the last scan lies on the device (fls_scan_attach_preprocessed); false: only the host has it (the planar
+    // cloud the host filter made) -- `host_rows` then
+    bool device_cloud(int what, fls::HandoffCloud& c, const std::vector<fls::PtI>*& host_rows) const {
+        c = fls::HandoffCloud{};
+        host_rows = nullptr;
+        if (what == FLS_PRE_ORDERED) { c.rows = d_ordered.p; c.n = n_ordered; return true; }
+        if (what == FLS_PRE_PLANAR) {
+            c.x = d_planar.p; c.y = d_planar.p + planar_cap; c.z = d_planar.p + 2 * planar_cap; c.in = d_planar.p + 3 * planar_cap; c.n = n_planar;
+            return true;
+        }
+        if (n_planar_f == 0 || filter_on_device) { c.x = vg.ox(); c.y = vg.oy(); c.z = vg.oz(); c.in = vg.oi(); c.n = n_planar_f; return true; }
+        host_rows = &planar_f;
+        return false;
+    }
+    hipEvent_t next_consumed_event() {
+        if (n_consumed == consumed.size()) {
+            hipEvent_t e = nullptr;
+            FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            consumed.push_back(e);
+        }
+        return consumed[n_consumed++];
     }
 
     template <class T>
@@ -276,11 +372,12 @@ struct fls_preprocess {
         return n;
     }
     size_t get(int what, void* out, size_t cap) {
+        if (out) fetch(what);
         switch (what) {
-            case FLS_PRE_ORDERED: return copy_out(ordered.data(), ordered.size(), out, cap);
-            case FLS_PRE_ORDERED_INDEX: return copy_out(ordered_idx.data(), ordered_idx.size(), out, cap);
-            case FLS_PRE_PLANAR: return copy_out(planar.data(), planar.size(), out, cap);
-            case FLS_PRE_PLANAR_FILTERED: return copy_out(planar_f.data(), planar_f.size(), out, cap);
+            case FLS_PRE_ORDERED: return copy_out(ordered.data(), n_ordered, out, cap);
+            case FLS_PRE_ORDERED_INDEX: return copy_out(ordered_idx.data(), n_ordered, out, cap);
+            case FLS_PRE_PLANAR: return copy_out(planar.data(), n_planar, out, cap);
+            case FLS_PRE_PLANAR_FILTERED: return copy_out(planar_f.data(), n_planar_f, out, cap);
             case FLS_PRE_SEGMENT_T: return copy_out(ds.seg_t.data(), ds.seg_t.size(), out, cap);
             case FLS_PRE_SEGMENT_Q: {
                 const size_t m = ds.seg_t.size();

@@ -84,8 +84,39 @@ class ScanPreprocessor:
         if rc not in (_lib.FLS_OK, _lib.FLS_ERR_STATE):
             raise FlsError(rc, "fls_preprocess_scan")
         self.last = res
+        return self.output(rc)
+
+    def scan_device(self, raw: np.ndarray, stamp_us: int, imu_t_us, imu_q_xyzw) -> PreprocessResult:
+        """scan() with the clouds left in device memory (fls_preprocess_scan_device): returns the result struct (status in `.status`,
+        counts, imu_status, filter_on_device); get() downloads an array on its first request; a matcher takes a cloud over with
+        RegistrationInterface.attach_preprocessed(self, which)."""
+        raw = np.ascontiguousarray(raw)
+        lay = raw_layout(raw.dtype)
+        t, q = imu_arrays(imu_t_us, imu_q_xyzw)
+        res = PreprocessResult()
+        res.struct_size = C.sizeof(PreprocessResult)
+        rc = _lib.lib().fls_preprocess_scan_device(self._h, raw.ctypes.data, raw.shape[0], C.byref(lay), int(stamp_us),
+                                                   t.ctypes.data_as(C.POINTER(C.c_uint64)), q.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], C.byref(res))
+        if rc not in (_lib.FLS_OK, _lib.FLS_ERR_STATE):
+            raise FlsError(rc, "fls_preprocess_scan_device")
+        self.last = res
+        res.status = rc
+        return res
+
+    def output(self, status: int | None = None) -> PreprocessOutput:
+        """The PreprocessOutput of the last scan (after scan_device: downloads the four clouds)."""
+        res = self.last
+        rc = getattr(res, "status", _lib.FLS_OK) if status is None else status
         return PreprocessOutput(rc, IMU_STATUS[res.imu_status], int(res.cloud_start_us), int(res.cloud_end_us), self.get("ordered"),
                                 self.get("ordered_index"), self.get("planar"), self.get("planar_filtered"), bool(res.filter_on_device))
+
+    def host_bytes(self) -> int:
+        """Bytes copied device -> host on behalf of the last scan so far (fls_preprocess_get_host_bytes), lazy downloads included."""
+        n = C.c_uint64()
+        rc = _lib.lib().fls_preprocess_get_host_bytes(self._h, C.byref(n))
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_preprocess_get_host_bytes")
+        return int(n.value)
 
     def get(self, name: str) -> np.ndarray:
         what, dt, cols = ARRAYS[name]

@@ -158,6 +158,14 @@ class RegistrationInterface:
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_scan_upload_raw")
 
+    def attach_preprocessed(self, pre, which: str = "planar_filtered") -> int:
+        """fls_scan_attach_preprocessed: a cloud of `pre`'s last scan ("ordered", "planar", "planar_filtered"; a ScanPreprocessor)
+        becomes the resident scan, device to device -- the state UploadScanRaw of pre.get(which) would leave.  Returns the status
+        (FLS_OK, or FLS_ERR_STATE / FLS_ERR_INVALID as include/fls_preprocess.h lists them)."""
+        from .preprocess import ARRAYS
+        what = ARRAYS[which][0] if which in ("ordered", "planar", "planar_filtered") else -1
+        return int(_lib.lib().fls_scan_attach_preprocessed(self._h, getattr(pre, "_h", None), what))
+
     def MatchResident(self, T: np.ndarray, update_map: bool = False) -> bool:
         # hot in bench.py: one preallocated column-major pose buffer, no per-call ctypes object construction
         buf = getattr(self, "_Tbuf", None)

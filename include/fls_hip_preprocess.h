@@ -43,6 +43,31 @@ public:
     // FLS_IMU_WAIT: keep it and retry when more IMU data has arrived; -1: invalid input (the reference would CHECK-abort)
     template <class Cluster, class RawCloud, class ImuVec>
     int Run(Cluster& c, const RawCloud& raw, uint64_t stamp_us, const ImuVec& imu) {
+        const int st = Scan(raw, stamp_us, imu, /*on_device=*/false);
+        if (st >= 0 && st != FLS_IMU_DROP && st != FLS_IMU_WAIT) FillCluster(c);
+        return st;
+    }
+    // Run() with the clouds left in device memory for HipRegistration::MatchPreprocessed (fls_hip_registration.h): no cluster is
+    // filled, the host learns the counts only.  Same return values.
+    template <class RawCloud, class ImuVec>
+    int RunOnDevice(uint64_t stamp_us, const RawCloud& raw, const ImuVec& imu) {
+        return Scan(raw, stamp_us, imu, /*on_device=*/true);
+    }
+    // the PCL clouds of the last scan, for callers that still need them on the host (visualisation, keyframes): after RunOnDevice
+    // each cloud is downloaded here, on its first request
+    template <class Cluster>
+    void FillCluster(Cluster& c) {
+        FetchCloud(FLS_PRE_ORDERED, c.ordered_cloud_);
+        FetchCloud(planar_what(), c.planar_cloud_);
+    }
+    fls_preprocess_handle handle() const { return h_; }
+    // the array PreProcessing::Run() puts into planar_cloud_: filtered when a leaf size is set
+    int planar_what() const { return leaf_ > 0.f ? FLS_PRE_PLANAR_FILTERED : FLS_PRE_PLANAR; }
+    const fls_preprocess_result& last_result() const { return r_; }
+
+private:
+    template <class RawCloud, class ImuVec>
+    int Scan(const RawCloud& raw, uint64_t stamp_us, const ImuVec& imu, bool on_device) {
         using P = typename std::remove_const<typename std::remove_reference<decltype(raw.points[0])>::type>::type;
         static const fls_raw_layout lay{static_cast<uint32_t>(sizeof(P)), static_cast<uint32_t>(offsetof(P, x)), static_cast<uint32_t>(offsetof(P, intensity)),
                                         static_cast<uint32_t>(offsetof(P, ring)), static_cast<uint32_t>(sizeof(P::ring)),
@@ -56,18 +81,13 @@ public:
             q_[4 * k + 2] = imu[k].orientation_.z();
             q_[4 * k + 3] = imu[k].orientation_.w();
         }
-        fls_preprocess_result r{};
-        r.struct_size = sizeof(r);
-        const fls_status rc = fls_preprocess_scan(h_, raw.points.data(), raw.points.size(), &lay, stamp_us, t_.data(), q_.data(), t_.size(), &r);
+        r_ = fls_preprocess_result{};
+        r_.struct_size = sizeof(r_);
+        const fls_status rc = (on_device ? fls_preprocess_scan_device : fls_preprocess_scan)(h_, raw.points.data(), raw.points.size(), &lay, stamp_us,
+                                                                                            t_.data(), q_.data(), t_.size(), &r_);
         if (rc != FLS_OK && rc != FLS_ERR_STATE) { std::fprintf(stderr, "HipScanPreprocessor::Run: %s\n", fls_status_string(rc)); return -1; }
-        if (rc == FLS_OK) {
-            FetchCloud(FLS_PRE_ORDERED, c.ordered_cloud_);
-            FetchCloud(leaf_ > 0.f ? FLS_PRE_PLANAR_FILTERED : FLS_PRE_PLANAR, c.planar_cloud_);
-        }
-        return r.imu_status;
+        return r_.imu_status;
     }
-
-private:
     template <class Cloud>
     void FetchCloud(int what, Cloud& out) {
         const size_t n = fls_preprocess_get(h_, what, nullptr, 0);
@@ -84,6 +104,7 @@ private:
     }
     fls_preprocess_handle h_ = nullptr;
     float leaf_ = 0.f;
+    fls_preprocess_result r_{};
     std::vector<uint64_t> t_;
     std::vector<double> q_;
     std::vector<float> rows_;

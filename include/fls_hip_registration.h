@@ -18,6 +18,7 @@
 
 #include "registration/registration_interface.h"
 #include "fls_reg.h"
+#include "fls_preprocess.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -146,6 +147,18 @@ public:
                                         T.data(), /*update_map=*/1, &stats_);
         if (rc < 0) std::fprintf(stderr, "HipRegistration::Match: %s\n", fls_status_string(rc));
         return rc == FLS_OK;  // errors and FLS_NOT_CONVERGED both mean "drop this frame" (frontend.cpp:208-210)
+    }
+
+    // Match on the scan a HipScanPreprocessor (fls_hip_preprocess.h) has just preprocessed, without the clouds visiting the host:
+    // the cloud Match above would read from the cluster (ordered for IcpOptimized / IncrementalNDT, planar -- filtered when a leaf
+    // size is set -- for the two point-to-plane kinds) is attached device to device.  Not for LoamFull (false).
+    template <class Preprocessor>
+    bool MatchPreprocessed(Preprocessor& pre, Mat4d& T) {
+        const bool ordered = (kind_ == FLS_ICP_OPTIMIZED || kind_ == FLS_INCREMENTAL_NDT);
+        fls_status rc = fls_scan_attach_preprocessed(handle_, pre.handle(), ordered ? FLS_PRE_ORDERED : pre.planar_what());
+        if (rc == FLS_OK) rc = fls_match_resident(handle_, T.data(), /*update_map=*/1, &stats_);
+        if (rc < 0) std::fprintf(stderr, "HipRegistration::MatchPreprocessed: %s\n", fls_status_string(rc));
+        return rc == FLS_OK;
     }
 
     void AddCloudToLocalMap(const std::initializer_list<PCLPointCloudXYZI>& cloud_list) override {

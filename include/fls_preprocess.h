@@ -1,5 +1,5 @@
 /* ============================================================================
- * fls_preprocess.h -- C ABI of the per-scan preprocessing that feeds Match (same shared library as fls_reg.h, revision 8):
+ * fls_preprocess.h -- C ABI of the per-scan preprocessing that feeds Match (same shared library as fls_reg.h, revisions 8 and 9):
  * IMU de-skew of a raw driver cloud, the range gate, the point-jump subsample and the planar VoxelGrid, on MI355X (gfx950).
  *
  *   PreProcessing::Run() per-scan loop            src/slam/preprocessing.cpp:86-223
@@ -80,6 +80,26 @@ fls_status fls_preprocess_scan(fls_preprocess_handle h, const void* raw_points, 
                                const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, fls_preprocess_result* result);
 /* copy a result array of the last scan into `out` (NULL: only the size); returns its element count */
 size_t fls_preprocess_get(fls_preprocess_handle h, int what, void* out, size_t cap_elems);
+/* Revision 9: fls_preprocess_scan with the clouds left in device memory.  Same arguments, validation, status codes, result struct and
+ * bits in every cloud; the host learns the counts only.  fls_preprocess_get after such a scan downloads the requested array on its
+ * first request (cached until the next scan) and returns what it returns after fls_preprocess_scan.  Where the device VoxelGrid
+ * declines (filter_on_device = 0) the planar cloud is downloaded for the exact host filter, as in fls_preprocess_scan. */
+fls_status fls_preprocess_scan_device(fls_preprocess_handle h, const void* raw_points, size_t n, const fls_raw_layout* layout, uint64_t stamp_us,
+                                      const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, fls_preprocess_result* result);
+/* Revision 9: make a cloud of `pre`'s last scan (what = FLS_PRE_ORDERED, FLS_PRE_PLANAR or FLS_PRE_PLANAR_FILTERED; after either scan
+ * function) the resident scan of `m`, device to device.  Afterwards `m` is in the state fls_scan_upload_raw(m, rows, n, NULL, 0, 4) leaves
+ * it in, rows = what fls_preprocess_get(pre, what, ...) returns: fls_match_resident runs the in-Match VoxelGrid of IcpOptimized /
+ * IncrementalNDT on the attached cloud, and for either value of update_map the result, the map and every later call equal the host
+ * path's.  The copy is queued on `m`'s stream behind the scan, and `pre`'s next scan is queued behind the copy (hipEvents; the host
+ * does not wait): `pre` may scan again at once, before `m` has matched.  `m` fetches host copies of the scan only when a map update or
+ * a declined device filter needs them; a Match with update_map == 0 downloads nothing of it.
+ * Kinds: FLS_P2PLANE_IVOX, FLS_P2PLANE_KDTREE, FLS_ICP_OPTIMIZED, FLS_INCREMENTAL_NDT.  FLS_ERR_STATE: no completed scan on `pre`, its
+ * last scan was DROP / WAIT (or invalid), or `m` is FLS_LOAM_FULL (its clouds come from fls_features_*).  FLS_ERR_INVALID: NULL handle,
+ * unknown `what`, handles on different devices.  On an error `m` keeps its resident scan.  An EMPTY_SEGMENT / EMPTY_CLOUD scan
+ * attaches an empty cloud.  A read-only replica accepts the call as it accepts fls_scan_upload. */
+fls_status fls_scan_attach_preprocessed(fls_handle m, fls_preprocess_handle pre, int what);
+/* introspection: bytes of result arrays and counts copied device -> host on behalf of the last scan so far (lazy downloads included) */
+fls_status fls_preprocess_get_host_bytes(fls_preprocess_handle h, uint64_t* d2h_bytes);
 /* device time of the last scan [ms] (hipEvents on the handle's stream): deskew_ms = the upload of the raw cloud + the de-skew and
  * compaction kernels, filter_ms = the planar VoxelGrid */
 fls_status fls_preprocess_get_time(fls_preprocess_handle h, double* deskew_ms, double* filter_ms);

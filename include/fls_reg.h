@@ -38,9 +38,10 @@ extern "C" {
 /* Additive revision of ABI version 1: entry points are only ever ADDED under one FLS_ABI_VERSION (existing signatures, struct layouts and
  * status codes do not change), and this number counts the additions -- 1: fls_match_batch, map export / import; 2: fls_voxel_grid_cloud,
  * fls_features_*; 3: fls_replicas_*, fls_loop_match; 4: fls_debug_exact_sort; 5: fls_scan_upload_raw; 6: fls_map_image_*; 7: fls_debug_ldlt6; 8: fls_preprocess_create,
- * fls_preprocess_destroy, fls_preprocess_scan, fls_preprocess_get, fls_preprocess_get_time, fls_features_project_deskew (include/fls_preprocess.h).  A caller built against revision r works with any library
+ * fls_preprocess_destroy, fls_preprocess_scan, fls_preprocess_get, fls_preprocess_get_time, fls_features_project_deskew (include/fls_preprocess.h); 9: fls_preprocess_scan_device,
+ * fls_scan_attach_preprocessed, fls_preprocess_get_host_bytes (include/fls_preprocess.h: the preprocessed scan goes to Match without leaving the device).  A caller built against revision r works with any library
  * whose fls_abi_revision() >= r. */
-#define FLS_ABI_REVISION 8
+#define FLS_ABI_REVISION 9
 
 /* Which reference class the handle replaces (mode strings: include/common/constant_variable.h:21-25). */
 typedef enum fls_kind {
