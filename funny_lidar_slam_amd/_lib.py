@@ -30,6 +30,9 @@ PREPROCESS_SYMBOLS = [
     "fls_features_project_deskew",
 ] + HANDOFF_SYMBOLS
 
+# every symbol include/fls_ingest.h declares (FLS_INGEST_REVISION 1)
+INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_preprocess_scan_driver", "fls_features_project_driver"]
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -136,6 +139,33 @@ class PreprocessResult(C.Structure):
 
 
 FLS_IMU_OK, FLS_IMU_DROP, FLS_IMU_WAIT, FLS_IMU_EMPTY_SEGMENT, FLS_IMU_EMPTY_CLOUD = range(5)
+
+
+class DriverCloud(C.Structure):
+    """fls_driver_cloud (include/fls_ingest.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("sensor", C.c_int32), ("point_step", C.c_uint32), ("is_dense", C.c_int32),
+                ("x_offset", C.c_uint32), ("y_offset", C.c_uint32), ("z_offset", C.c_uint32), ("intensity_offset", C.c_uint32),
+                ("ring_offset", C.c_uint32), ("time_offset", C.c_uint32), ("tag_offset", C.c_uint32), ("line_offset", C.c_uint32)]
+
+
+class IngestParams(C.Structure):
+    """fls_ingest_params (include/fls_ingest.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("vertical_scan_num", C.c_int32), ("lidar_point_time_scale", C.c_double),
+                ("lower_angle", C.c_float), ("v_res", C.c_float)]
+
+
+class IngestInfo(C.Structure):
+    """fls_ingest_info (include/fls_ingest.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("timeless", C.c_int32), ("n_message", C.c_uint64), ("n_converted", C.c_uint64),
+                ("time_min", C.c_float), ("time_max", C.c_float), ("time_last", C.c_float), ("reserved", C.c_int32), ("t0", C.c_double)]
+
+
+# LidarModel::LidarSensorType, same order (FLS_SENSOR_*)
+SENSOR_VELODYNE, SENSOR_OUSTER, SENSOR_LIVOX_AVIA, SENSOR_ROBOSENSE, SENSOR_LEISHEN, SENSOR_LIVOX_MID_360, SENSOR_NONE = range(7)
+FLS_PRE_CONVERTED, FLS_PRE_CONVERTED_INDEX = 16, 17
 
 
 def build(force: bool = False) -> str:
@@ -264,6 +294,16 @@ def lib():
         L.fls_features_project_deskew.restype = C.c_int
         L.fls_features_project_deskew.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(RawLayout), C.c_uint64, u64p, dp, C.c_size_t, dp,
                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.fls_ingest_revision.restype = C.c_int
+        L.fls_ingest_revision.argtypes = []
+        L.fls_ingest_default_layout.restype = C.c_int
+        L.fls_ingest_default_layout.argtypes = [C.c_int, C.POINTER(DriverCloud)]
+        L.fls_preprocess_scan_driver.restype = C.c_int
+        L.fls_preprocess_scan_driver.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(DriverCloud), C.POINTER(IngestParams), C.c_uint64, u64p, dp,
+                                                 C.c_size_t, C.c_int, C.POINTER(PreprocessResult), u64p, C.POINTER(IngestInfo)]
+        L.fls_features_project_driver.restype = C.c_int
+        L.fls_features_project_driver.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(DriverCloud), C.POINTER(IngestParams), C.c_uint64, u64p, dp,
+                                                  C.c_size_t, dp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), u64p, C.POINTER(IngestInfo)]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

@@ -627,4 +627,51 @@ fls_status fls_features_project_deskew(fls_features_handle h, const void* raw, s
     });
 }
 
+// ---- the driver-cloud front end (include/fls_ingest.h) ---------------------------------------------------------------------------
+int fls_ingest_revision(void) { return FLS_INGEST_REVISION; }
+
+fls_status fls_ingest_default_layout(int sensor, fls_driver_cloud* out) {
+    if (!out || sensor < FLS_SENSOR_VELODYNE || sensor > FLS_SENSOR_NONE) return FLS_ERR_INVALID;
+    fls_driver_cloud d{};
+    d.struct_size = sizeof(d);
+    d.sensor = sensor;
+    d.point_step = 32;
+    d.is_dense = 1;
+    d.x_offset = 0; d.y_offset = 4; d.z_offset = 8; d.intensity_offset = 16;  // PCL_ADD_POINT4D, then the intensity
+    switch (sensor) {
+        case FLS_SENSOR_VELODYNE: d.ring_offset = 20; d.time_offset = 24; break;
+        case FLS_SENSOR_OUSTER: d.time_offset = 20; d.ring_offset = 26; d.point_step = 48; break;  // t, reflectivity, ring, noise, range
+        case FLS_SENSOR_LIVOX_AVIA: d.time_offset = 20; d.line_offset = 24; d.tag_offset = 25; break;
+        case FLS_SENSOR_ROBOSENSE:
+        case FLS_SENSOR_LEISHEN: d.ring_offset = 20; d.time_offset = 24; break;
+        case FLS_SENSOR_LIVOX_MID_360: d.tag_offset = 20; d.line_offset = 21; d.time_offset = 24; break;
+        default: break;  // pcl::PointXYZI
+    }
+    *out = d;
+    return FLS_OK;
+}
+
+fls_status fls_preprocess_scan_driver(fls_preprocess_handle h, const void* msg, size_t n, const fls_driver_cloud* cloud, const fls_ingest_params* ingest,
+                                      uint64_t stamp_us, const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, int keep_on_device,
+                                      fls_preprocess_result* result, uint64_t* stamp_out_us, fls_ingest_info* info) {
+    if (!h || !cloud || !ingest || (!msg && n) || (result && result->struct_size != sizeof(fls_preprocess_result)) ||
+        (info && info->struct_size != sizeof(fls_ingest_info)))
+        return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->scan_driver(msg, n, *cloud, *ingest, stamp_us, imu_t_us, imu_q_xyzw, n_imu, result, keep_on_device != 0, stamp_out_us, info);
+    });
+}
+
+fls_status fls_features_project_driver(fls_features_handle h, const void* msg, size_t n, const fls_driver_cloud* cloud, const fls_ingest_params* ingest,
+                                       uint64_t stamp_us, const uint64_t* imu_t_us, const double* imu_q_xyzw, size_t n_imu, const double T_lidar_to_imu[16],
+                                       size_t* n_ordered, int* imu_status, uint64_t* stamp_out_us, fls_ingest_info* info) {
+    if (!h || !cloud || !ingest || (!msg && n) || !T_lidar_to_imu || (info && info->struct_size != sizeof(fls_ingest_info))) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return features_project_driver(*h, msg, n, *cloud, *ingest, stamp_us, imu_t_us, imu_q_xyzw, n_imu, T_lidar_to_imu, n_ordered, imu_status,
+                                       stamp_out_us, info);
+    });
+}
+
 }  // extern "C"

@@ -1,10 +1,11 @@
 // preprocess_host.hpp -- host side of include/fls_preprocess.h: the per-scan IMU segment (GetDataSegment, slerp), SetRefTime, the
-// staging of the raw cloud, the launches of kernels_deskew.hpp, the planar VoxelGrid; and fls_features_project_deskew.
+// staging of the raw cloud, the launches of kernels_deskew.hpp, the planar VoxelGrid; and fls_features_project_deskew.  Also the host
+// side of include/fls_ingest.h: validation of the driver-cloud descriptor, the launches of kernels_ingest.hpp and the summary read-back.
 #pragma once
 #include "features_host.hpp"
 #include "device_voxelgrid.hpp"
-#include "kernels_deskew.hpp"
-#include "../../include/fls_preprocess.h"
+#include "kernels_ingest.hpp"
+#include "../../include/fls_ingest.h"
 #include <cmath>
 #include <limits>
 
@@ -85,6 +86,7 @@ struct DeskewScratch {
         for (size_t k = 1; k < n_imu; ++k)
             if (!(it[k] > it[k - 1])) return FLS_ERR_INVALID;  // the searcher's deque is in time order (CHECKs of the reference)
         n = n_;
+        ingested = false;
         L = DeskewRawDev{l.stride_bytes, l.xyz_offset, l.intensity_offset, l.ring_offset, l.ring_bytes, l.time_offset};
         seg_t.clear();
         seg_q.clear();
@@ -106,6 +108,11 @@ struct DeskewScratch {
             if (v < mn) mn = v;
             if (v > mx) mx = v;
         }
+        return segment_and_params(mn, mx, stamp, it, iq, n_imu, T);
+    }
+
+    // from the time range of the cloud on: IMU status, segment (into the stage at seg_off), q_ref_inv, the extrinsic
+    fls_status segment_and_params(const float mn, const float mx, uint64_t stamp, const uint64_t* it, const double* iq, size_t n_imu, const double* T) {
         start = (uint64_t)((int64_t)stamp + deskew_trunc_i64((double)mn * 1.0e6));  // (:89-96)
         end = (uint64_t)((int64_t)stamp + deskew_trunc_i64((double)mx * 1.0e6));
         if (stamp < start) start = stamp;  // (:100-104)
@@ -135,7 +142,125 @@ struct DeskewScratch {
         return FLS_OK;
     }
 
-    // H2D of the stage, pass 1 (gate + de-skew of every point); returns the block count
+    // ---- the driver-cloud front end (include/fls_ingest.h, kernels_ingest.hpp) ---------------------------------------------------
+    bool ingested = false;  // the last prepare was prepare_driver: `raw` of the de-skew kernels is d_conv, d_in holds message | segment
+    DevBuf<unsigned char> d_conv, d_iflag, d_ring8;  // 32-byte PointXYZIRT rows; keep flags; compact ring array
+    DevBuf<int> d_cidx;                              // message index of every converted point
+    DevBuf<uint2> d_iblk, d_ioff;
+    DevBuf<unsigned> d_ictl;  // tot[2] | first_kept | nonfinite | timeless | pad[3] | first point of ring r, r < 256
+    DevBuf<float> d_tb;
+    DevBuf<IngestMinMax> d_part;
+    DevBuf<IngestMail> d_mail;
+    PinnedBuf<IngestMail> h_mail;
+    IngestMail mail{};
+    size_t n_msg = 0;
+    uint64_t stamp_out = 0;
+
+    static bool ingest_check(const fls_driver_cloud& c, const fls_ingest_params& ip, IngestDev& D) {
+        if (c.struct_size != sizeof(fls_driver_cloud) || ip.struct_size != sizeof(fls_ingest_params)) return false;
+        if (c.sensor < FLS_SENSOR_VELODYNE || c.sensor > FLS_SENSOR_NONE || !std::isfinite(ip.lidar_point_time_scale)) return false;
+        const int s = c.sensor;
+        const uint64_t step = c.point_step;
+        auto fits = [&](uint32_t off, uint32_t bytes) { return uint64_t(off) + bytes <= step; };
+        if (step == 0 || !fits(c.x_offset, 4) || !fits(c.y_offset, 4) || !fits(c.z_offset, 4) || !fits(c.intensity_offset, 4)) return false;
+        const bool ring16 = s == FLS_SENSOR_VELODYNE || s == FLS_SENSOR_ROBOSENSE || s == FLS_SENSOR_LEISHEN;
+        if (ring16 && !fits(c.ring_offset, 2)) return false;
+        if (s == FLS_SENSOR_OUSTER && !fits(c.ring_offset, 1)) return false;
+        const bool time64 = s == FLS_SENSOR_ROBOSENSE || s == FLS_SENSOR_LEISHEN || s == FLS_SENSOR_LIVOX_MID_360;
+        if (s != FLS_SENSOR_NONE && !fits(c.time_offset, time64 ? 8 : 4)) return false;
+        if (s == FLS_SENSOR_LIVOX_AVIA && (!fits(c.tag_offset, 1) || !fits(c.line_offset, 1))) return false;
+        const bool need_vsn = s == FLS_SENSOR_VELODYNE || s == FLS_SENSOR_NONE;
+        if (need_vsn && (ip.vertical_scan_num < 1 || ip.vertical_scan_num > 255)) return false;
+        D = IngestDev{};
+        D.sensor = s;
+        D.drop_nonfinite = c.is_dense ? 0 : 1;
+        D.step = c.point_step;
+        D.off_x = c.x_offset; D.off_y = c.y_offset; D.off_z = c.z_offset; D.off_i = c.intensity_offset;
+        D.off_ring = c.ring_offset; D.off_time = c.time_offset; D.off_tag = c.tag_offset; D.off_line = c.line_offset;
+        D.vsn = need_vsn ? ip.vertical_scan_num : 0;
+        D.lower_angle = ip.lower_angle;
+        D.v_res = ip.v_res;
+        D.scale = ip.lidar_point_time_scale;
+        return true;
+    }
+
+    // static_cast<uint64_t>(double) as x86-64 executes it
+    static uint64_t trunc_u64(const double v) {
+        if (v >= 9223372036854775808.0) return (uint64_t)deskew_trunc_i64(v - 9223372036854775808.0) ^ 0x8000000000000000ull;
+        return (uint64_t)deskew_trunc_i64(v);
+    }
+
+    // prepare() for a driver message: the message goes to the device (d_in), the conversion runs there, the summary comes back, and
+    // from the time range on everything is prepare()'s.  Afterwards n = the converted count and L = the PointXYZIRT layout.
+    fls_status prepare_driver(hipStream_t s, const void* msg, size_t n_, const fls_driver_cloud& c, const fls_ingest_params& ip, uint64_t stamp,
+                              const uint64_t* it, const double* iq, size_t n_imu, const double* T) {
+        IngestDev D;
+        if (!ingest_check(c, ip, D) || (!msg && n_) || !it || !iq || !T || n_imu < 2 || n_ > 0x7FFFFFF0ull ||
+            uint64_t(n_) * c.point_step > 0x7FFFFFF0ull)
+            return FLS_ERR_INVALID;
+        for (size_t k = 1; k < n_imu; ++k)
+            if (!(it[k] > it[k - 1])) return FLS_ERR_INVALID;
+        n_msg = n_;
+        n = 0;
+        ingested = true;
+        L = DeskewRawDev{32, 0, 16, 20, 1, 24};
+        mail = IngestMail{};
+        stamp_out = stamp;
+        seg_t.clear();
+        seg_q.clear();
+        start = end = 0;
+        imu_status = FLS_IMU_EMPTY_CLOUD;
+        if (n_msg == 0) return FLS_OK;
+        D.n = unsigned(n_msg);
+        raw_bytes = n_msg * c.point_step;
+        seg_off = (raw_bytes + 15) & ~size_t(15);
+        const size_t all = seg_off + size_t(kDeskewMaxSeg) * 40;
+        stage.reserve(all);
+        d_in.reserve(all);
+        std::memcpy(stage.p, msg, raw_bytes);
+        const unsigned nb = unsigned((n_msg + kIngestThreads - 1) / kIngestThreads);
+        d_conv.reserve(32 * n_msg); d_iflag.reserve(n_msg); d_ring8.reserve(n_msg); d_cidx.reserve(n_msg); d_tb.reserve(n_msg);
+        d_iblk.reserve(nb); d_ioff.reserve(nb); d_part.reserve(nb);
+        d_ictl.reserve(8 + 256); d_mail.reserve(1); h_mail.reserve(1);
+        unsigned *tot = d_ictl.p, *first_kept = d_ictl.p + 2, *nonfinite = d_ictl.p + 3, *timeless = d_ictl.p + 4, *ring_first = d_ictl.p + 8;
+        uint4* rows = (uint4*)d_conv.p;
+        FLS_HIP(hipMemcpyAsync(d_in.p, stage.p, raw_bytes, hipMemcpyHostToDevice, s));
+        FLS_HIP(hipMemsetAsync(d_ictl.p, 0, 8 * sizeof(unsigned), s));
+        FLS_HIP(hipMemsetAsync(first_kept, 0xFF, sizeof(unsigned), s));
+        hipLaunchKernelGGL(ingest_count_kernel, dim3(nb), dim3(kIngestThreads), 0, s, d_in.p, D, d_iflag.p, d_iblk.p, first_kept);
+        hipLaunchKernelGGL(deskew_scan_kernel, dim3(1), dim3(1024), 0, s, d_iblk.p, nb, d_ioff.p, tot);
+        hipLaunchKernelGGL(ingest_write_kernel, dim3(nb), dim3(kIngestThreads), 0, s, d_in.p, D, d_iflag.p, d_ioff.p, first_kept, rows, d_cidx.p, d_ring8.p);
+        if (D.vsn) {  // Velodyne / None: ComputePointOffsetTime where the last converted time is <= 0 (decided on the device)
+            hipLaunchKernelGGL(ingest_ring_first_kernel, dim3(unsigned(D.vsn)), dim3(kIngestRingThreads), 0, s, D, tot, rows, d_ring8.p, ring_first, timeless);
+            hipLaunchKernelGGL(ingest_base_kernel, dim3(nb), dim3(kIngestThreads), 0, s, D, tot, rows, ring_first, timeless, d_tb.p);
+            hipLaunchKernelGGL(ingest_ring_scan_kernel, dim3(unsigned(D.vsn)), dim3(kIngestRingThreads), 0, s, D, tot, rows, d_ring8.p, ring_first, timeless,
+                               d_tb.p);
+        }
+        hipLaunchKernelGGL(ingest_minmax_kernel, dim3(nb), dim3(kIngestThreads), 0, s, tot, rows, d_part.p, nonfinite);
+        hipLaunchKernelGGL(ingest_summary_kernel, dim3(1), dim3(1024), 0, s, D, d_in.p, tot, rows, d_part.p, nb, first_kept, nonfinite, timeless, d_mail.p);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipMemcpyAsync(h_mail.p, d_mail.p, sizeof(IngestMail), hipMemcpyDeviceToHost, s));
+        FLS_HIP(hipStreamSynchronize(s));
+        mail = *h_mail.p;
+        n = mail.n_conv;
+        if (c.sensor == FLS_SENSOR_ROBOSENSE && n) stamp_out = trunc_u64(mail.t0 * 1.0e6);  // (:376)
+        if (n == 0) return FLS_OK;  // (the reference reads points.back() / [0] of the empty cloud: undefined there, EMPTY_CLOUD here)
+        if (mail.nonfinite) return FLS_ERR_INVALID;
+        return segment_and_params(mail.t_min, mail.t_max, stamp_out, it, iq, n_imu, T);
+    }
+    void fill_info(fls_ingest_info* info) const {
+        if (!info) return;
+        info->timeless = int32_t(mail.timeless);
+        info->n_message = n_msg;
+        info->n_converted = n;
+        info->time_min = mail.t_min; info->time_max = mail.t_max; info->time_last = mail.t_last;
+        info->reserved = 0;
+        info->t0 = mail.t0;
+    }
+    // the cloud the de-skew and projection kernels read (valid after upload_and_deskew)
+    const unsigned char* raw_dev() const { return ingested ? d_conv.p : d_in.p; }
+
+    // H2D of the stage (after prepare_driver: of the segment only), pass 1 (gate + de-skew of every point); returns the block count
     unsigned upload_and_deskew(hipStream_t s, bool gate, float min_d, float max_d, unsigned span) {
         P.gate = gate ? 1 : 0;
         P.min_dist = min_d;
@@ -148,10 +273,11 @@ struct DeskewScratch {
         d_flag.reserve(n);
         d_blk.reserve(nb);
         d_off.reserve(nb);
-        FLS_HIP(hipMemcpyAsync(d_in.p, stage.p, bytes, hipMemcpyHostToDevice, s));
+        if (ingested) FLS_HIP(hipMemcpyAsync(d_in.p + seg_off, stage.p + seg_off, seg_t.size() * 40, hipMemcpyHostToDevice, s));
+        else FLS_HIP(hipMemcpyAsync(d_in.p, stage.p, bytes, hipMemcpyHostToDevice, s));
         const auto* st = (const unsigned long long*)(d_in.p + seg_off);
         const auto* sq = (const double*)(d_in.p + seg_off + seg_t.size() * 8);
-        hipLaunchKernelGGL(deskew_point_kernel, dim3(nb), dim3(kDeskewThreads), seg_t.size() * 40, s, d_in.p, L, P, st, sq, d_corr.p, d_flag.p, d_blk.p);
+        hipLaunchKernelGGL(deskew_point_kernel, dim3(nb), dim3(kDeskewThreads), seg_t.size() * 40, s, raw_dev(), L, P, st, sq, d_corr.p, d_flag.p, d_blk.p);
         FLS_HIP(hipGetLastError());
         return nb;
     }
@@ -180,6 +306,10 @@ struct fls_preprocess {
     // have not been downloaded yet (fls_preprocess_get fetches them on first request)
     size_t n_ordered = 0, n_planar = 0, n_planar_f = 0, planar_cap = 0;
     bool stale_ordered = false, stale_idx = false, stale_planar = false, stale_planar_f = false;
+    // fls_preprocess_scan_driver: host copies of the converted cloud / its message indices, downloaded on their first request
+    std::vector<unsigned char> converted;
+    std::vector<int> converted_idx;
+    bool stale_conv = false, stale_cidx = false;
     bool scan_done = false;      // a scan has completed with clouds (not DROP / WAIT, not an invalid call)
     uint64_t d2h_bytes = 0;      // device -> host copies on behalf of the last scan so far
     // hand-off (fls_scan_attach_preprocessed): ready = "everything queued on this stream so far", recorded per attach and waited for
@@ -219,6 +349,8 @@ struct fls_preprocess {
         filter_on_device = false;
         n_ordered = n_planar = n_planar_f = 0;
         stale_ordered = stale_idx = stale_planar = stale_planar_f = false;
+        stale_conv = stale_cidx = false;
+        converted.clear(); converted_idx.clear();
         scan_done = false;
         d2h_bytes = 0;
     }
@@ -264,6 +396,25 @@ struct fls_preprocess {
         clear();
         const fls_status rc = ds.prepare(raw, n, L, stamp, it, iq, n_imu, p.T_lidar_to_imu, false);
         if (rc != FLS_OK) return rc;
+        return finish_scan(r, on_device);
+    }
+
+    // fls_preprocess_scan_driver: the conversion in front, then the same scan on the converted cloud
+    fls_status scan_driver(const void* msg, size_t n_msg, const fls_driver_cloud& c, const fls_ingest_params& ip, uint64_t stamp, const uint64_t* it,
+                           const double* iq, size_t n_imu, fls_preprocess_result* r, const bool on_device, uint64_t* stamp_out, fls_ingest_info* info) {
+        clear();
+        const fls_status rc = ds.prepare_driver(stream, msg, n_msg, c, ip, stamp, it, iq, n_imu, p.T_lidar_to_imu);
+        if (rc != FLS_OK) return rc;
+        d2h_bytes += sizeof(fls::IngestMail);
+        if (stamp_out) *stamp_out = ds.stamp_out;
+        ds.fill_info(info);
+        stale_conv = stale_cidx = true;
+        return finish_scan(r, on_device);
+    }
+
+    // after ds.prepare / ds.prepare_driver succeeded: the de-skew, the compaction, the planar VoxelGrid, the report
+    fls_status finish_scan(fls_preprocess_result* r, const bool on_device) {
+        const size_t n = ds.n;
         auto report = [&](fls_status s) {
             if (r) {
                 r->imu_status = ds.imu_status;
@@ -339,6 +490,24 @@ struct fls_preprocess {
             case FLS_PRE_ORDERED_INDEX: if (stale_idx) { enqueue_ordered_idx(); FLS_HIP(hipStreamSynchronize(stream)); } break;
             case FLS_PRE_PLANAR: if (stale_planar) { enqueue_planar(); FLS_HIP(hipStreamSynchronize(stream)); finish_planar(); } break;
             case FLS_PRE_PLANAR_FILTERED: if (stale_planar_f) fetch_planar_f(); break;
+            case FLS_PRE_CONVERTED:
+                if (stale_conv) {
+                    converted.resize(32 * ds.n);
+                    if (ds.n) FLS_HIP(hipMemcpyAsync(converted.data(), ds.d_conv.p, 32 * ds.n, hipMemcpyDeviceToHost, stream));
+                    FLS_HIP(hipStreamSynchronize(stream));
+                    d2h_bytes += 32 * ds.n;
+                    stale_conv = false;
+                }
+                break;
+            case FLS_PRE_CONVERTED_INDEX:
+                if (stale_cidx) {
+                    converted_idx.resize(ds.n);
+                    if (ds.n) FLS_HIP(hipMemcpyAsync(converted_idx.data(), ds.d_cidx.p, ds.n * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    FLS_HIP(hipStreamSynchronize(stream));
+                    d2h_bytes += ds.n * sizeof(int);
+                    stale_cidx = false;
+                }
+                break;
             default: break;
         }
     }
@@ -378,6 +547,12 @@ struct fls_preprocess {
             case FLS_PRE_ORDERED_INDEX: return copy_out(ordered_idx.data(), n_ordered, out, cap);
             case FLS_PRE_PLANAR: return copy_out(planar.data(), n_planar, out, cap);
             case FLS_PRE_PLANAR_FILTERED: return copy_out(planar_f.data(), n_planar_f, out, cap);
+            case FLS_PRE_CONVERTED: {
+                const size_t m = converted.size() / 32;
+                if (out && m) std::memcpy(out, converted.data(), std::min(cap, m) * 32);
+                return (stale_conv || !converted.empty()) ? ds.n : 0;
+            }
+            case FLS_PRE_CONVERTED_INDEX: return (stale_cidx || !converted_idx.empty()) ? copy_out(converted_idx.data(), ds.n, out, cap) : 0;
             case FLS_PRE_SEGMENT_T: return copy_out(ds.seg_t.data(), ds.seg_t.size(), out, cap);
             case FLS_PRE_SEGMENT_Q: {
                 const size_t m = ds.seg_t.size();
@@ -391,12 +566,33 @@ struct fls_preprocess {
 
 // fls_features_project_deskew: pass 1 without the gate (every point's ProcessPoint), then the projection where only points whose
 // de-skew succeeded compete for their cell, the usual ring compaction, and the corrected xyz into the ordered cloud
+inline fls_status features_project_prepared(fls_features& f, size_t* n_ordered, int* imu_status);
+
 inline fls_status features_project_deskew(fls_features& f, const void* raw, size_t n, const fls_raw_layout& L, uint64_t stamp, const uint64_t* it,
                                           const double* iq, size_t n_imu, const double* T, size_t* n_ordered, int* imu_status) {
     if (!f.deskew) f.deskew = std::make_shared<fls::DeskewScratch>();
-    fls::DeskewScratch& ds = *f.deskew;
-    const fls_status rc = ds.prepare(raw, n, L, stamp, it, iq, n_imu, T, true);
+    const fls_status rc = f.deskew->prepare(raw, n, L, stamp, it, iq, n_imu, T, true);
     if (rc != FLS_OK) return rc;
+    return features_project_prepared(f, n_ordered, imu_status);
+}
+
+// fls_features_project_driver: the conversion in front (on the feature handle's stream), then the same projection
+inline fls_status features_project_driver(fls_features& f, const void* msg, size_t n, const fls_driver_cloud& c, const fls_ingest_params& ip, uint64_t stamp,
+                                          const uint64_t* it, const double* iq, size_t n_imu, const double* T, size_t* n_ordered, int* imu_status,
+                                          uint64_t* stamp_out, fls_ingest_info* info) {
+    if (!f.deskew) f.deskew = std::make_shared<fls::DeskewScratch>();
+    const fls_status rc = f.deskew->prepare_driver(f.stream, msg, n, c, ip, stamp, it, iq, n_imu, T);
+    if (rc != FLS_OK) return rc;
+    if (stamp_out) *stamp_out = f.deskew->stamp_out;
+    f.deskew->fill_info(info);
+    return features_project_prepared(f, n_ordered, imu_status);
+}
+
+// after ds.prepare / ds.prepare_driver succeeded
+inline fls_status features_project_prepared(fls_features& f, size_t* n_ordered, int* imu_status) {
+    fls::DeskewScratch& ds = *f.deskew;
+    const size_t n = ds.n;
+    const fls::DeskewRawDev L{ds.L};
     if (imu_status) *imu_status = ds.imu_status;
     f.projected = f.extracted = false;
     f.have_raw_index = f.have_intro = false;
@@ -408,16 +604,16 @@ inline fls_status features_project_deskew(fls_features& f, const void* raw, size
     const fls::FeatParamsDev& pd = f.pd;
     const size_t cells = size_t(pd.rows) * size_t(pd.cols);
     // feat_compact_kernel reads the ring field as a uint16 it does not use: point it at the xyz (in bounds for any ring width)
-    f.layout = fls::RawLayoutDev{L.stride_bytes, L.xyz_offset, L.intensity_offset, L.xyz_offset};
+    f.layout = fls::RawLayoutDev{L.stride, L.off_xyz, L.off_i, L.off_xyz};
     FLS_HIP(hipEventRecord(f.ev[0], f.stream));
     FLS_HIP(hipMemsetAsync(f.d_owner.p, 0xFF, cells * sizeof(unsigned), f.stream));
     if (ds.imu_status == FLS_IMU_OK) {
         ds.upload_and_deskew(f.stream, false, pd.min_dist, pd.max_dist, 1u);
-        hipLaunchKernelGGL(fls::feat_project_deskew_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, f.stream, ds.d_in.p, unsigned(n), ds.L, pd,
+        hipLaunchKernelGGL(fls::feat_project_deskew_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, f.stream, ds.raw_dev(), unsigned(n), ds.L, pd,
                            ds.d_flag.p, f.d_owner.p);
     }
     // (EMPTY_SEGMENT / EMPTY_CLOUD: every ProcessPoint fails, no cell is claimed; the compaction runs on the empty image)
-    const unsigned char* raw_dev = ds.imu_status == FLS_IMU_OK ? ds.d_in.p : nullptr;
+    const unsigned char* raw_dev = ds.imu_status == FLS_IMU_OK ? ds.raw_dev() : nullptr;
     hipLaunchKernelGGL(fls::feat_count_kernel, dim3(unsigned(pd.rows)), dim3(256), 0, f.stream, f.d_owner.p, pd, f.d_row_count.p);
     hipLaunchKernelGGL(fls::feat_compact_kernel, dim3(unsigned(pd.rows)), dim3(256), 0, f.stream, raw_dev, f.layout, f.d_owner.p, pd, f.d_row_count.p,
                        f.d_ordered.p, f.d_depth.p, f.d_col.p, f.d_raw_index.p, f.d_valid.p, f.d_row_start.p, f.d_row_end.p, f.d_n.p);

@@ -71,6 +71,27 @@ class FeatureFrontEnd:
             raise e
         return int(n.value), IMU_STATUS[st.value]
 
+    def project_driver(self, msg: np.ndarray, sensor: int, stamp_us: int, imu_t_us, imu_q_xyzw, ingest, T_lidar_to_imu=None, is_dense: bool = True):
+        """project_deskew() on a driver message (fls_features_project_driver): ConvertMessageToCloud runs on the device first; ring,
+        corrected xyz and the raw index come from the converted cloud.  Returns (n_ordered, imu_status, stamp_out_us, IngestInfo)."""
+        from .preprocess import IMU_STATUS, driver_cloud, imu_arrays
+        msg = np.ascontiguousarray(msg)
+        dc = driver_cloud(msg.dtype, sensor, is_dense)
+        t, q = imu_arrays(imu_t_us, imu_q_xyzw)
+        T = np.eye(4) if T_lidar_to_imu is None else np.asarray(T_lidar_to_imu, dtype=np.float64)
+        Tc = np.ascontiguousarray(T.reshape(4, 4).T.reshape(-1))  # column-major
+        n, st, stamp_out = C.c_size_t(), C.c_int(-1), C.c_uint64()
+        info = _lib.IngestInfo()
+        info.struct_size = C.sizeof(_lib.IngestInfo)
+        rc = _lib.lib().fls_features_project_driver(self._h, msg.ctypes.data, msg.shape[0], C.byref(dc), C.byref(ingest), int(stamp_us),
+                                                    t.ctypes.data_as(C.POINTER(C.c_uint64)), q.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0],
+                                                    Tc.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n), C.byref(st), C.byref(stamp_out), C.byref(info))
+        if rc != _lib.FLS_OK:
+            e = FlsError(rc, "fls_features_project_driver")
+            e.imu_status = IMU_STATUS.get(st.value)
+            raise e
+        return int(n.value), IMU_STATUS[st.value], int(stamp_out.value), info
+
     def extract(self):
         nc, npl = C.c_size_t(), C.c_size_t()
         rc = _lib.lib().fls_features_extract(self._h, C.byref(nc), C.byref(npl))

@@ -12,12 +12,12 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import FlsError, PreprocessParams, PreprocessResult, RawLayout
+from ._lib import DriverCloud, FlsError, IngestInfo, IngestParams, PreprocessParams, PreprocessResult, RawLayout
 
 IMU_STATUS = {_lib.FLS_IMU_OK: "ok", _lib.FLS_IMU_DROP: "drop", _lib.FLS_IMU_WAIT: "wait", _lib.FLS_IMU_EMPTY_SEGMENT: "empty_segment",
               _lib.FLS_IMU_EMPTY_CLOUD: "empty_cloud"}
 ARRAYS = {"ordered": (0, np.float32, 4), "ordered_index": (1, np.int32, 1), "planar": (2, np.float32, 4), "planar_filtered": (3, np.float32, 4),
-          "segment_t": (4, np.uint64, 1), "segment_q": (5, np.float64, 4)}
+          "segment_t": (4, np.uint64, 1), "segment_q": (5, np.float64, 4), "converted_index": (_lib.FLS_PRE_CONVERTED_INDEX, np.int32, 1)}
 
 
 def raw_layout(dtype: np.dtype, need_ring: bool = False) -> RawLayout:
@@ -35,6 +35,28 @@ def raw_layout(dtype: np.dtype, need_ring: bool = False) -> RawLayout:
     elif need_ring:
         raise ValueError("the projection needs a ring field")
     return RawLayout(dtype.itemsize, f["x"][1], f["intensity"][1], ring_off, ring_bytes, f["time"][1])
+
+
+# the converted cloud fls_preprocess_get(FLS_PRE_CONVERTED) returns: PointXYZIRT, fls_raw_layout {32, 0, 16, 20, 1, 24}
+CONVERTED_DTYPE = np.dtype({"names": ["x", "y", "z", "intensity", "ring", "time"], "formats": ["<f4", "<f4", "<f4", "<f4", "u1", "<f4"],
+                            "offsets": [0, 4, 8, 16, 20, 24], "itemsize": 32})
+_TIME_NAMES = ("time", "t", "timestamp")
+
+
+def driver_cloud(dtype: np.dtype, sensor: int, is_dense: bool = True) -> DriverCloud:
+    """fls_driver_cloud of a structured message dtype: x, y, z, intensity by name, the time field as `time`, `t` or `timestamp`, and
+    ring / tag / line where the sensor has them.  Offsets and itemsize need not be aligned (the packed Livox message)."""
+    f = dtype.fields
+    if f is None or not all(k in f for k in ("x", "y", "z", "intensity")):
+        raise ValueError("a driver message must be a structured array with x, y, z, intensity")
+    off = {k: (f[k][1] if k in f else 0) for k in ("x", "y", "z", "intensity", "ring", "tag", "line")}
+    t = next((f[k][1] for k in _TIME_NAMES if k in f), 0)
+    return DriverCloud(C.sizeof(DriverCloud), int(sensor), dtype.itemsize, 1 if is_dense else 0, off["x"], off["y"], off["z"], off["intensity"],
+                       off["ring"], t, off["tag"], off["line"])
+
+
+def ingest_params(time_scale: float = 1.0, vertical_scan_num: int = 0, lower_angle: float = 0.0, v_res: float = 0.0) -> IngestParams:
+    return IngestParams(C.sizeof(IngestParams), int(vertical_scan_num), float(time_scale), float(lower_angle), float(v_res))
 
 
 def imu_arrays(t_us, q_xyzw):
@@ -103,6 +125,29 @@ class ScanPreprocessor:
         res.status = rc
         return res
 
+    def scan_driver(self, msg: np.ndarray, sensor: int, stamp_us: int, imu_t_us, imu_q_xyzw, ingest: IngestParams, keep_on_device: bool = False,
+                    is_dense: bool = True, cloud: DriverCloud | None = None) -> PreprocessResult:
+        """ConvertMessageToCloud on the device, then scan() / scan_device() on the converted cloud (fls_preprocess_scan_driver).  `msg`:
+        the driver message as a structured array (see driver_cloud()).  Returns the result struct with `.status`; `self.stamp_out` is
+        the header stamp the reference goes on with, `self.ingest_info` the conversion's summary; get("converted") /
+        get("converted_index") return the converted cloud and the message index of each of its points."""
+        msg = np.ascontiguousarray(msg)
+        dc = driver_cloud(msg.dtype, sensor, is_dense) if cloud is None else cloud
+        t, q = imu_arrays(imu_t_us, imu_q_xyzw)
+        res = PreprocessResult()
+        res.struct_size = C.sizeof(PreprocessResult)
+        info = IngestInfo()
+        info.struct_size = C.sizeof(IngestInfo)
+        stamp_out = C.c_uint64()
+        rc = _lib.lib().fls_preprocess_scan_driver(self._h, msg.ctypes.data, msg.shape[0], C.byref(dc), C.byref(ingest), int(stamp_us),
+                                                   t.ctypes.data_as(C.POINTER(C.c_uint64)), q.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0],
+                                                   1 if keep_on_device else 0, C.byref(res), C.byref(stamp_out), C.byref(info))
+        if rc not in (_lib.FLS_OK, _lib.FLS_ERR_STATE):
+            raise FlsError(rc, "fls_preprocess_scan_driver")
+        self.last, self.stamp_out, self.ingest_info = res, int(stamp_out.value), info
+        res.status = rc
+        return res
+
     def output(self, status: int | None = None) -> PreprocessOutput:
         """The PreprocessOutput of the last scan (after scan_device: downloads the four clouds)."""
         res = self.last
@@ -119,6 +164,11 @@ class ScanPreprocessor:
         return int(n.value)
 
     def get(self, name: str) -> np.ndarray:
+        if name == "converted":
+            n = _lib.lib().fls_preprocess_get(self._h, _lib.FLS_PRE_CONVERTED, None, 0)
+            rows = np.zeros(max(n, 1), dtype=CONVERTED_DTYPE)
+            _lib.lib().fls_preprocess_get(self._h, _lib.FLS_PRE_CONVERTED, rows.ctypes.data, n)
+            return rows[:n]
         what, dt, cols = ARRAYS[name]
         n = _lib.lib().fls_preprocess_get(self._h, what, None, 0)
         out = np.zeros((max(n, 1), cols), dtype=dt)

@@ -171,6 +171,67 @@ def cast_raw_scan(scene: dict, T_gt: np.ndarray, n_rings: int, n_az: int, elev0_
     return out
 
 
+# ---- driver messages of the seven sensor types (include/fls_ingest.h): the reference's PCL structs (include/lidar/lidar_point_type.h)
+# as numpy structured dtypes, and the packed 22-byte Livox row of the CustomMsg repacking (system.cpp:476-529) -------------------------
+def _dt(names, formats, offsets, itemsize):
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": itemsize})
+
+
+SENSORS = {"velodyne": 0, "ouster": 1, "livox_avia": 2, "robosense": 3, "leishen": 4, "livox_mid_360": 5, "none": 6}  # LidarSensorType
+_XYZI = (["x", "y", "z", "intensity"], ["<f4", "<f4", "<f4", "<f4"], [0, 4, 8, 16])
+DRIVER_DTYPES = {
+    "velodyne": RAW_POINT_DTYPE,
+    "ouster": _dt(_XYZI[0] + ["t", "reflectivity", "ring", "noise", "range"], _XYZI[1] + ["<u4", "<u2", "u1", "<u2", "<u4"], _XYZI[2] + [20, 24, 26, 28, 32], 48),
+    "livox_avia": _dt(_XYZI[0] + ["time", "line", "tag"], _XYZI[1] + ["<u4", "u1", "u1"], _XYZI[2] + [20, 24, 25], 32),
+    "robosense": _dt(_XYZI[0] + ["ring", "timestamp"], _XYZI[1] + ["<u2", "<f8"], _XYZI[2] + [20, 24], 32),
+    "leishen": _dt(_XYZI[0] + ["ring", "timestamp"], _XYZI[1] + ["<u2", "<f8"], _XYZI[2] + [20, 24], 32),
+    "livox_mid_360": _dt(_XYZI[0] + ["tag", "line", "timestamp"], _XYZI[1] + ["u1", "u1", "<f8"], _XYZI[2] + [20, 21, 24], 32),
+    "none": _dt(*_XYZI, 32),
+}
+LIVOX_PACKED_DTYPE = _dt(["x", "y", "z", "intensity", "time", "line", "tag"], ["<f4", "<f4", "<f4", "<f4", "<u4", "u1", "u1"], [0, 4, 8, 12, 16, 20, 21], 22)
+DRIVER_TIME_SCALE = {"velodyne": 1.0, "ouster": 1e-9, "livox_avia": 1e-9, "robosense": 1.0, "leishen": 1.0, "livox_mid_360": 1.0, "none": 1.0}
+
+
+def driver_message(sensor: str, raw: np.ndarray, stamp_us: int = 0, rng: np.random.Generator | None = None, packed: bool = False) -> np.ndarray:
+    """The message a `sensor` driver would publish for the Velodyne-style scan `raw` (RAW_POINT_DTYPE: xyz, intensity, ring, time [s]).
+    Times are encoded as the sensor encodes them (DRIVER_TIME_SCALE is the matching lidar_point_time_scale): uint32 ns, double
+    seconds, or double absolute seconds (RoboSense, Mid-360: header stamp + offset).  Livox: line and tag drawn at random over all
+    8 lines and 4 tag classes of bits 4-5 (other tag bits random too); `packed`: the 22-byte unaligned row."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    dt = LIVOX_PACKED_DTYPE if (packed and sensor == "livox_avia") else DRIVER_DTYPES[sensor]
+    n = raw.shape[0]
+    msg = np.zeros(n, dtype=dt)
+    for k in ("x", "y", "z", "intensity"):
+        msg[k] = raw[k]
+    t = raw["time"].astype(np.float64)
+    if sensor == "velodyne":
+        msg["ring"], msg["time"] = raw["ring"], raw["time"]
+    elif sensor == "ouster":
+        msg["ring"], msg["t"] = raw["ring"].astype(np.uint8), np.round(t * 1e9).astype(np.uint32)
+        msg["reflectivity"], msg["noise"], msg["range"] = rng.integers(0, 65535, n), rng.integers(0, 65535, n), rng.integers(0, 2**31, n)
+    elif sensor == "livox_avia":
+        msg["time"], msg["line"], msg["tag"] = np.round(t * 1e9).astype(np.uint32), rng.integers(0, 8, n), rng.integers(0, 256, n)
+    elif sensor in ("robosense", "leishen"):
+        msg["ring"] = raw["ring"]
+        msg["timestamp"] = t + (stamp_us * 1e-6 if sensor == "robosense" else 0.0)
+    elif sensor == "livox_mid_360":
+        msg["tag"], msg["line"], msg["timestamp"] = rng.integers(0, 256, n), rng.integers(0, 4, n), t + stamp_us * 1e-6
+    return msg
+
+
+def punch_nonfinite(msg: np.ndarray, idx, rng: np.random.Generator | None = None) -> np.ndarray:
+    """A non-dense copy of `msg`: the points `idx` get a NaN or an infinity in one of x, y, z."""
+    rng = np.random.default_rng(1) if rng is None else rng
+    out = msg.copy()
+    idx = np.asarray(idx, dtype=np.int64)
+    axis = rng.integers(0, 3, idx.size)
+    val = rng.choice(np.array([np.nan, np.inf, -np.inf], np.float32), idx.size)
+    for a, name in enumerate(("x", "y", "z")):
+        sel = idx[axis == a]
+        out[name][sel] = val[axis == a]
+    return out
+
+
 def _surfaces(scene: dict):
     """List of vertical wall rectangles (origin, u, v, normal) for area sampling."""
     rects = []

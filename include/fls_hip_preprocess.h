@@ -4,8 +4,10 @@
 // de-skewed on the device.  The caller keeps the queue logic of Run(): Run() below returns what the reference would do.
 // Templates over the cluster / cloud / IMU types; needs only fls_preprocess.h (no Eigen, no PCL).  IMU samples expose timestamp_ (us)
 // and orientation_.x() .y() .z() .w() (IMUData with an Eigen::Quaterniond).
+// RunDriver / RunDriverOnDevice take the driver message's bytes and an fls_driver_cloud instead of a
+// converted cloud: they replace ConvertMessageToCloud as well.
 #pragma once
-#include "fls_preprocess.h"
+#include "fls_ingest.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -53,6 +55,22 @@ public:
     int RunOnDevice(uint64_t stamp_us, const RawCloud& raw, const ImuVec& imu) {
         return Scan(raw, stamp_us, imu, /*on_device=*/true);
     }
+    // Run() / RunOnDevice() from the driver message itself (sensor_msgs::PointCloud2: data.data(), width * height, and a descriptor
+    // made from point_step, is_dense and the offsets of the message's fields): ConvertMessageToCloud runs on the device.
+    // *stamp_out_us: the header stamp the reference goes on with (RoboSense: the first kept point's time).
+    template <class Cluster, class ImuVec>
+    int RunDriver(Cluster& c, const void* msg_points, size_t n, const fls_driver_cloud& cloud, const fls_ingest_params& ingest, uint64_t stamp_us,
+                  const ImuVec& imu, uint64_t* stamp_out_us = nullptr) {
+        const int st = ScanDriver(msg_points, n, cloud, ingest, stamp_us, imu, /*on_device=*/false, stamp_out_us);
+        if (st >= 0 && st != FLS_IMU_DROP && st != FLS_IMU_WAIT) FillCluster(c);
+        return st;
+    }
+    template <class ImuVec>
+    int RunDriverOnDevice(const void* msg_points, size_t n, const fls_driver_cloud& cloud, const fls_ingest_params& ingest, uint64_t stamp_us,
+                          const ImuVec& imu, uint64_t* stamp_out_us = nullptr) {
+        return ScanDriver(msg_points, n, cloud, ingest, stamp_us, imu, /*on_device=*/true, stamp_out_us);
+    }
+    const fls_ingest_info& last_ingest() const { return info_; }
     // the PCL clouds of the last scan, for callers that still need them on the host (visualisation, keyframes): after RunOnDevice
     // each cloud is downloaded here, on its first request
     template <class Cluster>
@@ -66,12 +84,8 @@ public:
     const fls_preprocess_result& last_result() const { return r_; }
 
 private:
-    template <class RawCloud, class ImuVec>
-    int Scan(const RawCloud& raw, uint64_t stamp_us, const ImuVec& imu, bool on_device) {
-        using P = typename std::remove_const<typename std::remove_reference<decltype(raw.points[0])>::type>::type;
-        static const fls_raw_layout lay{static_cast<uint32_t>(sizeof(P)), static_cast<uint32_t>(offsetof(P, x)), static_cast<uint32_t>(offsetof(P, intensity)),
-                                        static_cast<uint32_t>(offsetof(P, ring)), static_cast<uint32_t>(sizeof(P::ring)),
-                                        static_cast<uint32_t>(offsetof(P, time))};
+    template <class ImuVec>
+    void PackImu(const ImuVec& imu) {
         t_.resize(imu.size());
         q_.resize(4 * imu.size());
         for (size_t k = 0; k < imu.size(); ++k) {
@@ -81,6 +95,27 @@ private:
             q_[4 * k + 2] = imu[k].orientation_.z();
             q_[4 * k + 3] = imu[k].orientation_.w();
         }
+    }
+    template <class ImuVec>
+    int ScanDriver(const void* msg, size_t n, const fls_driver_cloud& cloud, const fls_ingest_params& ingest, uint64_t stamp_us, const ImuVec& imu,
+                   bool on_device, uint64_t* stamp_out_us) {
+        PackImu(imu);
+        r_ = fls_preprocess_result{};
+        r_.struct_size = sizeof(r_);
+        info_ = fls_ingest_info{};
+        info_.struct_size = sizeof(info_);
+        const fls_status rc = fls_preprocess_scan_driver(h_, msg, n, &cloud, &ingest, stamp_us, t_.data(), q_.data(), t_.size(), on_device ? 1 : 0, &r_,
+                                                         stamp_out_us, &info_);
+        if (rc != FLS_OK && rc != FLS_ERR_STATE) { std::fprintf(stderr, "HipScanPreprocessor::RunDriver: %s\n", fls_status_string(rc)); return -1; }
+        return r_.imu_status;
+    }
+    template <class RawCloud, class ImuVec>
+    int Scan(const RawCloud& raw, uint64_t stamp_us, const ImuVec& imu, bool on_device) {
+        using P = typename std::remove_const<typename std::remove_reference<decltype(raw.points[0])>::type>::type;
+        static const fls_raw_layout lay{static_cast<uint32_t>(sizeof(P)), static_cast<uint32_t>(offsetof(P, x)), static_cast<uint32_t>(offsetof(P, intensity)),
+                                        static_cast<uint32_t>(offsetof(P, ring)), static_cast<uint32_t>(sizeof(P::ring)),
+                                        static_cast<uint32_t>(offsetof(P, time))};
+        PackImu(imu);
         r_ = fls_preprocess_result{};
         r_.struct_size = sizeof(r_);
         const fls_status rc = (on_device ? fls_preprocess_scan_device : fls_preprocess_scan)(h_, raw.points.data(), raw.points.size(), &lay, stamp_us,
@@ -105,6 +140,7 @@ private:
     fls_preprocess_handle h_ = nullptr;
     float leaf_ = 0.f;
     fls_preprocess_result r_{};
+    fls_ingest_info info_{};
     std::vector<uint64_t> t_;
     std::vector<double> q_;
     std::vector<float> rows_;
