@@ -364,17 +364,8 @@ struct DeviceVoxelGrid {
         hipLaunchKernelGGL(vg_centroid_plan, dim3(unsigned(nb1)), dim3(kVgBlock), 0, s, (const unsigned*)sort.k0, (const float4*)sorted.p, ni, (const VgPlan*)d_plan.p,
                            (const EsState*)exact.st.p, (const unsigned*)lx.p, (const unsigned*)(bt.p + nb2), out.p, out.p + n, out.p + 2 * n, out.p + 3 * n);
         FLS_HIP(hipGetLastError());
-        for (unsigned long long spin = 1;; ++spin) {
-            if (__atomic_load_n(&vmb_host->seq, __ATOMIC_ACQUIRE) == vseq) break;
-            if ((spin & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipSuccess) { if (__atomic_load_n(&vmb_host->seq, __ATOMIC_ACQUIRE) == vseq) break; FLS_HIP(hipErrorUnknown); }
-                if (q != hipErrorNotReady) FLS_HIP(q);
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
+        const auto published = [&] { return __atomic_load_n(&vmb_host->seq, __ATOMIC_ACQUIRE) == vseq; };
+        if (!spin_until(s, published) && !published()) FLS_HIP(hipErrorUnknown);  // (the stream went idle without a verdict)
         exact.print_debug_stamps();
         if (vmb_host->status != kVgOk || vmb_host->sort_fail != 0u) {
             FLS_HIP(hipStreamSynchronize(s));  // (the staging the caller reuses; the refused call is rare)
@@ -573,6 +564,50 @@ struct KdMapDevice {
         ++device_filters;
         return true;
     }
+};
+
+// The local map of one kd-tree kind (LoamFull: of one feature class): the reference's deque of clouds (AddCloudToLocalMap: icp_optimized.h:165-189,
+// loam_full_kdtree.h:65-104, loam_point_to_plane_kdtree.h:56-79) and what the Match searches, the cell grid over [the VoxelGrid of] the
+// concatenated deque.  The owner pushes / trims as its reference does and calls rebuild() at the same moments; cell size and search depth are
+// the owner's.  With `on_device` the deque is mirrored in a DeviceCloudRing and filter + grid build never leave the device.
+struct KdLocalMap {
+    std::deque<std::vector<PtI>> clouds;
+    DeviceCloudRing ring;     // the deque's clouds back to back on the device (device path only)
+    std::vector<PtI> local;   // the map cloud on the host: what the host path built, empty after a device rebuild
+    CellGridImage grid;
+    KdMapDevice dev;
+    size_t n = 0;             // points of the local map, whichever path built it (fls_map_size)
+    bool on_device = false;   // the deque is mirrored on the device: FLS_DEVICE_VOXELGRID != 0 and FLS_DEVICE_GRID_BUILD != 0
+    void init() {
+        dev.init();
+        on_device = dev.vg_on_device && dev.grid_on_device;
+    }
+    void push(const std::vector<PtI>& cloud, hipStream_t s) {
+        clouds.push_back(cloud);
+        if (on_device) ring.push_back(cloud, s);
+    }
+    void trim(size_t max_clouds) {
+        if (clouds.size() <= max_clouds) return;
+        clouds.pop_front();
+        if (on_device) ring.pop_front();
+    }
+    void reset_to(const std::vector<PtI>& cloud, hipStream_t s) {  // localization mode: the map is the last cloud alone
+        clouds.clear();
+        ring.clear();
+        push(cloud, s);
+    }
+    // local map = [VoxelGrid(leaf) of] the concatenated deque, then the grid (cells of `cell`, searched `rings` deep): on the device, or on
+    // the host for whatever the device declines
+    fls_status rebuild(bool filter, float leaf, float cell, int rings, hipStream_t s) {
+        if (on_device && dev.filter_and_build(grid, ring, filter, leaf, cell, rings, n, s)) { local.clear(); return FLS_OK; }
+        local.clear();
+        for (const auto& c : clouds) local.insert(local.end(), c.begin(), c.end());
+        if (filter) { local = voxel_grid(local, leaf); ++dev.host_filters; }
+        n = local.size();
+        return dev.build_from_host(grid, local, cell, s, rings);
+    }
+    // fls_map_size slots 114 / 115 / 116: cell grids built on the device / map updates filtered on the device / ... filtered on the host
+    size_t counter(int slot) const { return size_t(slot == 114 ? dev.builder.builds : slot == 115 ? dev.device_filters : dev.host_filters); }
 };
 
 // the source-scan filter of the kd-tree / NDT matchers (icp_optimized.h:57, incremental_ndt.h:232): on the device (default), the

@@ -437,7 +437,7 @@ fls_status fls_loop_match(int device_id, const float* source, size_t n_source, c
         hipDeviceProp_t prop;
         FLS_HIP(hipGetDeviceProperties(&prop, device_id));
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLS_ERR_DEVICE;
-        const bool timing = std::getenv("FLS_HOST_TIMING") && std::atoi(std::getenv("FLS_HOST_TIMING")) != 0;
+        const bool timing = host_timing_enabled();
         const auto t0 = std::chrono::steady_clock::now();
         // one matcher per device, kept for the life of the process (stream, result block, device buffers: ~3 ms to set up, the
         // reference's loop-closure thread calls Match once per candidate); calls on one device are serialised (run_mx).  Never destroyed:

@@ -1,4 +1,4 @@
-// host_util.hpp -- host-side plumbing: HIP error handling, device buffers, pinned staging.
+// host_util.hpp -- host-side plumbing: HIP error handling, the host-mapped-word spin wait, device buffers, pinned staging.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -24,6 +24,30 @@ struct HipError : std::runtime_error {
             throw ::fls::HipError(_e, _buf);                                                   \
         }                                                                                      \
     } while (0)
+
+// FLS_HOST_TIMING=1: host-side timing lines on stderr
+inline bool host_timing_enabled() {
+    const char* e = std::getenv("FLS_HOST_TIMING");
+    return e && std::atoi(e) != 0;
+}
+
+// Wait for a result the device publishes in host-mapped memory, without a blocking synchronisation: spin on ready() (the poll of that word).
+// Every 0x4000 polls the stream state is consulted, so that a faulted kernel cannot hang the host: an error throws, a drained stream ends the
+// wait.  true: ready() held; false: the stream drained first (whatever the device was going to write is there: the caller re-reads).
+template <class F>
+bool spin_until(hipStream_t stream, F&& ready) {
+    for (unsigned long long spin = 1;; ++spin) {
+        if (ready()) return true;
+        if ((spin & 0x3fffu) == 0) {
+            const hipError_t q = hipStreamQuery(stream);
+            if (q == hipSuccess) return false;
+            if (q != hipErrorNotReady) FLS_HIP(q);
+        }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+}
 
 // growable device buffer; contents are NOT preserved on growth unless keep=true
 template <typename T>

@@ -114,19 +114,9 @@ struct LoopMatcher {
         if (seq == 0u) seq = 1u;
         fill(LoopOut{d_rows.p, d_ticket.p, mail_dev, seq});
         FLS_HIP(hipGetLastError());
-        for (unsigned long long spin = 1;; ++spin) {
-            if (__atomic_load_n(&mail_host->seq, __ATOMIC_ACQUIRE) == seq) break;
-            if ((spin & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(stream);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) FLS_HIP(q);
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
+        const auto published = [&] { return __atomic_load_n(&mail_host->seq, __ATOMIC_ACQUIRE) == seq; };
         // (the stream went idle: the block must be there -- anything else is a lost fan-in, never a result to use)
-        if (__atomic_load_n(&mail_host->seq, __ATOMIC_ACQUIRE) != seq) throw HipError(hipErrorUnknown, "fls_loop_match: the device left no result block for an evaluation");
+        if (!spin_until(stream, published) && !published()) throw HipError(hipErrorUnknown, "fls_loop_match: the device left no result block for an evaluation");
         return mail_host->v;
     }
 
@@ -841,7 +831,7 @@ struct LoopMatcher {
         FLS_HIP(hipSetDevice(device));
         if (d_ticket.p) FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));  // (a Match that failed half-way must not poison the next)
         // FLS_HOST_TIMING=1: where the wall time of one Match goes (stderr)
-        const bool timing = std::getenv("FLS_HOST_TIMING") && std::atoi(std::getenv("FLS_HOST_TIMING")) != 0;
+        const bool timing = host_timing_enabled();
         double t_filter = 0, t_leaves = 0, t_ndt = 0, t_gicp_setup = 0, t_gicp = 0, t_fit = 0;
         auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         double t0 = now();

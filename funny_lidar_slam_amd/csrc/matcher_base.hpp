@@ -1,8 +1,11 @@
 // matcher_base.hpp -- common host state of one registration handle (stream, device
-// Gauss-Newton state, wave partials, profiling events) and the scan upload helper.
+// Gauss-Newton state, wave partials, profiling events), the launch loop and the Match
+// epilogue every kind shares (run_mailbox_loop, take_result), the batch-lane clone
+// (make_lane) and the scan upload helper.
 #pragma once
 #include "host_maps.hpp"
 #include "kernels_handoff.hpp"
+#include "kernels_p2plane.hpp"  // kTicketWords
 #include <memory>
 #include <thread>
 #if defined(__SSE__)
@@ -193,20 +196,26 @@ struct fls_matcher {
     // few thousand polls so that a faulted kernel cannot hang the host.
     unsigned wait_mailbox(int target_iter) {
         const unsigned want = match_id & 0x7fffffu;
-        for (unsigned long long spin = 1;; ++spin) {
-            const unsigned s = __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);
-            if ((s >> 9) == want && (((s >> 8) & 1u) || int(s & 0xffu) >= target_iter)) return s;
-            if ((spin & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(stream);
-                if (q == hipSuccess) {  // everything drained: the word is final
-                    return __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);
-                }
-                if (q != hipErrorNotReady) FLS_HIP(q);
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
+        unsigned s = 0;
+        const bool published = fls::spin_until(stream, [&] {
+            s = __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);
+            return (s >> 9) == want && (((s >> 8) & 1u) || int(s & 0xffu) >= target_iter);
+        });
+        return published ? s : __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);  // everything drained: the word is final
+    }
+    // the part of the Match epilogue every kind shares: the iteration count of the published word and the mailbox's residual block into `stats`
+    const fls::Mailbox& take_result(unsigned word) {
+        const fls::Mailbox& mb = *mb_host;
+        stats.iterations = int(word & 0xffu);
+        stats.n_valid = mb.n_valid;
+        stats.sum_res = mb.sum_res;
+        std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
+        return mb;
+    }
+    // the fan-in ticket words of a kind's fused tail: zero between launches (their last arrivers reset them), so zeroed once here
+    void init_tickets(fls::DevBuf<unsigned>& t) {
+        t.reserve(fls::kTicketWords);
+        FLS_HIP(hipMemsetAsync(t.p, 0, fls::kTicketWords * sizeof(unsigned), stream));
     }
     // fetch the full device state (iteration log) after a mailbox-path Match
     void refresh_log() {
@@ -377,6 +386,15 @@ struct DevScan {
         push(s);
     }
 };
+
+// a batch lane of `self` (fls_matcher::clone_for_lane): a fresh handle of the same kind, parameters and device; the caller points it at its map
+template <class M>
+std::unique_ptr<M> make_lane(const M& self) {
+    auto q = std::make_unique<M>();
+    q->kind = self.kind; q->p = self.p; q->device = self.device;
+    if (q->init() != FLS_OK) return nullptr;
+    return q;
+}
 
 inline fls_status check_common(const fls_params& p) {
     if (p.struct_size != sizeof(fls_params)) return FLS_ERR_INVALID;

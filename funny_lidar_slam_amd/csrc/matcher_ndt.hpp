@@ -85,9 +85,8 @@ struct NdtMatcher final : fls_matcher {
         if (!(p.ndt_voxel_size > 0.0) || !(p.source_cloud_filter_size > 0.f) || p.ndt_capacity <= 0) return FLS_ERR_INVALID;
         init_common();
         src_filter.init();
-        if (const char* e = std::getenv("FLS_HOST_TIMING")) host_timing = std::atoi(e) != 0;
-        d_ticket.reserve(kTicketWords);
-        FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
+        host_timing = host_timing_enabled();
+        init_tickets(d_ticket);
         if (const char* e = std::getenv("FLS_NDT_DEVICE_UPDATE")) allow_device_update = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_NDT_DEVICE_SLACK")) { const long c = std::atol(e); if (c >= 0) device_slack = size_t(c); }
         inv_voxel = 1.0 / p.ndt_voxel_size;
@@ -659,11 +658,7 @@ struct NdtMatcher final : fls_matcher {
             hipLaunchKernelGGL(gn_solve_lu_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_b.p, nblk, 1,
                                p.rotation_converge_thres, p.position_converge_thres, p.ndt_min_effective_pts, mb_dev, launch_word());
         });
-        const Mailbox& s = *mb_host;
-        stats.iterations = int(word & 0xffu);
-        stats.n_valid = s.n_valid;
-        stats.sum_res = s.sum_res;
-        std::memcpy(stats.last_dx, s.last_dx, sizeof(stats.last_dx));
+        const Mailbox& s = take_result(word);
         // the min_effective early-out sets done with converged == 0 on the device (:306-309: T = pose; return false)
         const bool early_fail = s.done && !s.converged && s.n_valid < p.ndt_min_effective_pts;
         if (early_fail) {
@@ -693,10 +688,8 @@ struct NdtMatcher final : fls_matcher {
     }
     const NdtMatcher* owner = nullptr;
     std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = std::make_unique<NdtMatcher>();
-        q->kind = kind; q->p = p; q->device = device;
-        if (q->init() != FLS_OK) return nullptr;
-        q->owner = this;
+        auto q = make_lane(*this);
+        if (q) q->owner = this;
         return q;
     }
     fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }

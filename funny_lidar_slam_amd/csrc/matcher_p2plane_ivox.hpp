@@ -95,14 +95,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             return FLS_ERR_INVALID;  // CHECK_NE(..., max()) at :45-48
         init_common();
         if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
-        if (const char* e = std::getenv("FLS_HOST_TIMING")) host_timing = std::atoi(e) != 0;
+        host_timing = host_timing_enabled();
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
         d_upd_state.reserve(1);
         FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
         std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
         FLS_HIP(hipHostGetDevicePointer((void**)&upd_mb_dev, upd_mb_host, 0));
-        d_ticket.reserve(kTicketWords);
-        FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
+        init_tickets(d_ticket);
         ivox.resolution = 0.5f;       // InitIVox :53-58
         ivox.inv_resolution = 1.0f / 0.5f;
         ivox.capacity = 1000000;
@@ -262,17 +261,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // the verdict of the batch queued last; true: applied.  (kUpdSkipped -- a speculative chain that found nothing to do -- reads as "not applied".)
     bool await_update_chain(const size_t n) {
         // (a few words in host-mapped memory; no copy, no stream synchronisation)
-        for (unsigned long long spin = 1;; ++spin) {
-            if (__atomic_load_n(&upd_mb_host->seq, __ATOMIC_ACQUIRE) == upd_seq) break;
-            if ((spin & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(stream);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) FLS_HIP(q);
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
+        (void)spin_until(stream, [&] { return __atomic_load_n(&upd_mb_host->seq, __ATOMIC_ACQUIRE) == upd_seq; });  // (a drained stream just ends the wait)
         dev_n_bricks = std::min<size_t>(upd_mb_host->n_bricks, image.n_bricks_cap);  // (bricks are created whatever the verdict)
         last_chain_skipped = (upd_mb_host->status & kUpdSkipped) != 0u;
         if (last_chain_skipped) return false;
@@ -600,18 +589,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         }, after_chunk);
         scan_in_staging = false;  // (the first launch left the device copy)
         nn_rows_current = false;  // the lists of every point with candidates are slots of the current image now
-        const Mailbox& mb = *mb_host;
-        const int used = int(word & 0xffu);
+        const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(T_, mb.T, sizeof(T_));
         std::memcpy(final_T, mb.T, sizeof(final_T));
         have_final = true;
         bool has_converge = true;
         if (mb.n_valid < 50) has_converge = false;  // :201-203
-        stats.iterations = used;
-        stats.n_valid = mb.n_valid;
-        stats.sum_res = mb.sum_res;
-        std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (has_converge && !p.is_localization_mode && update_map && !borrowed) {  // :205-206
@@ -796,10 +780,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     DevBuf<unsigned> d_counter_img;
 
     std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = std::make_unique<P2PlaneIvoxMatcher>();
-        q->kind = kind; q->p = p; q->device = device;
-        if (q->init() != FLS_OK) return nullptr;
-        q->borrowed = &image;
+        auto q = make_lane(*this);
+        if (q) q->borrowed = &image;
         return q;
     }
     fls_status prepare_batch() override {

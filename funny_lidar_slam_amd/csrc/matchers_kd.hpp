@@ -2,8 +2,8 @@
 //   IcpMatcher       <- IcpOptimized<double>            include/registration/icp_optimized.h
 //   LoamFullMatcher  <- LoamFull<double>                include/registration/loam_full_kdtree.h
 //   P2PlaneKdMatcher <- LoamPointToPlaneKdtree<double>  include/registration/loam_point_to_plane_kdtree.h
-// Map bookkeeping (deque of clouds, VoxelGrid, rebuild) stays on the host like the reference's
-// AddCloudToLocalMap; the kd-tree is replaced by an exact-kNN hash grid rebuilt at the same moments.
+// Map bookkeeping follows the reference's AddCloudToLocalMap (deque of clouds, VoxelGrid, rebuild): one KdLocalMap
+// (device_voxelgrid.hpp) per map, two for LoamFull; the kd-tree is replaced by an exact-kNN cell grid rebuilt at the same moments.
 #pragma once
 #include "matcher_base.hpp"
 #include "host_math.hpp"
@@ -11,7 +11,6 @@
 #include "kernels_knn.hpp"
 #include "kernels_grid_coop.hpp"
 #include "fitness_host.hpp"
-#include <deque>
 
 namespace fls {
 
@@ -22,16 +21,14 @@ constexpr int kGridRings = 2;
 inline float cell_for_gate(double gate_sq) {  // smallest safe cell for a squared-distance gate
     return float(std::sqrt(gate_sq) * 1.0001);
 }
+// workgroups of a search launch (eight lanes per query) over n queries: a multiple of 64, so that the kernels' XCD chunk re-map is a bijection
+inline unsigned knn_grid_blocks(size_t n) { return unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64); }
 
 // ---------------------------------------------------------------------------------------------
 struct IcpMatcher final : fls_matcher {
-    std::deque<std::vector<PtI>> cloud_deque;
-    std::vector<PtI> local_map, source;
+    KdLocalMap map;
+    std::vector<PtI> source;
     SourceFilter src_filter;
-    CellGridImage grid;
-    KdMapDevice mapdev;      // cell-grid build on the device (default); deque + map-side VoxelGrid on the device (opt-in)
-    DeviceCloudRing ring;    // the deque's clouds back to back on the device (opt-in path only)
-    size_t local_map_n = 0;  // points of the local map (the host vector is not produced on the device path)
     bool have_map = false;
     DevBuf<unsigned> d_ticket;
     const IcpMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
@@ -51,37 +48,16 @@ struct IcpMatcher final : fls_matcher {
         if (!(p.point_search_thres > 0.0) || !(p.map_cloud_filter_size > 0.f) || !(p.source_cloud_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
         src_filter.init();
-        mapdev.init();
-        d_ticket.reserve(kTicketWords);
-        FLS_HIP(hipMemsetAsync(d_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
+        map.init();
+        init_tickets(d_ticket);
         return FLS_OK;
     }
     fls_status add_cloud_impl(const std::vector<PtI>& new_cloud) {  // :165-189
-        const bool dev = mapdev.vg_on_device && mapdev.grid_on_device;
-        if (p.is_localization_mode) {
-            cloud_deque.clear();
-            cloud_deque.push_back(new_cloud);
-            if (dev) { ring.clear(); ring.push_back(new_cloud, stream); }
-        } else {
-            cloud_deque.push_back(new_cloud);
-            if (dev) ring.push_back(new_cloud, stream);
-            if (cloud_deque.size() > p.local_map_size) { cloud_deque.pop_front(); if (dev) ring.pop_front(); }
-        }
+        if (p.is_localization_mode) map.reset_to(new_cloud, stream);
+        else { map.push(new_cloud, stream); map.trim(p.local_map_size); }
         // gate-sized cells here: the ICP scan starts far from the map (1-NN often beyond half the gate in the early
         // iterations), the two-stage search would run its second stage for most queries (measured 25 vs 13.5 us / launch)
-        const float cell = cell_for_gate(p.point_search_thres);
-        // opt-in device path: the deque is resident, VoxelGrid (Q13: always) + grid build never leave the device
-        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, local_map_n, stream)) {
-            local_map.clear();
-            have_map = true;
-            return FLS_OK;
-        }
-        local_map.clear();
-        for (const auto& c : cloud_deque) local_map.insert(local_map.end(), c.begin(), c.end());
-        local_map = voxel_grid(local_map, p.map_cloud_filter_size);  // Q13: always
-        ++mapdev.host_filters;
-        local_map_n = local_map.size();
-        const fls_status rc = mapdev.build_from_host(grid, local_map, cell, stream);
+        const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, cell_for_gate(p.point_search_thres), 1, stream);  // Q13: always filtered
         have_map = rc == FLS_OK;
         return rc;
     }
@@ -115,8 +91,8 @@ struct IcpMatcher final : fls_matcher {
         stats.n_source = int(n);
         d_nn_id.reserve(std::max<size_t>(n, 1));
         d_eff.reserve(std::max<size_t>(n, 1));
-        const CellGridDev cg = cell_dev(owner ? owner->grid : grid);
-        const dim3 knn_grid_dim(unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64));  // multiple of 64: the XCD chunk re-map is a bijection
+        const CellGridDev cg = cell_dev(owner ? owner->map.grid : map.grid);
+        const dim3 knn_grid_dim(knn_grid_blocks(n));
         d_partials_b.reserve(size_t(std::max(knn_grid_dim.x, 1u)) * kPartialStride);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
@@ -130,15 +106,11 @@ struct IcpMatcher final : fls_matcher {
                                kTicketShards, tail);
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
         });
-        const Mailbox& mb = *mb_host;
+        const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(final_T, mb.T, sizeof(final_T));
         have_final = true;
         const bool has_converge = mb.converged != 0;  // Q10: false after max iterations
-        stats.iterations = int(word & 0xffu);
-        stats.n_valid = mb.n_valid;
-        stats.sum_res = mb.sum_res;
-        std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         // :153 `has_converge_ && IsNeedAddCloud(T) && !is_localization_mode_`: the gate (and its last_T) is evaluated before the mode
@@ -154,16 +126,14 @@ struct IcpMatcher final : fls_matcher {
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = std::make_unique<IcpMatcher>();
-        q->kind = kind; q->p = p; q->device = device;
-        if (q->init() != FLS_OK) return nullptr;
-        q->owner = this;
+        auto q = make_lane(*this);
+        if (q) q->owner = this;
         return q;
     }
     fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
-        return fitness_score_device(*this, grid, scan, final_T, max_range, score);
+        return fitness_score_device(*this, map.grid, scan, final_T, max_range, score);
     }
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override {
         const size_t n = std::min(cap, scan.n);
@@ -179,10 +149,8 @@ struct IcpMatcher final : fls_matcher {
     size_t map_size(int slot) const override {
         if (slot == 105) return size_t(src_filter.device_runs);  // source filters run on the device / on the host
         if (slot == 106) return size_t(src_filter.host_runs);
-        if (slot == 114) return size_t(mapdev.builder.builds);    // cell grids built on the device / map updates filtered on the device /
-        if (slot == 115) return size_t(mapdev.device_filters);    // ... filtered on the host
-        if (slot == 116) return size_t(mapdev.host_filters);
-        return local_map_n;
+        if (slot >= 114 && slot <= 116) return map.counter(slot);
+        return map.n;
     }
 };
 
@@ -219,7 +187,7 @@ struct FeatureDev {
     void launch(hipStream_t s, GnState* st, int first, const Pose16& T0, const CellGridDev& cg, float gate, double thres, double* partials) {
         const size_t n = scan.n;
         if (n == 0) return;
-        const dim3 knn_grid_dim(unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64));  // multiple of 64: the XCD chunk re-map is a bijection
+        const dim3 knn_grid_dim(knn_grid_blocks(n));
         if (std::isinf(gate))  // un-gated search (LoamPointToPlaneKdtree): the instantiation with the ring walk
             hipLaunchKernelGGL((grid_knn_kernel<5, false, true>), knn_grid_dim, dim3(256), 0, s, scan.x.p, scan.y.p, scan.z.p, int(n), st, first, T0, cg, gate,
                                nn_pts.p, nn_cnt.p, kth.p, flag.p);
@@ -233,12 +201,7 @@ struct FeatureDev {
 };
 
 struct LoamFullMatcher final : fls_matcher {
-    std::deque<std::vector<PtI>> corner_deque, planar_deque;
-    std::vector<PtI> local_corner, local_planar;
-    CellGridImage corner_grid, planar_grid;
-    KdMapDevice mapdev_planar, mapdev_corner;
-    DeviceCloudRing ring_planar, ring_corner;
-    size_t local_planar_n = 0, local_corner_n = 0;
+    KdLocalMap map_planar, map_corner;
     bool have_map = false;
     const LoamFullMatcher* owner = nullptr;  // batch lane: reads the owner's two map grids
     FeatureDev corner, planar;
@@ -253,36 +216,23 @@ struct LoamFullMatcher final : fls_matcher {
         if (p.local_planar_size == 0 || p.local_corner_size == 0) return FLS_ERR_INVALID;  // CHECK_GT :55-56
         if (!(p.point_search_thres > 0.0) || !(p.corner_voxel_filter_size > 0.f) || !(p.planar_voxel_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
-        d_loam_ticket.reserve(kTicketWords);
-        FLS_HIP(hipMemsetAsync(d_loam_ticket.p, 0, kTicketWords * sizeof(unsigned), stream));
-        mapdev_planar.init();
-        mapdev_corner.init();
+        init_tickets(d_loam_ticket);
+        map_planar.init();
+        map_corner.init();
+        map_corner.on_device = map_planar.on_device;  // one device-path decision per matcher, the planar map's (both read the same two switches)
         return FLS_OK;
     }
     fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud, const std::vector<PtI>& corner_cloud) {  // :65-104
-        const bool dev = mapdev_planar.vg_on_device && mapdev_planar.grid_on_device;
-        corner_deque.push_back(corner_cloud);
-        planar_deque.push_back(planar_cloud);
-        if (dev) { ring_corner.push_back(corner_cloud, stream); ring_planar.push_back(planar_cloud, stream); }
-        if (planar_deque.size() > p.local_planar_size) { planar_deque.pop_front(); if (dev) ring_planar.pop_front(); }
-        if (corner_deque.size() > p.local_corner_size) { corner_deque.pop_front(); if (dev) ring_corner.pop_front(); }
-        // half-gate cells + the two-stage kernel
+        map_corner.push(corner_cloud, stream);  // both classes are pushed before either deque is trimmed
+        map_planar.push(planar_cloud, stream);
+        map_planar.trim(p.local_planar_size);
+        map_corner.trim(p.local_corner_size);
+        // half-gate cells + the two-stage kernel; the VoxelGrid only once the deque holds more than 5 frames (:92-100)
         const float cs = 0.5f * cell_for_gate(p.point_search_thres);
-        // one feature class: [VoxelGrid of] the concatenated deque (the filter only once the deque holds more than 5 frames, :92-100)
-        auto rebuild = [&](std::deque<std::vector<PtI>>& dq, DeviceCloudRing& ring, KdMapDevice& md, CellGridImage& grid, std::vector<PtI>& local, size_t& n_local,
-                           float leaf) -> fls_status {
-            const bool filter = dq.size() > 5;
-            if (dev && md.filter_and_build(grid, ring, filter, leaf, cs, kGridRings, n_local, stream)) { local.clear(); return FLS_OK; }
-            local.clear();
-            for (const auto& c : dq) local.insert(local.end(), c.begin(), c.end());
-            if (filter) { local = voxel_grid(local, leaf); ++md.host_filters; }
-            n_local = local.size();
-            return md.build_from_host(grid, local, cs, stream, kGridRings);
-        };
-        fls_status rc = rebuild(planar_deque, ring_planar, mapdev_planar, planar_grid, local_planar, local_planar_n, p.planar_voxel_filter_size);
+        fls_status rc = map_planar.rebuild(map_planar.clouds.size() > 5, p.planar_voxel_filter_size, cs, kGridRings, stream);
         if (rc != FLS_OK) return rc;
-        rc = rebuild(corner_deque, ring_corner, mapdev_corner, corner_grid, local_corner, local_corner_n, p.corner_voxel_filter_size);
-        have_map = rc == FLS_OK;
+        rc = map_corner.rebuild(map_corner.clouds.size() > 5, p.corner_voxel_filter_size, cs, kGridRings, stream);
+        have_map = rc == FLS_OK;  // (the corner rebuild's status alone)
         return rc;
     }
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
@@ -305,7 +255,7 @@ struct LoamFullMatcher final : fls_matcher {
         corner.prepare();
         d_partials_a.reserve(size_t(std::max(nbc, 1)) * kPartialStride);
         d_partials_b.reserve(size_t(std::max(nbp, 1)) * kPartialStride);
-        const CellGridDev cgp = cell_dev(owner ? owner->planar_grid : planar_grid), cgc = cell_dev(owner ? owner->corner_grid : corner_grid);
+        const CellGridDev cgp = cell_dev(owner ? owner->map_planar.grid : map_planar.grid), cgc = cell_dev(owner ? owner->map_corner.grid : map_corner.grid);
         const float gate_f = float(p.point_search_thres);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
@@ -314,7 +264,7 @@ struct LoamFullMatcher final : fls_matcher {
             if (nc != 0 && np != 0) {
                 // both classes in one correspondence launch and one fit launch (they are independent until the solve), the Gauss-Newton
                 // tail in the fit launch's last workgroup
-                const int kc = int((((nc * 8 + 255) / 256) + 63) / 64 * 64), kp = int((((np * 8 + 255) / 256) + 63) / 64 * 64);
+                const int kc = int(knn_grid_blocks(nc)), kp = int(knn_grid_blocks(np));
                 hipLaunchKernelGGL((grid_knn_dual_kernel<5, false>), dim3(unsigned(kc + kp)), dim3(256), 0, stream, (const GnState*)d_state.p, first, T0,
                                    corner.knn_args(cgc, gate_f), planar.knn_args(cgp, gate_f), kc);
                 const LoamFusedTail tail{(const double*)d_partials_a.p, (const double*)d_partials_b.p, nbc, nbp, p.rotation_converge_thres, p.position_converge_thres,
@@ -331,16 +281,12 @@ struct LoamFullMatcher final : fls_matcher {
             hipLaunchKernelGGL(gn_solve_loam_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)d_partials_a.p,
                                nbc, (const double*)d_partials_b.p, nbp, p.rotation_converge_thres, p.position_converge_thres, mb_dev, launch_word());
         });
-        const Mailbox& mb = *mb_host;
+        const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         bool has_converge = true;
         if (mb.n_valid < 50) has_converge = false;  // number_valid_planar_ < 50 :181
-        stats.iterations = int(word & 0xffu);
-        stats.n_valid = mb.n_valid;
         stats.n_valid_corner = mb.n_valid2;
-        stats.sum_res = mb.sum_res;
         stats.sum_res_corner = mb.sum_res2;
-        std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (update_map && !owner && has_converge && gate.need(mb.T, p.dist_thre_add_cloud, p.rot_thre_add_cloud)) {  // :185-193 (no localization switch)
@@ -352,10 +298,8 @@ struct LoamFullMatcher final : fls_matcher {
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = std::make_unique<LoamFullMatcher>();
-        q->kind = kind; q->p = p; q->device = device;
-        if (q->init() != FLS_OK) return nullptr;
-        q->owner = this;
+        auto q = make_lane(*this);
+        if (q) q->owner = this;
         return q;
     }
     fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
@@ -364,21 +308,14 @@ struct LoamFullMatcher final : fls_matcher {
         return (slot == 1 ? corner : planar).fetch(stream, ids, cnt, valid, cap);
     }
     size_t map_size(int slot) const override {
-        if (slot == 114) return size_t(mapdev_planar.builder.builds + mapdev_corner.builder.builds);
-        if (slot == 115) return size_t(mapdev_planar.device_filters + mapdev_corner.device_filters);
-        if (slot == 116) return size_t(mapdev_planar.host_filters + mapdev_corner.host_filters);
-        return slot == 1 ? local_corner_n : local_planar_n;
+        if (slot >= 114 && slot <= 116) return map_planar.counter(slot) + map_corner.counter(slot);
+        return slot == 1 ? map_corner.n : map_planar.n;
     }
 };
 
 // ---------------------------------------------------------------------------------------------
 struct P2PlaneKdMatcher final : fls_matcher {
-    std::deque<std::vector<PtI>> cloud_deque;
-    std::vector<PtI> local_map;
-    CellGridImage grid;
-    KdMapDevice mapdev;
-    DeviceCloudRing ring;
-    size_t local_map_n = 0;
+    KdLocalMap map;
     bool have_map = false;
     const P2PlaneKdMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
     FeatureDev planar;
@@ -392,33 +329,14 @@ struct P2PlaneKdMatcher final : fls_matcher {
             return FLS_ERR_INVALID;  // CHECK_NE block loam_point_to_plane_kdtree.h:43-50
         if (!(p.map_cloud_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
-        mapdev.init();
+        map.init();
         return FLS_OK;
     }
     fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud) {  // :56-79
-        const bool dev = mapdev.vg_on_device && mapdev.grid_on_device;
-        if (p.is_localization_mode) {
-            cloud_deque.clear();
-            cloud_deque.push_back(planar_cloud);
-            if (dev) { ring.clear(); ring.push_back(planar_cloud, stream); }
-        } else {
-            cloud_deque.push_back(planar_cloud);
-            if (dev) ring.push_back(planar_cloud, stream);
-            if (cloud_deque.size() > p.local_map_size) { cloud_deque.pop_front(); if (dev) ring.pop_front(); }
-        }
+        if (p.is_localization_mode) map.reset_to(planar_cloud, stream);
+        else { map.push(planar_cloud, stream); map.trim(p.local_map_size); }
         // un-gated 5-NN: ring search with a cell of two map leaves (>= 1 point per leaf after VoxelGrid)
-        const float cell = std::max(2.0f * p.map_cloud_filter_size, 0.5f);
-        if (dev && mapdev.filter_and_build(grid, ring, true, p.map_cloud_filter_size, cell, 1, local_map_n, stream)) {
-            local_map.clear();
-            have_map = true;
-            return FLS_OK;
-        }
-        local_map.clear();
-        for (const auto& c : cloud_deque) local_map.insert(local_map.end(), c.begin(), c.end());
-        local_map = voxel_grid(local_map, p.map_cloud_filter_size);
-        ++mapdev.host_filters;
-        local_map_n = local_map.size();
-        const fls_status rc = mapdev.build_from_host(grid, local_map, cell, stream);
+        const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, std::max(2.0f * p.map_cloud_filter_size, 0.5f), 1, stream);
         have_map = rc == FLS_OK;
         return rc;
     }
@@ -442,7 +360,7 @@ struct P2PlaneKdMatcher final : fls_matcher {
         stats.n_source = int(n);
         planar.prepare();
         d_partials_b.reserve(size_t(std::max(nblk, 1)) * kPartialStride);
-        const CellGridDev cg = cell_dev(owner ? owner->grid : grid);
+        const CellGridDev cg = cell_dev(owner ? owner->map.grid : map.grid);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
         const unsigned word = run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
@@ -452,16 +370,12 @@ struct P2PlaneKdMatcher final : fls_matcher {
             hipLaunchKernelGGL(gn_solve_loam_kernel, dim3(1), dim3(kSolveThreads), 0, stream, d_state.p, first, T0, (const double*)nullptr, 0,
                                (const double*)d_partials_b.p, nblk, p.rotation_converge_thres, p.position_converge_thres, mb_dev, launch_word());
         });
-        const Mailbox& mb = *mb_host;
+        const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(final_T, mb.T, sizeof(final_T));
         have_final = true;
         bool has_converge = true;
         if (mb.n_valid < 50) has_converge = false;
-        stats.iterations = int(word & 0xffu);
-        stats.n_valid = mb.n_valid;
-        stats.sum_res = mb.sum_res;
-        std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {  // :145-149
@@ -474,23 +388,19 @@ struct P2PlaneKdMatcher final : fls_matcher {
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }
     std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = std::make_unique<P2PlaneKdMatcher>();
-        q->kind = kind; q->p = p; q->device = device;
-        if (q->init() != FLS_OK) return nullptr;
-        q->owner = this;
+        auto q = make_lane(*this);
+        if (q) q->owner = this;
         return q;
     }
     fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
-        return fitness_score_device(*this, grid, planar.scan, final_T, max_range, score);
+        return fitness_score_device(*this, map.grid, planar.scan, final_T, max_range, score);
     }
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override { return planar.fetch(stream, ids, cnt, valid, cap); }
     size_t map_size(int slot) const override {
-        if (slot == 114) return size_t(mapdev.builder.builds);
-        if (slot == 115) return size_t(mapdev.device_filters);
-        if (slot == 116) return size_t(mapdev.host_filters);
-        return local_map_n;
+        if (slot >= 114 && slot <= 116) return map.counter(slot);
+        return map.n;
     }
 };
 

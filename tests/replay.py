@@ -11,6 +11,8 @@ A scenario is built so that the reference rules that only show up over several s
                                                                                                incremental_ndt.h:130-227,325-334
   * LoamFull         corner / planar deques, VoxelGrid once a deque holds more than 5 frames, keyframe gate
                                                                                                loam_full_kdtree.h:65-104,374-389
+  * LoamPointToPlaneKdtree  mapping-mode deque + pop_front, VoxelGrid of the concatenated deque, keyframe gate
+                                                                                               loam_point_to_plane_kdtree.h:56-79,145-149
   * LoamPointToPlaneIVOX  down-sampling insert rule + LRU (already covered by test_gpu_parity._replay; here for _ref)
 Used by tests/test_gpu_mapping_replay.py (HIP vs oracle), tests/test_ref_pin.py (oracle vs compiled reference) and
 tests/golden/make_golden.py.
@@ -43,6 +45,12 @@ SCENARIOS = {
     "ndt_dev": dict(mode="IncrementalNDT", y=dict(reg.YAML_NCLT_NDT, ndt_capacity=100000), frames=10, n_az=100, rng_job=22, max_range=40.0, lidar="v64"),
     "loam": dict(mode="LoamFull_KdTree", y=dict(reg.YAML_NCLT_LOAM_FULL), frames=11, n_az=90, rng_job=23, max_range=45.0, lidar="v64"),
     "ivox": dict(mode="PointToPlane_IVOX", y=dict(reg.YAML_NCLT_IVOX), frames=7, n_az=60, rng_job=24, max_range=38.0, lidar="v64"),
+    # local_map_size=2: the deque is full after the first accepted frame and pops from the second on.  The localization YAML carries zero
+    # keyframe thresholds (the gate is never consulted in that mode; at zero any rounding residue passes it), so the scenario takes the
+    # mapping configs' 1.0 m / 0.2 rad: the short steps below must fail the gate
+    "p2plane_kd": dict(mode="PointToPlane_KdTree", y=dict(reg.YAML_NCLT_LOC_KDTREE, local_map_size=2, keyframe_delta_distance=1.0, keyframe_delta_rotation=0.2),
+                       frames=6, n_az=60, rng_job=25,
+                       max_range=40.0, lidar="v64"),
 }
 
 

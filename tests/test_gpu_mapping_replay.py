@@ -64,6 +64,16 @@ def test_icp_mapping_replay():
     assert all(x["upd"] == 0 for x in h if not x["ok"]), "Q10: no map update without convergence"
 
 
+def test_p2plane_kd_mapping_replay():
+    """LoamPointToPlaneKdtree in mapping mode (every other test of this kind runs in localization mode): deque growth, pop_front
+    once it holds more than local_map_size clouds, VoxelGrid of the concatenated deque, keyframe gate."""
+    r, h = run_replay("p2plane_kd")
+    clouds = 1 + np.cumsum([x["upd"] for x in h])  # clouds pushed so far (the initial one included), after every frame
+    full = clouds > r["y"]["local_map_size"]  # this frame's push found the deque full: pop_front
+    assert any(x["upd"] == 1 and f for x, f in zip(h, full)), "a map update must land on a full deque (pop_front)"
+    assert any(x["ok"] and not x["upd"] for x in h), "a converged frame must fail the keyframe gate"
+
+
 def test_ndt_mapping_replay_host_evictions(monkeypatch):
     """IncrementalNDT in mapping mode: non-first-scan UpdateVoxel (min / max points, pooled mean + covariance, SVD clamp),
     LRU eviction at the (shrunk) capacity, Q11 (map update with the input pose -- every guess differs from the result).
