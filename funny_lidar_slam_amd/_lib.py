@@ -33,6 +33,10 @@ PREPROCESS_SYMBOLS = [
 # every symbol include/fls_ingest.h declares (FLS_INGEST_REVISION 1)
 INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_preprocess_scan_driver", "fls_features_project_driver"]
 
+# every symbol include/fls_keyframes.h declares (FLS_KEYFRAMES_REVISION 1)
+KEYFRAMES_SYMBOLS = ["fls_keyframes_revision", "fls_keyframes_create", "fls_keyframes_destroy", "fls_keyframes_add", "fls_keyframes_add_preprocessed",
+                     "fls_keyframes_count", "fls_keyframes_get", "fls_keyframes_merge", "fls_keyframes_loop_match", "fls_keyframes_stat"]
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -304,6 +308,27 @@ def lib():
         L.fls_features_project_driver.restype = C.c_int
         L.fls_features_project_driver.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(DriverCloud), C.POINTER(IngestParams), C.c_uint64, u64p, dp,
                                                   C.c_size_t, dp, C.POINTER(C.c_size_t), C.POINTER(C.c_int), u64p, C.POINTER(IngestInfo)]
+        szp = C.POINTER(C.c_size_t)
+        L.fls_keyframes_revision.restype = C.c_int
+        L.fls_keyframes_revision.argtypes = []
+        L.fls_keyframes_create.restype = C.c_int
+        L.fls_keyframes_create.argtypes = [C.c_int, C.POINTER(hp)]
+        L.fls_keyframes_destroy.restype = None
+        L.fls_keyframes_destroy.argtypes = [hp]
+        L.fls_keyframes_add.restype = C.c_int
+        L.fls_keyframes_add.argtypes = [hp, fp, C.c_size_t, C.c_int, ip]
+        L.fls_keyframes_add_preprocessed.restype = C.c_int
+        L.fls_keyframes_add_preprocessed.argtypes = [hp, hp, C.c_int, ip]
+        L.fls_keyframes_count.restype = C.c_size_t
+        L.fls_keyframes_count.argtypes = [hp]
+        L.fls_keyframes_get.restype = C.c_int
+        L.fls_keyframes_get.argtypes = [hp, C.c_int32, C.c_float, fp, C.c_size_t, szp]
+        L.fls_keyframes_merge.restype = C.c_int
+        L.fls_keyframes_merge.argtypes = [hp, ip, dp, C.c_size_t, C.c_float, C.c_float, fp, C.c_size_t, szp]
+        L.fls_keyframes_loop_match.restype = C.c_int
+        L.fls_keyframes_loop_match.argtypes = [hp, ip, dp, C.c_size_t, ip, dp, C.c_size_t, dp, fp, C.c_void_p]
+        L.fls_keyframes_stat.restype = C.c_size_t
+        L.fls_keyframes_stat.argtypes = [hp, C.c_int]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

@@ -10,6 +10,8 @@
 #include "preprocess_host.hpp"
 #include "loop_closure.hpp"
 #include "replicas.hpp"
+#include "keyframes.hpp"
+#include "../../include/fls_keyframes.h"
 #include <new>
 
 using namespace fls;
@@ -672,6 +674,120 @@ fls_status fls_features_project_driver(fls_features_handle h, const void* msg, s
         return features_project_driver(*h, msg, n, *cloud, *ingest, stamp_us, imu_t_us, imu_q_xyzw, n_imu, T_lidar_to_imu, n_ordered, imu_status,
                                        stamp_out_us, info);
     });
+}
+
+}  // extern "C"
+
+// ---- the device keyframe store (include/fls_keyframes.h) --------------------------------------------------------------------------
+namespace {
+// guarded(), with a failed device allocation reported as what it is
+template <typename F>
+fls_status kf_guarded(F&& f) {
+    return guarded([&]() -> fls_status {
+        try {
+            return f();
+        } catch (const HipError& e) {
+            if (e.code != hipErrorOutOfMemory) throw;
+            (void)hipGetLastError();
+            return FLS_ERR_NOMEM;
+        }
+    });
+}
+bool kf_leaf_ok(float leaf) { return std::isfinite(leaf) && leaf >= 0.f; }
+bool kf_ids_ok(const fls_keyframes& h, const int32_t* ids, size_t n) {
+    for (size_t k = 0; k < n; ++k)
+        if (!h.valid_id(ids[k])) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int fls_keyframes_revision(void) { return FLS_KEYFRAMES_REVISION; }
+
+fls_status fls_keyframes_create(int device_id, fls_keyframes_handle* out) {
+    if (!out) return FLS_ERR_INVALID;
+    *out = nullptr;
+    return kf_guarded([&]() -> fls_status {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device_id < 0 || device_id >= n) return FLS_ERR_DEVICE;
+        hipDeviceProp_t prop;
+        FLS_HIP(hipGetDeviceProperties(&prop, device_id));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLS_ERR_DEVICE;
+        std::unique_ptr<fls_keyframes> s(new fls_keyframes());
+        s->device = device_id;
+        s->init();
+        *out = s.release();
+        return FLS_OK;
+    });
+}
+
+void fls_keyframes_destroy(fls_keyframes_handle h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+fls_status fls_keyframes_add(fls_keyframes_handle h, const float* pts, size_t n, int stride, int32_t* id) {
+    if (!h || !id || (!pts && n) || stride < 3) return FLS_ERR_INVALID;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->add(pts, n, stride, id);
+    });
+}
+
+fls_status fls_keyframes_add_preprocessed(fls_keyframes_handle h, fls_preprocess_handle pre, int what, int32_t* id) {
+    if (!h || !pre || !id || (what != FLS_PRE_ORDERED && what != FLS_PRE_PLANAR && what != FLS_PRE_PLANAR_FILTERED) || h->device != pre->device)
+        return FLS_ERR_INVALID;
+    if (!pre->scan_done) return FLS_ERR_STATE;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->add_preprocessed(*pre, what, id);
+    });
+}
+
+size_t fls_keyframes_count(fls_keyframes_handle h) { return h ? h->kf.size() : 0; }
+
+fls_status fls_keyframes_get(fls_keyframes_handle h, int32_t id, float leaf, float* out, size_t cap, size_t* n_out) {
+    if (!h || !n_out || (cap && !out) || !kf_leaf_ok(leaf) || !h->valid_id(id)) return FLS_ERR_INVALID;
+    *n_out = 0;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->get(id, leaf, out, cap, n_out);
+    });
+}
+
+fls_status fls_keyframes_merge(fls_keyframes_handle h, const int32_t* ids, const double* poses, size_t n_ids, float leaf_each, float leaf_final, float* out,
+                               size_t cap, size_t* n_out) {
+    if (!h || !n_out || (n_ids && (!ids || !poses)) || (cap && !out) || !kf_leaf_ok(leaf_each) || !kf_leaf_ok(leaf_final) || !kf_ids_ok(*h, ids, n_ids))
+        return FLS_ERR_INVALID;
+    *n_out = 0;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->merge(ids, poses, n_ids, leaf_each, leaf_final, out, cap, n_out);
+    });
+}
+
+fls_status fls_keyframes_loop_match(fls_keyframes_handle h, const int32_t* src_ids, const double* src_poses, size_t n_src, const int32_t* tgt_ids,
+                                    const double* tgt_poses, size_t n_tgt, double T[16], float* fitness, fls_loop_stats* stats) {
+    if (!h || !T || !fitness || (n_src && (!src_ids || !src_poses)) || (n_tgt && (!tgt_ids || !tgt_poses)) || !kf_ids_ok(*h, src_ids, n_src) ||
+        !kf_ids_ok(*h, tgt_ids, n_tgt))
+        return FLS_ERR_INVALID;
+    std::vector<float> src, tgt;
+    const fls_status rc = kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        size_t n = 0;  // GetSubMap's leaf (loop_closure.cpp:219)
+        const fls_status a = h->merge(src_ids, src_poses, n_src, 0.2f, 0.f, nullptr, 0, &n, &src);
+        return a != FLS_OK ? a : h->merge(tgt_ids, tgt_poses, n_tgt, 0.2f, 0.f, nullptr, 0, &n, &tgt);
+    });
+    if (rc != FLS_OK) return rc;
+    return fls_loop_match(h->device, src.data(), src.size() / 4, tgt.data(), tgt.size() / 4, 4, T, fitness, stats);
+}
+
+size_t fls_keyframes_stat(fls_keyframes_handle h, int slot) {
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    return h->stat(slot);
 }
 
 }  // extern "C"
