@@ -37,6 +37,9 @@ INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_prepr
 KEYFRAMES_SYMBOLS = ["fls_keyframes_revision", "fls_keyframes_create", "fls_keyframes_destroy", "fls_keyframes_add", "fls_keyframes_add_preprocessed",
                      "fls_keyframes_count", "fls_keyframes_get", "fls_keyframes_merge", "fls_keyframes_loop_match", "fls_keyframes_stat"]
 
+# every symbol include/fls_debug_linalg.h declares (FLS_DEBUG_LINALG_REVISION 1): test hooks of csrc/linalg_dev.hpp / wave_solve.hpp
+DEBUG_LINALG_SYMBOLS = ["fls_debug_linalg_revision", "fls_debug_plane_fit_5x3", "fls_debug_svd3", "fls_debug_lu6", "fls_debug_so3", "fls_debug_wave_sum"]
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -329,6 +332,18 @@ def lib():
         L.fls_keyframes_loop_match.argtypes = [hp, ip, dp, C.c_size_t, ip, dp, C.c_size_t, dp, fp, C.c_void_p]
         L.fls_keyframes_stat.restype = C.c_size_t
         L.fls_keyframes_stat.argtypes = [hp, C.c_int]
+        L.fls_debug_linalg_revision.restype = C.c_int
+        L.fls_debug_linalg_revision.argtypes = []
+        L.fls_debug_plane_fit_5x3.restype = C.c_int
+        L.fls_debug_plane_fit_5x3.argtypes = [C.c_int, dp, C.c_int, dp]
+        L.fls_debug_svd3.restype = C.c_int
+        L.fls_debug_svd3.argtypes = [C.c_int, dp, C.c_int, dp, dp]
+        L.fls_debug_lu6.restype = C.c_int
+        L.fls_debug_lu6.argtypes = [C.c_int, dp, dp, C.c_int, dp, dp, dp]
+        L.fls_debug_so3.restype = C.c_int
+        L.fls_debug_so3.argtypes = [C.c_int, dp, dp, C.c_int, dp, dp, dp]
+        L.fls_debug_wave_sum.restype = C.c_int
+        L.fls_debug_wave_sum.argtypes = [C.c_int, dp, C.c_int, dp]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

@@ -11,7 +11,9 @@
 #include "loop_closure.hpp"
 #include "replicas.hpp"
 #include "keyframes.hpp"
+#include "kernels_debug_linalg.hpp"
 #include "../../include/fls_keyframes.h"
+#include "../../include/fls_debug_linalg.h"
 #include <new>
 
 using namespace fls;
@@ -44,6 +46,33 @@ fls_status guarded(F&& f) {
     }
 }
 
+// test hooks of include/fls_debug_linalg.h: inputs up, one launch, outputs down: every array holds `w` doubles per system
+struct DebugIn { const double* p; int w; };
+struct DebugOut { double* p; int w; };
+template <typename Launch>
+fls_status debug_linalg_run(int device_id, int n, const std::vector<DebugIn>& in, const std::vector<DebugOut>& out, Launch&& launch) {
+    for (const DebugIn& a : in) if (!a.p) return FLS_ERR_INVALID;
+    for (const DebugOut& a : out) if (!a.p) return FLS_ERR_INVALID;
+    if (n < 0) return FLS_ERR_INVALID;
+    if (n == 0) return FLS_OK;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(device_id));
+        std::vector<DevBuf<double>> din(in.size()), dout(out.size());
+        std::vector<const double*> pin(in.size());
+        std::vector<double*> pout(out.size());
+        for (size_t i = 0; i < in.size(); ++i) {
+            din[i].reserve(size_t(n) * in[i].w);
+            FLS_HIP(hipMemcpy(din[i].p, in[i].p, size_t(n) * in[i].w * sizeof(double), hipMemcpyHostToDevice));
+            pin[i] = din[i].p;
+        }
+        for (size_t i = 0; i < out.size(); ++i) { dout[i].reserve(size_t(n) * out[i].w); pout[i] = dout[i].p; }
+        launch(pin.data(), pout.data());
+        FLS_HIP(hipGetLastError());
+        for (size_t i = 0; i < out.size(); ++i) FLS_HIP(hipMemcpy(out[i].p, dout[i].p, size_t(n) * out[i].w * sizeof(double), hipMemcpyDeviceToHost));
+        return FLS_OK;
+    });
+}
+inline dim3 debug_linalg_lanes(int n) { return dim3(unsigned((n + kDebugLinalgBlock - 1) / kDebugLinalgBlock)); }
 }  // namespace
 
 extern "C" {
@@ -338,6 +367,39 @@ fls_status fls_debug_ldlt6(int device_id, const double* H, const double* g, int 
         FLS_HIP(hipMemcpy(x, dx.p, size_t(n) * 6 * sizeof(double), hipMemcpyDeviceToHost));
         FLS_HIP(hipMemcpy(ok, dok.p, size_t(n) * sizeof(int), hipMemcpyDeviceToHost));
         return FLS_OK;
+    });
+}
+
+// ---- test hooks of the device linear-algebra primitives (include/fls_debug_linalg.h, kernels_debug_linalg.hpp) --------------------------
+int fls_debug_linalg_revision(void) { return FLS_DEBUG_LINALG_REVISION; }
+
+fls_status fls_debug_plane_fit_5x3(int device_id, const double* A, int n, double* x) {
+    return debug_linalg_run(device_id, n, {{A, 15}}, {{x, 3}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_plane_fit_5x3_kernel, debug_linalg_lanes(n), dim3(kDebugLinalgBlock), 0, nullptr, in[0], n, out[0]);
+    });
+}
+
+fls_status fls_debug_svd3(int device_id, const double* A, int n, double* S, double* V) {
+    return debug_linalg_run(device_id, n, {{A, 9}}, {{S, 3}, {V, 9}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_svd3_kernel, debug_linalg_lanes(n), dim3(kDebugLinalgBlock), 0, nullptr, in[0], n, out[0], out[1]);
+    });
+}
+
+fls_status fls_debug_lu6(int device_id, const double* H, const double* b, int n, double* det, double* inv, double* x) {
+    return debug_linalg_run(device_id, n, {{H, 36}, {b, 6}}, {{det, 1}, {inv, 36}, {x, 6}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_lu6_kernel, dim3(unsigned(n)), dim3(64), 0, nullptr, in[0], in[1], n, out[0], out[1], out[2]);
+    });
+}
+
+fls_status fls_debug_so3(int device_id, const double* v, const double* R, int n, double* Rd, double* R_Rd, double* Rd_R) {
+    return debug_linalg_run(device_id, n, {{v, 3}, {R, 9}}, {{Rd, 9}, {R_Rd, 9}, {Rd_R, 9}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_so3_kernel, debug_linalg_lanes(n), dim3(kDebugLinalgBlock), 0, nullptr, in[0], in[1], n, out[0], out[1], out[2]);
+    });
+}
+
+fls_status fls_debug_wave_sum(int device_id, const double* v, int n, double* total) {
+    return debug_linalg_run(device_id, n, {{v, 64}}, {{total, 1}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_wave_sum_kernel, dim3(unsigned(n)), dim3(64), 0, nullptr, in[0], n, out[0]);
     });
 }
 

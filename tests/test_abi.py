@@ -32,6 +32,28 @@ def test_header_symbols_all_exported(built):
     assert L.fls_abi_version() == 1 and L.fls_abi_revision() >= 4  # (additive revisions: include/fls_reg.h)
 
 
+def test_debug_linalg_hooks_declared_exported_and_listed(built):
+    """include/fls_debug_linalg.h (test hooks of the device linear-algebra primitives): a revision of its own, every declared symbol exported and
+    listed, FLS_ABI_REVISION and the symbol list of fls_reg.h untouched; arguments are validated before the device is looked at, n == 0 is OK."""
+    L = _lib.lib()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fls_debug_linalg.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(fls_[a-z_0-9]+)\s*\(", src))
+    assert len(declared) == 6 and declared == set(_lib.DEBUG_LINALG_SYMBOLS)
+    for s in declared:
+        assert hasattr(L, s), s
+    assert "#define FLS_DEBUG_LINALG_REVISION 1" in src and L.fls_debug_linalg_revision() == 1 and L.fls_abi_revision() == 9
+    assert not set(_lib.DEBUG_LINALG_SYMBOLS) & set(_lib.EXPORTED_SYMBOLS)
+    a = (C.c_double * 64)()
+    inv = _lib.FLS_ERR_INVALID
+    assert L.fls_debug_plane_fit_5x3(0, None, 1, a) == inv and L.fls_debug_plane_fit_5x3(0, a, 1, None) == inv and L.fls_debug_plane_fit_5x3(0, a, -1, a) == inv
+    assert L.fls_debug_svd3(0, None, 1, a, a) == inv and L.fls_debug_svd3(0, a, 1, None, a) == inv and L.fls_debug_svd3(0, a, 1, a, None) == inv
+    assert L.fls_debug_lu6(0, a, None, 1, a, a, a) == inv and L.fls_debug_lu6(0, a, a, 1, None, a, a) == inv and L.fls_debug_lu6(0, a, a, -2, a, a, a) == inv
+    assert L.fls_debug_so3(0, None, a, 1, a, a, a) == inv and L.fls_debug_so3(0, a, a, 1, a, a, None) == inv
+    assert L.fls_debug_wave_sum(0, None, 1, a) == inv and L.fls_debug_wave_sum(0, a, 1, None) == inv
+    assert L.fls_debug_plane_fit_5x3(0, a, 0, a) == 0 and L.fls_debug_svd3(0, a, 0, a, a) == 0 and L.fls_debug_lu6(0, a, a, 0, a, a, a) == 0
+    assert L.fls_debug_so3(0, a, a, 0, a, a, a) == 0 and L.fls_debug_wave_sum(0, a, 0, a) == 0
+
+
 def test_struct_layouts_match_header(built):
     src = open(os.path.join(ROOT, "include", "fls_reg.h")).read()
     body = re.search(r"typedef struct fls_params \{(.*?)\} fls_params;", src, re.S).group(1)
