@@ -6,7 +6,7 @@
 //                        voxel-wise (hash-table fallback, G = 8); every lane scans its candidates four loads at a
 //                        time into a private sorted top-5 of keys {float-bits(d2) : map slot} held as IEEE doubles
 //                        (v_min_f64 / v_max_f64 insertion), and the G private lists are merged by five rounds of a
-//                        DPP group-min.  58 VGPRs -> 8 waves/SIMD, G x more waves than points/64: the dependent
+//                        DPP group-min.  48 VGPRs -> 8 waves/SIMD, G x more waves than points/64: the dependent
 //                        gathers (cell -> voxel points) are hidden by thread-level parallelism instead of being
 //                        serialised in one lane (the first, fused kernel spent 117 us per launch that way).
 //                        Output: nearest_points_[i] (<=5 float4 {x,y,z,id}) + count; untouched when no
@@ -33,6 +33,24 @@ __device__ __forceinline__ void nearby18(const int k, int& dx, int& dy, int& dz)
     dy = (int)((DY >> (2 * k)) & 3ull) - 1;
     dz = (int)((DZ >> (2 * k)) & 3ull) - 1;
 }
+
+// The same offsets as slab offsets of the brick image, (dz * S + dy) * S + dx with S = kBrickStored (within +-111), for the four probes
+// k = sub + 4 r of round r packed as signed bytes, byte `sub`: a lane extracts its offset with one v_bfe_i32 on 8 * sub.
+// (k >= 19, the last lane of the last round: offset 0, its count is zeroed by the caller)
+constexpr int nearby18_slab(const int k) {
+    constexpr unsigned long long DX = 0x1548889561ull, DY = 0x895429495ull, DZ = 0x282956155ull;
+    const int dx = (int)((DX >> (2 * k)) & 3ull) - 1, dy = (int)((DY >> (2 * k)) & 3ull) - 1, dz = (int)((DZ >> (2 * k)) & 3ull) - 1;
+    return (dz * kBrickStored + dy) * kBrickStored + dx;
+}
+constexpr unsigned nearby18_slab_pack4(const int r) {
+    unsigned pk = 0u;
+    for (int s = 0; s < 4; ++s) {
+        const int k = s + 4 * r;
+        pk |= ((unsigned)(k < 19 ? nearby18_slab(k) : 0) & 0xffu) << (8 * s);
+    }
+    return pk;
+}
+static_assert((kBrickStored + 1) * kBrickStored + 1 <= 127, "slab offsets of the 18 neighbours fit a signed byte");
 
 // Butterfly exchange partners without LDS: lane^1 and lane^2 are quad permutes, the third pairing uses
 // row_half_mirror (lane i <-> 7-i inside each group of 8) -- any perfect pairing works for a min / sum.
@@ -138,7 +156,13 @@ __device__ __forceinline__ unsigned slot_select(const unsigned idx, const unsign
 // (2.7 us of this kernel + 3.2 us of re-reads in the fit kernel, measured by removing the stores).  Nontemporal stores
 // measured -0.5 us per launch, -0.5 us per Match (inside the noise), write-through (sc1) stores were slower (18.6-21.2 us
 // per launch): the rows are plain stores.
-template <int G, bool COUNT, bool DENSE, bool FIRST, bool BAL = false>
+// GEN (the general form) keeps two things the host can rule out for a whole map (matcher_p2plane_ivox.hpp::launch_knn):
+//   - the max_range gate d2 < 25 per candidate.  A query lies within half a voxel of its voxel's centre on each axis, a candidate within
+//     half a voxel of a centre at most one voxel away: every axis difference is <= 2 res, d2 <= 12 res^2 (3 at the 0.5 m of InitIVox).
+//     The host drops the gate where 27 res^2 < 25, i.e. with a whole extra voxel per axis (3 res) for the float rounding of key and
+//     difference (at |key| near 2^20 one ulp of a coordinate is res / 8); the selection keys then stay finite doubles as with the gate.
+//   - 64-bit candidate addresses.  With slots x 16 bytes < 2^32 the four loads of a trip take a 32-bit byte offset from the uniform base.
+template <int G, bool COUNT, bool DENSE, bool FIRST, bool BAL = false, bool GEN = true>
 __global__ void __launch_bounds__(256)
 ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
                 const GnState* __restrict__ st, const Pose16 T0, const DevGrid grid, const BrickDir bd,
@@ -232,21 +256,29 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         const bool have = in_range && be.key == bkey && be.begin < bd.n_cap;
         const unsigned cbase = (have ? be.begin : 0u) * kBrickStride +
                                brick_slab_index((kx & (kBrickSide - 1)) + 1, (ky & (kBrickSide - 1)) + 1, (kz & (kBrickSide - 1)) + 1);
-        auto cell = [&](const int r, unsigned& beg, unsigned& cnt) {
+        constexpr unsigned PK[5] = {nearby18_slab_pack4(0), nearby18_slab_pack4(1), nearby18_slab_pack4(2), nearby18_slab_pack4(3), nearby18_slab_pack4(4)};
+        const unsigned sub8 = 8u * (unsigned)sub;
+        auto cell = [&](const int r, const unsigned pk4, unsigned& beg, unsigned& cnt) {
             const int k = sub + G * r;
-            int ox, oy, oz;
-            nearby18(k < 19 ? k : 0, ox, oy, oz);
+            int off;
+            if (G == 4) {
+                off = __builtin_amdgcn_sbfe((int)pk4, sub8, 8u);
+            } else {
+                int ox, oy, oz;
+                nearby18(k < 19 ? k : 0, ox, oy, oz);
+                off = (oz * kBrickStored + oy) * kBrickStored + ox;
+            }
             const bool ok = have && k < 19;
-            const uint2 e = bd.cells[cbase + (unsigned)((oz * kBrickStored + oy) * kBrickStored + ox)];  // (always inside the slab)
+            const uint2 e = bd.cells[cbase + (unsigned)off];  // (always inside the slab)
             beg = e.x;
             cnt = ok ? e.y : 0u;
-            if (COUNT && in_range && k < 19) { c_probes++; if (cnt) { c_hits++; c_cand += cnt; } }
+            if (COUNT && active && k < 19) { c_probes++; if (cnt) { c_hits++; c_cand += cnt; } }  // (a query beyond the key range probes 19 absent voxels)
         };
-        cell(0, b0, c0);
-        if (R > 1) cell(1, b1, c1);
-        if (R > 2) cell(2, b2, c2);
-        if (R > 3) cell(3, b3, c3);
-        if (R > 4) cell(4, b4, c4);
+        cell(0, PK[0], b0, c0);
+        if (R > 1) cell(1, PK[1], b1, c1);
+        if (R > 2) cell(2, PK[2], b2, c2);
+        if (R > 3) cell(3, PK[3], b3, c3);
+        if (R > 4) cell(4, PK[4], b4, c4);
     } else {
         bool pv0 = false, pv1 = false, pv2 = false, pv3 = false, pv4 = false;
         unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0, k4 = 0;
@@ -262,13 +294,21 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         if (R > 2) resolve(pv2, k2, h2, e2, b2, c2);
         if (R > 3) resolve(pv3, k3, h3, e3, b3, c3);
         if (R > 4) resolve(pv4, k4, h4, e4, b4, c4);
+        if (COUNT && active && !in_range) {  // (a query beyond the key range probes 19 absent voxels)
+#pragma unroll
+            for (int r = 0; r < R; ++r) c_probes += sub + G * r < 19 ? 1u : 0u;
+        }
     }
     // scan this lane's <= R voxels, 4 point loads in flight per trip (the dependent-load latency is paid
     // once per four candidates; the tail of a voxel re-reads its last point, masked out)
     auto consider = [&](const float4 p, const unsigned s, const bool ok) {
         const float dx = p.x - ptx, dy = p.y - pty, dz = p.z - ptz;
         const float d2 = dx * dx + (dy * dy + dz * dz);  // Eigen Vector3f::squaredNorm order
-        top5_insert_dkey(t5, make_dkey(d2, s, ok && d2 < 25.0f));  // max_range 5.0 squared (never binds at 0.5 m voxels)
+        top5_insert_dkey(t5, make_dkey(d2, s, GEN ? ok && d2 < 25.0f : ok));  // max_range 5.0 squared (!GEN: cannot bind, see above)
+    };
+    auto map_pt = [&](const unsigned s) -> float4 {
+        if (GEN) return grid.pts[s];
+        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(grid.pts) + (s << 4));  // (32-bit byte offset, as reduce_partials_trip)
     };
     // one flattened loop over this lane's <= R voxels: trip count = ceil(lane total / 4), not the sum of
     // per-voxel maxima
@@ -282,7 +322,7 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         // contiguous ranges, one per lane, instead of whole voxels per lane: a wave runs max-over-lanes trips of the
         // loop below, and voxels hold 1..20+ points (4.7 trips of four candidates per wave before, 2.8 after).
         // The hit voxels are compacted into a per-group LDS table {prefix end, begin - prefix start}; a lane walks
-        // its range through a 5-entry window of that table (four candidates span at most five voxels).
+        // its range through a two-entry window of that table (see the loop).
         __shared__ __attribute__((aligned(16))) unsigned s_end[QPB][24];
         __shared__ __attribute__((aligned(16))) unsigned s_off[QPB][24];
         const int g = threadIdx.x / G;
@@ -295,45 +335,70 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         const unsigned before = (sub > 0 ? t0 : 0u) + (sub > 1 ? t1 : 0u) + (sub > 2 ? t2 : 0u), all = t0 + t1 + t2 + t3;
         const unsigned TOT = all >> 5;
         unsigned pos = before & 31u, run = before >> 5;
-        // every entry behind the last real one is a sentinel (the window looks four entries ahead, the start search
-        // reads twenty): the whole row is filled first, the real entries overwrite (LDS operations of a wave are in order)
+        // every entry behind the last real one is a sentinel (the window looks one entry ahead, the start search
+        // four): the whole row is filled first, the real entries overwrite (LDS operations of a wave are in order)
         {
             uint2* const rowp = reinterpret_cast<uint2*>(&s_end[g][6 * sub]);
             rowp[0] = make_uint2(~0u, ~0u); rowp[1] = make_uint2(~0u, ~0u); rowp[2] = make_uint2(~0u, ~0u);
         }
-        if (c0) { s_off[g][pos] = b0 - run; run += c0; s_end[g][pos] = run; ++pos; }
-        if (c1) { s_off[g][pos] = b1 - run; run += c1; s_end[g][pos] = run; ++pos; }
-        if (c2) { s_off[g][pos] = b2 - run; run += c2; s_end[g][pos] = run; ++pos; }
-        if (c3) { s_off[g][pos] = b3 - run; run += c3; s_end[g][pos] = run; ++pos; }
-        if (c4) { s_off[g][pos] = b4 - run; run += c4; s_end[g][pos] = run; ++pos; }
+        // predicated, not branched: a missed probe writes its pair to a word of the lane's own behind the table (real entries: 0..18; the
+        // window reads k + 1 <= 19, the start search up to entry 18 + 4, so the s_end word is made a sentinel again after the last put)
+        const unsigned dmy = 20u + (unsigned)sub;
+        auto put = [&](const unsigned b, const unsigned c) {
+            const unsigned at = c ? pos : dmy;
+            s_off[g][at] = b - run;
+            run += c;
+            s_end[g][at] = run;
+            pos += c ? 1u : 0u;
+        };
+        put(b0, c0);
+        if (R > 1) put(b1, c1);
+        if (R > 2) put(b2, c2);
+        if (R > 3) put(b3, c3);
+        if (R > 4) put(b4, c4);
+        s_end[g][dmy] = ~0u;
         // a group lives inside one wave and the LDS serves a wave's operations in order: no workgroup barrier, only a
         // compiler-level ordering point between the table writes and the cross-lane reads
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const unsigned Q = (TOT + 3u) >> 2, a = sub * Q, e = a + Q < TOT ? a + Q : TOT;
-        unsigned k = 0;  // first table entry whose range reaches past a
-#pragma unroll
-        for (int v = 0; v < 5; ++v) {
-            const uint4 e4 = *reinterpret_cast<const uint4*>(&s_end[g][4 * v]);
-            k += (e4.x <= a ? 1u : 0u) + (e4.y <= a ? 1u : 0u) + (e4.z <= a ? 1u : 0u) + (e4.w <= a ? 1u : 0u);
+        // Start search: k = first table entry whose range reaches past a = number of entries that end at or before a.  The quad
+        // broadcasts already say which lane's entries hold candidate a: P_i = packed sum of the lanes before lane i = {candidates before
+        // lane i : entries before lane i}, and P_i <= 32 a + 31 <=> candidates before lane i <= a.  With j the last such lane, every entry
+        // before lane j's first one ends at or before a, lane j's own (at most five) are compared, and whatever follows them in the table
+        // (later lanes' entries, sentinels) ends past a.  Five compares in place of twenty.
+        const unsigned P2 = t0 + t1, P3 = P2 + t2, A32 = a * 32u + 31u;
+        unsigned ps = t0 <= A32 ? t0 : 0u;
+        ps = P2 <= A32 ? P2 : ps;
+        ps = P3 <= A32 ? P3 : ps;
+        unsigned k = ps & 31u;  // (<= 19: the five words read below stay inside the row)
+        {
+            const unsigned* const w = &s_end[g][k];
+            const unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+            k += (w0 <= a ? 1u : 0u) + (w1 <= a ? 1u : 0u) + (w2 <= a ? 1u : 0u) + (w3 <= a ? 1u : 0u) + (w4 <= a ? 1u : 0u);
         }
-        for (unsigned idx = a; idx < e; idx += 4) {
-            const unsigned E0 = s_end[g][k], E1 = s_end[g][k + 1], E2 = s_end[g][k + 2], E3 = s_end[g][k + 3];
-            const unsigned O0 = s_off[g][k], O1 = s_off[g][k + 1], O2 = s_off[g][k + 2], O3 = s_off[g][k + 3], O4 = s_off[g][k + 4];
-            const unsigned last = e - 1;
+        // Two-run window: a trip resolves its four candidates against the run idx lies in (entry k: E(k-1) <= idx < E(k)) and the
+        // next one, and ends where the second run ends -- 2.2 % of the trips would reach into a third run (runs average 5.1 points),
+        // cutting them costs 0.8 % more trips and saves a five-entry select chain per candidate.  The candidates of [a, e) are still
+        // taken once each, only grouped differently: the same top-5 set.  (Behind the last run E1 is the sentinel: the trip ends at e.)
+        for (unsigned idx = a; idx < e;) {
+            const unsigned E0 = s_end[g][k], E1 = s_end[g][k + 1];
+            const unsigned O0 = s_off[g][k], O1 = s_off[g][k + 1];
+            const unsigned last = (E1 < e ? E1 : e) - 1;
             const unsigned i1 = idx + 1, i2 = idx + 2, i3 = idx + 3;
-            const unsigned s0 = slot_select<5>(idx, E0, E1, E2, E3, O0, O1, O2, O3, O4);
-            const unsigned s1 = slot_select<5>(i1 < last ? i1 : last, E0, E1, E2, E3, O0, O1, O2, O3, O4);
-            const unsigned s2 = slot_select<5>(i2 < last ? i2 : last, E0, E1, E2, E3, O0, O1, O2, O3, O4);
-            const unsigned s3 = slot_select<5>(i3 < last ? i3 : last, E0, E1, E2, E3, O0, O1, O2, O3, O4);
-            const float4 q0 = grid.pts[s0], q1 = grid.pts[s1], q2 = grid.pts[s2], q3 = grid.pts[s3];
+            const unsigned j1 = i1 < last ? i1 : last, j2 = i2 < last ? i2 : last, j3 = i3 < last ? i3 : last;
+            const unsigned s0 = idx + O0;
+            const unsigned s1 = j1 + (j1 < E0 ? O0 : O1);
+            const unsigned s2 = j2 + (j2 < E0 ? O0 : O1);
+            const unsigned s3 = j3 + (j3 < E0 ? O0 : O1);
+            const float4 q0 = map_pt(s0), q1 = map_pt(s1), q2 = map_pt(s2), q3 = map_pt(s3);
             consider(q0, s0, true);
             consider(q1, s1, i1 <= last);
             consider(q2, s2, i2 <= last);
             consider(q3, s3, i3 <= last);
-            const unsigned nx = idx + 4;
-            k += (E0 <= nx ? 1u : 0u) + (E1 <= nx ? 1u : 0u) + (E2 <= nx ? 1u : 0u) + (E3 <= nx ? 1u : 0u);
+            idx = j3 + 1;  // min(idx + 4, end of the second run, e)
+            k += (E0 <= idx ? 1u : 0u) + (E1 <= idx ? 1u : 0u);  // (runs are never empty: E1 == idx puts idx into run k + 2)
         }
     } else
     for (unsigned j = 0; j < tot; j += 4) {
@@ -341,7 +406,7 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         const unsigned i1 = j + 1, i2 = j + 2, i3 = j + 3;
         const unsigned s0 = slot_of(j), s1 = slot_of(i1 < last ? i1 : last), s2 = slot_of(i2 < last ? i2 : last),
                        s3 = slot_of(i3 < last ? i3 : last);
-        const float4 p0 = grid.pts[s0], p1 = grid.pts[s1], p2 = grid.pts[s2], p3 = grid.pts[s3];
+        const float4 p0 = map_pt(s0), p1 = map_pt(s1), p2 = map_pt(s2), p3 = map_pt(s3);
         consider(p0, s0, true);
         consider(p1, s1, i1 <= last);
         consider(p2, s2, i2 <= last);

@@ -512,13 +512,18 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         float* const dev_copy = from_host ? scan.xyz.p : nullptr;
         const size_t nblk = (n * G + 255) / 256, gran = size_t(8) * size_t(kIvoxXcdChunk);
         const dim3 grid(unsigned((nblk + gran - 1) / gran * gran));  // multiple of 8 * chunk: the XCD re-map is a bijection
-#define FLS_KNN_L(C, D, F)                                                                                                           \
-    hipExtLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, true>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n),      \
+        // the kernel's general form (GEN) only where it can matter: voxels so large that a candidate of the 19 probed voxels could lie beyond
+        // max_range (3 res per axis, one voxel more than the geometry allows, reaches 5 m), or a point array of 4 GiB and more
+        const bool general = !(27.0f * ivox.resolution * ivox.resolution < 25.0f) || size_t(g.n_pts) > (size_t(1) << 28);
+#define FLS_KNN_G(C, D, F, GEN)                                                                                                      \
+    hipExtLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, true, GEN>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n), \
                           (const GnState*)d_state.p, T0, g, win, ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, kIvoxXcdChunk, \
                           d_nn_ids.p, nn_prev, dev_copy)
+#define FLS_KNN_L(C, D, F) do { if (general) FLS_KNN_G(C, D, F, true); else FLS_KNN_G(C, D, F, false); } while (0)
 #define FLS_KNN(C, D) do { if (first) FLS_KNN_L(C, D, true); else FLS_KNN_L(C, D, false); } while (0)
         if (win.cells) { if (count_traffic) FLS_KNN(true, true); else FLS_KNN(false, true); }
         else { if (count_traffic) FLS_KNN(true, false); else FLS_KNN(false, false); }
+#undef FLS_KNN_G
 #undef FLS_KNN_L
 #undef FLS_KNN
     }
