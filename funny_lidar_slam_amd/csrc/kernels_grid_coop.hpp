@@ -19,7 +19,7 @@
 // Gauss-Newton tail runs in gn_solve_loam_kernel / gn_solve_lu_kernel.
 #pragma once
 #include "kernels_knn.hpp"
-#include "kernels_ivox_coop.hpp"
+#include "lane_group.hpp"
 
 namespace fls {
 
@@ -46,12 +46,6 @@ __device__ __forceinline__ void topk_insert(unsigned long long (&t)[K], unsigned
             }
         }
     }
-}
-__device__ __forceinline__ unsigned group8_min_u32(unsigned v) {
-    unsigned o = dpp_pair_u32<0>(v); v = o < v ? o : v;
-    o = dpp_pair_u32<1>(v); v = o < v ? o : v;
-    o = dpp_pair_u32<2>(v); v = o < v ? o : v;
-    return v;
 }
 
 // (the body is a device function of the block index so that two queries -- the corner and the planar class of the LOAM
@@ -176,7 +170,7 @@ grid_knn_body(const int bid, const float* __restrict__ sx, const float* __restri
     }
     // ---- bound after round 0 (non-negative floats order like their bit patterns)
     const unsigned my_kth = (t[K - 1] != ~0ull) ? (unsigned)(t[K - 1] >> 32) : 0x7f800000u;
-    float bound = __uint_as_float(group8_min_u32(my_kth));
+    float bound = __uint_as_float(group_min_u32<G>(my_kth));
     bound = gate < bound ? gate : bound;
     // ---- rounds 1..3: probe + scan only the cells that can still matter
     const double qdx = (double)qx, qdy = (double)qy, qdz = (double)qz;
@@ -200,7 +194,7 @@ grid_knn_body(const int bid, const float* __restrict__ sx, const float* __restri
     plan(2, b2, c2);
     plan(3, b3, c3);
     const unsigned tot = c1 + c2 + c3;
-    // candidate index -> map slot: compare / select chain on values (kernels_ivox_coop.hpp slot_select), no branches
+    // candidate index -> map slot: compare / select chain on values (lane_group.hpp slot_select), no branches
     const unsigned p1 = c1, p2 = c1 + c2, o0 = b1, o1 = b2 - p1, o2 = b3 - p2;
     auto slot_of = [=](const unsigned idx) -> unsigned { return slot_select<3>(idx, p1, p2, 0u, 0u, o0, o1, o2, 0u, 0u); };
     for (unsigned j = 0; j < tot; j += 4) {
@@ -227,11 +221,11 @@ grid_knn_body(const int bid, const float* __restrict__ sx, const float* __restri
         for (int j = 0; j < K; ++j) {
             const unsigned long long m = group_min_u64<G>(t[0]);
             const bool owner = (t[0] == m) && (m != ~0ull);
-            const unsigned ms = group8_min_u32(owner ? sl[0] : 0xffffffffu);
+            const unsigned ms = group_min_u32<G>(owner ? sl[0] : 0xffffffffu);
             if constexpr (CARRY) {  // keys are unique (the map index is the low word): one owner, whose coordinates every lane of the group receives
-                mine_x = __uint_as_float(group8_min_u32(owner ? __float_as_uint(best_x) : 0xffffffffu));
-                mine_y = __uint_as_float(group8_min_u32(owner ? __float_as_uint(best_y) : 0xffffffffu));
-                mine_z = __uint_as_float(group8_min_u32(owner ? __float_as_uint(best_z) : 0xffffffffu));
+                mine_x = __uint_as_float(group_min_u32<G>(owner ? __float_as_uint(best_x) : 0xffffffffu));
+                mine_y = __uint_as_float(group_min_u32<G>(owner ? __float_as_uint(best_y) : 0xffffffffu));
+                mine_z = __uint_as_float(group_min_u32<G>(owner ? __float_as_uint(best_z) : 0xffffffffu));
             }
             if (owner) {
 #pragma unroll

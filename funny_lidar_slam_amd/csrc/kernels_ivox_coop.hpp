@@ -1,24 +1,29 @@
 // kernels_ivox_coop.hpp -- the production iVox point-to-plane path, split for the machine:
 //
-//   ivox_knn_kernel<G>   G lanes cooperate on ONE source point: the 19 voxel probes are dealt round-robin to the G
-//                        lanes (all probe loads of a wave are in flight together); the hit voxels' points are then
-//                        split into equal contiguous ranges per lane (BAL: per-group LDS voxel table) or taken
-//                        voxel-wise (hash-table fallback, G = 8); every lane scans its candidates four loads at a
-//                        time into a private sorted top-5 of keys {float-bits(d2) : map slot} held as IEEE doubles
-//                        (v_min_f64 / v_max_f64 insertion), and the G private lists are merged by five rounds of a
-//                        DPP group-min.  48 VGPRs -> 8 waves/SIMD, G x more waves than points/64: the dependent
+//   ivox_knn_kernel      four lanes cooperate on ONE source point, for the brick image (DENSE) and the hash-table image alike:
+//                        the 19 voxel probes are dealt round-robin to the four lanes (all probe loads of a wave are in
+//                        flight together); the hit voxels are compacted into a per-group LDS table and their points,
+//                        concatenated, cut into four equal contiguous ranges, one per lane (balanced split); every lane
+//                        scans its range four loads at a time into a private sorted top-5 of keys
+//                        {float-bits(d2) : map slot} held as IEEE doubles (v_min_f64 / v_max_f64 insertion), and the
+//                        four private lists are merged by five rounds of a DPP group-min.  48-62 VGPRs over the 16
+//                        instantiations (48 / 54 for the brick image's product forms, lean / GEN) and 12 KiB of LDS per
+//                        256-thread workgroup -> 8 waves/SIMD, four times as many waves as points/64: the dependent
 //                        gathers (cell -> voxel points) are hidden by thread-level parallelism instead of being
 //                        serialised in one lane (the first, fused kernel spent 117 us per launch that way).
-//                        Output: nearest_points_[i] (<=5 float4 {x,y,z,id}) + count; untouched when no
-//                        candidate exists (ivox_map.cpp:21-23 quirk).
+//                        Output: the neighbour list of point i as <= 5 map slots (ids form, nn_ids[i][8]) + count;
+//                        untouched when no candidate exists (ivox_map.cpp:21-23 quirk).  (With nn_ids == nullptr the
+//                        list leaves as gathered rows nearest_points_[i] instead; the matcher never asks for that.)
 //   p2plane_fit_solve_kernel  one lane per source point: 5x3 column-pivoted Householder plane fit, gates,
 //                        Jacobian (FP64), the Q1 stale-slot rule, DPP wave reduction of the 6x6 system; the last
 //                        workgroup to finish also runs the Gauss-Newton tail (solve, pose update, stop rule).
+//                        127-128 VGPRs; the compiler's occupancy figure is 4 waves/SIMD for the 512-thread form, 3 for the 256-thread one.
 //
 // Exact-tie rule of the selection: lower map slot wins (the reference's order under exact float ties is
 // libstdc++-introselect-defined; parity tests count such queries).
 #pragma once
 #include "kernels_p2plane.hpp"
+#include "lane_group.hpp"
 
 namespace fls {
 
@@ -52,48 +57,6 @@ constexpr unsigned nearby18_slab_pack4(const int r) {
 }
 static_assert((kBrickStored + 1) * kBrickStored + 1 <= 127, "slab offsets of the 18 neighbours fit a signed byte");
 
-// Butterfly exchange partners without LDS: lane^1 and lane^2 are quad permutes, the third pairing uses
-// row_half_mirror (lane i <-> 7-i inside each group of 8) -- any perfect pairing works for a min / sum.
-template <int STEP>
-__device__ __forceinline__ unsigned dpp_pair_u32(const unsigned v) {
-    static_assert(STEP >= 0 && STEP <= 3, "");
-    if (STEP == 0) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
-    if (STEP == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-    if (STEP == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);  // row_half_mirror
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true);                 // row_mirror (16 lanes)
-}
-template <int G>
-__device__ __forceinline__ unsigned long long group_min_u64(unsigned long long v) {
-#define FLS_MIN_STEP(S)                                                                               \
-    {                                                                                                 \
-        const unsigned lo = dpp_pair_u32<S>((unsigned)(v & 0xffffffffull));                          \
-        const unsigned hi = dpp_pair_u32<S>((unsigned)(v >> 32));                                    \
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                            \
-        v = o < v ? o : v;                                                                            \
-    }
-    FLS_MIN_STEP(0)
-    if (G >= 4) FLS_MIN_STEP(1)
-    if (G >= 8) FLS_MIN_STEP(2)
-    if (G >= 16) FLS_MIN_STEP(3)
-#undef FLS_MIN_STEP
-    if (G == 32) {
-        const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), 16, 64);
-        const unsigned hi = __shfl_xor((unsigned)(v >> 32), 16, 64);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
-template <int G>
-__device__ __forceinline__ int group_sum_i32(int v) {
-    v += (int)dpp_pair_u32<0>((unsigned)v);
-    if (G >= 4) v += (int)dpp_pair_u32<1>((unsigned)v);
-    if (G >= 8) v += (int)dpp_pair_u32<2>((unsigned)v);
-    if (G >= 16) v += (int)dpp_pair_u32<3>((unsigned)v);
-    if (G == 32) v += __shfl_xor(v, 16, 64);
-    return v;
-}
-
 // Selection keys as IEEE doubles: the 64-bit key {float-bits(d2) + kKeyBias : map slot} read as a positive NORMAL
 // double orders exactly like the unsigned integer (sign 0, exponent field >= 1 thanks to the bias, never Inf/NaN
 // because d2 < 25), so a sorted insertion is nine full-rate v_min_f64 / v_max_f64 instead of five 64-bit
@@ -124,35 +87,17 @@ __device__ __forceinline__ void top5_insert_dkey(double (&t)[5], const double ke
     }
     t[0] = x;
 }
-template <int G>
-__device__ __forceinline__ double group_min_dkey(double v) {
-#define FLS_DMIN_STEP(S)                                                                              \
-    {                                                                                                 \
-        const unsigned lo = dpp_pair_u32<S>((unsigned)__double2loint(v));                             \
-        const unsigned hi = dpp_pair_u32<S>((unsigned)__double2hiint(v));                             \
-        v = kmin_f64(v, __hiloint2double((int)hi, (int)lo));                                          \
-    }
-    FLS_DMIN_STEP(0)
-    if (G >= 4) FLS_DMIN_STEP(1)
-    if (G >= 8) FLS_DMIN_STEP(2)
-#undef FLS_DMIN_STEP
-    return v;
+// minimum over the four lanes of a query's group: two quad-permute exchanges
+template <int STEP>
+__device__ __forceinline__ double dpp_min_dkey(const double v) {
+    const unsigned lo = dpp_pair_u32<STEP>((unsigned)__double2loint(v));
+    const unsigned hi = dpp_pair_u32<STEP>((unsigned)__double2hiint(v));
+    return kmin_f64(v, __hiloint2double((int)hi, (int)lo));
 }
+__device__ __forceinline__ double group_min_dkey(const double v) { return dpp_min_dkey<1>(dpp_min_dkey<0>(v)); }
 
-// candidate index -> map slot as a compare / select chain on VALUES (written as a function of scalars: a lambda
-// capturing the offsets by reference made the compiler select between ADDRESSES and load through them)
-template <int R>
-__device__ __forceinline__ unsigned slot_select(const unsigned idx, const unsigned p1, const unsigned p2, const unsigned p3, const unsigned p4,
-                                                const unsigned o0, const unsigned o1, const unsigned o2, const unsigned o3, const unsigned o4) {
-    unsigned sel = R == 5 ? o4 : R == 4 ? o3 : R == 3 ? o2 : R == 2 ? o1 : o0;
-    if (R > 4) sel = idx < p4 ? o3 : sel;
-    if (R > 3) sel = idx < p3 ? o2 : sel;
-    if (R > 2) sel = idx < p2 ? o1 : sel;
-    if (R > 1) sel = idx < p1 ? o0 : sel;
-    return idx + sel;
-}
-
-// nearest_points_ rows: 9.2 MB per launch at the benchmark size, flushed from the write-back L2 at the kernel boundary
+// Rows form (nn_ids == nullptr, the only form before round 3): 9.2 MB of nearest_points_ rows per launch at the benchmark size,
+// flushed from the write-back L2 at the kernel boundary
 // (2.7 us of this kernel + 3.2 us of re-reads in the fit kernel, measured by removing the stores).  Nontemporal stores
 // measured -0.5 us per launch, -0.5 us per Match (inside the noise), write-through (sc1) stores were slower (18.6-21.2 us
 // per launch): the rows are plain stores.
@@ -162,7 +107,7 @@ __device__ __forceinline__ unsigned slot_select(const unsigned idx, const unsign
 //     The host drops the gate where 27 res^2 < 25, i.e. with a whole extra voxel per axis (3 res) for the float rounding of key and
 //     difference (at |key| near 2^20 one ulp of a coordinate is res / 8); the selection keys then stay finite doubles as with the gate.
 //   - 64-bit candidate addresses.  With slots x 16 bytes < 2^32 the four loads of a trip take a 32-bit byte offset from the uniform base.
-template <int G, bool COUNT, bool DENSE, bool FIRST, bool BAL = false, bool GEN = true>
+template <bool COUNT, bool DENSE, bool FIRST, bool GEN>
 __global__ void __launch_bounds__(256)
 ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
                 const GnState* __restrict__ st, const Pose16 T0, const DevGrid grid, const BrickDir bd,
@@ -172,8 +117,8 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
                 const int nn_prev /* FIRST: size of nearest_points_ before this Match; the grown tail starts empty (:257 resize) */,
                 float* __restrict__ dev_copy /* FIRST, may be null: sx / sy / sz point into the pinned staging buffer (host memory);
                                                 leave the device copy x[n] | y[n] | z[n] here for the launches that follow */) {
-    static_assert(G == 4 || G == 8, "group size");
-    constexpr int QPB = 256 / G;       // queries per workgroup
+    constexpr int G = 4;                 // lanes per query
+    constexpr int QPB = 256 / G;         // queries per workgroup
     constexpr int R = (19 + G - 1) / G;  // probe rounds per lane
     // XCD-aware block order: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, each with its own
     // 4 MiB L2.  Re-map so that XCD x walks CHUNKS of `chunk` consecutive workgroups (chunk * QPB consecutive points of
@@ -260,14 +205,7 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         const unsigned sub8 = 8u * (unsigned)sub;
         auto cell = [&](const int r, const unsigned pk4, unsigned& beg, unsigned& cnt) {
             const int k = sub + G * r;
-            int off;
-            if (G == 4) {
-                off = __builtin_amdgcn_sbfe((int)pk4, sub8, 8u);
-            } else {
-                int ox, oy, oz;
-                nearby18(k < 19 ? k : 0, ox, oy, oz);
-                off = (oz * kBrickStored + oy) * kBrickStored + ox;
-            }
+            const int off = __builtin_amdgcn_sbfe((int)pk4, sub8, 8u);
             const bool ok = have && k < 19;
             const uint2 e = bd.cells[cbase + (unsigned)off];  // (always inside the slab)
             beg = e.x;
@@ -275,25 +213,25 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
             if (COUNT && active && k < 19) { c_probes++; if (cnt) { c_hits++; c_cand += cnt; } }  // (a query beyond the key range probes 19 absent voxels)
         };
         cell(0, PK[0], b0, c0);
-        if (R > 1) cell(1, PK[1], b1, c1);
-        if (R > 2) cell(2, PK[2], b2, c2);
-        if (R > 3) cell(3, PK[3], b3, c3);
-        if (R > 4) cell(4, PK[4], b4, c4);
+        cell(1, PK[1], b1, c1);
+        cell(2, PK[2], b2, c2);
+        cell(3, PK[3], b3, c3);
+        cell(4, PK[4], b4, c4);
     } else {
         bool pv0 = false, pv1 = false, pv2 = false, pv3 = false, pv4 = false;
         unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0, k4 = 0;
         unsigned h0 = 0, h1 = 0, h2 = 0, h3 = 0, h4 = 0;
         HashEntry e0{kEmptyKey, 0u, 0u}, e1 = e0, e2 = e0, e3 = e0, e4 = e0;
         k0 = probe_key(0, pv0); e0 = first_load(pv0, k0, h0);
-        if (R > 1) { k1 = probe_key(1, pv1); e1 = first_load(pv1, k1, h1); }
-        if (R > 2) { k2 = probe_key(2, pv2); e2 = first_load(pv2, k2, h2); }
-        if (R > 3) { k3 = probe_key(3, pv3); e3 = first_load(pv3, k3, h3); }
-        if (R > 4) { k4 = probe_key(4, pv4); e4 = first_load(pv4, k4, h4); }
+        k1 = probe_key(1, pv1); e1 = first_load(pv1, k1, h1);
+        k2 = probe_key(2, pv2); e2 = first_load(pv2, k2, h2);
+        k3 = probe_key(3, pv3); e3 = first_load(pv3, k3, h3);
+        k4 = probe_key(4, pv4); e4 = first_load(pv4, k4, h4);
         resolve(pv0, k0, h0, e0, b0, c0);
-        if (R > 1) resolve(pv1, k1, h1, e1, b1, c1);
-        if (R > 2) resolve(pv2, k2, h2, e2, b2, c2);
-        if (R > 3) resolve(pv3, k3, h3, e3, b3, c3);
-        if (R > 4) resolve(pv4, k4, h4, e4, b4, c4);
+        resolve(pv1, k1, h1, e1, b1, c1);
+        resolve(pv2, k2, h2, e2, b2, c2);
+        resolve(pv3, k3, h3, e3, b3, c3);
+        resolve(pv4, k4, h4, e4, b4, c4);
         if (COUNT && active && !in_range) {  // (a query beyond the key range probes 19 absent voxels)
 #pragma unroll
             for (int r = 0; r < R; ++r) c_probes += sub + G * r < 19 ? 1u : 0u;
@@ -310,126 +248,105 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         if (GEN) return grid.pts[s];
         return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(grid.pts) + (s << 4));  // (32-bit byte offset, as reduce_partials_trip)
     };
-    // one flattened loop over this lane's <= R voxels: trip count = ceil(lane total / 4), not the sum of
-    // per-voxel maxima
-    const unsigned p1 = c0, p2 = p1 + c1, p3 = p2 + c2, p4 = p3 + c3, tot = p4 + c4;
-    // candidate index -> map slot, branch-free: slot = idx + (begin - prefix) of the voxel the index falls in
-    // (unsigned wrap-around is intended)
-    const unsigned o0 = b0, o1 = b1 - p1, o2 = b2 - p2, o3 = b3 - p3, o4 = b4 - p4;
-    auto slot_of = [=](const unsigned idx) -> unsigned { return slot_select<R>(idx, p1, p2, p3, p4, o0, o1, o2, o3, o4); };
-    if (BAL && G == 4) {
-        // Balanced split: the group's candidates (all hit voxels of the query, concatenated) are cut into four equal
-        // contiguous ranges, one per lane, instead of whole voxels per lane: a wave runs max-over-lanes trips of the
-        // loop below, and voxels hold 1..20+ points (4.7 trips of four candidates per wave before, 2.8 after).
-        // The hit voxels are compacted into a per-group LDS table {prefix end, begin - prefix start}; a lane walks
-        // its range through a two-entry window of that table (see the loop).
-        __shared__ __attribute__((aligned(16))) unsigned s_end[QPB][24];
-        __shared__ __attribute__((aligned(16))) unsigned s_off[QPB][24];
-        const int g = threadIdx.x / G;
-        const unsigned nz = (c0 ? 1u : 0u) + (c1 ? 1u : 0u) + (c2 ? 1u : 0u) + (c3 ? 1u : 0u) + (c4 ? 1u : 0u);
-        const unsigned packed = tot * 32u + nz;  // candidates (< 2^27) and hit voxels (<= 19 per group) of this lane
-        const unsigned t0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0x00, 0xf, 0xf, true);  // quad broadcasts
-        const unsigned t1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0x55, 0xf, 0xf, true);
-        const unsigned t2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0xAA, 0xf, 0xf, true);
-        const unsigned t3 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0xFF, 0xf, 0xf, true);
-        const unsigned before = (sub > 0 ? t0 : 0u) + (sub > 1 ? t1 : 0u) + (sub > 2 ? t2 : 0u), all = t0 + t1 + t2 + t3;
-        const unsigned TOT = all >> 5;
-        unsigned pos = before & 31u, run = before >> 5;
-        // every entry behind the last real one is a sentinel (the window looks one entry ahead, the start search
-        // four): the whole row is filled first, the real entries overwrite (LDS operations of a wave are in order)
-        {
-            uint2* const rowp = reinterpret_cast<uint2*>(&s_end[g][6 * sub]);
-            rowp[0] = make_uint2(~0u, ~0u); rowp[1] = make_uint2(~0u, ~0u); rowp[2] = make_uint2(~0u, ~0u);
-        }
-        // predicated, not branched: a missed probe writes its pair to a word of the lane's own behind the table (real entries: 0..18; the
-        // window reads k + 1 <= 19, the start search up to entry 18 + 4, so the s_end word is made a sentinel again after the last put)
-        const unsigned dmy = 20u + (unsigned)sub;
-        auto put = [&](const unsigned b, const unsigned c) {
-            const unsigned at = c ? pos : dmy;
-            s_off[g][at] = b - run;
-            run += c;
-            s_end[g][at] = run;
-            pos += c ? 1u : 0u;
-        };
-        put(b0, c0);
-        if (R > 1) put(b1, c1);
-        if (R > 2) put(b2, c2);
-        if (R > 3) put(b3, c3);
-        if (R > 4) put(b4, c4);
-        s_end[g][dmy] = ~0u;
-        // a group lives inside one wave and the LDS serves a wave's operations in order: no workgroup barrier, only a
-        // compiler-level ordering point between the table writes and the cross-lane reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const unsigned Q = (TOT + 3u) >> 2, a = sub * Q, e = a + Q < TOT ? a + Q : TOT;
-        // Start search: k = first table entry whose range reaches past a = number of entries that end at or before a.  The quad
-        // broadcasts already say which lane's entries hold candidate a: P_i = packed sum of the lanes before lane i = {candidates before
-        // lane i : entries before lane i}, and P_i <= 32 a + 31 <=> candidates before lane i <= a.  With j the last such lane, every entry
-        // before lane j's first one ends at or before a, lane j's own (at most five) are compared, and whatever follows them in the table
-        // (later lanes' entries, sentinels) ends past a.  Five compares in place of twenty.
-        const unsigned P2 = t0 + t1, P3 = P2 + t2, A32 = a * 32u + 31u;
-        unsigned ps = t0 <= A32 ? t0 : 0u;
-        ps = P2 <= A32 ? P2 : ps;
-        ps = P3 <= A32 ? P3 : ps;
-        unsigned k = ps & 31u;  // (<= 19: the five words read below stay inside the row)
-        {
-            const unsigned* const w = &s_end[g][k];
-            const unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-            k += (w0 <= a ? 1u : 0u) + (w1 <= a ? 1u : 0u) + (w2 <= a ? 1u : 0u) + (w3 <= a ? 1u : 0u) + (w4 <= a ? 1u : 0u);
-        }
-        // Two-run window: a trip resolves its four candidates against the run idx lies in (entry k: E(k-1) <= idx < E(k)) and the
-        // next one, and ends where the second run ends -- 2.2 % of the trips would reach into a third run (runs average 5.1 points),
-        // cutting them costs 0.8 % more trips and saves a five-entry select chain per candidate.  The candidates of [a, e) are still
-        // taken once each, only grouped differently: the same top-5 set.  (Behind the last run E1 is the sentinel: the trip ends at e.)
-        for (unsigned idx = a; idx < e;) {
-            const unsigned E0 = s_end[g][k], E1 = s_end[g][k + 1];
-            const unsigned O0 = s_off[g][k], O1 = s_off[g][k + 1];
-            const unsigned last = (E1 < e ? E1 : e) - 1;
-            const unsigned i1 = idx + 1, i2 = idx + 2, i3 = idx + 3;
-            const unsigned j1 = i1 < last ? i1 : last, j2 = i2 < last ? i2 : last, j3 = i3 < last ? i3 : last;
-            const unsigned s0 = idx + O0;
-            const unsigned s1 = j1 + (j1 < E0 ? O0 : O1);
-            const unsigned s2 = j2 + (j2 < E0 ? O0 : O1);
-            const unsigned s3 = j3 + (j3 < E0 ? O0 : O1);
-            const float4 q0 = map_pt(s0), q1 = map_pt(s1), q2 = map_pt(s2), q3 = map_pt(s3);
-            consider(q0, s0, true);
-            consider(q1, s1, i1 <= last);
-            consider(q2, s2, i2 <= last);
-            consider(q3, s3, i3 <= last);
-            idx = j3 + 1;  // min(idx + 4, end of the second run, e)
-            k += (E0 <= idx ? 1u : 0u) + (E1 <= idx ? 1u : 0u);  // (runs are never empty: E1 == idx puts idx into run k + 2)
-        }
-    } else
-    for (unsigned j = 0; j < tot; j += 4) {
-        const unsigned last = tot - 1;
-        const unsigned i1 = j + 1, i2 = j + 2, i3 = j + 3;
-        const unsigned s0 = slot_of(j), s1 = slot_of(i1 < last ? i1 : last), s2 = slot_of(i2 < last ? i2 : last),
-                       s3 = slot_of(i3 < last ? i3 : last);
-        const float4 p0 = map_pt(s0), p1 = map_pt(s1), p2 = map_pt(s2), p3 = map_pt(s3);
-        consider(p0, s0, true);
-        consider(p1, s1, i1 <= last);
-        consider(p2, s2, i2 <= last);
-        consider(p3, s3, i3 <= last);
+    const unsigned tot = c0 + c1 + c2 + c3 + c4;  // this lane's candidates
+    // Balanced split: the group's candidates (all hit voxels of the query, concatenated) are cut into four equal
+    // contiguous ranges, one per lane, instead of whole voxels per lane: a wave runs max-over-lanes trips of the
+    // loop below, and voxels hold 1..20+ points (4.7 trips of four candidates per wave before, 2.8 after).
+    // The hit voxels are compacted into a per-group LDS table {prefix end, begin - prefix start}; a lane walks
+    // its range through a two-entry window of that table (see the loop).
+    __shared__ __attribute__((aligned(16))) unsigned s_end[QPB][24];
+    __shared__ __attribute__((aligned(16))) unsigned s_off[QPB][24];
+    const int g = threadIdx.x / G;
+    const unsigned nz = (c0 ? 1u : 0u) + (c1 ? 1u : 0u) + (c2 ? 1u : 0u) + (c3 ? 1u : 0u) + (c4 ? 1u : 0u);
+    const unsigned packed = tot * 32u + nz;  // candidates (< 2^27) and hit voxels (<= 19 per group) of this lane
+    const unsigned t0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0x00, 0xf, 0xf, true);  // quad broadcasts
+    const unsigned t1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0x55, 0xf, 0xf, true);
+    const unsigned t2 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0xAA, 0xf, 0xf, true);
+    const unsigned t3 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0xFF, 0xf, 0xf, true);
+    const unsigned before = (sub > 0 ? t0 : 0u) + (sub > 1 ? t1 : 0u) + (sub > 2 ? t2 : 0u), all = t0 + t1 + t2 + t3;
+    const unsigned TOT = all >> 5;
+    unsigned pos = before & 31u, run = before >> 5;
+    // every entry behind the last real one is a sentinel (the window looks one entry ahead, the start search
+    // four): the whole row is filled first, the real entries overwrite (LDS operations of a wave are in order)
+    {
+        uint2* const rowp = reinterpret_cast<uint2*>(&s_end[g][6 * sub]);
+        rowp[0] = make_uint2(~0u, ~0u); rowp[1] = make_uint2(~0u, ~0u); rowp[2] = make_uint2(~0u, ~0u);
     }
-    // phase 2: merge the G private lists: five rounds of group-min + pop (keys are unique -- the slot is the low
+    // predicated, not branched: a missed probe writes its pair to a word of the lane's own behind the table (real entries: 0..18; the
+    // window reads k + 1 <= 19, the start search up to entry 18 + 4, so the s_end word is made a sentinel again after the last put)
+    const unsigned dmy = 20u + (unsigned)sub;
+    auto put = [&](const unsigned b, const unsigned c) {
+        const unsigned at = c ? pos : dmy;
+        s_off[g][at] = b - run;
+        run += c;
+        s_end[g][at] = run;
+        pos += c ? 1u : 0u;
+    };
+    put(b0, c0);
+    put(b1, c1);
+    put(b2, c2);
+    put(b3, c3);
+    put(b4, c4);
+    s_end[g][dmy] = ~0u;
+    // a group lives inside one wave and the LDS serves a wave's operations in order: no workgroup barrier, only a
+    // compiler-level ordering point between the table writes and the cross-lane reads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const unsigned Q = (TOT + 3u) >> 2, a = sub * Q, e = a + Q < TOT ? a + Q : TOT;
+    // Start search: k = first table entry whose range reaches past a = number of entries that end at or before a.  The quad
+    // broadcasts already say which lane's entries hold candidate a: P_i = packed sum of the lanes before lane i = {candidates before
+    // lane i : entries before lane i}, and P_i <= 32 a + 31 <=> candidates before lane i <= a.  With j the last such lane, every entry
+    // before lane j's first one ends at or before a, lane j's own (at most five) are compared, and whatever follows them in the table
+    // (later lanes' entries, sentinels) ends past a.  Five compares in place of twenty.
+    const unsigned P2 = t0 + t1, P3 = P2 + t2, A32 = a * 32u + 31u;
+    unsigned ps = t0 <= A32 ? t0 : 0u;
+    ps = P2 <= A32 ? P2 : ps;
+    ps = P3 <= A32 ? P3 : ps;
+    unsigned k = ps & 31u;  // (<= 19: the five words read below stay inside the row)
+    {
+        const unsigned* const w = &s_end[g][k];
+        const unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+        k += (w0 <= a ? 1u : 0u) + (w1 <= a ? 1u : 0u) + (w2 <= a ? 1u : 0u) + (w3 <= a ? 1u : 0u) + (w4 <= a ? 1u : 0u);
+    }
+    // Two-run window: a trip resolves its four candidates against the run idx lies in (entry k: E(k-1) <= idx < E(k)) and the
+    // next one, and ends where the second run ends -- 2.2 % of the trips would reach into a third run (runs average 5.1 points),
+    // cutting them costs 0.8 % more trips and saves a five-entry select chain per candidate.  The candidates of [a, e) are still
+    // taken once each, only grouped differently: the same top-5 set.  (Behind the last run E1 is the sentinel: the trip ends at e.)
+    for (unsigned idx = a; idx < e;) {
+        const unsigned E0 = s_end[g][k], E1 = s_end[g][k + 1];
+        const unsigned O0 = s_off[g][k], O1 = s_off[g][k + 1];
+        const unsigned last = (E1 < e ? E1 : e) - 1;
+        const unsigned i1 = idx + 1, i2 = idx + 2, i3 = idx + 3;
+        const unsigned j1 = i1 < last ? i1 : last, j2 = i2 < last ? i2 : last, j3 = i3 < last ? i3 : last;
+        const unsigned s0 = idx + O0;
+        const unsigned s1 = j1 + (j1 < E0 ? O0 : O1);
+        const unsigned s2 = j2 + (j2 < E0 ? O0 : O1);
+        const unsigned s3 = j3 + (j3 < E0 ? O0 : O1);
+        const float4 q0 = map_pt(s0), q1 = map_pt(s1), q2 = map_pt(s2), q3 = map_pt(s3);
+        consider(q0, s0, true);
+        consider(q1, s1, i1 <= last);
+        consider(q2, s2, i2 <= last);
+        consider(q3, s3, i3 <= last);
+        idx = j3 + 1;  // min(idx + 4, end of the second run, e)
+        k += (E0 <= idx ? 1u : 0u) + (E1 <= idx ? 1u : 0u);  // (runs are never empty: E1 == idx puts idx into run k + 2)
+    }
+    // phase 2: merge the four private lists: five rounds of group-min + pop (keys are unique -- the slot is the low
     // word -- so exactly one lane pops per round); the neighbour count is the number of valid minima
-    const double m0 = group_min_dkey<G>(t5[0]);
+    const double m0 = group_min_dkey(t5[0]);
     if (dkey_valid(m0)) {  // uniform within the group: at least one candidate (else nothing is written, ivox_map.cpp:21-23)
         int cnt = 0;
-        double mine = kNone;  // G == 8: the j-th smallest key lands in lane sub == j
         unsigned sid[5] = {~0u, ~0u, ~0u, ~0u, ~0u};
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
-            const double m = j == 0 ? m0 : group_min_dkey<G>(t5[0]);
+            const double m = j == 0 ? m0 : group_min_dkey(t5[0]);
             const bool mv = dkey_valid(m);
             cnt += mv ? 1 : 0;
             if (mv && __double_as_longlong(t5[0]) == __double_as_longlong(m)) {
                 t5[0] = t5[1]; t5[1] = t5[2]; t5[2] = t5[3]; t5[3] = t5[4]; t5[4] = kNone;
             }
-            if (G >= 8) { if (sub == j) mine = m; }
-            else if (nn_ids) sid[j] = mv ? dkey_slot(m) : ~0u;
-            else if (sub == 0 && active) {  // G == 4, rows form: lane 0 writes all five
+            if (nn_ids) sid[j] = mv ? dkey_slot(m) : ~0u;
+            else if (sub == 0 && active) {  // rows form: lane 0 writes all five
                 nn_pts[(size_t)q * 5 + j] = mv ? grid.pts[dkey_slot(m)] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
             }
         }
@@ -439,15 +356,12 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
         // (0x80 = rows): a point without candidates keeps its previous list in whatever form it was (Q15); the lists are turned into
         // rows before anything moves map slots (matcher_p2plane_ivox.hpp::ensure_nn_rows).
         if (nn_ids) {
-            if (G >= 8) { if (sub < 5 && active) nn_ids[(size_t)q * 8 + sub] = dkey_valid(mine) ? dkey_slot(mine) : ~0u; }
-            else if (sub == 0 && active) {
+            if (sub == 0 && active) {
                 *reinterpret_cast<uint4*>(nn_ids + (size_t)q * 8) = make_uint4(sid[0], sid[1], sid[2], sid[3]);
                 nn_ids[(size_t)q * 8 + 4] = sid[4];
             }
             if (sub == 0 && active) nn_cnt[q] = (unsigned char)cnt;
         } else {
-            if (G >= 8 && sub < 5 && active)
-                nn_pts[(size_t)q * 5 + sub] = dkey_valid(mine) ? grid.pts[dkey_slot(mine)] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
             if (sub == 0 && active) nn_cnt[q] = (unsigned char)(cnt | 0x80);
         }
     }

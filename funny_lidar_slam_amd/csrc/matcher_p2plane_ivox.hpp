@@ -500,9 +500,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // e0 / e1 (profiling only): start / stop events attached to the kernel's own dispatch packet (hipExtLaunchKernelGGL),
     // i.e. the kernel's execution time as a kernel trace sees it -- a hipEventRecord bracket also times the dispatch of
     // the kernel between its two marker packets (about 3 us more on an 18 us kernel)
-    // (4 lanes per query with the balanced candidate split: ivox_knn_kernel<4, ..., true>)
+    // (4 lanes per query: 64 queries per 256-thread workgroup)
     void launch_knn(const size_t n, const int first, const Pose16& T0, const DevGrid& g, const BrickDir& win, hipEvent_t e0, hipEvent_t e1) {
-        constexpr int G = 4;
         // first launch of a Match whose scan is still in the staging buffer: read it there, write the device copy
         const bool from_host = first && scan_in_staging;
         const float* const hx = from_host ? scan.stage_dev() : nullptr;
@@ -510,13 +509,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         const float* const src_y = from_host ? hx + n : (const float*)scan.y.p;
         const float* const src_z = from_host ? hx + 2 * n : (const float*)scan.z.p;
         float* const dev_copy = from_host ? scan.xyz.p : nullptr;
-        const size_t nblk = (n * G + 255) / 256, gran = size_t(8) * size_t(kIvoxXcdChunk);
+        const size_t nblk = (n + 63) / 64, gran = size_t(8) * size_t(kIvoxXcdChunk);
         const dim3 grid(unsigned((nblk + gran - 1) / gran * gran));  // multiple of 8 * chunk: the XCD re-map is a bijection
         // the kernel's general form (GEN) only where it can matter: voxels so large that a candidate of the 19 probed voxels could lie beyond
         // max_range (3 res per axis, one voxel more than the geometry allows, reaches 5 m), or a point array of 4 GiB and more
         const bool general = !(27.0f * ivox.resolution * ivox.resolution < 25.0f) || size_t(g.n_pts) > (size_t(1) << 28);
 #define FLS_KNN_G(C, D, F, GEN)                                                                                                      \
-    hipExtLaunchKernelGGL((ivox_knn_kernel<G, C, D, F, true, GEN>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n), \
+    hipExtLaunchKernelGGL((ivox_knn_kernel<C, D, F, GEN>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n),       \
                           (const GnState*)d_state.p, T0, g, win, ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, kIvoxXcdChunk, \
                           d_nn_ids.p, nn_prev, dev_copy)
 #define FLS_KNN_L(C, D, F) do { if (general) FLS_KNN_G(C, D, F, true); else FLS_KNN_G(C, D, F, false); } while (0)

@@ -8,8 +8,9 @@ vals = collections.defaultdict(list)
 for f in sorted(glob.glob(os.path.join(d, "pmc*_counter_collection.csv"))):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        if "ivox_knn_kernel<4, false" not in k and "ivox_knn_kernelILi4ELb0" not in k:
-            continue  # (the counting variant <4, true, ...> runs once, outside the timed region)
+        # the product instantiations <COUNT = false, ...>; CSVs from before the group size left the template name them <4, false, ...>
+        if not any(t in k for t in ("ivox_knn_kernel<false", "ivox_knn_kernelILb0E", "ivox_knn_kernel<4, false", "ivox_knn_kernelILi4ELb0")):
+            continue  # (the counting variant <true, ...> runs once, outside the timed region)
         vals[r["Counter_Name"]].append(float(r["Counter_Value"]))
 
 
@@ -23,7 +24,7 @@ def active_mean(name):
 
 
 fetch, write = active_mean("FETCH_SIZE"), active_mean("WRITE_SIZE")
-out = {"kernel": "ivox_knn_kernel<4,false,true,*,true>", "source": "rocprofv3 --kernel-trace --pmc <one group per pass>, python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-extras (tools/prof_round4.sh, profiles/r04_d_pmc_summary.txt)",
+out = {"kernel": "ivox_knn_kernel<false,true,*,*>", "source": "rocprofv3 --kernel-trace --pmc <one group per pass>, python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batch --no-extras (tools/prof_round4.sh, profiles/r04_d_pmc_summary.txt)",
        "fetch_size_kb_per_launch_raw": fetch, "write_size_kb_per_launch_raw": write, "fetch_correction": 2.0,
        "hbm_bytes_per_launch": (2.0 * fetch + write) * 1024.0 if fetch is not None and write is not None else None}
 rd = active_mean("TCP_TCC_READ_REQ_sum")
