@@ -37,6 +37,9 @@ INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_prepr
 KEYFRAMES_SYMBOLS = ["fls_keyframes_revision", "fls_keyframes_create", "fls_keyframes_destroy", "fls_keyframes_add", "fls_keyframes_add_preprocessed",
                      "fls_keyframes_count", "fls_keyframes_get", "fls_keyframes_merge", "fls_keyframes_loop_match", "fls_keyframes_stat"]
 
+# every symbol include/fls_batch.h declares (FLS_BATCH_REVISION 1)
+BATCH_SYMBOLS = ["fls_batch_revision", "fls_match_batch_fused", "fls_batch_stat"]
+
 # every symbol include/fls_debug_linalg.h declares (FLS_DEBUG_LINALG_REVISION 1): test hooks of csrc/linalg_dev.hpp / wave_solve.hpp
 DEBUG_LINALG_SYMBOLS = ["fls_debug_linalg_revision", "fls_debug_plane_fit_5x3", "fls_debug_svd3", "fls_debug_lu6", "fls_debug_so3", "fls_debug_wave_sum"]
 
@@ -332,6 +335,12 @@ def lib():
         L.fls_keyframes_loop_match.argtypes = [hp, ip, dp, C.c_size_t, ip, dp, C.c_size_t, dp, fp, C.c_void_p]
         L.fls_keyframes_stat.restype = C.c_size_t
         L.fls_keyframes_stat.argtypes = [hp, C.c_int]
+        L.fls_batch_revision.restype = C.c_int
+        L.fls_batch_revision.argtypes = []
+        L.fls_match_batch_fused.restype = C.c_int
+        L.fls_match_batch_fused.argtypes = L.fls_match_batch.argtypes
+        L.fls_batch_stat.restype = C.c_size_t
+        L.fls_batch_stat.argtypes = [hp, C.c_int]
         L.fls_debug_linalg_revision.restype = C.c_int
         L.fls_debug_linalg_revision.argtypes = []
         L.fls_debug_plane_fit_5x3.restype = C.c_int

@@ -450,18 +450,42 @@ __device__ __forceinline__ void icp_point_rows(const double (&T)[16], const floa
 // IcpOptimized correspondence search AND fit in one launch: the 1-NN of a query ends up in lane 0 of its 8-lane group, which
 // forms the point's terms at once (no neighbour arrays through memory, one launch per iteration fewer); every workgroup of the
 // search grid writes one partial row (rows of idle workgroups are zero), gn_solve_lu_kernel sums them in row order.
-__global__ void __launch_bounds__(256)
-icp_knn_fit_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
-                   GnState* __restrict__ st, const int first, const Pose16 T0, const CellGridDev cg, const float gate, const double max_corr /* squared */,
-                   int* __restrict__ nn_id, unsigned char* __restrict__ eff, double* __restrict__ partials,
-                   unsigned* __restrict__ ticket /* nullptr: the tail runs as its own launch */, const int shards, const LuTailArgs tail) {
+// The body of workgroup blockIdx.x of ONE registration whose search grid has `nrows` workgroups: icp_knn_fit_kernel is that registration alone
+// (nrows = LaunchBlocksX, the launch's gridDim.x), icp_knn_fit_jobs_kernel runs one per blockIdx.y (nrows = the job's own count).  The LDS is the calling kernel's (declared there under the names the
+// single-job kernel has always used, so that kernel keeps its LDS layout).
+struct Pose16Ref {
+    const Pose16* p;
+    __device__ __forceinline__ operator const Pose16&() const { return *p; }
+};
+#if FLS_FIT_MFMA
+#define FLS_ICP_FIT_SMEM_PARAMS double (&wsum)[4][32], double (&mfma_tile)[4][512], unsigned& s_ticket, LuTailSmem& sm
+#define FLS_ICP_FIT_SMEM_DECL                                                 \
+    __shared__ double wsum[4][32];                                            \
+    __shared__ __attribute__((aligned(64))) double mfma_tile[4][512];         \
+    __shared__ unsigned s_ticket;                                             \
+    __shared__ LuTailSmem sm
+#define FLS_ICP_FIT_SMEM_ARGS wsum, mfma_tile, s_ticket, sm
+#else
+#define FLS_ICP_FIT_SMEM_PARAMS double (&wsum)[4][32], unsigned& s_ticket, LuTailSmem& sm
+#define FLS_ICP_FIT_SMEM_DECL                                                 \
+    __shared__ double wsum[4][32];                                            \
+    __shared__ unsigned s_ticket;                                             \
+    __shared__ LuTailSmem sm
+#define FLS_ICP_FIT_SMEM_ARGS wsum, s_ticket, sm
+#endif
+template <class N, class P>
+__device__ __forceinline__ void
+icp_knn_fit_body(FLS_ICP_FIT_SMEM_PARAMS, const N nrows, const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
+                 GnState* __restrict__ st, const int first, const P T0p /* Pose16, or Pose16Ref: the pose stays where it is */, const CellGridDev cg, const float gate,
+                 const double max_corr /* squared */, int* __restrict__ nn_id, unsigned char* __restrict__ eff, double* __restrict__ partials,
+                 unsigned* __restrict__ ticket /* nullptr: the tail runs as its own launch */, const int shards, const LuTailArgs tail) {
+    const Pose16& T0 = T0p;
 #ifdef FLS_TIMING
     const long long t_begin = (long long)__builtin_readcyclecounter();
 #endif
     const int done = first ? 0 : st->done;
     const int it = first ? 0 : st->iter;
-    if (done) return;  // uniform over the launch
-    __shared__ double wsum[4][32];
+    if (done) return;  // uniform over the registration's workgroups
     GridKnnLane r;
     r.key = ~0ull; r.slot = 0u; r.found = 0; r.q = -1; r.kth = INFINITY;
     r.bx = r.by = r.bz = r.px = r.py = r.pz = 0.f;
@@ -493,7 +517,6 @@ icp_knn_fit_kernel(const float* __restrict__ sx, const float* __restrict__ sy, c
             contrib = true;
         }
     }
-    __shared__ __attribute__((aligned(64))) double mfma_tile[4][512];
     reduce_rank1x3_mfma_and_store(contrib, Jr, er, row, &mfma_tile[threadIdx.x >> 6][0]);
     const double sr = wave_sum_dpp(res);
     if (lane == 63) row[27] = sr;
@@ -528,16 +551,56 @@ icp_knn_fit_kernel(const float* __restrict__ sx, const float* __restrict__ sy, c
     const long long t_sync = (long long)__builtin_readcyclecounter();  // (the workgroup's slowest wave has arrived)
 #endif
     const double v = threadIdx.x < 29 ? ((wsum[0][threadIdx.x] + wsum[1][threadIdx.x]) + wsum[2][threadIdx.x]) + wsum[3][threadIdx.x] : 0.0;
-    __shared__ unsigned s_ticket;
-    __shared__ LuTailSmem sm;
-    if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, s_ticket)) { store_ids(); return; }
+    if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, nrows, s_ticket)) { store_ids(); return; }
 #ifdef FLS_TIMING
     if (threadIdx.x == 0) { st->dbg[0] = t_begin; st->dbg[12] = t_knn; st->dbg[13] = t_red; st->dbg[14] = t_sync; }
 #endif
     FLS_STAMP(1);
-    lu_tail<256, true>(st, sm, partials, (int)gridDim.x, tail, T, it);
+    lu_tail<256, true>(st, sm, partials, (int)(unsigned)nrows, tail, T, it);
     store_ids();
 }
+
+__global__ void __launch_bounds__(256)
+icp_knn_fit_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
+                   GnState* __restrict__ st, const int first, const Pose16 T0, const CellGridDev cg, const float gate, const double max_corr /* squared */,
+                   int* __restrict__ nn_id, unsigned char* __restrict__ eff, double* __restrict__ partials,
+                   unsigned* __restrict__ ticket /* nullptr: the tail runs as its own launch */, const int shards, const LuTailArgs tail) {
+    FLS_ICP_FIT_SMEM_DECL;
+    icp_knn_fit_body(FLS_ICP_FIT_SMEM_ARGS, LaunchBlocksX{}, sx, sy, sz, n, st, first, T0, cg, gate, max_corr, nn_id, eff, partials, ticket, shards, tail);
+}
+
+// The same iteration for a GROUP of independent registrations against one map in one launch (fls_match_batch_fused): grid (rows_max, G), blockIdx.y
+// the job slot, blockIdx.x the workgroup of that job's own search grid of `rows` = knn_grid_blocks(n) workgroups (rows_max = the group's largest;
+// every count is a multiple of 64, so the XCD re-map of grid_knn_body is a bijection per job).  A workgroup past its job's rows leaves before any
+// barrier, row or ticket; a job that has stopped leaves at once; every other workgroup is icp_knn_fit_body for its job, so the job's rows, their order
+// in the tail's sum and the ticket protocol are the single-job launch's, and the last arriver OF THE JOB solves and publishes the job's mailbox: the
+// tails of the group's jobs run side by side in different workgroups, behind each other's searches.
+// The job entries sit in a device table read through a uniform index (scalar loads): sixteen entries are 3.5 KB, most of the 4 KB a launch can carry as
+// arguments next to the grid descriptor, and a table is written once per group while arguments would travel with every launch.
+struct IcpJob {
+    const float *sx, *sy, *sz;  // the job's filtered scan
+    int n, rows;                // points; workgroups of its search grid (knn_grid_blocks(n))
+    GnState* st;
+    int* nn_id;
+    unsigned char* eff;
+    double* partials;           // [rows][kPartialStride]
+    unsigned* ticket;           // kTicketWords words of the job's own, zero between launches
+    Mailbox* mb;
+    unsigned launch_word, pad;
+    Pose16 T0;                  // the initial pose (read by the group's first launch)
+};
+__global__ void __launch_bounds__(256)
+icp_knn_fit_jobs_kernel(const IcpJob* __restrict__ jobs, const int first, const CellGridDev cg, const float gate, const double max_corr /* squared */,
+                        const int shards, const double rot_thr, const double pos_thr) {
+    const IcpJob& j = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= j.rows) return;
+    FLS_ICP_FIT_SMEM_DECL;
+    const LuTailArgs tail{0, rot_thr, pos_thr, 0, j.mb, j.launch_word};
+    icp_knn_fit_body(FLS_ICP_FIT_SMEM_ARGS, (unsigned)j.rows, j.sx, j.sy, j.sz, j.n, j.st, first, Pose16Ref{&j.T0}, cg, gate, max_corr, j.nn_id, j.eff, j.partials, j.ticket, shards, tail);
+}
+#undef FLS_ICP_FIT_SMEM_PARAMS
+#undef FLS_ICP_FIT_SMEM_DECL
+#undef FLS_ICP_FIT_SMEM_ARGS
 
 // what the last workgroup of a fused fit + Gauss-Newton launch needs (LoamFull's dual launch)
 struct LoamFusedTail {
@@ -635,7 +698,7 @@ feature_fit_body(const int bid, const float* __restrict__ sx, const float* __res
                            __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ft->ticket, ft->shards);
+    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ft->ticket, ft->shards, LaunchBlocksX{});
     __syncthreads();
     if (!s_ticket) { store_outputs(); return; }
     GnState* const stw = const_cast<GnState*>(st);

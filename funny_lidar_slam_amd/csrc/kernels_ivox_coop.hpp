@@ -494,7 +494,7 @@ p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__
 #endif
     __syncthreads();
     // sharded fan-in (kernels_p2plane.hpp::fanin_last_arriver): which workgroup arrives last
-    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards);
+    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards, LaunchBlocksX{});
     __syncthreads();
     if (!s_ticket) { store_point(); return; }
     // ---- last workgroup: Gauss-Newton tail (reads the rows with sc1 loads: no acquire fence either) ----

@@ -610,7 +610,7 @@ ndt_lanes_kernel(const float* __restrict__ sx, const float* __restrict__ sy, con
     // fused Gauss-Newton tail (round 3): the row goes out write-through, the last workgroup to arrive solves and publishes
     __shared__ unsigned s_ticket;
     __shared__ LuTailSmem sm;
-    if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, s_ticket)) return;
+    if (!publish_row_and_arrive(v, threadIdx.x < 29, partials, ticket, shards, LaunchBlocksX{}, s_ticket)) return;
     double Tl[16];  // (the pose parked in LDS at the start: sixteen doubles kept in registers across the per-point part cost the kernel its fourth wave per SIMD)
 #pragma unroll
     for (int q = 0; q < 16; ++q) Tl[q] = s_pose[q];

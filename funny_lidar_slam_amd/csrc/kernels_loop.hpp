@@ -70,7 +70,7 @@ __device__ __forceinline__ void loop_block_reduce(const double (&acc)[NV], const
     if (!out.ticket) return;  // (no ticket: the rows only)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) s_last = fanin_last_arriver(out.ticket, 8);
+    if (threadIdx.x == 0) s_last = fanin_last_arriver(out.ticket, 8, LaunchBlocksX{});
     __syncthreads();
     if (!s_last || threadIdx.x >= 64) return;
     const int c = threadIdx.x, nrows = (int)gridDim.x;

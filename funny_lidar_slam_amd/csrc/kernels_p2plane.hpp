@@ -280,15 +280,22 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ parti
 // normally runs on -- a speed matter only, every atomic is agent scope) take their arrivals in parallel, the last arriver of a shard
 // moves on to the top counter, the last of those is THE last.  Counters sit 128 bytes apart and are reset by their last arriver, so
 // they are zero at every launch.  Call with one thread after the workgroup's row is published and drained; kTicketWords words.
+// `nblocks`: how many workgroups (blockIdx.x = 0 .. nblocks - 1) arrive on these words -- the launch's gridDim.x (LaunchBlocksX), or a job's own row
+// count (unsigned) where one launch serves several jobs, each with ticket words of its own (icp_knn_fit_jobs_kernel).
+// (LaunchBlocksX is gridDim.x read where it is used: the kernels that pass it keep the machine code they had when these functions read gridDim.x themselves.)
+struct LaunchBlocksX {
+    __device__ __forceinline__ operator unsigned() const { return gridDim.x; }
+};
 constexpr int kTicketWords = 32 * 10;  // [0] single counter (shards <= 1) | [32 (1 + s)] shard s | [32 * 9] top counter
 constexpr int kTicketShards = 8;       // the shard count every host launch passes
-__device__ __forceinline__ unsigned fanin_last_arriver(unsigned* __restrict__ ticket, const int shards) {
+template <class N>
+__device__ __forceinline__ unsigned fanin_last_arriver(unsigned* __restrict__ ticket, const int shards, const N nblocks) {
     if (shards <= 1) {
-        const unsigned last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+        const unsigned last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1 ? 1u : 0u;
         if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return last;
     }
-    const unsigned sh = blockIdx.x & 7u, nsh = (gridDim.x - sh + 7u) >> 3, ntop = gridDim.x < 8u ? gridDim.x : 8u;
+    const unsigned sh = blockIdx.x & 7u, nsh = (nblocks - sh + 7u) >> 3, ntop = nblocks < 8u ? nblocks : 8u;
     unsigned* const cs = ticket + 32u * (1u + sh);
     unsigned* const ct = ticket + 32u * 9u;
     if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nsh - 1u) return 0u;
@@ -298,14 +305,15 @@ __device__ __forceinline__ unsigned fanin_last_arriver(unsigned* __restrict__ ti
     return 1u;
 }
 // publish one partial row write-through (sc1) + drain + ticket: returns (uniformly over the workgroup) whether this workgroup is the last
+template <class N>
 __device__ __forceinline__ bool publish_row_and_arrive(const double v, const bool has_value, double* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                       const int shards, unsigned& s_ticket) {
+                                                       const int shards, const N nblocks, unsigned& s_ticket) {
     if (has_value)
         __hip_atomic_store((unsigned long long*)partials + (size_t)blockIdx.x * kPartialStride + threadIdx.x, (unsigned long long)__double_as_longlong(v),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards);
+    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards, nblocks);
     __syncthreads();
     return s_ticket != 0u;
 }

@@ -97,6 +97,16 @@ struct fls_matcher {
     virtual std::unique_ptr<fls_matcher> clone_for_lane() { return nullptr; }  // same kind, borrowing this handle's map
     virtual fls_status prepare_batch() { return FLS_OK; }                     // map image current and complete on the device
     virtual void tune_lane(fls_matcher&) {}                                    // copy run-time switches to a lane
+    // at least `want` lane clones, if they can be set up; returns how many of `want` exist
+    size_t ensure_lanes(size_t want) {
+        while (lanes.size() < want) {
+            std::unique_ptr<fls_matcher> q = clone_for_lane();
+            if (!q) break;
+            q->is_lane = true;
+            lanes.push_back(std::move(q));
+        }
+        return std::min(want, lanes.size());
+    }
     fls_status match_batch(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const* s1, const size_t* n1, int stride,
                            double* T, fls_stats* st, int32_t* status, int n_lanes) {
         if (is_lane) return FLS_ERR_STATE;
@@ -107,14 +117,8 @@ struct fls_matcher {
         // belongs to the SLAM thread's next fls_match.  lanes <= 1 (or a single job) = one lane clone, back to back.
         const fls_status prc = prepare_batch();
         if (prc != FLS_OK) return prc;
-        while (lanes.size() < L) {
-            std::unique_ptr<fls_matcher> q = clone_for_lane();
-            if (!q) break;
-            q->is_lane = true;
-            lanes.push_back(std::move(q));
-        }
-        if (lanes.empty()) return FLS_ERR_NOMEM;  // the clone could not be set up
-        L = std::min(L, lanes.size());
+        L = ensure_lanes(L);
+        if (L == 0) return FLS_ERR_NOMEM;  // the clone could not be set up
         std::vector<fls_status> lane_rc(L, FLS_OK);
         std::vector<std::thread> th;
         struct JoinAll {  // a joinable std::thread must never be destroyed: also when starting a later lane throws
@@ -148,6 +152,17 @@ struct fls_matcher {
         for (auto& t : th) t.join();  // (join_all is the exception path)
         for (const fls_status rc : lane_rc) if (rc < 0) return rc;
         return FLS_OK;
+    }
+
+    // fls_match_batch_fused (include/fls_batch.h): the same jobs, but the iteration launches of up to n_slots jobs are SHARED (one launch per
+    // iteration for the whole group; slots = the lane clones above).  A kind without that form runs the jobs as match_batch does, on n_slots lanes.
+    // fls_batch_stat: [0] shared iteration launches queued, [1] jobs that ran in shared launches, [2] jobs that took the per-lane path, [3] groups
+    // (since the handle was created)
+    size_t batch_counters[4] = {0, 0, 0, 0};
+    virtual fls_status match_batch_fused(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const* s1, const size_t* n1, int stride,
+                                         double* T, fls_stats* st, int32_t* status, int n_slots) {
+        if (!is_lane) batch_counters[2] += n_jobs;
+        return match_batch(n_jobs, s0, n0, s1, n1, stride, T, st, status, n_slots);
     }
 
     void init_common() {

@@ -82,7 +82,15 @@ struct IcpMatcher final : fls_matcher {
         have_final = false;
         return FLS_OK;
     }
-    fls_status match_resident(double* T, int update_map, fls_stats* out) override {
+    // One Match in three parts -- prepare (checks, the source filter, buffers), launch (the iteration launches and the wait for the mailbox), finish
+    // (the epilogue) -- so that a group of batch jobs can share the middle part (match_batch_fused) around the same prepare and finish.
+    struct MatchPlan {
+        size_t n = 0;       // filtered source points
+        unsigned rows = 0;  // workgroups of the search grid = partial rows
+        CellGridDev cg{};
+        Pose16 T0{};
+    };
+    fls_status match_prepare(const double* T, MatchPlan& m) {
         if (raw_n <= 10) return FLS_ERR_INVALID;  // CHECK_GT(ordered_cloud_.size(), 10u) :55
         if (src_filter.raw_pending) src_filter.refilter(stream, scan, source);  // :57, on the resident raw scan
         if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
@@ -91,12 +99,19 @@ struct IcpMatcher final : fls_matcher {
         stats.n_source = int(n);
         d_nn_id.reserve(std::max<size_t>(n, 1));
         d_eff.reserve(std::max<size_t>(n, 1));
-        const CellGridDev cg = cell_dev(owner ? owner->map.grid : map.grid);
-        const dim3 knn_grid_dim(knn_grid_blocks(n));
-        d_partials_b.reserve(size_t(std::max(knn_grid_dim.x, 1u)) * kPartialStride);
-        Pose16 T0;
-        std::memcpy(T0.m, T, sizeof(T0.m));
-        const unsigned word = run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
+        m.n = n;
+        m.cg = cell_dev(owner ? owner->map.grid : map.grid);
+        m.rows = knn_grid_blocks(n);
+        d_partials_b.reserve(size_t(std::max(m.rows, 1u)) * kPartialStride);
+        std::memcpy(m.T0.m, T, sizeof(m.T0.m));
+        return FLS_OK;
+    }
+    unsigned match_launch(const MatchPlan& m) {
+        const size_t n = m.n;
+        const dim3 knn_grid_dim(m.rows);
+        const CellGridDev& cg = m.cg;
+        const Pose16& T0 = m.T0;
+        return run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it], stream));
             // search + fit in one launch (one partial row per workgroup of the search grid) and the Gauss-Newton tail in its last
             // workgroup: one launch per iteration
@@ -106,6 +121,8 @@ struct IcpMatcher final : fls_matcher {
                                kTicketShards, tail);
             if (profiling) FLS_HIP(hipEventRecord(ev[2 * it + 1], stream));
         });
+    }
+    fls_status match_finish(double* T, unsigned word, int update_map, fls_stats* out) {
         const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(final_T, mb.T, sizeof(final_T));
@@ -123,6 +140,189 @@ struct IcpMatcher final : fls_matcher {
         }
         if (out) *out = stats;
         return rc;
+    }
+    fls_status match_resident(double* T, int update_map, fls_stats* out) override {
+        MatchPlan m;
+        const fls_status prc = match_prepare(T, m);
+        if (prc != FLS_OK) return prc;
+        return match_finish(T, match_launch(m), update_map, out);
+    }
+
+    // ---- fls_match_batch_fused: groups of up to n_slots jobs share one icp_knn_fit_jobs_kernel launch per iteration ----
+    // Slots are the lane clones.  Per group: every slot uploads and filters its job on its own stream and its own host thread (the filters are
+    // latency chains with a host wait each: they overlap), records an event, and the batch stream, behind those events, carries the group's iteration
+    // launches, chunked as in run_mailbox_loop; the host waits on all the group's mailboxes.  Prepare and finish are the single-job path's.
+    // With more than one group there are two sets of slots: the next group's filters run while this group iterates.
+    hipStream_t batch_stream = nullptr;
+    hipEvent_t batch_tail_ev[2] = {nullptr, nullptr};  // per slot set: behind the last launch queued for the set's previous group
+    std::vector<hipEvent_t> slot_ev;                   // per slot: its job's scan is filtered and resident
+    PinnedBuf<IcpJob> h_jobs;
+    DevBuf<IcpJob> d_jobs;
+    int fused_expect_iters = 4;                        // the first chunk of a group: the previous group's largest iteration count
+    static constexpr size_t kMaxSlots = 16;
+    ~IcpMatcher() override {
+        for (hipEvent_t e : slot_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : batch_tail_ev) if (e) (void)hipEventDestroy(e);
+        if (batch_stream) { (void)hipStreamSynchronize(batch_stream); (void)hipStreamDestroy(batch_stream); }
+    }
+    fls_status match_batch_fused(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const*, const size_t*, int stride, double* T,
+                                 fls_stats* st, int32_t* status, int n_slots) override {
+        if (is_lane) return FLS_ERR_STATE;
+        if (status) for (size_t j = 0; j < n_jobs; ++j) status[j] = FLS_SKIPPED;  // overwritten by every job that runs
+        if (n_jobs == 0) return FLS_OK;
+        const fls_status prc = prepare_batch();
+        if (prc != FLS_OK) return prc;
+        const size_t want = std::min(size_t(std::max(1, std::min(n_slots, int(kMaxSlots)))), n_jobs);
+        const size_t G = ensure_lanes(want);
+        if (G == 0) return FLS_ERR_NOMEM;  // the clone could not be set up
+        const size_t n_groups = (n_jobs + G - 1) / G;
+        const size_t n_sets = (n_groups > 1 && ensure_lanes(2 * G) == 2 * G) ? 2 : 1;
+        if (!batch_stream) {
+            FLS_HIP(hipStreamCreateWithFlags(&batch_stream, hipStreamNonBlocking));
+            for (hipEvent_t& e : batch_tail_ev) FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            h_jobs.reserve(kMaxSlots);
+            d_jobs.reserve(kMaxSlots);
+        }
+        while (slot_ev.size() < n_sets * G) {
+            hipEvent_t e = nullptr;
+            FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            slot_ev.push_back(e);
+        }
+        std::vector<fls_status> job_rc(n_jobs, FLS_SKIPPED);
+        auto set_rc = [&](const size_t j, const fls_status rc) { job_rc[j] = rc; if (status) status[j] = int32_t(rc); };
+        std::vector<MatchPlan> plan(n_sets * G);
+        std::vector<char> shared(n_sets * G);
+        bool tail_pending[2] = {false, false};  // launches of the set's previous group may still be queued on the batch stream
+        // (1) per slot, side by side: upload + source filter + prepare.  A rejected job keeps its status; a job whose filtered scan is empty is the
+        // per-lane path's from here (its launches go to the slot's own stream).
+        auto slot_work = [&](const size_t set, const size_t l, const size_t j) {
+            const size_t s = set * G + l;
+            IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
+            shared[s] = 0;
+            try {
+                FLS_HIP(hipSetDevice(q->device));
+                // an exit-at-once launch of the set's previous group reads this slot's state words: the slot's stream stays behind it
+                if (tail_pending[set]) FLS_HIP(hipStreamWaitEvent(q->stream, batch_tail_ev[set], 0));
+                q->reset_job_state();
+                fls_status rc = q->scan_upload(s0[j], n0[j], nullptr, 0, stride);
+                if (rc == FLS_OK) rc = q->match_prepare(T + 16 * j, plan[s]);
+                if (rc == FLS_OK && plan[s].n == 0) rc = q->match_finish(T + 16 * j, q->match_launch(plan[s]), 0, st ? &st[j] : nullptr);
+                else if (rc == FLS_OK) { FLS_HIP(hipEventRecord(slot_ev[s], q->stream)); shared[s] = 1; }
+                set_rc(j, rc);
+            } catch (const fls::HipError& e) {
+                std::fprintf(stderr, "[fls_reg] fused batch slot %zu: %s\n", s, e.what());
+                set_rc(j, FLS_ERR_DEVICE);
+            } catch (const std::bad_alloc&) {
+                set_rc(j, FLS_ERR_NOMEM);
+            } catch (...) {
+                set_rc(j, FLS_ERR_INVALID);
+            }
+        };
+        std::vector<std::thread> th[2];
+        struct JoinAll {  // a joinable std::thread must never be destroyed: also when something below throws
+            std::vector<std::thread> (&t)[2];
+            ~JoinAll() { for (auto& v : t) for (auto& x : v) if (x.joinable()) x.join(); }
+        } join_all{th};
+        auto start_group = [&](const size_t k) {
+            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
+            if (n_jobs == 1) { slot_work(set, 0, base); return; }
+            for (size_t l = 0; l < g; ++l) th[set].emplace_back(slot_work, set, l, base + l);
+        };
+        auto join_group = [&](const size_t k) {
+            for (auto& x : th[k % n_sets]) x.join();
+            th[k % n_sets].clear();
+        };
+        start_group(0);
+        for (size_t k = 0; k < n_groups; ++k) {
+            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
+            ++batch_counters[3];
+            join_group(k);
+            if (n_sets == 2 && k + 1 < n_groups) start_group(k + 1);  // the next group's filters run beside this group's iterations
+            // (2) the job table and the shared launches
+            std::vector<IcpMatcher*> act;
+            std::vector<size_t> act_job;
+            unsigned rows_max = 0;
+            CellGridDev cg{};  // one map for every job: the owner's grid
+            for (size_t l = 0; l < g; ++l) {
+                const size_t s = set * G + l;
+                if (!shared[s]) {
+                    if (job_rc[base + l] >= 0) ++batch_counters[2];  // (it ran, on the per-lane path)
+                    continue;
+                }
+                IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
+                q->match_id = (q->match_id + 1) & 0x7fffffu;
+                FLS_HIP(hipStreamWaitEvent(batch_stream, slot_ev[s], 0));
+                const MatchPlan& m = plan[s];
+                IcpJob& e = h_jobs.p[act.size()];
+                e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
+                e.n = int(m.n); e.rows = int(m.rows);
+                e.st = q->d_state.p; e.nn_id = q->d_nn_id.p; e.eff = q->d_eff.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
+                e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
+                e.T0 = m.T0;
+                rows_max = std::max(rows_max, m.rows);
+                cg = m.cg;
+                act.push_back(q);
+                act_job.push_back(base + l);
+            }
+            if (!act.empty()) {
+                const size_t A = act.size();
+                batch_counters[1] += A;
+                // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
+                // and the copy below is ordered behind them on the batch stream)
+                FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IcpJob), hipMemcpyHostToDevice, batch_stream));
+                const int iters = int(p.max_iterations);
+                std::vector<unsigned> word(A, 0u);
+                int launched = 0;
+                int chunk = std::max(1, std::min(iters, fused_expect_iters));
+                for (;;) {
+                    const int end = std::min(iters, launched + chunk);
+                    for (int it = launched; it < end; ++it)
+                        hipLaunchKernelGGL(icp_knn_fit_jobs_kernel, dim3(rows_max, unsigned(A)), dim3(256), 0, batch_stream, (const IcpJob*)d_jobs.p, it == 0 ? 1 : 0,
+                                           cg, float(p.point_search_thres), p.point_search_thres, kTicketShards, p.rotation_converge_thres, p.position_converge_thres);
+                    batch_counters[0] += size_t(end - launched);
+                    launched = end;
+                    FLS_HIP(hipGetLastError());
+                    // every job of the group has stopped or has run `launched` iterations (the stream-state fallback of spin_until: a faulted kernel cannot hang the host)
+                    bool all_done = true;
+                    auto ready = [&] {
+                        bool ok = true;
+                        all_done = true;
+                        for (size_t i = 0; i < A; ++i) {
+                            const unsigned sq = __atomic_load_n(&act[i]->mb_host->seq, __ATOMIC_ACQUIRE);
+                            word[i] = sq;
+                            const bool mine = (sq >> 9) == (act[i]->match_id & 0x7fffffu), done = mine && ((sq >> 8) & 1u);
+                            if (!done) all_done = false;
+                            if (!(mine && (done || int(sq & 0xffu) >= launched))) ok = false;
+                        }
+                        return ok;
+                    };
+                    if (!fls::spin_until(batch_stream, ready)) (void)ready();  // everything drained: the words are final
+                    if (all_done || launched >= iters) break;
+                    chunk = 2;
+                }
+                FLS_HIP(hipEventRecord(batch_tail_ev[set], batch_stream));
+                tail_pending[set] = true;
+                // (3) the epilogue per job
+                int most = 2;
+                for (size_t i = 0; i < A; ++i) {
+                    IcpMatcher* q = act[i];
+                    const size_t j = act_job[i];
+                    const int used = int(word[i] & 0xffu);
+                    most = std::max(most, used);
+                    q->expect_iters = std::max(2, used);
+                    q->log_stale = true;
+                    q->log_n = std::min(used, fls::kMaxIter);
+                    set_rc(j, q->match_finish(T + 16 * j, word[i], 0, st ? &st[j] : nullptr));
+                }
+                fused_expect_iters = most;
+            }
+            if (n_sets == 1 && k + 1 < n_groups) start_group(k + 1);
+        }
+        // the slots are also match_batch's lanes, which launch on their own streams: nothing of this call stays queued behind the return
+        if (tail_pending[0] || tail_pending[1]) FLS_HIP(hipStreamSynchronize(batch_stream));
+        for (size_t j = 0; j < n_jobs; ++j)
+            if (job_rc[j] < 0) return job_rc[j];  // the first negative status by job index; every job has run
+        return FLS_OK;
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override {
