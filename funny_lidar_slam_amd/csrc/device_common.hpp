@@ -114,7 +114,7 @@ struct GnState {
 
 // Result mailbox in host-mapped pinned memory: the Gauss-Newton tail writes the few words a Match returns
 // (pose, counters) straight to the host and publishes them with one system-scope release store of `seq`
-// = match_id << 9 | done << 8 | iterations.  The host spins on that word instead of paying a blocking
+// (a SeqWord).  The host spins on that word instead of paying a blocking
 // hipStreamSynchronize (~25 us wake-up) plus a device-to-host copy kernel per Match.
 struct Mailbox {
     double T[16];
@@ -124,12 +124,39 @@ struct Mailbox {
     unsigned seq;
 };
 
+// The two words of the mailbox protocol; their layout is known here and nowhere else.
+struct LaunchWord {  // what every tail kernel gets: max_iterations (clamped to 255) << 24 | exact-solver flag << 23 | match id (23 bits, wrapping)
+    static constexpr unsigned kIdMask = 0x7fffffu, kExactShift = 23, kMaxItShift = 24, kMaxItLimit = 255u;
+    unsigned w;
+    static __host__ __device__ constexpr LaunchWord pack(const unsigned id, const bool exact, const unsigned max_iterations) {
+        return LaunchWord{(id & kIdMask) | (exact ? 1u << kExactShift : 0u) | ((max_iterations < kMaxItLimit ? max_iterations : kMaxItLimit) << kMaxItShift)};
+    }
+    static __host__ __device__ constexpr unsigned next_id(const unsigned id) { return (id + 1u) & kIdMask; }
+    __host__ __device__ constexpr unsigned id() const { return w & kIdMask; }
+    __host__ __device__ constexpr bool exact() const { return ((w >> kExactShift) & 1u) != 0u; }
+    __host__ __device__ constexpr int max_iterations() const { return int(w >> kMaxItShift); }
+};
+struct SeqWord {  // what a tail publishes in Mailbox::seq: match id << 9 | done << 8 | iterations executed
+    static constexpr unsigned kIdShift = 9, kDoneShift = 8, kIterMask = 0xffu;
+    unsigned w;
+    static __host__ __device__ constexpr SeqWord pack(const unsigned id, const bool done, const int iterations) {
+        return SeqWord{((id & LaunchWord::kIdMask) << kIdShift) | (done ? 1u << kDoneShift : 0u) | (unsigned(iterations) & kIterMask)};
+    }
+    __host__ __device__ constexpr unsigned id() const { return w >> kIdShift; }
+    __host__ __device__ constexpr bool done() const { return ((w >> kDoneShift) & 1u) != 0u; }
+    __host__ __device__ constexpr int iterations() const { return int(w & kIterMask); }
+    // this word belongs to Match `match_id` and that Match has run `target` iterations or has stopped
+    __host__ __device__ constexpr bool reached(const unsigned match_id, const int target) const {
+        return id() == (match_id & LaunchWord::kIdMask) && (done() || iterations() >= target);
+    }
+};
+
 #ifdef __HIPCC__
 // Publish an iteration result to the host-mapped mailbox without a release FENCE (a system-scope release writes
 // back the whole XCD L2 first -- megabytes of freshly written Jacobian rows -- on the critical path): every
 // payload word goes out as a write-through relaxed system-scope store, the wave drains its stores, then `seq`
-// follows.  The host's acquire load of `seq` (matcher_base.hpp wait_mailbox) completes the hand-off.
-// launch_word = max_iterations << 24 | match_id (23 bits).  The payload (pose, statistics) crosses PCIe only when the host will
+// follows.  The host's acquire load of `seq` (matcher_base.hpp wait_mailboxes) completes the hand-off.
+// launch_word: a LaunchWord.  The payload (pose, statistics) crosses PCIe only when the host will
 // read it -- the iteration that stops the Match or the last one the host can launch; every other iteration publishes the
 // sequence word alone (the host only counts iterations then) and does not wait for its stores.
 __device__ __forceinline__ void mailbox_publish(Mailbox* __restrict__ mb, const double (&T)[16], const double (&dx)[6], const double sum_res,
@@ -137,8 +164,8 @@ __device__ __forceinline__ void mailbox_publish(Mailbox* __restrict__ mb, const 
                                                 const int n_valid, const int n_valid2, const unsigned launch_word) {
 #define FLS_MB_F64(dst, v) __hip_atomic_store((unsigned long long*)&(dst), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
 #define FLS_MB_I32(dst, v) __hip_atomic_store(&(dst), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-    const int max_it = (int)(launch_word >> 24);
-    const unsigned seq = ((launch_word & 0x7fffffu) << 9) | ((unsigned)done << 8) | (unsigned)iter;
+    const int max_it = (int)(launch_word >> LaunchWord::kMaxItShift);
+    const unsigned seq = ((launch_word & LaunchWord::kIdMask) << SeqWord::kIdShift) | ((unsigned)done << SeqWord::kDoneShift) | (unsigned)iter;
     if (done || max_it == 0 || iter >= max_it) {
         for (int q = 0; q < 16; ++q) FLS_MB_F64(mb->T[q], T[q]);
         for (int q = 0; q < 6; ++q) FLS_MB_F64(mb->last_dx[q], dx[q]);

@@ -33,20 +33,6 @@ int gfx950_device_count() {
     return ok;
 }
 
-template <typename F>
-fls_status guarded(F&& f) {
-    try {
-        return f();
-    } catch (const HipError& e) {
-        std::fprintf(stderr, "[fls_reg] %s\n", e.what());
-        return FLS_ERR_DEVICE;
-    } catch (const std::bad_alloc&) {
-        return FLS_ERR_NOMEM;
-    } catch (...) {
-        return FLS_ERR_INVALID;
-    }
-}
-
 // test hooks of include/fls_debug_linalg.h: inputs up, one launch, outputs down: every array holds `w` doubles per system
 struct DebugIn { const double* p; int w; };
 struct DebugOut { double* p; int w; };

@@ -1,4 +1,4 @@
-// host_parallel.hpp -- a small worker pool for the host side of the product, and an EXACT parallel restatement of
+// host_parallel.hpp -- a join-on-exit thread group, a small worker pool for the host side of the product, and an EXACT parallel restatement of
 // libstdc++'s std::sort.
 //
 // Why: pcl::VoxelGrid (include/common/pointcloud_utility.h:216-271 -> PCL voxel_grid.hpp) sums the points of a leaf in the
@@ -29,6 +29,14 @@
 #include <vector>
 
 namespace fls {
+
+// Host threads that are joined on every exit (a joinable std::thread must never be destroyed), also when starting the next one or the code up to join() throws
+struct Threads {
+    std::vector<std::thread> th;
+    template <class F> void start(F&& f) { th.emplace_back(std::forward<F>(f)); }
+    void join() { for (auto& t : th) if (t.joinable()) t.join(); th.clear(); }
+    ~Threads() { join(); }
+};
 
 // Worker pool for short data-parallel phases on the host.  A region belongs to the calling thread, which runs a sequence
 // of PHASES; a phase is a set of chunks handed out through one atomic ticket.  Workers are only HELPERS: a worker that wakes

@@ -1,9 +1,11 @@
-// host_util.hpp -- host-side plumbing: HIP error handling, the host-mapped-word spin wait, device buffers, pinned staging.
+// host_util.hpp -- host-side plumbing: HIP error handling, the exception-to-status ladder, the host-mapped-word spin wait, device
+// buffers, pinned staging.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <vector>
 #include <stdexcept>
 #include "../../include/fls_reg.h"
@@ -24,6 +26,23 @@ struct HipError : std::runtime_error {
             throw ::fls::HipError(_e, _buf);                                                   \
         }                                                                                      \
     } while (0)
+
+// No exception crosses the C ABI or leaves a host thread: f()'s status, or the status its exception stands for.  `context` (with
+// `index`) names the thread in the message: "[fls_reg] batch lane 3: ...".
+template <typename F>
+fls_status guarded(F&& f, const char* context = nullptr, size_t index = 0) {
+    try {
+        return f();
+    } catch (const HipError& e) {
+        if (context) std::fprintf(stderr, "[fls_reg] %s %zu: %s\n", context, index, e.what());
+        else std::fprintf(stderr, "[fls_reg] %s\n", e.what());
+        return FLS_ERR_DEVICE;
+    } catch (const std::bad_alloc&) {
+        return FLS_ERR_NOMEM;
+    } catch (...) {
+        return FLS_ERR_INVALID;
+    }
+}
 
 // FLS_HOST_TIMING=1: host-side timing lines on stderr
 inline bool host_timing_enabled() {

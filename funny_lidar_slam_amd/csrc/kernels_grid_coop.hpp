@@ -16,7 +16,8 @@
 //                                                                 loam_full_kdtree.h:291-343, loam_point_to_plane_kdtree.h:219-271
 //   corner_fit_kernel    LoamFull::CornerMatch (after the k-NN)   loam_full_kdtree.h:227-271
 // Fit kernels: one lane per point, FP64, DPP wave reduction, one partial row per 256-thread workgroup; the
-// Gauss-Newton tail runs in gn_solve_loam_kernel / gn_solve_lu_kernel.
+// Gauss-Newton tail runs in the last workgroup of the fit launch (the stand-alone gn_solve_* launches serve the
+// single-class and traffic-counting paths).
 #pragma once
 #include "kernels_knn.hpp"
 #include "lane_group.hpp"

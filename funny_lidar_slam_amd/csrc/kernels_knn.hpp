@@ -413,7 +413,7 @@ struct LuTailArgs {  // what the tail needs besides the rows (one struct so that
     double rot_thr, pos_thr;
     int min_effective;
     Mailbox* mb;
-    unsigned match_id;   // launch word: max_iterations << 24 | exact-solver flag << 23 | match id
+    unsigned match_id;   // a LaunchWord (device_common.hpp)
 };
 // executed by a whole workgroup of NT threads (all reduce the rows, wave 0 solves); SC1: the rows were published write-through by
 // other workgroups of the SAME launch (fused search + fit + tail kernels)
@@ -489,7 +489,7 @@ __device__ __forceinline__ void lu_tail(GnState* __restrict__ st, LuTailSmem& sm
         }
         st->iter = it + 1;
         if (mb) {
-            mailbox_publish(mb, Tl, dxo, sres, 0.0, it + 1, stop, conv, effective, 0, match_id);  // launch word: max_iterations << 24 | match id
+            mailbox_publish(mb, Tl, dxo, sres, 0.0, it + 1, stop, conv, effective, 0, match_id);  // (a LaunchWord, device_common.hpp)
         }
         FLS_STAMP(5);
     }

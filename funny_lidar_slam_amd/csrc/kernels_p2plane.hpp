@@ -11,9 +11,10 @@
 //       DistanceSquared (float)                  include/common/pointcloud_utility.h:14-17
 //     5x3 plane fit + gates + Jacobian           :275-321
 //   and the per-wave part of SumCoefficient      :326-340
-// gn_solve_loam_kernel finishes SumCoefficient (fixed-order reduction of the wave partials) and runs
+// The Gauss-Newton tail finishes SumCoefficient (fixed-order reduction of the wave partials) and runs
 //   dx = H.fullPivHouseholderQr().solve(g); R <- Exp(dx[0:3]) R; t += dx[3:6]; stop rule   :167-195
-// on the device: the host never synchronises inside a Match, it polls the result mailbox.
+// in the last workgroup of the fit launch (the stand-alone gn_solve_loam_kernel launch serves the single-class and
+// traffic-counting paths): the host never synchronises inside a Match, it polls the result mailbox.
 //
 // This header holds what every LOAM-family kind shares: the point-to-plane residual, the wave reduction of
 // the rank-1 normal-equation terms and the Gauss-Newton tail.  The 29 sums of a wave are entries of sum_p v_p v_p^T with
@@ -331,9 +332,9 @@ __device__ __forceinline__ bool publish_row_and_arrive(const double v, const boo
 // with the oracle's to <= 1e-12 instead of <= 1e-14, every per-iteration n_valid / flag / id comparison of the test-suite is
 // unchanged).  The Eigen-arithmetic solvers remain the fallback whenever a pivot is not safely positive (rank-deficient or
 // badly conditioned systems: there Eigen's rank-revealing behaviour IS the semantics) and can be forced for every system
-// with FLS_TAIL_EXACT=1 (launch word bit 23).  Called by the whole wave 0, uniform result; 0 when the caller must run the exact solver.
+// with FLS_TAIL_EXACT=1 (LaunchWord's exact flag).  Called by the whole wave 0, uniform result; 0 when the caller must run the exact solver.
 __device__ __forceinline__ int ldlt_fast_path(const double* __restrict__ H, const double* __restrict__ g, double* __restrict__ x, const unsigned launch_word) {
-    if ((launch_word >> 23) & 1u) return 0;
+    if ((launch_word >> LaunchWord::kExactShift) & 1u) return 0;
     return ldlt_solve6_wave(H, g, x) ? 1 : 0;
 }
 
@@ -417,7 +418,7 @@ __device__ __forceinline__ void loam_tail(GnState* __restrict__ st, LoamTailSmem
         const int stop = ((rn < rot_thr && pn < pos_thr) || (drot < 1.0e-4 && dpos < 1.0e-4)) ? 1 : 0;
         st->done = stop;
         if (mb) {
-            mailbox_publish(mb, Tl, dx, srb, sra, it + 1, stop, 0, nvb, nva, match_id);  // launch word: max_iterations << 24 | match id
+            mailbox_publish(mb, Tl, dx, srb, sra, it + 1, stop, 0, nvb, nva, match_id);  // (a LaunchWord, device_common.hpp)
         }
         FLS_STAMP(5);
     }

@@ -1,7 +1,7 @@
 // matcher_base.hpp -- common host state of one registration handle (stream, device
 // Gauss-Newton state, wave partials, profiling events), the launch loop and the Match
-// epilogue every kind shares (run_mailbox_loop, take_result), the batch-lane clone
-// (make_lane) and the scan upload helper.
+// epilogue every kind shares (run_mailbox_loop = begin_match, run_chunks over wait_mailboxes, end_match;
+// take_result), the batch-lane clone (make_lane, make_owned_lane) and the scan upload helper.
 #pragma once
 #include "host_maps.hpp"
 #include "kernels_handoff.hpp"
@@ -49,11 +49,8 @@ struct fls_matcher {
     fls::Mailbox* mb_host = nullptr;
     fls::Mailbox* mb_dev = nullptr;
     unsigned match_id = 0;
-    // what the tail kernels get: max_iterations << 24 | exact-solver flag << 23 | match id (mailbox_publish, device_common.hpp)
     bool tail_exact = false;  // FLS_TAIL_EXACT=1: every 6x6 system through the Eigen-arithmetic solver (no LDL^T fast path)
-    unsigned launch_word() const {
-        return (match_id & 0x7fffffu) | (tail_exact ? (1u << 23) : 0u) | (std::min<unsigned>(p.max_iterations, 255u) << 24);
-    }
+    unsigned launch_word() const { return fls::LaunchWord::pack(match_id, tail_exact, p.max_iterations).w; }  // what the tail kernels get
 
     virtual ~fls_matcher() {
         for (auto e : ev_pool) if (e) (void)hipEventDestroy(e);
@@ -95,7 +92,9 @@ struct fls_matcher {
     std::vector<std::unique_ptr<fls_matcher>> lanes;
     bool is_lane = false;
     virtual std::unique_ptr<fls_matcher> clone_for_lane() { return nullptr; }  // same kind, borrowing this handle's map
-    virtual fls_status prepare_batch() { return FLS_OK; }                     // map image current and complete on the device
+    bool have_map = false;  // a map has been built on the device (every kind but iVox, whose image is built on demand)
+    // the map image current and complete on the device, the owner's stream idle
+    virtual fls_status prepare_batch() { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
     virtual void tune_lane(fls_matcher&) {}                                    // copy run-time switches to a lane
     // at least `want` lane clones, if they can be set up; returns how many of `want` exist
     size_t ensure_lanes(size_t want) {
@@ -107,49 +106,45 @@ struct fls_matcher {
         }
         return std::min(want, lanes.size());
     }
-    fls_status match_batch(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const* s1, const size_t* n1, int stride,
-                           double* T, fls_stats* st, int32_t* status, int n_lanes) {
+    // The start of fls_match_batch / fls_match_batch_fused: every status FLS_SKIPPED (overwritten by every job that runs), the map made
+    // ready; returns how many of the `want` lanes (clamped to [1, kMaxLanes] and to n_jobs) exist, or the status (<= 0) to return at once.  Jobs never
+    // run on the owner itself: its Match state (nearest_points_, keyframe gate, resident scan, final pose) belongs to the SLAM thread's next fls_match.
+    static constexpr int kMaxLanes = 16;
+    int begin_batch(size_t n_jobs, int32_t* status, int want) {
         if (is_lane) return FLS_ERR_STATE;
-        if (status) for (size_t j = 0; j < n_jobs; ++j) status[j] = FLS_SKIPPED;  // overwritten by every job that runs
+        if (status) for (size_t j = 0; j < n_jobs; ++j) status[j] = FLS_SKIPPED;
         if (n_jobs == 0) return FLS_OK;
-        size_t L = std::min(size_t(std::max(1, std::min(n_lanes, 16))), n_jobs);
-        // Jobs never run on the owner itself: its Match state (nearest_points_, keyframe gate, resident scan, final pose)
-        // belongs to the SLAM thread's next fls_match.  lanes <= 1 (or a single job) = one lane clone, back to back.
         const fls_status prc = prepare_batch();
         if (prc != FLS_OK) return prc;
-        L = ensure_lanes(L);
-        if (L == 0) return FLS_ERR_NOMEM;  // the clone could not be set up
+        const size_t width = ensure_lanes(std::min(size_t(std::max(1, std::min(want, kMaxLanes))), n_jobs));
+        return width ? int(width) : int(FLS_ERR_NOMEM);  // (the clone could not be set up)
+    }
+    fls_status match_batch(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const* s1, const size_t* n1, int stride,
+                           double* T, fls_stats* st, int32_t* status, int n_lanes) {
+        const int width = begin_batch(n_jobs, status, n_lanes);  // lanes <= 1 (or a single job) = one lane clone, back to back
+        if (width <= 0) return fls_status(width);
+        const size_t L = size_t(width);
         std::vector<fls_status> lane_rc(L, FLS_OK);
-        std::vector<std::thread> th;
-        struct JoinAll {  // a joinable std::thread must never be destroyed: also when starting a later lane throws
-            std::vector<std::thread>& t;
-            ~JoinAll() { for (auto& x : t) if (x.joinable()) x.join(); }
-        } join_all{th};
+        fls::Threads th;
         for (size_t l = 0; l < L; ++l) {
             fls_matcher* q = lanes[l].get();
             tune_lane(*q);
             q->expect_iters = expect_iters;
-            th.emplace_back([=, &lane_rc]() {
-                try {
+            th.start([=, &lane_rc]() {
+                lane_rc[l] = fls::guarded([&]() -> fls_status {
                     FLS_HIP(hipSetDevice(q->device));
                     for (size_t j = l; j < n_jobs; j += L) {
                         q->reset_job_state();
                         fls_status rc = q->scan_upload(s0[j], n0[j], s1 ? s1[j] : nullptr, n1 ? n1[j] : 0, stride);
                         if (rc == FLS_OK) rc = q->match_resident(T + 16 * j, 0, st ? &st[j] : nullptr);
                         if (status) status[j] = int32_t(rc);
-                        if (rc < 0) { lane_rc[l] = rc; return; }
+                        if (rc < 0) return rc;  // (the lane's remaining jobs stay FLS_SKIPPED)
                     }
-                } catch (const fls::HipError& e) {
-                    std::fprintf(stderr, "[fls_reg] batch lane %zu: %s\n", l, e.what());
-                    lane_rc[l] = FLS_ERR_DEVICE;
-                } catch (const std::bad_alloc&) {
-                    lane_rc[l] = FLS_ERR_NOMEM;
-                } catch (...) {
-                    lane_rc[l] = FLS_ERR_INVALID;
-                }
+                    return FLS_OK;
+                }, "batch lane", l);
             });
         }
-        for (auto& t : th) t.join();  // (join_all is the exception path)
+        th.join();
         for (const fls_status rc : lane_rc) if (rc < 0) return rc;
         return FLS_OK;
     }
@@ -206,22 +201,29 @@ struct fls_matcher {
         }
         ev_pending.clear();
     }
-    // Spin on the mailbox until the Gauss-Newton tail of iteration `target` (or an earlier one that hit the stop
-    // rule) has published its result.  Returns the published word.  Falls back to the stream state every
-    // few thousand polls so that a faulted kernel cannot hang the host.
-    unsigned wait_mailbox(int target_iter) {
-        const unsigned want = match_id & 0x7fffffu;
-        unsigned s = 0;
-        const bool published = fls::spin_until(stream, [&] {
-            s = __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);
-            return (s >> 9) == want && (((s >> 8) & 1u) || int(s & 0xffu) >= target_iter);
-        });
-        return published ? s : __atomic_load_n(&mb_host->seq, __ATOMIC_ACQUIRE);  // everything drained: the word is final
+    // Spin on the mailboxes of hs[0, n) (all launched on `s`) until every one carries its handle's current Match and that Match has
+    // run `target` iterations or has hit the stop rule.  words[i] = what hs[i] published; returns whether every Match has stopped.
+    // Falls back to the stream state every few thousand polls so that a faulted kernel cannot hang the host.
+    template <class M>
+    static bool wait_mailboxes(hipStream_t s, M* const* hs, size_t n, unsigned* words, int target) {
+        bool all_stopped = true;
+        auto ready = [&] {
+            bool ok = all_stopped = true;
+            for (size_t i = 0; i < n; ++i) {
+                const fls::SeqWord sq{__atomic_load_n(&hs[i]->mb_host->seq, __ATOMIC_ACQUIRE)};
+                words[i] = sq.w;
+                if (!sq.reached(hs[i]->match_id, target)) ok = false;
+                if (!sq.done()) all_stopped = false;
+            }
+            return ok;
+        };
+        if (!fls::spin_until(s, ready)) (void)ready();  // everything drained: the words are final
+        return all_stopped;
     }
     // the part of the Match epilogue every kind shares: the iteration count of the published word and the mailbox's residual block into `stats`
     const fls::Mailbox& take_result(unsigned word) {
         const fls::Mailbox& mb = *mb_host;
-        stats.iterations = int(word & 0xffu);
+        stats.iterations = fls::SeqWord{word}.iterations();
         stats.n_valid = mb.n_valid;
         stats.sum_res = mb.sum_res;
         std::memcpy(stats.last_dx, mb.last_dx, sizeof(stats.last_dx));
@@ -249,32 +251,32 @@ struct fls_matcher {
     // Gauss-Newton launch loop shared by every kind.  Iterations are enqueued in chunks sized by the previous
     // Match (steady-state SLAM needs about the same number every scan); the device decides convergence, kernels
     // of a finished Match exit at once, and the host learns the outcome from the mailbox without a blocking
-    // synchronisation.  launch(it, first) enqueues one iteration; returns the published mailbox word.
+    // synchronisation.  Three parts, so that a group of handles can share the middle one (IcpMatcher::match_batch_fused):
+    // begin_match per handle, run_chunks once, end_match per handle with the word that handle published.
     int expect_iters = 4;
-    template <class F>
-    unsigned run_mailbox_loop(int iters, size_t points_per_iter, F&& launch) {
-        return run_mailbox_loop(iters, points_per_iter, launch, [](int) {});
-    }
-    // after_chunk(launched): called after every chunk of iterations has been queued, before the host waits (speculative work behind the chunk)
-    template <class F, class G>
-    unsigned run_mailbox_loop(int iters, size_t points_per_iter, F&& launch, G&& after_chunk) {
-        match_id = (match_id + 1) & 0x7fffffu;
+    void begin_match(int iters) {
+        match_id = fls::LaunchWord::next_id(match_id);
         if (profiling) ensure_events(iters);
         if (count_traffic) FLS_HIP(hipMemsetAsync(d_tc.p, 0, sizeof(fls::TrafficCounters), stream));
+    }
+    // queue(it, first) enqueues one iteration; after_chunk(launched) runs once a chunk is queued, before the host waits (speculative work
+    // behind the chunk); wait(launched) returns once every mailbox it watches shows `launched` iterations or a stop: true when all stopped
+    template <class Q, class A, class W>
+    static void run_chunks(int iters, int first_chunk, Q&& queue, A&& after_chunk, W&& wait) {
         int launched = 0;
-        unsigned word = 0;
-        int chunk = std::max(1, std::min(iters, expect_iters));
+        int chunk = std::max(1, std::min(iters, first_chunk));
         for (;;) {
             const int end = std::min(iters, launched + chunk);
-            for (int it = launched; it < end; ++it) launch(it, it == 0 ? 1 : 0);
+            for (int it = launched; it < end; ++it) queue(it, it == 0 ? 1 : 0);
             launched = end;
             after_chunk(launched);
             FLS_HIP(hipGetLastError());
-            word = wait_mailbox(launched);
-            if (((word >> 8) & 1u) || launched >= iters) break;
+            if (wait(launched) || launched >= iters) break;
             chunk = 2;
         }
-        const int used = int(word & 0xffu);
+    }
+    void end_match(unsigned word, size_t points_per_iter) {
+        const int used = fls::SeqWord{word}.iterations();
         expect_iters = std::max(2, used);
         log_stale = true;
         log_n = std::min(used, fls::kMaxIter);
@@ -284,6 +286,19 @@ struct fls_matcher {
             FLS_HIP(hipStreamSynchronize(stream));
             last_tc = *h_tc.p;
         }
+    }
+    // launch(it, first) enqueues one iteration; returns the published mailbox word
+    template <class F>
+    unsigned run_mailbox_loop(int iters, size_t points_per_iter, F&& launch) {
+        return run_mailbox_loop(iters, points_per_iter, launch, [](int) {});
+    }
+    template <class F, class G>
+    unsigned run_mailbox_loop(int iters, size_t points_per_iter, F&& launch, G&& after_chunk) {
+        begin_match(iters);
+        fls_matcher* const self = this;  // the one-handle case of the wait
+        unsigned word = 0;
+        run_chunks(iters, expect_iters, launch, after_chunk, [&](int launched) { return wait_mailboxes(stream, &self, 1, &word, launched); });
+        end_match(word, points_per_iter);
         return word;
     }
 };
@@ -410,6 +425,8 @@ std::unique_ptr<M> make_lane(const M& self) {
     if (q->init() != FLS_OK) return nullptr;
     return q;
 }
+template <class M>  // the same for the kinds whose lanes read the map through an `owner` pointer
+std::unique_ptr<M> make_owned_lane(const M& self) { auto q = make_lane(self); if (q) q->owner = &self; return q; }
 
 inline fls_status check_common(const fls_params& p) {
     if (p.struct_size != sizeof(fls_params)) return FLS_ERR_INVALID;

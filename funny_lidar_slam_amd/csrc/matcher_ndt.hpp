@@ -63,7 +63,6 @@ struct NdtMatcher final : fls_matcher {
     DevBuf<double> d_mu, d_info;
     DevBuf<int> d_vid;
     unsigned mask = 0;
-    bool have_map = false;
 
     DevScan scan;
     std::vector<PtI> source;
@@ -687,12 +686,7 @@ struct NdtMatcher final : fls_matcher {
         return rc;
     }
     const NdtMatcher* owner = nullptr;
-    std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = make_lane(*this);
-        if (q) q->owner = this;
-        return q;
-    }
-    fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
+    std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float max_range, float* score) override {
         if (!p.is_localization_mode) { *score = std::numeric_limits<float>::max(); return FLS_OK; }  // :346-348
         if (!have_fitness_grid || src_filter.withdrawn) return FLS_ERR_STATE;

@@ -29,7 +29,6 @@ struct IcpMatcher final : fls_matcher {
     KdLocalMap map;
     std::vector<PtI> source;
     SourceFilter src_filter;
-    bool have_map = false;
     DevBuf<unsigned> d_ticket;
     const IcpMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
     DevScan scan;
@@ -151,7 +150,7 @@ struct IcpMatcher final : fls_matcher {
     // ---- fls_match_batch_fused: groups of up to n_slots jobs share one icp_knn_fit_jobs_kernel launch per iteration ----
     // Slots are the lane clones.  Per group: every slot uploads and filters its job on its own stream and its own host thread (the filters are
     // latency chains with a host wait each: they overlap), records an event, and the batch stream, behind those events, carries the group's iteration
-    // launches, chunked as in run_mailbox_loop; the host waits on all the group's mailboxes.  Prepare and finish are the single-job path's.
+    // launches through run_chunks; the host waits on all the group's mailboxes.  Prepare, begin / end and finish are the single-job path's.
     // With more than one group there are two sets of slots: the next group's filters run while this group iterates.
     hipStream_t batch_stream = nullptr;
     hipEvent_t batch_tail_ev[2] = {nullptr, nullptr};  // per slot set: behind the last launch queued for the set's previous group
@@ -159,178 +158,142 @@ struct IcpMatcher final : fls_matcher {
     PinnedBuf<IcpJob> h_jobs;
     DevBuf<IcpJob> d_jobs;
     int fused_expect_iters = 4;                        // the first chunk of a group: the previous group's largest iteration count
-    static constexpr size_t kMaxSlots = 16;
     ~IcpMatcher() override {
         for (hipEvent_t e : slot_ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : batch_tail_ev) if (e) (void)hipEventDestroy(e);
         if (batch_stream) { (void)hipStreamSynchronize(batch_stream); (void)hipStreamDestroy(batch_stream); }
     }
+    static hipEvent_t new_event() { hipEvent_t e = nullptr; FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; }
+    // what the steps of one call share
+    struct FusedCall {
+        const float* const* s0; const size_t* n0; int stride;  // the caller's arrays
+        double* T; fls_stats* st; int32_t* status;
+        size_t G;                          // slots per set
+        std::vector<fls_status> job_rc;    // per job
+        std::vector<MatchPlan> plan;       // per slot
+        std::vector<char> shared;          // per slot: its job waits for the group's shared launches
+        bool tail_pending[2] = {false, false};  // launches of the set's previous group may still be queued on the batch stream
+        // the jobs of the current group that run in its shared launches, in job-table order
+        std::vector<IcpMatcher*> act;
+        std::vector<size_t> act_job;
+        std::vector<unsigned> word;             // what each published last
+        unsigned rows_max = 0; CellGridDev cg{};  // of the group's launches (one map for every job: the owner's grid)
+        void set_rc(const size_t j, const fls_status rc) { job_rc[j] = rc; if (status) status[j] = int32_t(rc); }
+        fls_stats* stats_of(const size_t j) const { return st ? &st[j] : nullptr; }
+    };
+    // (1) per slot, side by side: upload + source filter + prepare.  A rejected job keeps its status; a job whose filtered scan is empty is the
+    // per-lane path's from here (its launches go to the slot's own stream).
+    void fused_slot(FusedCall& c, const size_t set, const size_t l, const size_t j) {
+        const size_t s = set * c.G + l;
+        IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
+        c.shared[s] = 0;
+        c.set_rc(j, guarded([&]() -> fls_status {
+            FLS_HIP(hipSetDevice(q->device));
+            // an exit-at-once launch of the set's previous group reads this slot's state words: the slot's stream stays behind it
+            if (c.tail_pending[set]) FLS_HIP(hipStreamWaitEvent(q->stream, batch_tail_ev[set], 0));
+            q->reset_job_state();
+            fls_status rc = q->scan_upload(c.s0[j], c.n0[j], nullptr, 0, c.stride);
+            if (rc == FLS_OK) rc = q->match_prepare(c.T + 16 * j, c.plan[s]);
+            if (rc == FLS_OK && c.plan[s].n == 0) rc = q->match_finish(c.T + 16 * j, q->match_launch(c.plan[s]), 0, c.stats_of(j));
+            else if (rc == FLS_OK) { FLS_HIP(hipEventRecord(slot_ev[s], q->stream)); c.shared[s] = 1; }
+            return rc;
+        }, "fused batch slot", s));
+    }
+    // (2) the job table of the group in slots [set * G, set * G + g), jobs base ..: a Match begins on every slot that waits for the shared launches
+    void fused_job_table(FusedCall& c, const size_t set, const size_t base, const size_t g) {
+        c.act.clear(); c.act_job.clear(); c.rows_max = 0;
+        for (size_t l = 0; l < g; ++l) {
+            const size_t s = set * c.G + l;
+            if (!c.shared[s]) {
+                if (c.job_rc[base + l] >= 0) ++batch_counters[2];  // (it ran, on the per-lane path)
+                continue;
+            }
+            IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
+            q->begin_match(int(p.max_iterations));
+            FLS_HIP(hipStreamWaitEvent(batch_stream, slot_ev[s], 0));
+            const MatchPlan& m = c.plan[s];
+            IcpJob& e = h_jobs.p[c.act.size()];
+            e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
+            e.n = int(m.n); e.rows = int(m.rows);
+            e.st = q->d_state.p; e.nn_id = q->d_nn_id.p; e.eff = q->d_eff.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
+            e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
+            e.T0 = m.T0;
+            c.rows_max = std::max(c.rows_max, m.rows);
+            c.cg = m.cg;
+            c.act.push_back(q);
+            c.act_job.push_back(base + l);
+        }
+        c.word.assign(c.act.size(), 0u);
+    }
+    // (3) the group's launches on the batch stream, until every job has stopped or run max_iterations
+    void fused_launch(FusedCall& c, const size_t set) {
+        const size_t A = c.act.size();
+        batch_counters[1] += A;
+        // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
+        // and the copy below is ordered behind them on the batch stream)
+        FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IcpJob), hipMemcpyHostToDevice, batch_stream));
+        run_chunks(int(p.max_iterations), fused_expect_iters,
+                   [&](int, int first) {
+                       hipLaunchKernelGGL(icp_knn_fit_jobs_kernel, dim3(c.rows_max, unsigned(A)), dim3(256), 0, batch_stream, (const IcpJob*)d_jobs.p, first, c.cg,
+                                          float(p.point_search_thres), p.point_search_thres, kTicketShards, p.rotation_converge_thres, p.position_converge_thres);
+                       ++batch_counters[0];
+                   },
+                   [](int) {}, [&](int launched) { return wait_mailboxes(batch_stream, c.act.data(), A, c.word.data(), launched); });
+        FLS_HIP(hipEventRecord(batch_tail_ev[set], batch_stream));
+        c.tail_pending[set] = true;
+    }
+    // (4) the epilogue per job
+    void fused_finish(FusedCall& c) {
+        fused_expect_iters = 2;
+        for (size_t i = 0; i < c.act.size(); ++i) {
+            IcpMatcher* q = c.act[i];
+            const size_t j = c.act_job[i];
+            q->end_match(c.word[i], q->scan.n);
+            fused_expect_iters = std::max(fused_expect_iters, q->expect_iters);
+            c.set_rc(j, q->match_finish(c.T + 16 * j, c.word[i], 0, c.stats_of(j)));
+        }
+    }
     fls_status match_batch_fused(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const*, const size_t*, int stride, double* T,
                                  fls_stats* st, int32_t* status, int n_slots) override {
-        if (is_lane) return FLS_ERR_STATE;
-        if (status) for (size_t j = 0; j < n_jobs; ++j) status[j] = FLS_SKIPPED;  // overwritten by every job that runs
-        if (n_jobs == 0) return FLS_OK;
-        const fls_status prc = prepare_batch();
-        if (prc != FLS_OK) return prc;
-        const size_t want = std::min(size_t(std::max(1, std::min(n_slots, int(kMaxSlots)))), n_jobs);
-        const size_t G = ensure_lanes(want);
-        if (G == 0) return FLS_ERR_NOMEM;  // the clone could not be set up
-        const size_t n_groups = (n_jobs + G - 1) / G;
+        const int width = begin_batch(n_jobs, status, n_slots);
+        if (width <= 0) return fls_status(width);
+        FusedCall c{s0, n0, stride, T, st, status, size_t(width)};
+        const size_t G = c.G, n_groups = (n_jobs + G - 1) / G;
         const size_t n_sets = (n_groups > 1 && ensure_lanes(2 * G) == 2 * G) ? 2 : 1;
         if (!batch_stream) {
             FLS_HIP(hipStreamCreateWithFlags(&batch_stream, hipStreamNonBlocking));
-            for (hipEvent_t& e : batch_tail_ev) FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            h_jobs.reserve(kMaxSlots);
-            d_jobs.reserve(kMaxSlots);
+            for (hipEvent_t& e : batch_tail_ev) e = new_event();
+            h_jobs.reserve(kMaxLanes);
+            d_jobs.reserve(kMaxLanes);
         }
-        while (slot_ev.size() < n_sets * G) {
-            hipEvent_t e = nullptr;
-            FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            slot_ev.push_back(e);
-        }
-        std::vector<fls_status> job_rc(n_jobs, FLS_SKIPPED);
-        auto set_rc = [&](const size_t j, const fls_status rc) { job_rc[j] = rc; if (status) status[j] = int32_t(rc); };
-        std::vector<MatchPlan> plan(n_sets * G);
-        std::vector<char> shared(n_sets * G);
-        bool tail_pending[2] = {false, false};  // launches of the set's previous group may still be queued on the batch stream
-        // (1) per slot, side by side: upload + source filter + prepare.  A rejected job keeps its status; a job whose filtered scan is empty is the
-        // per-lane path's from here (its launches go to the slot's own stream).
-        auto slot_work = [&](const size_t set, const size_t l, const size_t j) {
-            const size_t s = set * G + l;
-            IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
-            shared[s] = 0;
-            try {
-                FLS_HIP(hipSetDevice(q->device));
-                // an exit-at-once launch of the set's previous group reads this slot's state words: the slot's stream stays behind it
-                if (tail_pending[set]) FLS_HIP(hipStreamWaitEvent(q->stream, batch_tail_ev[set], 0));
-                q->reset_job_state();
-                fls_status rc = q->scan_upload(s0[j], n0[j], nullptr, 0, stride);
-                if (rc == FLS_OK) rc = q->match_prepare(T + 16 * j, plan[s]);
-                if (rc == FLS_OK && plan[s].n == 0) rc = q->match_finish(T + 16 * j, q->match_launch(plan[s]), 0, st ? &st[j] : nullptr);
-                else if (rc == FLS_OK) { FLS_HIP(hipEventRecord(slot_ev[s], q->stream)); shared[s] = 1; }
-                set_rc(j, rc);
-            } catch (const fls::HipError& e) {
-                std::fprintf(stderr, "[fls_reg] fused batch slot %zu: %s\n", s, e.what());
-                set_rc(j, FLS_ERR_DEVICE);
-            } catch (const std::bad_alloc&) {
-                set_rc(j, FLS_ERR_NOMEM);
-            } catch (...) {
-                set_rc(j, FLS_ERR_INVALID);
-            }
-        };
-        std::vector<std::thread> th[2];
-        struct JoinAll {  // a joinable std::thread must never be destroyed: also when something below throws
-            std::vector<std::thread> (&t)[2];
-            ~JoinAll() { for (auto& v : t) for (auto& x : v) if (x.joinable()) x.join(); }
-        } join_all{th};
+        while (slot_ev.size() < n_sets * G) { slot_ev.push_back(nullptr); slot_ev.back() = new_event(); }
+        c.job_rc.assign(n_jobs, FLS_SKIPPED);
+        c.plan.resize(n_sets * G);
+        c.shared.resize(n_sets * G);
+        Threads th[2];  // per slot set
         auto start_group = [&](const size_t k) {
             const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
-            if (n_jobs == 1) { slot_work(set, 0, base); return; }
-            for (size_t l = 0; l < g; ++l) th[set].emplace_back(slot_work, set, l, base + l);
-        };
-        auto join_group = [&](const size_t k) {
-            for (auto& x : th[k % n_sets]) x.join();
-            th[k % n_sets].clear();
+            if (n_jobs == 1) { fused_slot(c, set, 0, base); return; }
+            for (size_t l = 0; l < g; ++l) th[set].start([this, &c, set, l, base] { fused_slot(c, set, l, base + l); });
         };
         start_group(0);
         for (size_t k = 0; k < n_groups; ++k) {
             const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
             ++batch_counters[3];
-            join_group(k);
+            th[set].join();
             if (n_sets == 2 && k + 1 < n_groups) start_group(k + 1);  // the next group's filters run beside this group's iterations
-            // (2) the job table and the shared launches
-            std::vector<IcpMatcher*> act;
-            std::vector<size_t> act_job;
-            unsigned rows_max = 0;
-            CellGridDev cg{};  // one map for every job: the owner's grid
-            for (size_t l = 0; l < g; ++l) {
-                const size_t s = set * G + l;
-                if (!shared[s]) {
-                    if (job_rc[base + l] >= 0) ++batch_counters[2];  // (it ran, on the per-lane path)
-                    continue;
-                }
-                IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
-                q->match_id = (q->match_id + 1) & 0x7fffffu;
-                FLS_HIP(hipStreamWaitEvent(batch_stream, slot_ev[s], 0));
-                const MatchPlan& m = plan[s];
-                IcpJob& e = h_jobs.p[act.size()];
-                e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
-                e.n = int(m.n); e.rows = int(m.rows);
-                e.st = q->d_state.p; e.nn_id = q->d_nn_id.p; e.eff = q->d_eff.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
-                e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
-                e.T0 = m.T0;
-                rows_max = std::max(rows_max, m.rows);
-                cg = m.cg;
-                act.push_back(q);
-                act_job.push_back(base + l);
-            }
-            if (!act.empty()) {
-                const size_t A = act.size();
-                batch_counters[1] += A;
-                // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
-                // and the copy below is ordered behind them on the batch stream)
-                FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IcpJob), hipMemcpyHostToDevice, batch_stream));
-                const int iters = int(p.max_iterations);
-                std::vector<unsigned> word(A, 0u);
-                int launched = 0;
-                int chunk = std::max(1, std::min(iters, fused_expect_iters));
-                for (;;) {
-                    const int end = std::min(iters, launched + chunk);
-                    for (int it = launched; it < end; ++it)
-                        hipLaunchKernelGGL(icp_knn_fit_jobs_kernel, dim3(rows_max, unsigned(A)), dim3(256), 0, batch_stream, (const IcpJob*)d_jobs.p, it == 0 ? 1 : 0,
-                                           cg, float(p.point_search_thres), p.point_search_thres, kTicketShards, p.rotation_converge_thres, p.position_converge_thres);
-                    batch_counters[0] += size_t(end - launched);
-                    launched = end;
-                    FLS_HIP(hipGetLastError());
-                    // every job of the group has stopped or has run `launched` iterations (the stream-state fallback of spin_until: a faulted kernel cannot hang the host)
-                    bool all_done = true;
-                    auto ready = [&] {
-                        bool ok = true;
-                        all_done = true;
-                        for (size_t i = 0; i < A; ++i) {
-                            const unsigned sq = __atomic_load_n(&act[i]->mb_host->seq, __ATOMIC_ACQUIRE);
-                            word[i] = sq;
-                            const bool mine = (sq >> 9) == (act[i]->match_id & 0x7fffffu), done = mine && ((sq >> 8) & 1u);
-                            if (!done) all_done = false;
-                            if (!(mine && (done || int(sq & 0xffu) >= launched))) ok = false;
-                        }
-                        return ok;
-                    };
-                    if (!fls::spin_until(batch_stream, ready)) (void)ready();  // everything drained: the words are final
-                    if (all_done || launched >= iters) break;
-                    chunk = 2;
-                }
-                FLS_HIP(hipEventRecord(batch_tail_ev[set], batch_stream));
-                tail_pending[set] = true;
-                // (3) the epilogue per job
-                int most = 2;
-                for (size_t i = 0; i < A; ++i) {
-                    IcpMatcher* q = act[i];
-                    const size_t j = act_job[i];
-                    const int used = int(word[i] & 0xffu);
-                    most = std::max(most, used);
-                    q->expect_iters = std::max(2, used);
-                    q->log_stale = true;
-                    q->log_n = std::min(used, fls::kMaxIter);
-                    set_rc(j, q->match_finish(T + 16 * j, word[i], 0, st ? &st[j] : nullptr));
-                }
-                fused_expect_iters = most;
-            }
+            fused_job_table(c, set, base, g);
+            if (!c.act.empty()) { fused_launch(c, set); fused_finish(c); }
             if (n_sets == 1 && k + 1 < n_groups) start_group(k + 1);
         }
         // the slots are also match_batch's lanes, which launch on their own streams: nothing of this call stays queued behind the return
-        if (tail_pending[0] || tail_pending[1]) FLS_HIP(hipStreamSynchronize(batch_stream));
+        if (c.tail_pending[0] || c.tail_pending[1]) FLS_HIP(hipStreamSynchronize(batch_stream));
         for (size_t j = 0; j < n_jobs; ++j)
-            if (job_rc[j] < 0) return job_rc[j];  // the first negative status by job index; every job has run
+            if (c.job_rc[j] < 0) return c.job_rc[j];  // the first negative status by job index; every job has run
         return FLS_OK;
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
-    std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = make_lane(*this);
-        if (q) q->owner = this;
-        return q;
-    }
-    fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
+    std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
         return fitness_score_device(*this, map.grid, scan, final_T, max_range, score);
@@ -402,7 +365,6 @@ struct FeatureDev {
 
 struct LoamFullMatcher final : fls_matcher {
     KdLocalMap map_planar, map_corner;
-    bool have_map = false;
     const LoamFullMatcher* owner = nullptr;  // batch lane: reads the owner's two map grids
     FeatureDev corner, planar;
     hm::KeyframeGate gate;
@@ -497,12 +459,7 @@ struct LoamFullMatcher final : fls_matcher {
         return rc;
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); }  // function-static last_T of a fresh process (Q12)
-    std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = make_lane(*this);
-        if (q) q->owner = this;
-        return q;
-    }
-    fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
+    std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float, float* score) override { *score = std::numeric_limits<float>::max(); return FLS_OK; }  // FloatNaN :206-208
     int correspondences(int slot, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override {
         return (slot == 1 ? corner : planar).fetch(stream, ids, cnt, valid, cap);
@@ -516,7 +473,6 @@ struct LoamFullMatcher final : fls_matcher {
 // ---------------------------------------------------------------------------------------------
 struct P2PlaneKdMatcher final : fls_matcher {
     KdLocalMap map;
-    bool have_map = false;
     const P2PlaneKdMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
     FeatureDev planar;
     hm::KeyframeGate gate;
@@ -587,12 +543,7 @@ struct P2PlaneKdMatcher final : fls_matcher {
         return rc;
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }
-    std::unique_ptr<fls_matcher> clone_for_lane() override {
-        auto q = make_lane(*this);
-        if (q) q->owner = this;
-        return q;
-    }
-    fls_status prepare_batch() override { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
+    std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
         return fitness_score_device(*this, map.grid, planar.scan, final_T, max_range, score);

@@ -19,13 +19,6 @@
 #include <vector>
 
 struct fls_replicas {
-    // joins whatever was started, also when starting the next thread throws (std::system_error): a joinable std::thread must never be destroyed
-    struct Threads {
-        std::vector<std::thread> th;
-        template <class F> void start(F&& f) { th.emplace_back(std::forward<F>(f)); }
-        void join() { for (auto& t : th) if (t.joinable()) t.join(); }
-        ~Threads() { join(); }
-    };
     fls_handle owner = nullptr;
     std::vector<int> devices;
     std::vector<fls_handle> handles;  // handles[i] serves devices[i]; the owner itself serves the first entry that names its device
@@ -73,7 +66,7 @@ struct fls_replicas {
         std::vector<unsigned char> blob(need);
         if (fls_map_export(owner, blob.data(), blob.size()) != need) return FLS_ERR_STATE;
         std::vector<fls_status> rc(handles.size(), FLS_OK);
-        Threads th;
+        fls::Threads th;
         for (size_t i = 0; i < handles.size(); ++i) {
             if (!owned[i]) continue;
             th.start([&, i] {
@@ -98,7 +91,7 @@ struct fls_replicas {
                            fls_stats* stats, int32_t* status, int lanes) {
         const size_t world = handles.size();
         std::vector<fls_status> rc(world, FLS_OK);
-        Threads th;
+        fls::Threads th;
         for (size_t r = 0; r < world; ++r) {
             size_t b, e;
             block(n_jobs, world, r, b, e);

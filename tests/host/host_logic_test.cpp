@@ -2,6 +2,7 @@
 //   * HostIvox insert / LRU-evict semantics vs a straightforward list+map model and vs the oracle's iVox
 //   * voxel_grid (PCL VoxelGrid semantics) vs the oracle's
 //   * IvoxImage::collect_incremental invariants (disjoint slot regions, unique cell records, eviction records, halo mirrors of the brick image)
+//   * the mailbox protocol words (device_common.hpp LaunchWord / SeqWord): layout, id wrap, the host wait predicate
 // No HIP runtime call is made: only host members are touched.
 #include "../../funny_lidar_slam_amd/csrc/host_maps.hpp"
 #include "../../funny_lidar_slam_amd/csrc/ivox_image.hpp"
@@ -317,6 +318,37 @@ int main() {
             g.dir_mask = 4095; CHECK(!IvoxImage::flat_header_ok(g, size_t(g.total_bytes)));
         }
         CHECK(IvoxImage::kPoolBrickBytes > 25000 && IvoxImage::kPoolBrickBytes < 27000);
+    }
+    // ---- the two words of the mailbox protocol (device_common.hpp LaunchWord / SeqWord): pack / unpack, the id wrap, the wait predicate ----
+    {
+        const unsigned ids[] = {0u, 1u, 0x7ffffeu, 0x7fffffu};
+        const int iterations[] = {0, 1, 64, 255};
+        const unsigned max_its[][2] = {{1u, 1u}, {64u, 64u}, {255u, 255u}, {300u, 255u}};  // {asked, carried}: clamped to 255
+        CHECK(LaunchWord::next_id(0x7fffffu) == 0u && LaunchWord::next_id(0u) == 1u && LaunchWord::next_id(0x7ffffeu) == 0x7fffffu);
+        for (const unsigned id : ids) {
+            for (int exact = 0; exact < 2; ++exact)
+                for (const auto& mi : max_its) {
+                    const LaunchWord lw = LaunchWord::pack(id, exact != 0, mi[0]);
+                    CHECK(lw.id() == id && lw.exact() == (exact != 0) && lw.max_iterations() == int(mi[1]));
+                    CHECK(lw.w == (id | (unsigned(exact) << 23) | (mi[1] << 24)));
+                    // what mailbox_publish writes for this launch word
+                    for (int d = 0; d < 2; ++d)
+                        for (const int i : iterations) {
+                            const unsigned literal = ((lw.w & 0x7fffffu) << 9) | ((unsigned)d << 8) | (unsigned)i;
+                            CHECK(SeqWord::pack(LaunchWord{lw.w}.id(), d != 0, i).w == literal);
+                        }
+                }
+            for (int d = 0; d < 2; ++d)
+                for (const int i : iterations) {
+                    const SeqWord sq = SeqWord::pack(id, d != 0, i);
+                    CHECK(sq.id() == id && sq.done() == (d != 0) && sq.iterations() == i);
+                    for (int target = 0; target <= 256; ++target) {
+                        CHECK(!sq.reached(LaunchWord::next_id(id), target));           // the previous Match's word, whatever its done bit
+                        CHECK(sq.reached(id, target) == (d != 0 || i >= target));    // stopped: any target; running: from iterations >= target
+                    }
+                }
+        }
+        static_assert(SeqWord::pack(5u, true, 7).w == ((5u << 9) | (1u << 8) | 7u) && LaunchWord::pack(5u, true, 300u).w == (5u | (1u << 23) | (255u << 24)), "constexpr");
     }
     std::printf("host logic ok\n");
     return 0;
