@@ -40,6 +40,9 @@ KEYFRAMES_SYMBOLS = ["fls_keyframes_revision", "fls_keyframes_create", "fls_keyf
 # every symbol include/fls_batch.h declares (FLS_BATCH_REVISION 1)
 BATCH_SYMBOLS = ["fls_batch_revision", "fls_match_batch_fused", "fls_batch_stat"]
 
+# every symbol include/fls_batch_ivox.h declares (FLS_BATCH_IVOX_REVISION 1)
+BATCH_IVOX_SYMBOLS = ["fls_batch_ivox_revision", "fls_match_batch_shared_ivox", "fls_batch_ivox_stat"]
+
 # every symbol include/fls_debug_linalg.h declares (FLS_DEBUG_LINALG_REVISION 1): test hooks of csrc/linalg_dev.hpp / wave_solve.hpp
 DEBUG_LINALG_SYMBOLS = ["fls_debug_linalg_revision", "fls_debug_plane_fit_5x3", "fls_debug_svd3", "fls_debug_lu6", "fls_debug_so3", "fls_debug_wave_sum"]
 
@@ -341,6 +344,13 @@ def lib():
         L.fls_match_batch_fused.argtypes = L.fls_match_batch.argtypes
         L.fls_batch_stat.restype = C.c_size_t
         L.fls_batch_stat.argtypes = [hp, C.c_int]
+        if hasattr(L, "fls_batch_ivox_revision"):  # (FLS_REG_LIB may name the parent commit's build in an A/B: calling what it lacks still raises)
+            L.fls_batch_ivox_revision.restype = C.c_int
+            L.fls_batch_ivox_revision.argtypes = []
+            L.fls_match_batch_shared_ivox.restype = C.c_int
+            L.fls_match_batch_shared_ivox.argtypes = L.fls_match_batch.argtypes
+            L.fls_batch_ivox_stat.restype = C.c_size_t
+            L.fls_batch_ivox_stat.argtypes = [hp, C.c_int]
         L.fls_debug_linalg_revision.restype = C.c_int
         L.fls_debug_linalg_revision.argtypes = []
         L.fls_debug_plane_fit_5x3.restype = C.c_int

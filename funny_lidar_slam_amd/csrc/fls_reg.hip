@@ -14,6 +14,7 @@
 #include "kernels_debug_linalg.hpp"
 #include "../../include/fls_keyframes.h"
 #include "../../include/fls_batch.h"
+#include "../../include/fls_batch_ivox.h"
 #include "../../include/fls_debug_linalg.h"
 #include <new>
 
@@ -211,6 +212,24 @@ fls_status fls_match_batch_fused(fls_handle h, size_t n_jobs, const float* const
 }
 
 size_t fls_batch_stat(fls_handle h, int slot) { return (h && slot >= 0 && slot < 4) ? h->batch_counters[slot] : 0; }
+
+// ---- include/fls_batch_ivox.h ----
+int fls_batch_ivox_revision(void) { return FLS_BATCH_IVOX_REVISION; }
+
+fls_status fls_match_batch_shared_ivox(fls_handle h, size_t n_jobs, const float* const* src0, const size_t* n0, const float* const* src1,
+                                       const size_t* n1, int stride, double* T, fls_stats* stats, int32_t* status, int n_slots) {
+    if (!h || stride < 3 || (n_jobs && (!src0 || !n0 || !T))) return FLS_ERR_INVALID;
+    if ((src1 == nullptr) != (n1 == nullptr)) return FLS_ERR_INVALID;
+    for (size_t j = 0; j < n_jobs; ++j)
+        if (!src0[j] && n0[j]) return FLS_ERR_INVALID;
+    if (n_jobs == 0) return FLS_OK;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->match_batch_shared_ivox(n_jobs, src0, n0, src1, n1, stride, T, stats, status, n_slots);
+    });
+}
+
+size_t fls_batch_ivox_stat(fls_handle h, int slot) { return (h && slot >= 0 && slot < 5) ? h->batch_ivox_counters[slot] : 0; }
 
 size_t fls_map_export(fls_handle h, void* blob, size_t cap) {
     if (!h) return 0;

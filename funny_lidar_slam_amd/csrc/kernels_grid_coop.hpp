@@ -454,10 +454,6 @@ __device__ __forceinline__ void icp_point_rows(const double (&T)[16], const floa
 // The body of workgroup blockIdx.x of ONE registration whose search grid has `nrows` workgroups: icp_knn_fit_kernel is that registration alone
 // (nrows = LaunchBlocksX, the launch's gridDim.x), icp_knn_fit_jobs_kernel runs one per blockIdx.y (nrows = the job's own count).  The LDS is the calling kernel's (declared there under the names the
 // single-job kernel has always used, so that kernel keeps its LDS layout).
-struct Pose16Ref {
-    const Pose16* p;
-    __device__ __forceinline__ operator const Pose16&() const { return *p; }
-};
 #if FLS_FIT_MFMA
 #define FLS_ICP_FIT_SMEM_PARAMS double (&wsum)[4][32], double (&mfma_tile)[4][512], unsigned& s_ticket, LuTailSmem& sm
 #define FLS_ICP_FIT_SMEM_DECL                                                 \

@@ -18,6 +18,8 @@
 //                        Jacobian (FP64), the Q1 stale-slot rule, DPP wave reduction of the 6x6 system; the last
 //                        workgroup to finish also runs the Gauss-Newton tail (solve, pose update, stop rule).
 //                        127-128 VGPRs; the compiler's occupancy figure is 4 waves/SIMD for the 512-thread form, 3 for the 256-thread one.
+//   ivox_knn_jobs_kernel / p2plane_fit_solve_jobs_kernel  the same two launches for a group of independent registrations against one map
+//                        (fls_match_batch_shared_ivox): grid (rows_max, jobs), a device job table; the bodies are the single-job kernels' own.
 //
 // Exact-tie rule of the selection: lower map slot wins (the reference's order under exact float ties is
 // libstdc++-introselect-defined; parity tests count such queries).
@@ -107,18 +109,27 @@ __device__ __forceinline__ double group_min_dkey(const double v) { return dpp_mi
 //     The host drops the gate where 27 res^2 < 25, i.e. with a whole extra voxel per axis (3 res) for the float rounding of key and
 //     difference (at |key| near 2^20 one ulp of a coordinate is res / 8); the selection keys then stay finite doubles as with the gate.
 //   - 64-bit candidate addresses.  With slots x 16 bytes < 2^32 the four loads of a trip take a 32-bit byte offset from the uniform base.
-template <bool COUNT, bool DENSE, bool FIRST, bool GEN>
-__global__ void __launch_bounds__(256)
-ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
-                const GnState* __restrict__ st, const Pose16 T0, const DevGrid grid, const BrickDir bd,
-                const float inv_res, float4* __restrict__ nn_pts /* [n][5] */, unsigned char* __restrict__ nn_cnt,
-                unsigned char* __restrict__ flag, TrafficCounters* __restrict__ tc, const int chunk,
-                unsigned* __restrict__ nn_ids /* [n][8]: map slots of the neighbours (ids form); nullptr: rows form */,
-                const int nn_prev /* FIRST: size of nearest_points_ before this Match; the grown tail starts empty (:257 resize) */,
-                float* __restrict__ dev_copy /* FIRST, may be null: sx / sy / sz point into the pinned staging buffer (host memory);
-                                                leave the device copy x[n] | y[n] | z[n] here for the launches that follow */) {
+// The body of workgroup blockIdx.x of ONE registration: ivox_knn_kernel is that registration alone, ivox_knn_jobs_kernel runs one per blockIdx.y.
+// The LDS is the calling kernel's (declared there under the names the single-job kernel has always used, as icp_knn_fit_body's is).
+constexpr int kIvoxKnnQueries = 256 / 4;  // queries per workgroup (four lanes each)
+#define FLS_IVOX_KNN_SMEM_PARAMS unsigned (&s_end)[kIvoxKnnQueries][24], unsigned (&s_off)[kIvoxKnnQueries][24]
+#define FLS_IVOX_KNN_SMEM_DECL                                                             \
+    __shared__ __attribute__((aligned(16))) unsigned s_end[kIvoxKnnQueries][24];           \
+    __shared__ __attribute__((aligned(16))) unsigned s_off[kIvoxKnnQueries][24]
+#define FLS_IVOX_KNN_SMEM_ARGS s_end, s_off
+template <bool COUNT, bool DENSE, bool FIRST, bool GEN, class P>
+__device__ __forceinline__ void
+ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
+              const GnState* __restrict__ st, const P& T0p /* Pose16, or Pose16Ref: the pose stays where it is */, const DevGrid grid, const BrickDir bd,
+              const float inv_res, float4* __restrict__ nn_pts /* [n][5] */, unsigned char* __restrict__ nn_cnt,
+              unsigned char* __restrict__ flag, TrafficCounters* __restrict__ tc, const int chunk,
+              unsigned* __restrict__ nn_ids /* [n][8]: map slots of the neighbours (ids form); nullptr: rows form */,
+              const int nn_prev /* FIRST: size of nearest_points_ before this Match; the grown tail starts empty (:257 resize) */,
+              float* __restrict__ dev_copy /* FIRST, may be null: sx / sy / sz point into the pinned staging buffer (host memory);
+                                              leave the device copy x[n] | y[n] | z[n] here for the launches that follow */) {
+    const Pose16& T0 = T0p;
     constexpr int G = 4;                 // lanes per query
-    constexpr int QPB = 256 / G;         // queries per workgroup
+    constexpr int QPB = kIvoxKnnQueries; // queries per workgroup
     constexpr int R = (19 + G - 1) / G;  // probe rounds per lane
     // XCD-aware block order: the dispatcher deals consecutive workgroups round-robin to the 8 XCDs, each with its own
     // 4 MiB L2.  Re-map so that XCD x walks CHUNKS of `chunk` consecutive workgroups (chunk * QPB consecutive points of
@@ -254,8 +265,6 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
     // loop below, and voxels hold 1..20+ points (4.7 trips of four candidates per wave before, 2.8 after).
     // The hit voxels are compacted into a per-group LDS table {prefix end, begin - prefix start}; a lane walks
     // its range through a two-entry window of that table (see the loop).
-    __shared__ __attribute__((aligned(16))) unsigned s_end[QPB][24];
-    __shared__ __attribute__((aligned(16))) unsigned s_off[QPB][24];
     const int g = threadIdx.x / G;
     const unsigned nz = (c0 ? 1u : 0u) + (c1 ? 1u : 0u) + (c2 ? 1u : 0u) + (c3 ? 1u : 0u) + (c4 ? 1u : 0u);
     const unsigned packed = tot * 32u + nz;  // candidates (< 2^27) and hit voxels (<= 19 per group) of this lane
@@ -375,6 +384,64 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
     }
 }
 
+template <bool COUNT, bool DENSE, bool FIRST, bool GEN>
+__global__ void __launch_bounds__(256)
+ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
+                const GnState* __restrict__ st, const Pose16 T0, const DevGrid grid, const BrickDir bd,
+                const float inv_res, float4* __restrict__ nn_pts, unsigned char* __restrict__ nn_cnt,
+                unsigned char* __restrict__ flag, TrafficCounters* __restrict__ tc, const int chunk,
+                unsigned* __restrict__ nn_ids, const int nn_prev, float* __restrict__ dev_copy) {
+    FLS_IVOX_KNN_SMEM_DECL;
+    ivox_knn_body<COUNT, DENSE, FIRST, GEN>(FLS_IVOX_KNN_SMEM_ARGS, sx, sy, sz, n, st, T0, grid, bd, inv_res, nn_pts, nn_cnt, flag, tc, chunk, nn_ids, nn_prev, dev_copy);
+}
+
+// One Gauss-Newton iteration's two launches for a GROUP of independent registrations against one map (fls_match_batch_shared_ivox): grid
+// (rows_max, jobs), blockIdx.y the job's entry in a device table (read through a uniform index: scalar loads), blockIdx.x the workgroup of
+// that job's OWN grid.  Every job's kNN grid is ceil(n / 64) rounded up to a multiple of 8 * chunk, as the single-job launch's, so the XCD
+// re-map of blockIdx.x stays a bijection per job; a workgroup past its job's grid leaves before anything else, a job that has stopped
+// leaves where the single-job kernel does.  Per job: the scan, the Gauss-Newton state, the neighbour lists, flags and stored rows, the
+// partial rows, ticket words and mailbox.  One for the group: the map image, its resolution and the thresholds.
+// A pointer read from the job table is a generic pointer to the compiler: loads through it would be flat loads, and the Gauss-Newton state, which
+// the single-job kernels (whose pointers are launch arguments) read with scalar loads, would arrive in vector registers -- 164 VGPRs instead of 128
+// in the fit kernel, one wave per SIMD fewer.  Every table pointer is device memory; saying so (through an integer, or the round trip is folded
+// away) gives the jobs kernels the single-job kernels' loads and registers.
+template <class T>
+__device__ __forceinline__ T* job_ptr(T* p) {
+    typedef __attribute__((address_space(1))) T* global_ptr;
+    return (T*)(global_ptr)(unsigned long long)p;
+}
+struct IvoxJob {
+    const float *sx, *sy, *sz;  // the job's scan
+    int n;                      // points
+    int knn_blocks;             // workgroups of its kNN grid (a multiple of 8 * chunk)
+    int nwg;                    // workgroups of its fit grid = partial rows
+    int nn_prev;                // size of nearest_points_ before the Match
+    GnState* st;
+    float4* nn_pts;
+    unsigned char* nn_cnt;
+    unsigned char* flag;
+    unsigned* nn_ids;
+    double* Jst;
+    double* partials;           // [nwg][kPartialStride]
+    unsigned* ticket;           // kTicketWords words of the job's own, zero between launches
+    Mailbox* mb;
+    unsigned launch_word, pad;
+    Pose16 T0;                  // the initial pose (read by the group's first launches)
+};
+template <bool DENSE, bool FIRST, bool GEN>
+__global__ void __launch_bounds__(256)
+ivox_knn_jobs_kernel(const IvoxJob* __restrict__ jobs, const DevGrid grid, const BrickDir bd, const float inv_res, const int chunk) {
+    const IvoxJob& j = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= j.knn_blocks) return;
+    FLS_IVOX_KNN_SMEM_DECL;
+    ivox_knn_body<false, DENSE, FIRST, GEN>(FLS_IVOX_KNN_SMEM_ARGS, job_ptr(j.sx), job_ptr(j.sy), job_ptr(j.sz), j.n, (const GnState*)job_ptr(j.st), Pose16Ref{&j.T0},
+                                            grid, bd, inv_res, job_ptr(j.nn_pts), job_ptr(j.nn_cnt), job_ptr(j.flag), (TrafficCounters*)nullptr, chunk,
+                                            job_ptr(j.nn_ids), j.nn_prev, (float*)nullptr);
+}
+#undef FLS_IVOX_KNN_SMEM_PARAMS
+#undef FLS_IVOX_KNN_SMEM_DECL
+#undef FLS_IVOX_KNN_SMEM_ARGS
+
 // ---------------------------------------------------------------------------------------------
 // p2plane_fit_solve_kernel: fit + residual + block reduction (one lane per source point, reading what
 // ivox_knn_kernel left behind), and the LAST workgroup to finish runs the Gauss-Newton
@@ -394,14 +461,34 @@ ivox_knn_kernel(const float* __restrict__ sx, const float* __restrict__ sy, cons
 // + state + mailbox 1.9 us.
 // ---------------------------------------------------------------------------------------------
 constexpr int kFitThreads = 512;
-template <bool FIRST, int NT = kFitThreads>
-__global__ void __launch_bounds__(NT)
-p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
-                         GnState* __restrict__ st, const Pose16 T0, const float4* __restrict__ nn_pts,
-                         const unsigned char* __restrict__ nn_cnt, double* __restrict__ Jst /* [7][n] */, unsigned char* __restrict__ flag,
-                         double* __restrict__ partials, unsigned* __restrict__ ticket, Mailbox* __restrict__ mb, const unsigned match_id,
-                         const double plane_thres, const double rot_thr, const double pos_thr, const int shards,
-                         const unsigned* __restrict__ nn_ids /* may be null */, const float4* __restrict__ map_pts, const unsigned n_slots) {
+// The body of workgroup blockIdx.x of ONE registration whose fit grid has `nrows` workgroups: p2plane_fit_solve_kernel is that registration alone
+// (nrows = LaunchBlocksX, the launch's gridDim.x), p2plane_fit_solve_jobs_kernel runs one per blockIdx.y (nrows = the job's own count).  The LDS
+// is the calling kernel's, as in icp_knn_fit_body.
+#if FLS_FIT_MFMA
+#define FLS_P2P_FIT_SMEM_PARAMS LoamTailSmem& sm, double (&wsum)[NT / 64][32], unsigned& s_ticket, double (&mfma_tile)[NT / 64][512]
+#define FLS_P2P_FIT_SMEM_DECL                                                      \
+    __shared__ LoamTailSmem sm;                                                    \
+    __shared__ double wsum[NT / 64][32];                                           \
+    __shared__ unsigned s_ticket;                                                  \
+    __shared__ __attribute__((aligned(64))) double mfma_tile[NT / 64][512]
+#define FLS_P2P_FIT_SMEM_ARGS sm, wsum, s_ticket, mfma_tile
+#else
+#define FLS_P2P_FIT_SMEM_PARAMS LoamTailSmem& sm, double (&wsum)[NT / 64][32], unsigned& s_ticket
+#define FLS_P2P_FIT_SMEM_DECL                                                      \
+    __shared__ LoamTailSmem sm;                                                    \
+    __shared__ double wsum[NT / 64][32];                                           \
+    __shared__ unsigned s_ticket
+#define FLS_P2P_FIT_SMEM_ARGS sm, wsum, s_ticket
+#endif
+template <bool FIRST, int NT, class N, class P>
+__device__ __forceinline__ void
+p2plane_fit_solve_body(FLS_P2P_FIT_SMEM_PARAMS, const N nrows, const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
+                       const int n, GnState* __restrict__ st, const P& T0p /* Pose16, or Pose16Ref */, const float4* __restrict__ nn_pts,
+                       const unsigned char* __restrict__ nn_cnt, double* __restrict__ Jst /* [7][n] */, unsigned char* __restrict__ flag,
+                       double* __restrict__ partials, unsigned* __restrict__ ticket, Mailbox* __restrict__ mb, const unsigned match_id,
+                       const double plane_thres, const double rot_thr, const double pos_thr, const int shards,
+                       const unsigned* __restrict__ nn_ids /* may be null */, const float4* __restrict__ map_pts, const unsigned n_slots) {
+    const Pose16& T0 = T0p;
     const int i = blockIdx.x * NT + threadIdx.x;
     const int done = FIRST ? 0 : st->done;
     double T44[16];
@@ -432,9 +519,6 @@ p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__
     const float px = sx[ii], py = sy[ii], pz = sz[ii];
     const unsigned char stale = FIRST ? (unsigned char)0 : flag[ii];  // the first kNN launch of a Match cleared the flags
     if (done) return;
-    __shared__ LoamTailSmem sm;
-    __shared__ double wsum[NT / 64][32];
-    __shared__ unsigned s_ticket;
 #ifdef FLS_TIMING
     const long long t_begin = (long long)__builtin_readcyclecounter();
 #endif
@@ -471,7 +555,6 @@ p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__
 #endif
     // wave sums -> LDS -> one row per workgroup (fixed order: wave 0 + wave 1 + ...)
 #if FLS_FIT_MFMA
-    __shared__ __attribute__((aligned(64))) double mfma_tile[NT / 64][512];
     reduce_rank1_mfma_and_store(contrib, J, res, &wsum[threadIdx.x >> 6][0], &mfma_tile[threadIdx.x >> 6][0]);
 #else
     reduce_rank1_and_store(contrib, J, res, &wsum[threadIdx.x >> 6][0]);
@@ -494,7 +577,7 @@ p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__
 #endif
     __syncthreads();
     // sharded fan-in (kernels_p2plane.hpp::fanin_last_arriver): which workgroup arrives last
-    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards, LaunchBlocksX{});
+    if (threadIdx.x == 0) s_ticket = fanin_last_arriver(ticket, shards, nrows);
     __syncthreads();
     if (!s_ticket) { store_point(); return; }
     // ---- last workgroup: Gauss-Newton tail (reads the rows with sc1 loads: no acquire fence either) ----
@@ -502,9 +585,42 @@ p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__
     if (threadIdx.x == 0) { st->dbg[0] = t_begin; st->dbg[13] = t_fit; st->dbg[14] = t_red; st->dbg[15] = t_drain; }
 #endif
     FLS_STAMP(1);
-    loam_tail<NT, true>(st, sm, nullptr, 0, partials, (int)gridDim.x, rot_thr, pos_thr, T44, last_rot, last_pos, it, mb, match_id);
+    loam_tail<NT, true>(st, sm, nullptr, 0, partials, (int)(unsigned)nrows, rot_thr, pos_thr, T44, last_rot, last_pos, it, mb, match_id);
     store_point();  // (every thread comes back from the tail: waves 1.. at once, wave 0 after it has published)
 }
+
+template <bool FIRST, int NT = kFitThreads>
+__global__ void __launch_bounds__(NT)
+p2plane_fit_solve_kernel(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
+                         GnState* __restrict__ st, const Pose16 T0, const float4* __restrict__ nn_pts,
+                         const unsigned char* __restrict__ nn_cnt, double* __restrict__ Jst, unsigned char* __restrict__ flag,
+                         double* __restrict__ partials, unsigned* __restrict__ ticket, Mailbox* __restrict__ mb, const unsigned match_id,
+                         const double plane_thres, const double rot_thr, const double pos_thr, const int shards,
+                         const unsigned* __restrict__ nn_ids, const float4* __restrict__ map_pts, const unsigned n_slots) {
+    FLS_P2P_FIT_SMEM_DECL;
+    p2plane_fit_solve_body<FIRST, NT>(FLS_P2P_FIT_SMEM_ARGS, LaunchBlocksX{}, sx, sy, sz, n, st, T0, nn_pts, nn_cnt, Jst, flag, partials, ticket, mb, match_id,
+                                      plane_thres, rot_thr, pos_thr, shards, nn_ids, map_pts, n_slots);
+}
+
+// The fit launch of a group (IvoxJob above): the jobs of ONE workgroup size -- NT is per job what the single-job path chooses, because another NT
+// regroups the wave sums -- as the rows of one grid (nwg_max, jobs).  A workgroup past its job's rows leaves before any barrier, row store or
+// ticket; the fan-in and the tail count the job's own nwg, so the job's rows, their order in the sum and the ticket protocol are the single-job
+// launch's, and the last arriver OF THE JOB solves and publishes the job's mailbox beside the other jobs' fits.
+template <bool FIRST, int NT>
+__global__ void __launch_bounds__(NT)
+p2plane_fit_solve_jobs_kernel(const IvoxJob* __restrict__ jobs, const double plane_thres, const double rot_thr, const double pos_thr, const int shards,
+                              const float4* __restrict__ map_pts, const unsigned n_slots) {
+    const IvoxJob& j = jobs[blockIdx.y];
+    if ((int)blockIdx.x >= j.nwg) return;
+    FLS_P2P_FIT_SMEM_DECL;
+    p2plane_fit_solve_body<FIRST, NT>(FLS_P2P_FIT_SMEM_ARGS, (unsigned)j.nwg, job_ptr(j.sx), job_ptr(j.sy), job_ptr(j.sz), j.n, job_ptr(j.st), Pose16Ref{&j.T0},
+                                      (const float4*)job_ptr(j.nn_pts), (const unsigned char*)job_ptr(j.nn_cnt), job_ptr(j.Jst), job_ptr(j.flag),
+                                      job_ptr(j.partials), job_ptr(j.ticket), job_ptr(j.mb), j.launch_word, plane_thres, rot_thr, pos_thr, shards,
+                                      (const unsigned*)job_ptr(j.nn_ids), map_pts, n_slots);
+}
+#undef FLS_P2P_FIT_SMEM_PARAMS
+#undef FLS_P2P_FIT_SMEM_DECL
+#undef FLS_P2P_FIT_SMEM_ARGS
 
 // ---------------------------------------------------------------------------------------------
 // Map maintenance on the device

@@ -287,6 +287,11 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ parti
 struct LaunchBlocksX {
     __device__ __forceinline__ operator unsigned() const { return gridDim.x; }
 };
+// an initial pose that stays where it is (a job-table entry) where a single-job kernel takes its Pose16 as a launch argument
+struct Pose16Ref {
+    const Pose16* p;
+    __device__ __forceinline__ operator const Pose16&() const { return *p; }
+};
 constexpr int kTicketWords = 32 * 10;  // [0] single counter (shards <= 1) | [32 (1 + s)] shard s | [32 * 9] top counter
 constexpr int kTicketShards = 8;       // the shard count every host launch passes
 template <class N>

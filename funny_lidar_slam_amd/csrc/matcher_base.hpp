@@ -1,7 +1,8 @@
 // matcher_base.hpp -- common host state of one registration handle (stream, device
 // Gauss-Newton state, wave partials, profiling events), the launch loop and the Match
 // epilogue every kind shares (run_mailbox_loop = begin_match, run_chunks over wait_mailboxes, end_match;
-// take_result), the batch-lane clone (make_lane, make_owned_lane) and the scan upload helper.
+// take_result), the group driver of the shared-launch batches (run_job_groups), the batch-lane clone (make_lane, make_owned_lane) and the
+// scan upload helper.
 #pragma once
 #include "host_maps.hpp"
 #include "kernels_handoff.hpp"
@@ -53,6 +54,9 @@ struct fls_matcher {
     unsigned launch_word() const { return fls::LaunchWord::pack(match_id, tail_exact, p.max_iterations).w; }  // what the tail kernels get
 
     virtual ~fls_matcher() {
+        for (hipEvent_t e : slot_ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : batch_tail_ev) if (e) (void)hipEventDestroy(e);
+        if (batch_stream) { (void)hipStreamSynchronize(batch_stream); (void)hipStreamDestroy(batch_stream); }
         for (auto e : ev_pool) if (e) (void)hipEventDestroy(e);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         if (mb_host) (void)hipHostFree(mb_host);
@@ -160,6 +164,133 @@ struct fls_matcher {
         return match_batch(n_jobs, s0, n0, s1, n1, stride, T, st, status, n_slots);
     }
 
+    // fls_match_batch_shared_ivox (include/fls_batch_ivox.h): the shared form of the iVox point-to-plane kind; every other kind answers as
+    // fls_match_batch_fused does.  fls_batch_ivox_stat: [0] shared kNN launches queued, [1] shared fit launches queued, [2] jobs that ran in
+    // shared launches, [3] jobs that ran outside them, [4] groups (since the handle was created)
+    size_t batch_ivox_counters[5] = {0, 0, 0, 0, 0};
+    virtual fls_status match_batch_shared_ivox(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const* s1, const size_t* n1, int stride,
+                                               double* T, fls_stats* st, int32_t* status, int n_slots) {
+        return match_batch_fused(n_jobs, s0, n0, s1, n1, stride, T, st, status, n_slots);
+    }
+
+    // ---- the group driver of the shared-launch batches (IcpMatcher::match_batch_fused, P2PlaneIvoxMatcher::match_batch_shared_ivox) ----
+    // Slots are the lane clones.  Per group: every slot uploads and prepares its job on its own stream and its own host thread (the ICP source filters
+    // are latency chains with a host wait each: they overlap), records an event, and the batch stream, behind those events, carries the group's iteration
+    // launches through run_chunks; the host waits on all the group's mailboxes.  Prepare, begin / end and finish are the single-job path's.
+    // With more than one group there are two sets of slots: the next group's uploads run while this group iterates.
+    // A kind supplies: prepare(q, slot, job, shared&) -- reset_job_state has run; upload + prepare of one job on slot q, `shared` = it waits for the
+    // group's launches (otherwise the status returned is the job's answer); table(call) -- the job-table entries of call.act (a Match has begun on each)
+    // and whatever else the group's launches need, queued on the batch stream; queue(call, first) -- one iteration's launches for the group on the batch
+    // stream; finish(q, job, word) -- end_match + the epilogue of one job.
+    hipStream_t batch_stream = nullptr;
+    hipEvent_t batch_tail_ev[2] = {nullptr, nullptr};  // per slot set: behind the last launch queued for the set's previous group
+    std::vector<hipEvent_t> slot_ev;                   // per slot: its job's scan is resident and prepared
+    int fused_expect_iters = 4;                        // the first chunk of a group: the previous group's largest iteration count
+    static hipEvent_t new_event() { hipEvent_t e = nullptr; FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; }
+    // what the steps of one call share
+    template <class M>
+    struct GroupCall {
+        const float* const* s0; const size_t* n0; int stride;  // the caller's arrays
+        double* T; fls_stats* st; int32_t* status;
+        size_t G;                          // slots per set
+        std::vector<fls_status> job_rc;    // per job
+        std::vector<char> shared;          // per slot: its job waits for the group's shared launches
+        bool tail_pending[2] = {false, false};  // launches of the set's previous group may still be queued on the batch stream
+        // the jobs of the current group that run in its shared launches
+        std::vector<M*> act;
+        std::vector<size_t> act_job, act_slot;
+        std::vector<unsigned> word;             // what each published last
+        void set_rc(const size_t j, const fls_status rc) { job_rc[j] = rc; if (status) status[j] = int32_t(rc); }
+        fls_stats* stats_of(const size_t j) const { return st ? &st[j] : nullptr; }
+    };
+    struct GroupCounters { size_t *shared_jobs, *outside_jobs, *groups; };
+    template <class M, class Prep, class Table, class Queue, class Finish>
+    fls_status run_job_groups(size_t n_jobs, const float* const* s0, const size_t* n0, int stride, double* T, fls_stats* st, int32_t* status, int n_slots,
+                              const GroupCounters ctr, Prep&& prepare, Table&& table, Queue&& queue, Finish&& finish) {
+        const int width = begin_batch(n_jobs, status, n_slots);
+        if (width <= 0) return fls_status(width);
+        GroupCall<M> c{s0, n0, stride, T, st, status, size_t(width)};
+        const size_t G = c.G, n_groups = (n_jobs + G - 1) / G;
+        const size_t n_sets = (n_groups > 1 && ensure_lanes(2 * G) == 2 * G) ? 2 : 1;
+        if (!batch_stream) {
+            FLS_HIP(hipStreamCreateWithFlags(&batch_stream, hipStreamNonBlocking));
+            for (hipEvent_t& e : batch_tail_ev) e = new_event();
+        }
+        while (slot_ev.size() < n_sets * G) { slot_ev.push_back(nullptr); slot_ev.back() = new_event(); }
+        c.job_rc.assign(n_jobs, FLS_SKIPPED);
+        c.shared.resize(n_sets * G);
+        // (1) per slot, side by side: upload + prepare.  A rejected job keeps its status; a job that does not wait for the shared launches is
+        // answered here (on the slot's own stream, if it launches at all).
+        auto slot_step = [this, &c, &prepare](const size_t set, const size_t l, const size_t j) {
+            const size_t s = set * c.G + l;
+            M* q = static_cast<M*>(lanes[s].get());
+            c.shared[s] = 0;
+            c.set_rc(j, fls::guarded([&]() -> fls_status {
+                FLS_HIP(hipSetDevice(q->device));
+                // an exit-at-once launch of the set's previous group reads this slot's state words: the slot's stream stays behind it
+                if (c.tail_pending[set]) FLS_HIP(hipStreamWaitEvent(q->stream, batch_tail_ev[set], 0));
+                tune_lane(*q);
+                q->reset_job_state();
+                bool shared = false;
+                const fls_status rc = prepare(q, s, j, shared);
+                if (rc == FLS_OK && shared) { FLS_HIP(hipEventRecord(slot_ev[s], q->stream)); c.shared[s] = 1; }
+                return rc;
+            }, "shared batch slot", s));
+        };
+        fls::Threads th[2];  // per slot set
+        auto start_group = [&](const size_t k) {
+            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
+            if (n_jobs == 1) { slot_step(set, 0, base); return; }
+            for (size_t l = 0; l < g; ++l) th[set].start([&slot_step, set, l, base] { slot_step(set, l, base + l); });
+        };
+        start_group(0);
+        for (size_t k = 0; k < n_groups; ++k) {
+            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
+            ++*ctr.groups;
+            th[set].join();
+            if (n_sets == 2 && k + 1 < n_groups) start_group(k + 1);  // the next group's uploads run beside this group's iterations
+            // (2) a Match begins on every slot of [set * G, set * G + g) that waits for the shared launches
+            c.act.clear(); c.act_job.clear(); c.act_slot.clear();
+            for (size_t l = 0; l < g; ++l) {
+                const size_t s = set * G + l;
+                if (!c.shared[s]) {
+                    if (c.job_rc[base + l] >= 0) ++*ctr.outside_jobs;  // (it ran, outside the shared launches)
+                    continue;
+                }
+                M* q = static_cast<M*>(lanes[s].get());
+                q->begin_match(int(p.max_iterations));
+                FLS_HIP(hipStreamWaitEvent(batch_stream, slot_ev[s], 0));
+                c.act.push_back(q);
+                c.act_job.push_back(base + l);
+                c.act_slot.push_back(s);
+            }
+            c.word.assign(c.act.size(), 0u);
+            if (!c.act.empty()) {
+                // (3) the group's launches on the batch stream, until every job has stopped or run max_iterations
+                const size_t A = c.act.size();
+                *ctr.shared_jobs += A;
+                table(c);
+                run_chunks(int(p.max_iterations), fused_expect_iters, [&](int, int first) { queue(c, first); }, [](int) {},
+                           [&](int launched) { return wait_mailboxes(batch_stream, c.act.data(), A, c.word.data(), launched); });
+                FLS_HIP(hipEventRecord(batch_tail_ev[set], batch_stream));
+                c.tail_pending[set] = true;
+                // (4) the epilogue per job
+                fused_expect_iters = 2;
+                for (size_t i = 0; i < A; ++i) {
+                    M* q = c.act[i];
+                    c.set_rc(c.act_job[i], finish(q, c.act_job[i], c.word[i]));
+                    fused_expect_iters = std::max(fused_expect_iters, q->expect_iters);
+                }
+            }
+            if (n_sets == 1 && k + 1 < n_groups) start_group(k + 1);
+        }
+        // the slots are also match_batch's lanes, which launch on their own streams: nothing of this call stays queued behind the return
+        if (c.tail_pending[0] || c.tail_pending[1]) FLS_HIP(hipStreamSynchronize(batch_stream));
+        for (size_t j = 0; j < n_jobs; ++j)
+            if (c.job_rc[j] < 0) return c.job_rc[j];  // the first negative status by job index; every job has run
+        return FLS_OK;
+    }
+
     void init_common() {
         if (const char* e = std::getenv("FLS_TAIL_EXACT")) tail_exact = std::atoi(e) != 0;
         FLS_HIP(hipSetDevice(device));
@@ -251,7 +382,7 @@ struct fls_matcher {
     // Gauss-Newton launch loop shared by every kind.  Iterations are enqueued in chunks sized by the previous
     // Match (steady-state SLAM needs about the same number every scan); the device decides convergence, kernels
     // of a finished Match exit at once, and the host learns the outcome from the mailbox without a blocking
-    // synchronisation.  Three parts, so that a group of handles can share the middle one (IcpMatcher::match_batch_fused):
+    // synchronisation.  Three parts, so that a group of handles can share the middle one (run_job_groups):
     // begin_match per handle, run_chunks once, end_match per handle with the word that handle published.
     int expect_iters = 4;
     void begin_match(int iters) {

@@ -6,6 +6,7 @@
 //   Match               :141-216  device-resident Gauss-Newton loop (2 launches / iteration, the host waits on a
 //                                 mailbox word instead of synchronising the stream)
 //   GetFitnessScore     :225-253  localization mode only (FloatNaN otherwise)
+//   fls_match_batch_shared_ivox   groups of batch jobs in shared launches (include/fls_batch_ivox.h; the group driver is matcher_base.hpp's)
 #pragma once
 #include "matcher_base.hpp"
 #include "kernels_p2plane.hpp"
@@ -509,11 +510,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         const float* const src_y = from_host ? hx + n : (const float*)scan.y.p;
         const float* const src_z = from_host ? hx + 2 * n : (const float*)scan.z.p;
         float* const dev_copy = from_host ? scan.xyz.p : nullptr;
-        const size_t nblk = (n + 63) / 64, gran = size_t(8) * size_t(kIvoxXcdChunk);
-        const dim3 grid(unsigned((nblk + gran - 1) / gran * gran));  // multiple of 8 * chunk: the XCD re-map is a bijection
-        // the kernel's general form (GEN) only where it can matter: voxels so large that a candidate of the 19 probed voxels could lie beyond
-        // max_range (3 res per axis, one voxel more than the geometry allows, reaches 5 m), or a point array of 4 GiB and more
-        const bool general = !(27.0f * ivox.resolution * ivox.resolution < 25.0f) || size_t(g.n_pts) > (size_t(1) << 28);
+        const dim3 grid(knn_grid_blocks(n));  // multiple of 8 * chunk: the XCD re-map is a bijection
+        const bool general = knn_general(g);
 #define FLS_KNN_G(C, D, F, GEN)                                                                                                      \
     hipExtLaunchKernelGGL((ivox_knn_kernel<C, D, F, GEN>), grid, dim3(256), 0, stream, e0, e1, 0, src_x, src_y, src_z, int(n),       \
                           (const GnState*)d_state.p, T0, g, win, ivox.inv_resolution, d_nn.p, d_nn_cnt.p, d_flag.p, d_tc.p, kIvoxXcdChunk, \
@@ -527,7 +525,28 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
 #undef FLS_KNN
     }
 
-    fls_status match_resident(double* T, int update_map, fls_stats* out) override {
+    // One Match in three parts -- prepare (checks, buffers, nn_prev, the grids, the initial pose), launch (the iteration launches and the wait for the
+    // mailbox), finish (the epilogue) -- so that a group of batch jobs can share the middle part (match_batch_shared_ivox) around the same prepare and finish.
+    struct MatchPlan {
+        bool go = false;      // false: prepare has answered the call (an error, or the empty scan)
+        size_t n = 0;
+        int fit_threads = 256, nwg = 0;
+        unsigned knn_blocks = 0;  // workgroups of the kNN grid: a multiple of 8 * kIvoxXcdChunk, so that the XCD re-map is a bijection
+        const IvoxImage* im = nullptr;
+        DevGrid g{};
+        BrickDir win{nullptr, 0u, nullptr, 0u};
+        Pose16 T0{};
+        bool spec = false;    // the speculative map-update chain rides behind the iteration chunks (single-job launch only)
+    };
+    static unsigned knn_grid_blocks(const size_t n) {
+        const size_t nblk = (n + 63) / 64, gran = size_t(8) * size_t(kIvoxXcdChunk);
+        return unsigned((nblk + gran - 1) / gran * gran);
+    }
+    // the kernel's general form (GEN) only where it can matter: voxels so large that a candidate of the 19 probed voxels could lie beyond
+    // max_range (3 res per axis, one voxel more than the geometry allows, reaches 5 m), or a point array of 4 GiB and more
+    bool knn_general(const DevGrid& g) const { return !(27.0f * ivox.resolution * ivox.resolution < 25.0f) || size_t(g.n_pts) > (size_t(1) << 28); }
+    fls_status match_prepare(double* T, int update_map, fls_stats* out, MatchPlan& m) {
+        m.go = false;
         if (replica_only && update_map) return FLS_ERR_STATE;  // (a replica's image has no AddPoints side and no mirror)
         const size_t n = scan.n;
         number_planar_point = n;
@@ -560,18 +579,30 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         // workgroup size of the fit kernel: 512 threads (two waves per SIMD of a CU) when the scan fills the machine anyway; 256 (one wave per
         // SIMD) up to 65,536 points, where 256 workgroups spread the same waves over every CU -- the 9.8k-point planar cloud the pipeline feeds
         // ran its 2,500-instruction fit phase two waves deep on 20 CUs with 236 CUs idle
-        const int fit_threads = n <= 65536 ? 256 : kFitThreads;
-        const int nwg = int((n + size_t(fit_threads) - 1) / size_t(fit_threads));
-        d_partials_b.reserve(size_t(nwg) * kPartialStride);
-        const int iters = int(p.max_iterations);
-        const DevGrid g = im.dev();
-        const BrickDir win = use_dense ? im.bricks() : BrickDir{nullptr, 0u, nullptr, 0u};
-        Pose16 T0;
-        std::memcpy(T0.m, T, sizeof(T0.m));
+        m.n = n;
+        m.fit_threads = n <= 65536 ? 256 : kFitThreads;
+        m.nwg = int((n + size_t(m.fit_threads) - 1) / size_t(m.fit_threads));
+        m.knn_blocks = knn_grid_blocks(n);
+        d_partials_b.reserve(size_t(m.nwg) * kPartialStride);
+        m.im = &im;
+        m.g = im.dev();
+        m.win = use_dense ? im.bricks() : BrickDir{nullptr, 0u, nullptr, 0u};
+        std::memcpy(m.T0.m, T, sizeof(m.T0.m));
         // speculative map update (see spec_pending): only where the short chain applies and the call would update the map if it converges
-        const bool spec = update_map && !p.is_localization_mode && !borrowed && !is_first && device_map &&
-                          dev_n_alive + n < ivox.capacity && int((n + kUpdBlock - 1) / kUpdBlock) <= kUpdMaxBlocks;
+        m.spec = update_map && !p.is_localization_mode && !borrowed && !is_first && device_map &&
+                 dev_n_alive + n < ivox.capacity && int((n + kUpdBlock - 1) / kUpdBlock) <= kUpdMaxBlocks;
         spec_pending = false;
+        m.go = true;
+        return FLS_OK;
+    }
+    unsigned match_launch(const MatchPlan& m) {
+        const size_t n = m.n;
+        const int iters = int(p.max_iterations), fit_threads = m.fit_threads, nwg = m.nwg;
+        const IvoxImage& im = *m.im;
+        const DevGrid& g = m.g;
+        const BrickDir& win = m.win;
+        const Pose16& T0 = m.T0;
+        const bool spec = m.spec;
         auto after_chunk = [&](int) {
             if (!spec) return;
             if (spec_pending) ++n_speculative_skipped;  // (the chain behind the previous chunk found the Match unfinished)
@@ -579,7 +610,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             spec_pending = counted && enqueue_update_chain(n, counted);
             ++n_speculative;
         };
-        const unsigned word = run_mailbox_loop(iters, n, [&](int it, int first) {
+        return run_mailbox_loop(iters, n, [&](int it, int first) {
             launch_knn(n, first, T0, g, win, profiling ? ev[2 * it] : nullptr, profiling ? ev[2 * it + 1] : nullptr);
 #define FLS_FIT_NT(F, NT)                                                                                                            \
     hipExtLaunchKernelGGL((p2plane_fit_solve_kernel<F, NT>), dim3(nwg), dim3(NT), 0, stream, nullptr, nullptr, 0, scan.x.p, scan.y.p, scan.z.p, int(n), \
@@ -591,6 +622,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
 #undef FLS_FIT_NT
 #undef FLS_FIT
         }, after_chunk);
+    }
+    fls_status match_finish(double* T, unsigned word, int update_map, fls_stats* out) {
         scan_in_staging = false;  // (the first launch left the device copy)
         nn_rows_current = false;  // the lists of every point with candidates are slots of the current image now
         const Mailbox& mb = take_result(word);
@@ -612,6 +645,91 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         spec_pending = false;
         if (out) *out = stats;
         return rc;
+    }
+    fls_status match_resident(double* T, int update_map, fls_stats* out) override {
+        MatchPlan m;
+        const fls_status prc = match_prepare(T, update_map, out, m);
+        if (!m.go) return prc;
+        return match_finish(T, match_launch(m), update_map, out);
+    }
+
+    // ---- fls_match_batch_shared_ivox (include/fls_batch_ivox.h): groups of up to n_slots jobs share the two launches of an iteration ----
+    // The group driver is the base's (matcher_base.hpp::run_job_groups).  Slots are the lane clones (they read this handle's image and upload with
+    // scan_upload, never from the staging buffer).  The job table holds the jobs of the 256-thread fit class first, then those of the 512-thread
+    // class: the kNN launch takes the whole table, each fit launch its class's part (a class keeps the workgroup size the single-job path gives its
+    // jobs, because another size regroups the wave sums) -- one fit launch per iteration for a group of one class, two for a mixed one.
+    PinnedBuf<IvoxJob> h_jobs;
+    DevBuf<IvoxJob> d_jobs;
+    fls_status match_batch_shared_ivox(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const*, const size_t*, int stride, double* T,
+                                       fls_stats* st, int32_t* status, int n_slots) override {
+        std::vector<MatchPlan> plan(size_t(2) * kMaxLanes);  // per slot
+        size_t n_class[2] = {0, 0};                           // jobs of the 256- / 512-thread fit class in the current group
+        unsigned knn_rows_max = 0, fit_rows_max[2] = {0, 0};
+        auto stats_of = [&](const size_t j) { return st ? &st[j] : nullptr; };
+        // the group's one map: this handle's image, with the predicates of launch_knn (read once the driver's prepare_batch has made it current)
+        DevGrid g{};
+        BrickDir win{nullptr, 0u, nullptr, 0u};
+        bool dense = false, general = false;
+        // an empty scan is answered on the host, as the single-job path answers it
+        auto prepare = [&](P2PlaneIvoxMatcher* q, const size_t s, const size_t j, bool& shared) -> fls_status {
+            fls_status rc = q->scan_upload(s0[j], n0[j], nullptr, 0, stride);
+            if (rc != FLS_OK) return rc;
+            rc = q->match_prepare(T + 16 * j, 0, stats_of(j), plan[s]);
+            shared = plan[s].go;
+            return rc;
+        };
+        auto table = [&](GroupCall<P2PlaneIvoxMatcher>& c) {
+            const size_t A = c.act.size();
+            if (!h_jobs.p) { h_jobs.reserve(kMaxLanes); d_jobs.reserve(kMaxLanes); }
+            g = image.dev();
+            win = use_dense ? image.bricks() : BrickDir{nullptr, 0u, nullptr, 0u};
+            dense = win.cells != nullptr;
+            general = knn_general(g);
+            n_class[0] = n_class[1] = 0;
+            knn_rows_max = fit_rows_max[0] = fit_rows_max[1] = 0;
+            for (size_t i = 0; i < A; ++i) ++n_class[plan[c.act_slot[i]].fit_threads == 256 ? 0 : 1];
+            size_t at[2] = {0, n_class[0]};
+            for (size_t i = 0; i < A; ++i) {
+                P2PlaneIvoxMatcher* q = c.act[i];
+                const MatchPlan& m = plan[c.act_slot[i]];
+                const int k = m.fit_threads == 256 ? 0 : 1;
+                IvoxJob& e = h_jobs.p[at[k]++];
+                e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
+                e.n = int(m.n); e.knn_blocks = int(m.knn_blocks); e.nwg = m.nwg; e.nn_prev = q->nn_prev;
+                e.st = q->d_state.p; e.nn_pts = q->d_nn.p; e.nn_cnt = q->d_nn_cnt.p; e.flag = q->d_flag.p; e.nn_ids = q->d_nn_ids.p;
+                e.Jst = q->d_J.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
+                e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
+                e.T0 = m.T0;
+                knn_rows_max = std::max(knn_rows_max, m.knn_blocks);
+                fit_rows_max[k] = std::max(fit_rows_max[k], unsigned(m.nwg));
+            }
+            // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
+            // and the copy below is ordered behind them on the batch stream)
+            FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IvoxJob), hipMemcpyHostToDevice, batch_stream));
+        };
+        auto queue = [&](GroupCall<P2PlaneIvoxMatcher>& c, const int first) {
+            const dim3 kg(knn_rows_max, unsigned(c.act.size()));
+#define FLS_KNN_J(D, F, GEN) hipLaunchKernelGGL((ivox_knn_jobs_kernel<D, F, GEN>), kg, dim3(256), 0, batch_stream, (const IvoxJob*)d_jobs.p, g, win, ivox.inv_resolution, kIvoxXcdChunk)
+#define FLS_KNN_L(D, F) do { if (general) FLS_KNN_J(D, F, true); else FLS_KNN_J(D, F, false); } while (0)
+#define FLS_KNN(D) do { if (first) FLS_KNN_L(D, true); else FLS_KNN_L(D, false); } while (0)
+            if (dense) FLS_KNN(true); else FLS_KNN(false);
+#undef FLS_KNN_J
+#undef FLS_KNN_L
+#undef FLS_KNN
+            ++batch_ivox_counters[0];
+#define FLS_FIT_J(F, NT, K, TAB)                                                                                                                          \
+    hipLaunchKernelGGL((p2plane_fit_solve_jobs_kernel<F, NT>), dim3(fit_rows_max[K], unsigned(n_class[K])), dim3(NT), 0, batch_stream, (const IvoxJob*)(TAB), \
+                       p.point_to_planar_thres, p.rotation_converge_thres, p.position_converge_thres, kTicketShards, (const float4*)g.pts, unsigned(image.d_pts.cap))
+            if (n_class[0]) { if (first) FLS_FIT_J(true, 256, 0, d_jobs.p); else FLS_FIT_J(false, 256, 0, d_jobs.p); ++batch_ivox_counters[1]; }
+            if (n_class[1]) { if (first) FLS_FIT_J(true, kFitThreads, 1, d_jobs.p + n_class[0]); else FLS_FIT_J(false, kFitThreads, 1, d_jobs.p + n_class[0]); ++batch_ivox_counters[1]; }
+#undef FLS_FIT_J
+        };
+        auto finish = [&](P2PlaneIvoxMatcher* q, const size_t j, const unsigned word) -> fls_status {
+            q->end_match(word, q->scan.n);
+            return q->match_finish(T + 16 * j, word, 0, stats_of(j));
+        };
+        return run_job_groups<P2PlaneIvoxMatcher>(n_jobs, s0, n0, stride, T, st, status, n_slots,
+                                                  GroupCounters{&batch_ivox_counters[2], &batch_ivox_counters[3], &batch_ivox_counters[4]}, prepare, table, queue, finish);
     }
 
     void reset_job_state() override { nn_n = 0; have_final = false; }  // nearest_points_ of a fresh matcher is empty

@@ -148,149 +148,54 @@ struct IcpMatcher final : fls_matcher {
     }
 
     // ---- fls_match_batch_fused: groups of up to n_slots jobs share one icp_knn_fit_jobs_kernel launch per iteration ----
-    // Slots are the lane clones.  Per group: every slot uploads and filters its job on its own stream and its own host thread (the filters are
-    // latency chains with a host wait each: they overlap), records an event, and the batch stream, behind those events, carries the group's iteration
-    // launches through run_chunks; the host waits on all the group's mailboxes.  Prepare, begin / end and finish are the single-job path's.
-    // With more than one group there are two sets of slots: the next group's filters run while this group iterates.
-    hipStream_t batch_stream = nullptr;
-    hipEvent_t batch_tail_ev[2] = {nullptr, nullptr};  // per slot set: behind the last launch queued for the set's previous group
-    std::vector<hipEvent_t> slot_ev;                   // per slot: its job's scan is filtered and resident
+    // The group driver is the base's (matcher_base.hpp::run_job_groups); this kind supplies the slot's upload + source filter + prepare, its job-table
+    // entries and the one launch of an iteration.
     PinnedBuf<IcpJob> h_jobs;
     DevBuf<IcpJob> d_jobs;
-    int fused_expect_iters = 4;                        // the first chunk of a group: the previous group's largest iteration count
-    ~IcpMatcher() override {
-        for (hipEvent_t e : slot_ev) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : batch_tail_ev) if (e) (void)hipEventDestroy(e);
-        if (batch_stream) { (void)hipStreamSynchronize(batch_stream); (void)hipStreamDestroy(batch_stream); }
-    }
-    static hipEvent_t new_event() { hipEvent_t e = nullptr; FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; }
-    // what the steps of one call share
-    struct FusedCall {
-        const float* const* s0; const size_t* n0; int stride;  // the caller's arrays
-        double* T; fls_stats* st; int32_t* status;
-        size_t G;                          // slots per set
-        std::vector<fls_status> job_rc;    // per job
-        std::vector<MatchPlan> plan;       // per slot
-        std::vector<char> shared;          // per slot: its job waits for the group's shared launches
-        bool tail_pending[2] = {false, false};  // launches of the set's previous group may still be queued on the batch stream
-        // the jobs of the current group that run in its shared launches, in job-table order
-        std::vector<IcpMatcher*> act;
-        std::vector<size_t> act_job;
-        std::vector<unsigned> word;             // what each published last
-        unsigned rows_max = 0; CellGridDev cg{};  // of the group's launches (one map for every job: the owner's grid)
-        void set_rc(const size_t j, const fls_status rc) { job_rc[j] = rc; if (status) status[j] = int32_t(rc); }
-        fls_stats* stats_of(const size_t j) const { return st ? &st[j] : nullptr; }
-    };
-    // (1) per slot, side by side: upload + source filter + prepare.  A rejected job keeps its status; a job whose filtered scan is empty is the
-    // per-lane path's from here (its launches go to the slot's own stream).
-    void fused_slot(FusedCall& c, const size_t set, const size_t l, const size_t j) {
-        const size_t s = set * c.G + l;
-        IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
-        c.shared[s] = 0;
-        c.set_rc(j, guarded([&]() -> fls_status {
-            FLS_HIP(hipSetDevice(q->device));
-            // an exit-at-once launch of the set's previous group reads this slot's state words: the slot's stream stays behind it
-            if (c.tail_pending[set]) FLS_HIP(hipStreamWaitEvent(q->stream, batch_tail_ev[set], 0));
-            q->reset_job_state();
-            fls_status rc = q->scan_upload(c.s0[j], c.n0[j], nullptr, 0, c.stride);
-            if (rc == FLS_OK) rc = q->match_prepare(c.T + 16 * j, c.plan[s]);
-            if (rc == FLS_OK && c.plan[s].n == 0) rc = q->match_finish(c.T + 16 * j, q->match_launch(c.plan[s]), 0, c.stats_of(j));
-            else if (rc == FLS_OK) { FLS_HIP(hipEventRecord(slot_ev[s], q->stream)); c.shared[s] = 1; }
-            return rc;
-        }, "fused batch slot", s));
-    }
-    // (2) the job table of the group in slots [set * G, set * G + g), jobs base ..: a Match begins on every slot that waits for the shared launches
-    void fused_job_table(FusedCall& c, const size_t set, const size_t base, const size_t g) {
-        c.act.clear(); c.act_job.clear(); c.rows_max = 0;
-        for (size_t l = 0; l < g; ++l) {
-            const size_t s = set * c.G + l;
-            if (!c.shared[s]) {
-                if (c.job_rc[base + l] >= 0) ++batch_counters[2];  // (it ran, on the per-lane path)
-                continue;
-            }
-            IcpMatcher* q = static_cast<IcpMatcher*>(lanes[s].get());
-            q->begin_match(int(p.max_iterations));
-            FLS_HIP(hipStreamWaitEvent(batch_stream, slot_ev[s], 0));
-            const MatchPlan& m = c.plan[s];
-            IcpJob& e = h_jobs.p[c.act.size()];
-            e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
-            e.n = int(m.n); e.rows = int(m.rows);
-            e.st = q->d_state.p; e.nn_id = q->d_nn_id.p; e.eff = q->d_eff.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
-            e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
-            e.T0 = m.T0;
-            c.rows_max = std::max(c.rows_max, m.rows);
-            c.cg = m.cg;
-            c.act.push_back(q);
-            c.act_job.push_back(base + l);
-        }
-        c.word.assign(c.act.size(), 0u);
-    }
-    // (3) the group's launches on the batch stream, until every job has stopped or run max_iterations
-    void fused_launch(FusedCall& c, const size_t set) {
-        const size_t A = c.act.size();
-        batch_counters[1] += A;
-        // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
-        // and the copy below is ordered behind them on the batch stream)
-        FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IcpJob), hipMemcpyHostToDevice, batch_stream));
-        run_chunks(int(p.max_iterations), fused_expect_iters,
-                   [&](int, int first) {
-                       hipLaunchKernelGGL(icp_knn_fit_jobs_kernel, dim3(c.rows_max, unsigned(A)), dim3(256), 0, batch_stream, (const IcpJob*)d_jobs.p, first, c.cg,
-                                          float(p.point_search_thres), p.point_search_thres, kTicketShards, p.rotation_converge_thres, p.position_converge_thres);
-                       ++batch_counters[0];
-                   },
-                   [](int) {}, [&](int launched) { return wait_mailboxes(batch_stream, c.act.data(), A, c.word.data(), launched); });
-        FLS_HIP(hipEventRecord(batch_tail_ev[set], batch_stream));
-        c.tail_pending[set] = true;
-    }
-    // (4) the epilogue per job
-    void fused_finish(FusedCall& c) {
-        fused_expect_iters = 2;
-        for (size_t i = 0; i < c.act.size(); ++i) {
-            IcpMatcher* q = c.act[i];
-            const size_t j = c.act_job[i];
-            q->end_match(c.word[i], q->scan.n);
-            fused_expect_iters = std::max(fused_expect_iters, q->expect_iters);
-            c.set_rc(j, q->match_finish(c.T + 16 * j, c.word[i], 0, c.stats_of(j)));
-        }
-    }
     fls_status match_batch_fused(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const*, const size_t*, int stride, double* T,
                                  fls_stats* st, int32_t* status, int n_slots) override {
-        const int width = begin_batch(n_jobs, status, n_slots);
-        if (width <= 0) return fls_status(width);
-        FusedCall c{s0, n0, stride, T, st, status, size_t(width)};
-        const size_t G = c.G, n_groups = (n_jobs + G - 1) / G;
-        const size_t n_sets = (n_groups > 1 && ensure_lanes(2 * G) == 2 * G) ? 2 : 1;
-        if (!batch_stream) {
-            FLS_HIP(hipStreamCreateWithFlags(&batch_stream, hipStreamNonBlocking));
-            for (hipEvent_t& e : batch_tail_ev) e = new_event();
-            h_jobs.reserve(kMaxLanes);
-            d_jobs.reserve(kMaxLanes);
-        }
-        while (slot_ev.size() < n_sets * G) { slot_ev.push_back(nullptr); slot_ev.back() = new_event(); }
-        c.job_rc.assign(n_jobs, FLS_SKIPPED);
-        c.plan.resize(n_sets * G);
-        c.shared.resize(n_sets * G);
-        Threads th[2];  // per slot set
-        auto start_group = [&](const size_t k) {
-            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
-            if (n_jobs == 1) { fused_slot(c, set, 0, base); return; }
-            for (size_t l = 0; l < g; ++l) th[set].start([this, &c, set, l, base] { fused_slot(c, set, l, base + l); });
+        std::vector<MatchPlan> plan(size_t(2) * kMaxLanes);  // per slot
+        unsigned rows_max = 0; CellGridDev cg{};              // of the group's launches (one map for every job: the owner's grid)
+        auto stats_of = [&](const size_t j) { return st ? &st[j] : nullptr; };
+        // a rejected job keeps its status; a job whose filtered scan is empty is the per-lane path's from here (its launches go to the slot's own stream)
+        auto prepare = [&](IcpMatcher* q, const size_t s, const size_t j, bool& shared) -> fls_status {
+            fls_status rc = q->scan_upload(s0[j], n0[j], nullptr, 0, stride);
+            if (rc == FLS_OK) rc = q->match_prepare(T + 16 * j, plan[s]);
+            if (rc == FLS_OK && plan[s].n == 0) return q->match_finish(T + 16 * j, q->match_launch(plan[s]), 0, stats_of(j));
+            shared = rc == FLS_OK;
+            return rc;
         };
-        start_group(0);
-        for (size_t k = 0; k < n_groups; ++k) {
-            const size_t base = k * G, g = std::min(G, n_jobs - base), set = k % n_sets;
-            ++batch_counters[3];
-            th[set].join();
-            if (n_sets == 2 && k + 1 < n_groups) start_group(k + 1);  // the next group's filters run beside this group's iterations
-            fused_job_table(c, set, base, g);
-            if (!c.act.empty()) { fused_launch(c, set); fused_finish(c); }
-            if (n_sets == 1 && k + 1 < n_groups) start_group(k + 1);
-        }
-        // the slots are also match_batch's lanes, which launch on their own streams: nothing of this call stays queued behind the return
-        if (c.tail_pending[0] || c.tail_pending[1]) FLS_HIP(hipStreamSynchronize(batch_stream));
-        for (size_t j = 0; j < n_jobs; ++j)
-            if (c.job_rc[j] < 0) return c.job_rc[j];  // the first negative status by job index; every job has run
-        return FLS_OK;
+        auto table = [&](GroupCall<IcpMatcher>& c) {
+            const size_t A = c.act.size();
+            if (!h_jobs.p) { h_jobs.reserve(kMaxLanes); d_jobs.reserve(kMaxLanes); }
+            rows_max = 0;
+            for (size_t i = 0; i < A; ++i) {
+                IcpMatcher* q = c.act[i];
+                const MatchPlan& m = plan[c.act_slot[i]];
+                IcpJob& e = h_jobs.p[i];
+                e.sx = q->scan.x.p; e.sy = q->scan.y.p; e.sz = q->scan.z.p;
+                e.n = int(m.n); e.rows = int(m.rows);
+                e.st = q->d_state.p; e.nn_id = q->d_nn_id.p; e.eff = q->d_eff.p; e.partials = q->d_partials_b.p; e.ticket = q->d_ticket.p;
+                e.mb = q->mb_dev; e.launch_word = q->launch_word(); e.pad = 0u;
+                e.T0 = m.T0;
+                rows_max = std::max(rows_max, m.rows);
+                cg = m.cg;
+            }
+            // (the pinned table is free: every launch that could read the device copy of the previous group's has been waited for or exits at once,
+            // and the copy below is ordered behind them on the batch stream)
+            FLS_HIP(hipMemcpyAsync(d_jobs.p, h_jobs.p, A * sizeof(IcpJob), hipMemcpyHostToDevice, batch_stream));
+        };
+        auto queue = [&](GroupCall<IcpMatcher>& c, const int first) {
+            hipLaunchKernelGGL(icp_knn_fit_jobs_kernel, dim3(rows_max, unsigned(c.act.size())), dim3(256), 0, batch_stream, (const IcpJob*)d_jobs.p, first, cg,
+                               float(p.point_search_thres), p.point_search_thres, kTicketShards, p.rotation_converge_thres, p.position_converge_thres);
+            ++batch_counters[0];
+        };
+        auto finish = [&](IcpMatcher* q, const size_t j, const unsigned word) -> fls_status {
+            q->end_match(word, q->scan.n);
+            return q->match_finish(T + 16 * j, word, 0, stats_of(j));
+        };
+        return run_job_groups<IcpMatcher>(n_jobs, s0, n0, stride, T, st, status, n_slots, GroupCounters{&batch_counters[1], &batch_counters[2], &batch_counters[3]},
+                                          prepare, table, queue, finish);
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }

@@ -147,6 +147,26 @@ class RegistrationInterface:
         """fls_batch_stat: 0 shared iteration launches queued, 1 jobs that ran in shared launches, 2 jobs on the per-lane path, 3 groups."""
         return int(_lib.lib().fls_batch_stat(self._h, int(slot)))
 
+    def MatchBatchSharedIvox(self, clusters, T_inits, slots: int = 8, raise_on_error: bool = True):
+        """fls_match_batch_shared_ivox (include/fls_batch_ivox.h): MatchBatch's jobs with the two launches of an iteration shared by up to
+        `slots` jobs (PointToPlane_IVOX; every other kind runs as MatchBatchFused).  Every job is what a fresh handle's
+        Match(..., update_map=False) on this map returns, bit for bit.  Returns (ok[j], T[j] (n,4,4), stats[j]); every job runs whatever
+        the others return, the per-job statuses stay in `batch_status`, the call's own in `batch_rc` (the first negative status by job
+        index), which raises FlsError unless raise_on_error is False."""
+        n, keep, p0s, n0s, p1s, n1s, stride, Tf, stats, status = self._batch_args(clusters, T_inits)
+        rc = _lib.lib().fls_match_batch_shared_ivox(self._h, n, p0s, n0s, p1s, n1s, stride, Tf.ctypes.data_as(C.POINTER(C.c_double)), stats, status,
+                                                    int(slots))
+        self.batch_rc, self.batch_status = int(rc), [int(status[j]) for j in range(n)]
+        if rc < 0 and raise_on_error:
+            raise FlsError(rc, "fls_match_batch_shared_ivox")
+        T = Tf.reshape(n, 4, 4).transpose(0, 2, 1).copy()
+        return [status[j] == _lib.FLS_OK for j in range(n)], T, list(stats)
+
+    def BatchIvoxStat(self, slot: int) -> int:
+        """fls_batch_ivox_stat: 0 shared kNN launches queued, 1 shared fit launches queued, 2 jobs that ran in shared launches, 3 jobs that ran
+        outside them, 4 groups."""
+        return int(_lib.lib().fls_batch_ivox_stat(self._h, int(slot)))
+
     def Replicas(self, device_ids):
         """fls_replicas_create: one handle per entry of device_ids, each with a copy of this handle's map (one process, N GPUs)."""
         return ReplicaSet(self, device_ids)
