@@ -1,11 +1,12 @@
-// host_util.hpp -- host-side plumbing: HIP error handling, the exception-to-status ladder, the host-mapped-word spin wait, device
-// buffers, pinned staging.
+// host_util.hpp -- host-side plumbing: HIP error handling, the exception-to-status ladder, the host-mapped-word spin wait, the
+// bools-to-template-arguments dispatch, device buffers, pinned staging.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 #include <stdexcept>
 #include "../../include/fls_reg.h"
@@ -66,6 +67,16 @@ bool spin_until(hipStream_t stream, F&& ready) {
         __builtin_ia32_pause();
 #endif
     }
+}
+
+// Run-time bools into template arguments: with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), so a generic
+// lambda can name kernel<A.value, B.value, ...> -- one instantiation per combination, selected by a ladder of ifs written here once.
+template <class F>
+void with_bools(F&& f) { f(); }
+template <class F, class... Rest>
+void with_bools(F&& f, const bool b, const Rest... rest) {
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 // growable device buffer; contents are NOT preserved on growth unless keep=true

@@ -137,7 +137,7 @@ struct IvoxImage {
     // what one brick of the pool costs: cells 8 B + the per-cell side arrays of the device AddPoints (cap 1 + stamp 8 + pend 4 + rank 4) per
     // slab cell, the reverse key and the neighbour-index row
     static constexpr size_t kPoolBrickBytes = size_t(kBrickStride) * (8 + 1 + 8 + 4 + 4) + 8 + 32 * 4;
-    bool budget_exceeded = false;  // sticky: the owner switches to the hash-table form (P2PlaneIvoxMatcher::refresh_image)
+    bool budget_exceeded = false;  // sticky: the owner switches to the hash-table form (IvoxMap::refresh)
     static size_t brick_budget_bytes() {
         static const size_t v = [] { const char* e = std::getenv("FLS_IVOX_BRICK_BUDGET_MB"); return size_t(e ? std::max(1L, std::atol(e)) : 16384L) << 20; }();
         return v;
@@ -249,7 +249,7 @@ struct IvoxImage {
     }
     // ---- read-only replica (fls_replicas_*): the kNN side of another handle's image, device to device ----
     // points, directory and slabs (or the per-voxel table) and nothing of the AddPoints side: the handle that owns this copy serves
-    // fls_match_batch only (P2PlaneIvoxMatcher::replicate_from).  `used_slots` / `n_bricks_live` are the SOURCE's current counts (its device
+    // fls_match_batch only (IvoxMap::replicate).  `used_slots` / `n_bricks_live` are the SOURCE's current counts (its device
     // state while the device maintains the map); the source's stream must be idle.
     void clone_for_reading(const IvoxImage& src, size_t used_slots, size_t n_bricks_live, int src_device, int dst_device, hipStream_t s) {
         auto copy = [&](void* d, const void* q, size_t bytes) {

@@ -1,0 +1,435 @@
+// ivox_map.hpp -- the iVox local map of FLS_P2PLANE_IVOX without a matcher around it: the replacement of IVoxMap as LoamPointToPlaneIVOX
+// uses it (InitIVox :53-58, the AddPoints side of AddCloudToLocalMap :60-139).  Host mirror (HostIvox) + device image (IvoxImage) + the rule
+// which of the two is the map (State; diagram in DESIGN.md 3), the device-side AddPoints (enqueue_update / await_update) and the ways a
+// map travels (blob, replica, flat image).  Everything is queued on the one stream given to init().
+#pragma once
+#include "ivox_image.hpp"
+#include "device_voxelgrid.hpp"
+#include <algorithm>
+
+namespace fls {
+
+struct IvoxMap {
+    HostIvox ivox;
+    IvoxImage image;
+    // Who holds the map, and (while the mirror does) how the image stands against it.  The image of a Device or Replica map is current by
+    // definition.  Transitions: the functions marked "-> State" below, nothing else assigns `state`.
+    enum class State {
+        MirrorUnbuilt,  // the host mirror is the map; the image must be flattened from it (never built, or the device refused a batch for lack of room)
+        MirrorStale,    // the host mirror is the map; the image lacks the mirror's journal
+        MirrorCurrent,  // the host mirror is the map; the image shows it
+        Device,         // the device image is the map (points, voxel table, LRU stamps, counts); the mirror is stale until to_mirror()
+        Replica,        // the image is a read-only copy of another map's kNN side; the mirror is empty, there is no AddPoints side
+    };
+    State state = State::MirrorUnbuilt;
+    bool on_device() const { return state == State::Device; }
+    bool is_replica() const { return state == State::Replica; }
+
+    hipStream_t stream = nullptr;
+    unsigned kind = 0;
+    bool mapping_mode = true;      // !is_localization_mode: only a map that Match updates goes to the device
+    bool allow_device_map = true;  // FLS_IVOX_DEVICE_UPDATE=0: always the host path (A/B)
+    bool use_dense = true;         // brick image instead of the hash table (FLS_IVOX_DENSE=0 disables; a brick pool over its budget too)
+    bool is_first = true;          // the reference's function-static flag (:62), per map here
+    // map_size slots 100-104, 117, 119-126 (see counter())
+    size_t n_incremental = 0, n_full_rebuilds = 0;
+    size_t n_device_updates = 0, n_host_fallbacks = 0, n_device_evictions = 0, n_device_recreated = 0, n_refused_conflict = 0, n_refused_full = 0, n_refused_outside = 0;
+    size_t n_short_updates = 0, n_speculative = 0, n_speculative_skipped = 0;
+    // ---- device-side AddPoints: persistent state, the mailbox its commit kernel writes, the counts mirrored from it ----
+    DevBuf<IvoxUpdState> d_upd_state;
+    IvoxUpdMailbox* upd_mb_host = nullptr;
+    IvoxUpdMailbox* upd_mb_dev = nullptr;
+    unsigned upd_seq = 0;
+    size_t dev_n_points = 0, dev_n_alive = 0, dev_n_bricks = 0;
+    unsigned long long stamp_bound = 0;  // upper bound of every LRU stamp on the device (sizes the second sort round)
+    // scratch of one update chain
+    DevBuf<uint2> d_lx, d_bt;
+    DevBuf<unsigned> d_seq_src, d_seq_cell, d_jj, d_tlist;
+    DevBuf<uint4> d_px, d_bt2;
+    DevBuf<unsigned char> d_fbit;
+    DevicePairSort ev_sort;
+    DevBuf<unsigned> d_ev_bt, d_crank, d_evict_list;
+    PinnedBuf<char> upd_stage;
+    DevBuf<unsigned> d_counter_img;
+
+    ~IvoxMap() {
+        if (stream) (void)hipStreamSynchronize(stream);  // (the owner destroys the stream after its members)
+        if (upd_mb_host) (void)hipHostFree(upd_mb_host);
+    }
+    void init(hipStream_t s, unsigned kind_, bool localization_mode) {
+        stream = s; kind = kind_; mapping_mode = !localization_mode;
+        if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
+        d_upd_state.reserve(1);
+        FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
+        std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
+        FLS_HIP(hipHostGetDevicePointer((void**)&upd_mb_dev, upd_mb_host, 0));
+        ivox.resolution = 0.5f;       // InitIVox :53-58
+        ivox.inv_resolution = 1.0f / 0.5f;
+        ivox.capacity = 1000000;
+        if (const char* e = std::getenv("FLS_IVOX_CAPACITY")) { const long c = std::atol(e); if (c > 1) ivox.capacity = size_t(c); }  // test hook (LRU eviction)
+    }
+
+    // ---- transitions ----
+    // -> MirrorStale (MirrorUnbuilt stays).  Pre: the mirror is the map and the caller has inserted into `ivox`.
+    void mirror_changed() { if (state == State::MirrorCurrent) state = State::MirrorStale; }
+    // -> MirrorUnbuilt, the mirror empty.  Pre: none (the stream idle if the image may be in use).
+    void become_empty() { ivox.clear(); state = State::MirrorUnbuilt; }
+    // -> Replica.  Pre: become_empty(), then `image` filled with a complete kNN side (clone_for_reading / import_flat).
+    void become_replica() { state = State::Replica; }
+    // -> MirrorCurrent, then Device where enter_device() allows.  Pre: none; a Device, Replica or MirrorCurrent map is left as it is.
+    // Scatters the mirror's journal into the image when possible, else re-flattens.
+    void refresh() {
+        if (state != State::MirrorUnbuilt && state != State::MirrorStale) return;
+        image.want_hash = !use_dense;
+        if (state == State::MirrorStale && image.collect_incremental(ivox)) {
+            if (image.dir_dirty) image.upload_directory(stream);  // the host path created bricks (their slabs are still zero)
+            image.scatter_cell_records(stream, upd_stage);
+            ++n_incremental;
+        } else {
+            image.build_from_ivox(ivox, stream, upd_stage);
+            if (image.budget_exceeded) use_dense = false;  // brick pool over its byte budget: per-voxel hash table from now on (map_size(132))
+            ++n_full_rebuilds;
+        }
+        state = State::MirrorCurrent;
+        enter_device();
+    }
+    // -> Device.  Pre: MirrorCurrent.  Hands the map over to the device-side AddPoints: the brick image has no extent limit, so the only
+    // conditions are the A/B switch, a brick image, mapping mode and an LRU capacity the eviction selection can work with.
+    void enter_device() {
+        if (!allow_device_map || !use_dense || !image.have_bricks || image.want_hash || !mapping_mode || ivox.capacity < 4) return;
+        const unsigned long long stamp_base = image.upload_update_meta(ivox, stream, upd_stage);
+        IvoxUpdState st{};
+        st.n_points = ivox.n_points; st.used = image.used; st.garbage = image.garbage; st.stamp_base = stamp_base;
+        st.pts_capacity = image.d_pts.cap; st.n_alive = unsigned(ivox.n_alive); st.lru_capacity = unsigned(std::min<size_t>(ivox.capacity, 0xffffffffu));
+        st.next_id = ivox.next_id;
+        st.n_bricks = unsigned(image.n_bricks());
+        FLS_HIP(hipMemcpyAsync(d_upd_state.p, &st, sizeof(st), hipMemcpyHostToDevice, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        dev_n_points = ivox.n_points; dev_n_alive = ivox.n_alive; dev_n_bricks = image.n_bricks();
+        stamp_bound = stamp_base;
+        state = State::Device;
+    }
+    // -> MirrorCurrent.  Pre: none; anything but a Device map is left as it is.  The device image back into the host mirror: the alive
+    // voxels as records (one compaction kernel), their points, the LRU order from the stamps, and the bricks the device created.
+    void to_mirror() {
+        if (!on_device()) return;
+        IvoxUpdState st{};
+        FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        const size_t nb = std::min<size_t>(st.n_bricks, image.n_bricks_cap), ncell = nb * kBrickStride, n_alive = st.n_alive;
+        image.d_alive_rec.reserve(std::max<size_t>(n_alive, 1));
+        image.d_counter.reserve(1);
+        FLS_HIP(hipMemsetAsync(image.d_counter.p, 0, sizeof(unsigned), stream));
+        if (ncell)
+            hipLaunchKernelGGL(ivox_list_alive_kernel, dim3(unsigned((ncell + 255) / 256)), dim3(256), 0, stream, (const uint2*)image.d_cells.p,
+                               (const unsigned long long*)image.d_brick_key.p, unsigned(ncell), (const unsigned char*)image.d_cap_log2.p,
+                               (const unsigned long long*)image.d_stamp.p, image.d_alive_rec.p, image.d_counter.p, unsigned(n_alive));
+        FLS_HIP(hipGetLastError());
+        unsigned n_listed = 0;
+        std::vector<IvoxAliveRec> recs(n_alive);
+        std::vector<Pt4> pts(st.used);
+        FLS_HIP(hipMemcpyAsync(&n_listed, image.d_counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        if (n_alive) FLS_HIP(hipMemcpyAsync(recs.data(), image.d_alive_rec.p, n_alive * sizeof(IvoxAliveRec), hipMemcpyDeviceToHost, stream));
+        if (st.used) FLS_HIP(hipMemcpyAsync(pts.data(), image.d_pts.p, st.used * sizeof(Pt4), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        if (n_listed != n_alive) throw std::runtime_error("iVox image: the alive-voxel count of the device state does not match its cells");
+        image.download_directory(nb, stream);
+        std::vector<HostIvox::ImageVoxel> vox;
+        vox.reserve(n_alive);
+        for (const IvoxAliveRec& r : recs) vox.push_back(HostIvox::ImageVoxel{r.key, r.begin, r.count, r.cap_log2 ? (1u << r.cap_log2) : 0u, r.stamp});
+        load_mirror(vox, pts.data(), size_t(st.n_points), st.next_id);
+        image.used = size_t(st.used);
+        image.garbage = size_t(st.garbage);
+        image.n_pts_live = size_t(st.n_points);
+        state = State::MirrorCurrent;
+    }
+    // what await_update learned of the batch queued last
+    enum class Verdict {
+        Applied,
+        Skipped,         // a speculative chain that found nothing to do: nothing ran
+        Refused,         // an eviction-order conflict or a point outside the key range: nothing was applied
+        RefusedForRoom,  // the point array or the brick pool is full: nothing was applied, the image needs more room
+    };
+    // -> MirrorCurrent, or MirrorUnbuilt after RefusedForRoom (the next refresh re-flattens with more room).  Pre: Device, and the batch
+    // at hand was refused (`v`) or is too large for the device (Refused).  The caller replays it on the mirror.
+    void fall_back(const Verdict v) {
+        ++n_host_fallbacks;
+        to_mirror();
+        if (v == Verdict::RefusedForRoom) state = State::MirrorUnbuilt;
+    }
+
+    // ---- the device-side AddPoints ----
+    static int update_blocks(const size_t n) { return int((n + kUpdBlock - 1) / kUpdBlock); }
+    // the count side of a batch of n points, for the launch that decides the insertion codes (it then counts them per block and opens the
+    // batch: ivox_upd_count's job).  All null unless the device holds the map and the batch fits one scan workgroup.
+    struct CountArgs { uint2 *lx = nullptr, *bt = nullptr; unsigned *status = nullptr, *apply = nullptr; };
+    CountArgs count_args(const size_t n) {
+        const int nb = update_blocks(n);
+        if (!on_device() || nb > kUpdMaxBlocks) return CountArgs{};
+        d_lx.reserve(n); d_bt.reserve(size_t(nb));
+        return CountArgs{d_lx.p, d_bt.p, &d_upd_state.p->status, &d_upd_state.p->apply};
+    }
+    // a batch of n points takes the short chain behind a counting decision launch: it fits and cannot reach the LRU capacity
+    bool short_chain_applies(const size_t n) const { return on_device() && dev_n_alive + n < ivox.capacity && update_blocks(n) <= kUpdMaxBlocks; }
+    // The launches of one batch (no waiting): `code` / `pw` are the decision launch's insertion codes and world points, `counted` says it
+    // has counted them (count_args).  Pre: Device.  false: the batch is too large for the device path, nothing was queued.
+    // Two forms of the same phases (kernels_ivox_update.hpp): the SHORT chain (five launches behind the decision) and the LONG chain,
+    // which batches that may reach the LRU capacity need (the eviction selection has grid-wide steps of its own).
+    bool enqueue_update(const unsigned char* code, const float4* pw, const size_t n, const bool counted) {
+        const int nb = update_blocks(n);
+        if (nb > kUpdMaxBlocks) return false;
+        d_lx.reserve(n); d_bt.reserve(size_t(nb)); d_seq_src.reserve(n); d_seq_cell.reserve(n); d_jj.reserve(n); d_tlist.reserve(n);
+        d_px.reserve(n); d_bt2.reserve(size_t(nb)); d_fbit.reserve(n);
+        const IvoxUpdBatch b{code, pw, int(n), d_lx.p, d_bt.p, d_seq_src.p, d_seq_cell.p, d_jj.p, d_px.p, d_bt2.p, d_fbit.p, d_tlist.p};
+        const IvoxUpdArrays a{image.d_cells.p, image.d_pts.p, image.d_cap_log2.p, image.d_stamp.p, image.d_pend.p, image.d_rank_mm.p,
+                              image.d_dir.p, image.dir_mask, unsigned(image.n_bricks_cap), image.d_brick_key.p, image.d_nbr.p, ivox.inv_resolution};
+        upd_seq = (upd_seq + 1u) & 0x7fffffffu;
+        if (upd_seq == 0u) upd_seq = 1u;
+        const dim3 g{unsigned(nb), 1u, 1u}, t{unsigned(kUpdBlock), 1u, 1u};
+        IvoxUpdState* const st = d_upd_state.p;
+        const IvoxUpdState* const cst = st;
+        const bool short_chain = dev_n_alive + n < ivox.capacity && counted;
+        if (short_chain) {
+            hipLaunchKernelGGL(ivox_upd_seq_nb, g, t, 0, stream, b, a, st, nb);
+        } else {
+            hipLaunchKernelGGL(ivox_upd_count, g, t, 0, stream, b);
+            hipLaunchKernelGGL(ivox_upd_scan1, dim3(1), dim3(kUpdMaxBlocks), 0, stream, b, nb, st);
+            hipLaunchKernelGGL(ivox_upd_seq, g, t, 0, stream, b, a, st);
+        }
+        hipLaunchKernelGGL(ivox_upd_plan, g, t, 0, stream, b, a, cst);
+        if (short_chain) {
+            hipLaunchKernelGGL(ivox_upd_last_regions, g, t, 0, stream, b, a, st);
+            ++n_short_updates;
+        } else {
+            // LRU evictions inside the batch: whenever the batch COULD reach the capacity (every point a new voxel), the alive cells are
+            // listed and sorted by their 64-bit stamp (two stable 32-bit radix rounds) so that scan2 / ivox_evict_check can pick the tail
+            const bool may_evict = dev_n_alive + n >= ivox.capacity && dev_n_alive > 0;
+            const unsigned n_list = may_evict ? unsigned(dev_n_alive) : 0u;
+            if (may_evict) {
+                const unsigned ncell = unsigned(dev_n_bricks * kBrickStride), nbe = (ncell + kEvBlock - 1) / kEvBlock;  // (bricks this batch creates hold no candidate)
+                d_ev_bt.reserve(size_t(2) * nbe);
+                ev_sort.prepare(n_list);
+                hipLaunchKernelGGL(ivox_evict_count, dim3(nbe), dim3(kEvBlock), 0, stream, (const uint2*)image.d_cells.p, ncell, d_ev_bt.p);
+                hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)d_ev_bt.p, d_ev_bt.p + nbe, int(nbe), (unsigned*)nullptr);
+                hipLaunchKernelGGL(ivox_evict_list, dim3(nbe), dim3(kEvBlock), 0, stream, (const uint2*)image.d_cells.p, (const unsigned long long*)image.d_stamp.p, ncell,
+                                   (const unsigned*)(d_ev_bt.p + nbe), ev_sort.k0, ev_sort.v0);
+                ev_sort.run(4, stream);
+                hipLaunchKernelGGL(ivox_evict_hikeys, dim3((n_list + 255u) / 256u), dim3(256), 0, stream, (const unsigned long long*)image.d_stamp.p,
+                                   (const unsigned*)ev_sort.v0, n_list, ev_sort.k0);
+                ev_sort.run(DevicePairSort::passes_for((unsigned long long)((stamp_bound + n) >> 32) + 1ull), stream);
+            }
+            hipLaunchKernelGGL(ivox_upd_scan2, dim3(1), dim3(kUpdMaxBlocks), 0, stream, b, st, may_evict ? 1u : 0u, n_list);  // (also decides when no eviction selection follows)
+            if (may_evict) {
+                d_crank.reserve(n);
+                d_evict_list.reserve(n);
+                hipLaunchKernelGGL(ivox_upd_cranks, g, t, 0, stream, b, a, cst, d_crank.p);
+                hipLaunchKernelGGL(ivox_evict_select, dim3(1), dim3(kEvBlock), 0, stream, (const unsigned*)ev_sort.v0, a, st, (const unsigned*)d_crank.p, d_evict_list.p);
+                // voxels the selection evicts BEFORE their first point of this batch arrives are re-created by it (such a batch used to be
+                // refused): the plan runs again seeing them as creations, and the totals / block offsets / point-array check with it
+                hipLaunchKernelGGL(ivox_upd_plan, g, t, 0, stream, b, a, cst);
+                hipLaunchKernelGGL(ivox_upd_scan2_again, dim3(1), dim3(kUpdMaxBlocks), 0, stream, b, st);
+                hipLaunchKernelGGL(ivox_upd_decide, dim3(1), dim3(64), 0, stream, st);  // (the selection may still refuse the batch)
+                hipLaunchKernelGGL(ivox_evict_apply, g, t, 0, stream, (const unsigned*)d_evict_list.p, a, st);
+            }
+            hipLaunchKernelGGL(ivox_upd_last, g, t, 0, stream, b, a, cst);
+            hipLaunchKernelGGL(ivox_upd_regions, g, t, 0, stream, b, a, cst);
+        }
+        hipLaunchKernelGGL(ivox_upd_points, g, t, 0, stream, b, a, cst);
+        hipLaunchKernelGGL(ivox_upd_finish, dim3(unsigned((n + kUpdBlock / 64 - 1) / (kUpdBlock / 64))), t, 0, stream, b, a, cst);
+        hipLaunchKernelGGL(ivox_upd_commit, dim3(1), dim3(64), 0, stream, st, upd_mb_dev, upd_seq, unsigned(image.n_bricks_cap));
+        FLS_HIP(hipGetLastError());
+        return true;
+    }
+    // The verdict of the batch of n points queued last.  Pre: Device.  (A few words in host-mapped memory: no copy, no stream synchronisation.)
+    Verdict await_update(const size_t n) {
+        (void)spin_until(stream, [&] { return __atomic_load_n(&upd_mb_host->seq, __ATOMIC_ACQUIRE) == upd_seq; });  // (a drained stream just ends the wait)
+        dev_n_bricks = std::min<size_t>(upd_mb_host->n_bricks, image.n_bricks_cap);  // (bricks are created whatever the verdict)
+        const unsigned status = upd_mb_host->status;
+        if (status & kUpdSkipped) return Verdict::Skipped;
+        if (status != kUpdOk) {
+            if (status & kUpdEvictConflict) ++n_refused_conflict;
+            if (status & kUpdArrayFull) ++n_refused_full;
+            if (status & kUpdOutside) ++n_refused_outside;
+            return (status & kUpdArrayFull) ? Verdict::RefusedForRoom : Verdict::Refused;
+        }
+        dev_n_points = size_t(upd_mb_host->n_points);
+        dev_n_alive = size_t(upd_mb_host->n_alive);
+        stamp_bound += n;
+        n_device_evictions += upd_mb_host->evicted;
+        n_device_recreated += upd_mb_host->recreated;
+        ++n_device_updates;
+        return Verdict::Applied;
+    }
+
+    // slots in use + bricks, from the device's own state while it maintains the map
+    size_t live_counts(size_t& n_bricks_live) {
+        if (!on_device()) { n_bricks_live = image.n_bricks(); return image.used; }
+        IvoxUpdState st{};
+        FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        n_bricks_live = std::min<size_t>(st.n_bricks, image.n_bricks_cap);
+        return size_t(st.used);
+    }
+    // the mirror from voxel records + their points; resolution and capacity are the map's own, not the records'
+    void load_mirror(std::vector<HostIvox::ImageVoxel>& vox, const Pt4* pts, const size_t n_points, const int next_id) {
+        const float res = ivox.resolution, inv = ivox.inv_resolution;
+        const size_t capacity = ivox.capacity;
+        ivox.rebuild_from_image(vox, pts, n_points, next_id);
+        ivox.resolution = res; ivox.inv_resolution = inv; ivox.capacity = capacity;
+    }
+
+    // ---- map export / import (fls_reg.h): header, voxels from the LRU tail (oldest) to the head {key, count}, then the
+    // points {x, y, z, id} of the voxels in the same order
+    struct BlobHeader {
+        char magic[8];
+        unsigned version, kind;
+        float resolution;
+        unsigned is_first;
+        unsigned long long capacity, n_voxels, n_points;
+        long long next_id;
+    };
+    struct BlobVoxel { unsigned long long key; unsigned count, pad; };
+    // Pre: not a Replica.  A Device map passes through the mirror and goes back to the device.
+    size_t export_blob(void* blob, size_t cap) {
+        const bool was_device = on_device();
+        to_mirror();
+        const size_t need = sizeof(BlobHeader) + ivox.n_alive * sizeof(BlobVoxel) + ivox.n_points * sizeof(Pt4);
+        if (blob && cap >= need) {
+            char* w = static_cast<char*>(blob);
+            BlobHeader hd{};
+            std::memcpy(hd.magic, "FLSIVOX1", 8);
+            hd.version = 1; hd.kind = kind; hd.resolution = ivox.resolution; hd.is_first = is_first ? 1u : 0u;
+            hd.capacity = ivox.capacity; hd.n_voxels = ivox.n_alive; hd.n_points = ivox.n_points; hd.next_id = ivox.next_id;
+            std::memcpy(w, &hd, sizeof(hd));
+            BlobVoxel* bv = reinterpret_cast<BlobVoxel*>(w + sizeof(hd));
+            Pt4* bp = reinterpret_cast<Pt4*>(w + sizeof(hd) + ivox.n_alive * sizeof(BlobVoxel));
+            size_t k = 0, q = 0;
+            for (int v = ivox.tail; v >= 0; v = ivox.pool[v].prev) {
+                const HostIvox::Voxel& vx = ivox.pool[v];
+                bv[k++] = BlobVoxel{vx.key, unsigned(vx.pts.size()), 0u};
+                std::memcpy(bp + q, vx.pts.data(), vx.pts.size() * sizeof(Pt4));
+                q += vx.pts.size();
+            }
+        }
+        if (was_device) enter_device();
+        return need;
+    }
+    // Any state -> an ordinary map holding the blob's voxels (refreshed: MirrorCurrent or Device).  An invalid blob leaves the map as it was.
+    fls_status import_blob(const void* blob, size_t n) {
+        if (n < sizeof(BlobHeader)) return FLS_ERR_INVALID;
+        const char* r = static_cast<const char*>(blob);
+        BlobHeader hd;
+        std::memcpy(&hd, r, sizeof(hd));
+        if (std::memcmp(hd.magic, "FLSIVOX1", 8) != 0 || hd.version != 1 || hd.kind != kind) return FLS_ERR_INVALID;
+        // the header is untrusted (it may come off a broadcast): bound both counts by the payload BEFORE multiplying (no u64 wrap),
+        // the resolution must be this map's, every voxel non-empty and unique, the counts must add up in 64 bits
+        static_assert(sizeof(BlobVoxel) == 16 && sizeof(Pt4) == 16, "blob records");
+        const unsigned long long payload = (unsigned long long)(n - sizeof(BlobHeader)) / 16ull;
+        if ((n - sizeof(BlobHeader)) % 16u != 0 || hd.n_voxels > payload || hd.n_points > payload || hd.n_voxels + hd.n_points != payload) return FLS_ERR_INVALID;
+        if (!(hd.resolution > 0.f) || !std::isfinite(hd.resolution) || hd.resolution != ivox.resolution) return FLS_ERR_INVALID;
+        if (hd.n_voxels > hd.n_points || hd.next_id < 0 || (unsigned long long)hd.next_id < hd.n_points) return FLS_ERR_INVALID;
+        const BlobVoxel* bv = reinterpret_cast<const BlobVoxel*>(r + sizeof(hd));
+        const Pt4* bp = reinterpret_cast<const Pt4*>(r + sizeof(hd) + hd.n_voxels * sizeof(BlobVoxel));
+        std::vector<HostIvox::ImageVoxel> vox(size_t(hd.n_voxels));
+        unsigned long long qsum = 0;
+        for (size_t k = 0; k < vox.size(); ++k) {  // stamp = position in the LRU order (tail first)
+            if (bv[k].count == 0u || qsum + bv[k].count > hd.n_points) return FLS_ERR_INVALID;
+            vox[k] = HostIvox::ImageVoxel{bv[k].key, unsigned(qsum), bv[k].count, 0u, (unsigned long long)(k + 1)};
+            qsum += bv[k].count;
+        }
+        if (qsum != hd.n_points) return FLS_ERR_INVALID;
+        {
+            std::vector<unsigned long long> keys(vox.size());
+            for (size_t k = 0; k < vox.size(); ++k) keys[k] = vox[k].key;
+            std::sort(keys.begin(), keys.end());
+            if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) return FLS_ERR_INVALID;  // a voxel listed twice
+        }
+        become_empty();  // (the slot layout is rebuilt from the mirror, window order, like the first build of the exporter)
+        load_mirror(vox, bp, size_t(hd.n_points), int(hd.next_id));  // (the resolution is the blob's: checked equal above)
+        is_first = hd.is_first != 0;
+        refresh();
+        return FLS_OK;
+    }
+
+    // ---- replica sets: `src`'s device image copied device to device (hipMemcpyPeer over xGMI between GPUs; no export blob, no host
+    // mirror rebuild, no re-flatten -- SURVEY 8e's replicated read-only map).  Any state -> Replica.  Pre: `src` refreshed and its stream idle,
+    // `used_now` / `n_bricks_now` its live_counts; this map's device current.  Both devices' streams are idle when this returns.
+    void replicate(const IvoxMap& src, size_t used_now, size_t n_bricks_now, int src_device, int device) {
+        FLS_HIP(hipStreamSynchronize(stream));
+        become_empty();  // (a copy that fails half-way leaves an empty map that rebuilds its image)
+        use_dense = src.use_dense;
+        image.clone_for_reading(src.image, used_now, n_bricks_now, src_device, device, stream);
+        is_first = src.is_first;
+        become_replica();
+    }
+
+    // ---- the device image as one flat buffer, for replicas in OTHER processes (torch.distributed ranks): fls_map_image_bytes / _export / _import.
+    // The exporter keeps its map; the importer becomes a read-only replica (fls_match / fls_match_batch with update_map == 0), like a
+    // member of a replica set.  No host mirror, no re-flatten: 44 MB for the 1e6-point map, copied at memory speed on either side.
+    // Pre (both): not a Replica, refreshed, the stream idle.
+    IvoxImage::FlatHeader flat_header() {
+        size_t nb = 0;
+        const size_t used_now = live_counts(nb);
+        IvoxImage::FlatHeader h = image.flat_header(used_now, nb);
+        h.kind = kind; h.is_first = is_first ? 1u : 0u; h.use_dense = h.have_bricks; h.resolution = ivox.resolution;
+        return h;
+    }
+    size_t image_bytes() { return size_t(flat_header().total_bytes); }
+    fls_status export_image(void* dst, size_t cap, bool on_device) {
+        const IvoxImage::FlatHeader h = flat_header();
+        if (cap < size_t(h.total_bytes)) return FLS_ERR_RANGE;
+        image.export_flat(h, dst, on_device, stream);
+        return FLS_OK;
+    }
+    // Any state -> Replica; a buffer whose contents do not validate leaves an empty map (MirrorUnbuilt), a bad header the map as it was.
+    fls_status import_image(const void* src, size_t n, bool on_device) {
+        if (!src || n < sizeof(IvoxImage::FlatHeader)) return FLS_ERR_INVALID;
+        IvoxImage::FlatHeader h;
+        FLS_HIP(hipMemcpy(&h, src, sizeof(h), on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+        if (!IvoxImage::flat_header_ok(h, n) || h.kind != kind) return FLS_ERR_INVALID;
+        if (!(h.resolution > 0.f) || h.resolution != ivox.resolution) return FLS_ERR_INVALID;
+        FLS_HIP(hipStreamSynchronize(stream));
+        become_empty();  // (an import that fails half-way leaves an empty map that rebuilds its image)
+        use_dense = h.have_bricks != 0;  // (derived, not trusted: the query takes the brick path exactly when the image carries bricks)
+        image.import_flat(h, src, on_device, stream);
+        // the contents are as untrusted as the header: no {begin, count} may leave the point array, no directory entry may name a missing brick
+        d_counter_img.reserve(1);
+        FLS_HIP(hipMemsetAsync(d_counter_img.p, 0, sizeof(unsigned), stream));
+        const unsigned long long n_cells = image.have_bricks ? (unsigned long long)h.n_bricks_live * kBrickStride : 0ull;
+        hipLaunchKernelGGL(ivox_image_validate_kernel, dim3(512), dim3(256), 0, stream, (const uint2*)image.d_cells.p, n_cells, (const HashEntry*)image.d_dir.p,
+                           image.have_bricks ? (unsigned long long)h.dir_mask + 1ull : 0ull, unsigned(h.n_bricks_live), (const HashEntry*)image.d_table.p,
+                           image.want_hash ? (unsigned long long)h.mask + 1ull : 0ull, (unsigned long long)h.used, d_counter_img.p);
+        unsigned bad = 0;
+        FLS_HIP(hipMemcpyAsync(&bad, d_counter_img.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        if (bad != 0u) return FLS_ERR_INVALID;
+        is_first = h.is_first != 0;
+        become_replica();
+        return FLS_OK;
+    }
+
+    // fls_map_size: the map's slots (every other slot: the number of points)
+    size_t counter(int slot) const {
+        switch (slot) {
+            case 100: return n_incremental;          // image updates applied as scatter lists
+            case 101: return n_full_rebuilds;        // ... as full re-flatten + upload
+            case 102: return on_device() ? dev_n_alive : ivox.n_alive;  // occupied voxels
+            case 103: return n_device_updates;       // ... by the device-side AddPoints
+            case 104: return n_host_fallbacks;       // batches the device refused (replayed on the host)
+            case 117: return n_device_evictions;     // voxels evicted inside device batches
+            case 119: return n_refused_conflict;     // refusals by reason: eviction order conflict / point array full / point outside the window
+            case 120: return n_refused_full;
+            case 121: return n_refused_outside;
+            case 122: return 0;                      // (the former one-launch form: the slot keeps its number)
+            case 123: return n_short_updates;        // device batches in the short chain (five launches behind the decision)
+            case 124: return n_speculative;          // chains queued speculatively behind the iterations
+            case 125: return n_speculative_skipped;  // ... that the device skipped (the Match needed more iterations / did not converge)
+            case 126: return n_device_recreated;     // evicted voxels re-created by a later point of the same batch
+            case 132: return image.budget_exceeded ? 1u : 0u;  // the brick pool went over FLS_IVOX_BRICK_BUDGET_MB: hash-table image, host AddPoints
+            default: return on_device() ? dev_n_points : ivox.n_points;
+        }
+    }
+};
+
+}  // namespace fls

@@ -103,7 +103,7 @@ __device__ __forceinline__ double group_min_dkey(const double v) { return dpp_mi
 // (2.7 us of this kernel + 3.2 us of re-reads in the fit kernel, measured by removing the stores).  Nontemporal stores
 // measured -0.5 us per launch, -0.5 us per Match (inside the noise), write-through (sc1) stores were slower (18.6-21.2 us
 // per launch): the rows are plain stores.
-// GEN (the general form) keeps two things the host can rule out for a whole map (matcher_p2plane_ivox.hpp::launch_knn):
+// GEN (the general form) keeps two things the host can rule out for a whole map (matcher_p2plane_ivox.hpp::map_view):
 //   - the max_range gate d2 < 25 per candidate.  A query lies within half a voxel of its voxel's centre on each axis, a candidate within
 //     half a voxel of a centre at most one voxel away: every axis difference is <= 2 res, d2 <= 12 res^2 (3 at the 0.5 m of InitIVox).
 //     The host drops the gate where 27 res^2 < 25, i.e. with a whole extra voxel per axis (3 res) for the float rounding of key and

@@ -703,7 +703,7 @@ ivox_upd_last_regions(const IvoxUpdBatch b, const IvoxUpdArrays a, IvoxUpdState*
     if (blockIdx.x == 0 && threadIdx.x == 0) upd_decide_totals(st, tot, 0u, 0u, status_in);
 }
 // ---- image <-> host mirror ---------------------------------------------------------------------------------------------------------
-// every alive voxel of the image as a record (sync_host_from_device: the device image back into the host mirror), in any order
+// every alive voxel of the image as a record (IvoxMap::to_mirror: the device image back into the host mirror), in any order
 struct IvoxAliveRec { unsigned long long key; unsigned begin, count, cap_log2, pad; unsigned long long stamp; };
 __global__ void __launch_bounds__(256)
 ivox_list_alive_kernel(const uint2* __restrict__ cells, const unsigned long long* __restrict__ brick_key, const unsigned ncell,
@@ -727,7 +727,7 @@ ivox_list_alive_kernel(const uint2* __restrict__ cells, const unsigned long long
     unpack_key(brick_key[c / kBrickStride], bx, by, bz);
     out[pos] = IvoxAliveRec{pack_key(bx * kBrickSide + sx - 1, by * kBrickSide + sy - 1, bz * kBrickSide + sz - 1), e.x, e.y, (unsigned)cap_log2[c], 0u, stamp[c]};
 }
-// per-voxel update metadata scattered into the (zeroed) per-cell arrays (enter_device_mode)
+// per-voxel update metadata scattered into the (zeroed) per-cell arrays (IvoxMap::enter_device)
 struct IvoxMetaRec { unsigned cell, cap_log2; unsigned long long stamp; };
 __global__ void __launch_bounds__(256)
 ivox_meta_scatter_kernel(const IvoxMetaRec* __restrict__ rec, const unsigned n, unsigned char* __restrict__ cap_log2, unsigned long long* __restrict__ stamp) {

@@ -102,6 +102,38 @@ def test_replica_set_follows_the_owner_after_refresh():
     rs.close(); m.close()
 
 
+def test_replica_becomes_an_ordinary_mapping_handle_again_by_map_import():
+    """ordinary handle -> read-only replica of an owner whose map the device maintains (the flat device image: what a member of a replica
+    set holds) -> ordinary again by fls_map_import of the owner's blob -> three mapping Matches.  It must then be indistinguishable from a
+    fresh handle that imported the same blob, and maintain its map on the device again."""
+    scale = 0.1
+    cfg = synth.make_config(1, job=0, scale=scale)
+    frames = [reg.PointcloudCluster(planar_cloud_=synth.make_config(1, job=j, scale=scale, with_map=False)["scan"]) for j in range(1, 6)]
+    owner, h, fresh = (reg.make_matcher("PointToPlane_IVOX", reg.YAML_NCLT_IVOX) for _ in range(3))
+    owner.AddCloudToLocalMap([cfg["map"]])
+    for f in frames[:2]:
+        owner.Match(f, np.eye(4), update_map=True)
+    assert owner.map_size(103) >= 1  # (device-side AddPoints batches: the owner is in device mode)
+    h.AddCloudToLocalMap([cfg["map"]])  # an ordinary handle with a map and Match state of its own
+    h.Match(frames[0], np.eye(4), update_map=False)
+    n = owner.MapImageBytes()
+    image = np.empty(n, np.uint8)
+    owner.ExportMapImage(image.ctypes.data, n, False)
+    h.ImportMapImage(image.ctypes.data, n, False)  # a replica now: no mirror, no AddPoints side
+    assert h.map_size(103) == 0
+    blob = owner.ExportMap()
+    h.ImportMap(blob)
+    fresh.ImportMap(blob)
+    for f in frames[2:5]:
+        Ta, Tb = np.eye(4), np.eye(4)
+        h.Match(f, Ta, update_map=True)
+        fresh.Match(f, Tb, update_map=True)
+        assert Ta.tobytes() == Tb.tobytes()
+    assert h.map_size(0) == fresh.map_size(0) and h.map_size(102) == fresh.map_size(102)
+    assert h.map_size(103) >= 1  # device authority regained
+    owner.close(); h.close(); fresh.close()
+
+
 def test_replica_set_rejects_what_it_cannot_serve():
     m = reg.make_matcher("IcpOptimized", reg.YAML_NCLT_ICP)  # no exportable image
     with pytest.raises(_lib.FlsError):
