@@ -18,6 +18,7 @@
 #include <climits>
 #include <cmath>
 #include <limits>
+#include <tuple>
 
 namespace fls {
 
@@ -178,6 +179,39 @@ public:
             last_v = v;
         }
         return FLS_OK;
+    }
+
+    // ---- the slot layout of a full image build (IvoxImage::build_from_ivox; DESIGN.md 3 "closed form") ----
+    // a voxel's slot region: a power of two, at least 4
+    static unsigned cap_for(size_t n) {
+        unsigned c = 4;
+        while (c < n) c <<= 1;
+        return c;
+    }
+    struct LayoutRef { int x, y, z; Voxel* v; };
+    // The alive voxels in brick order (z, y, x), inside a brick in (z, y, x) -- spatially adjacent voxels get adjacent point buckets -- each
+    // with its region {img_begin, img_cap, img_cnt} assigned back to back from slot 0.  Returns the slots in use.
+    size_t assign_layout(std::vector<LayoutRef>& refs) {
+        refs.clear();
+        refs.reserve(n_alive);
+        for (auto& v : pool) {
+            if (!v.alive) continue;
+            LayoutRef r;
+            unpack_key(v.key, r.x, r.y, r.z);
+            r.v = &v;
+            refs.push_back(r);
+        }
+        auto order_key = [](const LayoutRef& a) {
+            return std::make_tuple(a.z >> kBrickLog, a.y >> kBrickLog, a.x >> kBrickLog, a.z, a.y, a.x);
+        };
+        std::sort(refs.begin(), refs.end(), [&](const LayoutRef& a, const LayoutRef& b) { return order_key(a) < order_key(b); });
+        size_t slots = 0;
+        for (const LayoutRef& r : refs) {
+            Voxel& v = *r.v;
+            v.img_begin = unsigned(slots); v.img_cap = cap_for(v.pts.size()); v.img_cnt = unsigned(v.pts.size());
+            slots += v.img_cap;
+        }
+        return slots;
     }
 
     // Rebuild the mirror from a downloaded device image (the device was authoritative: kernels_ivox_update.hpp).  Voxels are

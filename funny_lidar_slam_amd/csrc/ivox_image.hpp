@@ -61,11 +61,7 @@ struct IvoxImage {
     }
     size_t n_bricks() const { return brick_keys.size(); }
 
-    static unsigned cap_for(size_t n) {
-        unsigned c = 4;
-        while (c < n) c <<= 1;
-        return c;
-    }
+    static unsigned cap_for(size_t n) { return HostIvox::cap_for(n); }
     static unsigned table_size_for(size_t n_keys) {
         size_t s = 1024;
         while (s < 2 * n_keys + 2) s <<= 1;
@@ -144,23 +140,10 @@ struct IvoxImage {
     }
     // ---- full build from the host mirror ----
     void build_from_ivox(HostIvox& m, hipStream_t s, PinnedBuf<char>& stage) {
-        // voxels in brick order (z, y, x), inside a brick in (z, y, x): spatially adjacent voxels get adjacent point buckets
-        struct Ref { int x, y, z; HostIvox::Voxel* v; };
+        // voxels in layout order, each with its slot region assigned (HostIvox::assign_layout)
+        using Ref = HostIvox::LayoutRef;
         std::vector<Ref> refs;
-        refs.reserve(m.n_alive);
-        size_t slots = 0;
-        for (auto& v : m.pool) {
-            if (!v.alive) continue;
-            Ref r;
-            unpack_key(v.key, r.x, r.y, r.z);
-            r.v = &v;
-            refs.push_back(r);
-            slots += cap_for(v.pts.size());
-        }
-        auto order_key = [](const Ref& a) {
-            return std::make_tuple(a.z >> kBrickLog, a.y >> kBrickLog, a.x >> kBrickLog, a.z, a.y, a.x);
-        };
-        std::sort(refs.begin(), refs.end(), [&](const Ref& a, const Ref& b) { return order_key(a) < order_key(b); });
+        const size_t slots = m.assign_layout(refs);
         std::vector<Pt4> pts;
         pts.reserve(slots);
         if (!want_hash) {
@@ -214,7 +197,7 @@ struct IvoxImage {
         pt_upd.clear();
         for (const Ref& r : refs) {
             HostIvox::Voxel& v = *r.v;
-            const unsigned beg = unsigned(pts.size()), cap = cap_for(v.pts.size());
+            const unsigned beg = v.img_begin, cap = v.img_cap;  // (== pts.size(): regions are back to back)
             if (want_hash) {
                 unsigned h = hash_key(v.key) & mask;
                 while (table[h].key != kEmptyKey) h = (h + 1) & mask;
@@ -224,7 +207,6 @@ struct IvoxImage {
             }
             pts.insert(pts.end(), v.pts.begin(), v.pts.end());
             pts.resize(size_t(beg) + cap, Pt4{0.f, 0.f, 0.f, -1});  // slack
-            v.img_begin = beg; v.img_cap = cap; v.img_cnt = unsigned(v.pts.size());
         }
         used = pts.size();
         garbage = 0;

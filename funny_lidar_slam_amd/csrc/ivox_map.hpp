@@ -1,10 +1,13 @@
 // ivox_map.hpp -- the iVox local map of FLS_P2PLANE_IVOX without a matcher around it: the replacement of IVoxMap as LoamPointToPlaneIVOX
 // uses it (InitIVox :53-58, the AddPoints side of AddCloudToLocalMap :60-139).  Host mirror (HostIvox) + device image (IvoxImage) + the rule
 // which of the two is the map (State; diagram in DESIGN.md 3), the device-side AddPoints (enqueue_update / await_update) and the ways a
-// map travels (blob, replica, flat image).  Everything is queued on the one stream given to init().
+// map travels (blob, replica, flat image).  A whole cloud going into an EMPTY map is built on the device (bulk_build, kernels_ivox_build.hpp):
+// the image then is the map and the mirror is only reconstructed when something asks for it.  Everything is queued on the one stream given to init().
 #pragma once
 #include "ivox_image.hpp"
 #include "device_voxelgrid.hpp"
+#include "kernels_ivox_build.hpp"
+#include <chrono>
 #include <algorithm>
 
 namespace fls {
@@ -19,22 +22,33 @@ struct IvoxMap {
         MirrorStale,    // the host mirror is the map; the image lacks the mirror's journal
         MirrorCurrent,  // the host mirror is the map; the image shows it
         Device,         // the device image is the map (points, voxel table, LRU stamps, counts); the mirror is stale until to_mirror()
+        ImageOnly,      // the device image is the map and nothing on the device updates it: image current, mirror NOT BUILT until to_mirror().  What
+                        // bulk_build leaves where enter_device() would refuse -- every localization handle between two reloads -- complete for
+                        // every reader (Match, lanes, replicas, flat image), with the AddPoints side arrays and IvoxUpdState written like a Device map's
         Replica,        // the image is a read-only copy of another map's kNN side; the mirror is empty, there is no AddPoints side
     };
     State state = State::MirrorUnbuilt;
     bool on_device() const { return state == State::Device; }
+    bool image_is_map() const { return state == State::Device || state == State::ImageOnly; }  // the mirror is stale or not built
     bool is_replica() const { return state == State::Replica; }
 
     hipStream_t stream = nullptr;
     unsigned kind = 0;
     bool mapping_mode = true;      // !is_localization_mode: only a map that Match updates goes to the device
     bool allow_device_map = true;  // FLS_IVOX_DEVICE_UPDATE=0: always the host path (A/B)
+    bool allow_device_build = true;  // FLS_IVOX_DEVICE_BUILD=0: a cloud into an empty map goes point by point through the mirror (A/B)
     bool use_dense = true;         // brick image instead of the hash table (FLS_IVOX_DENSE=0 disables; a brick pool over its budget too)
     bool is_first = true;          // the reference's function-static flag (:62), per map here
     // map_size slots 100-104, 117, 119-126 (see counter())
     size_t n_incremental = 0, n_full_rebuilds = 0;
     size_t n_device_updates = 0, n_host_fallbacks = 0, n_device_evictions = 0, n_device_recreated = 0, n_refused_conflict = 0, n_refused_full = 0, n_refused_outside = 0;
     size_t n_short_updates = 0, n_speculative = 0, n_speculative_skipped = 0;
+    // map_size slots 140-147: bulk builds done / declined, declines by reason, mirrors reconstructed after a bulk build
+    enum class BuildDecline { None = 0, TooMany, Capacity, Range, Budget, NotDense, SwitchedOff };
+    size_t n_bulk_builds = 0, n_bulk_declined = 0, n_bulk_decline_reason[7] = {}, n_lazy_mirrors = 0;
+    BuildDecline last_decline = BuildDecline::None;
+    bool mirror_pending = false;  // the map came from a bulk build and its mirror has not been reconstructed yet
+    double build_ms[3] = {0, 0, 0};  // FLS_HOST_TIMING: keys + sort + scans up to the mailbox | pool set-up + cells + points | total
     // ---- device-side AddPoints: persistent state, the mailbox its commit kernel writes, the counts mirrored from it ----
     DevBuf<IvoxUpdState> d_upd_state;
     IvoxUpdMailbox* upd_mb_host = nullptr;
@@ -51,15 +65,25 @@ struct IvoxMap {
     DevBuf<unsigned> d_ev_bt, d_crank, d_evict_list;
     PinnedBuf<char> upd_stage;
     DevBuf<unsigned> d_counter_img;
+    // scratch of one bulk build
+    DevicePairSort bb_sort;
+    DevBuf<unsigned long long> bb_vkey;
+    DevBuf<unsigned> bb_khi, bb_bt, bb_vidx, bb_first, bb_lcap, bb_btc, bb_vbegin, bb_flag;
+    DevBuf<uint2> bb_lx;
+    IvbMailbox* bb_mb_host = nullptr;
+    IvbMailbox* bb_mb_dev = nullptr;
+    unsigned bb_seq = 0;
 
     ~IvoxMap() {
         if (stream) (void)hipStreamSynchronize(stream);  // (the owner destroys the stream after its members)
         if (upd_mb_host) (void)hipHostFree(upd_mb_host);
+        if (bb_mb_host) (void)hipHostFree(bb_mb_host);
     }
     void init(hipStream_t s, unsigned kind_, bool localization_mode) {
         stream = s; kind = kind_; mapping_mode = !localization_mode;
         if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FLS_IVOX_DEVICE_BUILD")) allow_device_build = std::atoi(e) != 0;
         d_upd_state.reserve(1);
         FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
         std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
@@ -74,10 +98,10 @@ struct IvoxMap {
     // -> MirrorStale (MirrorUnbuilt stays).  Pre: the mirror is the map and the caller has inserted into `ivox`.
     void mirror_changed() { if (state == State::MirrorCurrent) state = State::MirrorStale; }
     // -> MirrorUnbuilt, the mirror empty.  Pre: none (the stream idle if the image may be in use).
-    void become_empty() { ivox.clear(); state = State::MirrorUnbuilt; }
+    void become_empty() { ivox.clear(); state = State::MirrorUnbuilt; mirror_pending = false; }
     // -> Replica.  Pre: become_empty(), then `image` filled with a complete kNN side (clone_for_reading / import_flat).
     void become_replica() { state = State::Replica; }
-    // -> MirrorCurrent, then Device where enter_device() allows.  Pre: none; a Device, Replica or MirrorCurrent map is left as it is.
+    // -> MirrorCurrent, then Device where enter_device() allows.  Pre: none; a Device, ImageOnly, Replica or MirrorCurrent map is left as it is.
     // Scatters the mirror's journal into the image when possible, else re-flattens.
     void refresh() {
         if (state != State::MirrorUnbuilt && state != State::MirrorStale) return;
@@ -96,8 +120,9 @@ struct IvoxMap {
     }
     // -> Device.  Pre: MirrorCurrent.  Hands the map over to the device-side AddPoints: the brick image has no extent limit, so the only
     // conditions are the A/B switch, a brick image, mapping mode and an LRU capacity the eviction selection can work with.
+    bool device_update_allowed() const { return allow_device_map && use_dense && image.have_bricks && !image.want_hash && mapping_mode && ivox.capacity >= 4; }
     void enter_device() {
-        if (!allow_device_map || !use_dense || !image.have_bricks || image.want_hash || !mapping_mode || ivox.capacity < 4) return;
+        if (!device_update_allowed()) return;
         const unsigned long long stamp_base = image.upload_update_meta(ivox, stream, upd_stage);
         IvoxUpdState st{};
         st.n_points = ivox.n_points; st.used = image.used; st.garbage = image.garbage; st.stamp_base = stamp_base;
@@ -110,10 +135,13 @@ struct IvoxMap {
         stamp_bound = stamp_base;
         state = State::Device;
     }
-    // -> MirrorCurrent.  Pre: none; anything but a Device map is left as it is.  The device image back into the host mirror: the alive
-    // voxels as records (one compaction kernel), their points, the LRU order from the stamps, and the bricks the device created.
+    // -> MirrorCurrent.  Pre: none; anything but a Device or ImageOnly map is left as it is.  The device image back into the host mirror: the
+    // alive voxels as records (one compaction kernel), their points, the LRU order from the stamps, and the bricks the device created.  After a
+    // bulk build this is where the mirror is built at all, the first time something needs it (export_blob, a host fallback, an external add_cloud).
     void to_mirror() {
-        if (!on_device()) return;
+        if (!image_is_map()) return;
+        if (mirror_pending) { ++n_lazy_mirrors; mirror_pending = false; }
+        if (image.dir.size() != size_t(image.dir_mask) + 1) image.dir.assign(size_t(image.dir_mask) + 1, HashEntry{kEmptyKey, kBrickPending, 0u});  // (a bulk build keeps no host copy)
         IvoxUpdState st{};
         FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
         FLS_HIP(hipStreamSynchronize(stream));
@@ -157,6 +185,141 @@ struct IvoxMap {
         ++n_host_fallbacks;
         to_mirror();
         if (v == Verdict::RefusedForRoom) state = State::MirrorUnbuilt;
+    }
+
+
+    // ---- a whole cloud into the EMPTY map, on the device (kernels_ivox_build.hpp; the closed form is DESIGN.md 3) ----
+    bool decline_build(const BuildDecline why) {
+        last_decline = why;
+        ++n_bulk_declined;
+        ++n_bulk_decline_reason[int(why)];
+        return false;
+    }
+    // what can be said before the cloud is touched.  false: declined (counted), the caller takes the host path.
+    bool bulk_build_applies(const size_t n) {
+        if (!allow_device_build) return decline_build(BuildDecline::SwitchedOff);
+        if (!use_dense) return decline_build(BuildDecline::NotDense);
+        if (n > size_t(kVgMaxBlocks) * kVgTile) return decline_build(BuildDecline::TooMany);
+        return true;
+    }
+    bool is_blank() const { return state == State::MirrorUnbuilt && ivox.n_alive == 0 && ivox.next_id == 0; }
+    // -> Device where enter_device() would go there, else ImageOnly.  Pre: is_blank(), bulk_build_applies(n), n > 0; x | y | z the cloud on the
+    // device, lo / hi its coordinate bounds over the points that are not NaN (round() is monotone: the extreme keys come from the extreme
+    // coordinates).  false: declined (counted), nothing the host path relies on was changed.  One host wait inside (the mailbox of ivb_report),
+    // one at the end (the call returns with the stream idle, like refresh()).
+    bool bulk_build(const float* x, const float* y, const float* z, const size_t n, const float (&lo)[3], const float (&hi)[3]) {
+        using clock = std::chrono::steady_clock;
+        const auto t0 = clock::now();
+        IvbExtent ext{};
+        int span_bits[3];
+        for (int a = 0; a < 3; ++a) {
+            const float flo = std::round(lo[a] * ivox.inv_resolution), fhi = std::round(hi[a] * ivox.inv_resolution);
+            if (!(std::fabs(flo) < float(kKeyLimit) && std::fabs(fhi) < float(kKeyLimit))) return decline_build(BuildDecline::Range);  // (an extreme point fails key_of)
+            ext.bmin[a] = int(flo) >> kBrickLog;
+            const unsigned span = unsigned((int(fhi) >> kBrickLog) - ext.bmin[a]);
+            span_bits[a] = 0;
+            while ((1u << span_bits[a]) <= span) ++span_bits[a];
+        }
+        ext.bx_bits = span_bits[0]; ext.by_bits = span_bits[1];
+        const int key_bits = span_bits[0] + span_bits[1] + span_bits[2] + 3 * kBrickLog;  // <= 3 * 18 + 9
+        const bool wide = key_bits > 32;
+        const int ni = int(n), nblk = (ni + kIvbBlock - 1) / kIvbBlock;
+        const dim3 g{unsigned(nblk), 1u, 1u}, t{unsigned(kIvbBlock), 1u, 1u};
+        if (!bb_mb_host) {
+            FLS_HIP(hipHostMalloc((void**)&bb_mb_host, sizeof(IvbMailbox), hipHostMallocMapped));
+            std::memset(bb_mb_host, 0, sizeof(IvbMailbox));
+            FLS_HIP(hipHostGetDevicePointer((void**)&bb_mb_dev, bb_mb_host, 0));
+        }
+        bb_sort.prepare(n);
+        bb_vkey.reserve(n); if (wide) bb_khi.reserve(n);
+        bb_lx.reserve(n); bb_vidx.reserve(n); bb_first.reserve(n + 1); bb_lcap.reserve(n); bb_vbegin.reserve(n);
+        bb_bt.reserve(size_t(4) * nblk + 1); bb_btc.reserve(size_t(2) * nblk + 1); bb_flag.reserve(1);
+        unsigned* const bts = bb_bt.p + 2 * nblk;    // scanned: voxel heads | brick heads, then the total
+        unsigned* const btcs = bb_btc.p + nblk;      // scanned capacities, then the total (= used)
+        FLS_HIP(hipMemsetAsync(bb_flag.p, 0, sizeof(unsigned), stream));
+        hipLaunchKernelGGL(ivb_keys, g, t, 0, stream, x, y, z, ni, ivox.inv_resolution, ext, bb_vkey.p, bb_sort.k0, wide ? bb_khi.p : (unsigned*)nullptr, bb_sort.v0, bb_flag.p);
+        bb_sort.run((std::min(key_bits, 32) + 7) / 8, stream);
+        if (wide) {  // two stable rounds, low word first (as the eviction selection sorts its 64-bit stamps)
+            hipLaunchKernelGGL(ivb_gather_hi, g, t, 0, stream, (const unsigned*)bb_khi.p, (const unsigned*)bb_sort.v0, ni, bb_sort.k0);
+            bb_sort.run((key_bits - 32 + 7) / 8, stream);
+        }
+        const unsigned* const order = bb_sort.v0;
+        hipLaunchKernelGGL(ivb_heads, g, t, 0, stream, (const unsigned long long*)bb_vkey.p, order, ni, bb_lx.p, bb_bt.p);
+        hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)bb_bt.p, bts, 2 * nblk, bts + 2 * nblk);
+        const unsigned* const d_n_voxels = bts + nblk;  // (the scan's value at the seam of the two planes)
+        hipLaunchKernelGGL(ivb_voxels, g, t, 0, stream, (const uint2*)bb_lx.p, (const unsigned*)bts, ni, bb_vidx.p, bb_first.p);
+        hipLaunchKernelGGL(ivb_caps, g, t, 0, stream, (const unsigned*)bb_first.p, d_n_voxels, bb_lcap.p, bb_btc.p);
+        hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)bb_btc.p, btcs, nblk, btcs + nblk);
+        bb_seq = (bb_seq + 1u) & 0x7fffffffu;
+        if (bb_seq == 0u) bb_seq = 1u;
+        hipLaunchKernelGGL(ivb_report, dim3(1), dim3(64), 0, stream, (const unsigned*)bb_flag.p, d_n_voxels, (const unsigned*)(bts + 2 * nblk), (const unsigned*)(btcs + nblk), bb_mb_dev, bb_seq);
+        FLS_HIP(hipGetLastError());
+        (void)spin_until(stream, [&] { return __atomic_load_n(&bb_mb_host->seq, __ATOMIC_ACQUIRE) == bb_seq; });
+        if (__atomic_load_n(&bb_mb_host->seq, __ATOMIC_ACQUIRE) != bb_seq) FLS_HIP(hipErrorUnknown);  // (the stream went idle without a report)
+        const auto t1 = clock::now();
+        if (bb_mb_host->flag != 0u) return decline_build(BuildDecline::Range);
+        const size_t V = bb_mb_host->n_voxels, own = bb_mb_host->own_bricks, used = size_t(bb_mb_host->used);
+        if (V >= ivox.capacity) return decline_build(BuildDecline::Capacity);  // (evict_tail fires when n_alive >= capacity after a creation)
+        // point array: the growth room build_from_ivox reserves.  Brick pool: its rule too -- three times the voxels' own bricks as a first guess,
+        // room for as many bricks again once they are all there, never over the byte budget (the host path then takes the hash-table form)
+        image.d_pts.reserve(used + used / 2 + (size_t(1) << 16));
+        size_t cap_guess = std::max<size_t>(image.n_bricks_cap, 256), ds = 0, n_bricks_made = 0;
+        while (cap_guess < 3 * own) cap_guess *= 2;
+        for (;;) {
+            if (cap_guess * IvoxImage::kPoolBrickBytes > IvoxImage::brick_budget_bytes()) {
+                FLS_HIP(hipStreamSynchronize(stream));
+                return decline_build(BuildDecline::Budget);
+            }
+            ds = 4096;
+            while (ds < 4 * cap_guess) ds <<= 1;
+            const size_t ncell = cap_guess * kBrickStride;
+            image.d_dir.reserve(ds); image.d_brick_key.reserve(cap_guess); image.d_cells.reserve(ncell); image.d_nbr.reserve(cap_guess * 32);
+            image.d_cap_log2.reserve(ncell); image.d_stamp.reserve(ncell); image.d_pend.reserve(ncell); image.d_rank_mm.reserve(ncell);
+            FLS_HIP(hipMemsetAsync(image.d_dir.p, 0xff, ds * sizeof(HashEntry), stream));  // every entry {kEmptyKey, kBrickPending, -}
+            FLS_HIP(hipMemsetAsync(image.d_cells.p, 0, ncell * sizeof(uint2), stream));
+            FLS_HIP(hipMemsetAsync(image.d_nbr.p, 0xff, cap_guess * 32 * sizeof(unsigned), stream));
+            FLS_HIP(hipMemsetAsync(image.d_cap_log2.p, 0, ncell, stream));
+            FLS_HIP(hipMemsetAsync(image.d_stamp.p, 0, ncell * sizeof(unsigned long long), stream));
+            FLS_HIP(hipMemsetAsync(image.d_pend.p, 0, ncell * sizeof(unsigned), stream));
+            FLS_HIP(hipMemsetAsync(image.d_rank_mm.p, 0xff, ncell * sizeof(unsigned), stream));
+            IvoxUpdState st{};
+            st.n_points = n; st.used = used; st.garbage = 0; st.stamp_base = n;  // (stamps are 1 .. n: index of the last member + 1)
+            st.pts_capacity = image.d_pts.cap; st.n_alive = unsigned(V); st.lru_capacity = unsigned(std::min<size_t>(ivox.capacity, 0xffffffffu));
+            st.next_id = int(n); st.n_bricks = 0u; st.status = kUpdOk;
+            FLS_HIP(hipMemcpyAsync(d_upd_state.p, &st, sizeof(st), hipMemcpyHostToDevice, stream));
+            const IvoxUpdArrays a{image.d_cells.p, image.d_pts.p, image.d_cap_log2.p, image.d_stamp.p, image.d_pend.p, image.d_rank_mm.p,
+                                  image.d_dir.p, unsigned(ds - 1), unsigned(cap_guess), image.d_brick_key.p, image.d_nbr.p, ivox.inv_resolution};
+            hipLaunchKernelGGL(ivb_cells, g, t, 0, stream, (const unsigned long long*)bb_vkey.p, order, (const unsigned*)bb_first.p, unsigned(V), (const unsigned*)bb_lcap.p,
+                               (const unsigned*)btcs, a, d_upd_state.p, bb_vbegin.p);
+            FLS_HIP(hipGetLastError());
+            FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            n_bricks_made = st.n_bricks;
+            if (!(st.status & kUpdArrayFull) && 2 * n_bricks_made <= cap_guess) break;
+            cap_guess = std::max(cap_guess * 2, 2 * n_bricks_made);  // (a refused launch counted every brick it wanted)
+        }
+        // (ivb_points reads the region begins ivb_cells writes: queued behind the launch that passed)
+        hipLaunchKernelGGL(ivb_points, g, t, 0, stream, x, y, z, order, ni, (const unsigned*)bb_vidx.p, (const unsigned*)bb_first.p, (const unsigned*)bb_vbegin.p, image.d_pts.p,
+                           (unsigned long long)image.d_pts.cap);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipStreamSynchronize(stream));
+        image.want_hash = false; image.have_bricks = true;
+        image.table.clear(); image.mask = 0;
+        image.brick_index.clear(); image.brick_keys.clear(); image.dir.clear(); image.dir_dirty = false;  // (no host copy of the directory: to_mirror downloads it)
+        image.dir_mask = unsigned(ds - 1); image.n_bricks_cap = cap_guess; image.meta_cells = cap_guess * kBrickStride;
+        image.cell_upd.clear(); image.pt_upd.clear();
+        image.used = used; image.garbage = 0; image.n_pts_live = n;
+        dev_n_points = n; dev_n_alive = V; dev_n_bricks = n_bricks_made;
+        stamp_bound = n;
+        mirror_pending = true;
+        state = device_update_allowed() ? State::Device : State::ImageOnly;
+        ++n_bulk_builds;
+        last_decline = BuildDecline::None;
+        const auto t2 = clock::now();
+        build_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        build_ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+        build_ms[2] = std::chrono::duration<double, std::milli>(t2 - t0).count();
+        return true;
     }
 
     // ---- the device-side AddPoints ----
@@ -264,7 +427,7 @@ struct IvoxMap {
 
     // slots in use + bricks, from the device's own state while it maintains the map
     size_t live_counts(size_t& n_bricks_live) {
-        if (!on_device()) { n_bricks_live = image.n_bricks(); return image.used; }
+        if (!image_is_map()) { n_bricks_live = image.n_bricks(); return image.used; }
         IvoxUpdState st{};
         FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
         FLS_HIP(hipStreamSynchronize(stream));
@@ -413,8 +576,8 @@ struct IvoxMap {
     size_t counter(int slot) const {
         switch (slot) {
             case 100: return n_incremental;          // image updates applied as scatter lists
-            case 101: return n_full_rebuilds;        // ... as full re-flatten + upload
-            case 102: return on_device() ? dev_n_alive : ivox.n_alive;  // occupied voxels
+            case 101: return n_full_rebuilds + n_bulk_builds;  // full builds of the image: re-flatten + upload from the mirror, or built on the device (slot 140 says how many of them)
+            case 102: return image_is_map() ? dev_n_alive : ivox.n_alive;  // occupied voxels (of a bulk-built map: without building the mirror)
             case 103: return n_device_updates;       // ... by the device-side AddPoints
             case 104: return n_host_fallbacks;       // batches the device refused (replayed on the host)
             case 117: return n_device_evictions;     // voxels evicted inside device batches
@@ -427,7 +590,15 @@ struct IvoxMap {
             case 125: return n_speculative_skipped;  // ... that the device skipped (the Match needed more iterations / did not converge)
             case 126: return n_device_recreated;     // evicted voxels re-created by a later point of the same batch
             case 132: return image.budget_exceeded ? 1u : 0u;  // the brick pool went over FLS_IVOX_BRICK_BUDGET_MB: hash-table image, host AddPoints
-            default: return on_device() ? dev_n_points : ivox.n_points;
+            case 140: return n_bulk_builds;          // whole clouds built into the empty map on the device (bulk_build)
+            case 141: return n_bulk_declined;        // ... declined to the host path (FLS_IVOX_DEVICE_BUILD=0 counts here and in no reason slot; an empty cloud nowhere)
+            case 142: return n_bulk_decline_reason[int(BuildDecline::TooMany)];   // declines by reason: more points than the sort takes /
+            case 143: return n_bulk_decline_reason[int(BuildDecline::Capacity)];  // as many voxels as the LRU capacity (evictions) /
+            case 144: return n_bulk_decline_reason[int(BuildDecline::Range)];     // a point outside the key range or not finite (FLS_ERR_RANGE) /
+            case 145: return n_bulk_decline_reason[int(BuildDecline::Budget)];    // a brick pool over its byte budget /
+            case 146: return n_bulk_decline_reason[int(BuildDecline::NotDense)];  // the hash-table form (FLS_IVOX_DENSE=0, or the budget exceeded earlier)
+            case 147: return n_lazy_mirrors;         // mirrors reconstructed from a bulk-built image (to_mirror)
+            default: return image_is_map() ? dev_n_points : ivox.n_points;
         }
     }
 };

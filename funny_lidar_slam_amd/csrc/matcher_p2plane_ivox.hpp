@@ -58,6 +58,9 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // localization-mode fitness map (kd-tree stand-in)
     CellGridImage fitness_grid;
     bool have_fitness_grid = false;
+    // a whole cloud on its way into the empty map (IvoxMap::bulk_build): staged and uploaded apart from the resident scan, which a reload must not disturb
+    DevScan cloud_dev;
+    DeviceGridBuilder fitness_builder;
     std::vector<Pt4> h_nn;
     std::vector<unsigned char> h_cnt, h_flag;
 
@@ -108,8 +111,60 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
 
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
         if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;  // CHECK_EQ(cloud_list.size(), 1) :61
+        if (!map.is_replica() && (p.is_localization_mode || map.is_first)) {  // the cloud goes in whole
+            fls_status rc = FLS_OK;
+            if (add_cloud_bulk(c0, n0, stride, rc)) return rc;
+        }
         const std::vector<PtI> cloud = cloud_from(c0, n0, stride);
         return add_cloud_impl(cloud);
+    }
+    // coordinate bounds of the staged cloud per axis, NaN ignored (an infinite coordinate shows: the build declines on it)
+    static void plane_bounds(const float* v, const size_t n, float& lo, float& hi) {
+        float mn = std::numeric_limits<float>::infinity(), mx = -mn;
+        size_t i = 0;
+#if defined(__SSE__)
+        __m128 vmn = _mm_set1_ps(mn), vmx = _mm_set1_ps(mx);
+        for (; i + 4 <= n; i += 4) {  // (min / max return their second operand when the first is NaN)
+            const __m128 q = _mm_loadu_ps(v + i);
+            vmn = _mm_min_ps(q, vmn); vmx = _mm_max_ps(q, vmx);
+        }
+        float a[4], b[4];
+        _mm_storeu_ps(a, vmn); _mm_storeu_ps(b, vmx);
+        for (int k = 0; k < 4; ++k) { if (a[k] < mn) mn = a[k]; if (b[k] > mx) mx = b[k]; }
+#endif
+        for (; i < n; ++i) { if (v[i] < mn) mn = v[i]; if (v[i] > mx) mx = v[i]; }
+        lo = mn; hi = mx;
+    }
+    // The first cloud of a mapping handle / every reload of a localization handle, built on the device.  true: `rc` answers the call.
+    // false: declined (IvoxMap counts why; an empty cloud and a map that is not blank count nowhere), the host path runs as ever.
+    bool add_cloud_bulk(const float* c0, const size_t n0, const int stride, fls_status& rc) {
+        if (n0 == 0 || c0 == nullptr) return false;
+        if (!p.is_localization_mode && !map.is_blank()) return false;  // (an imported map with is_first set: the cloud joins what is there)
+        if (!map.bulk_build_applies(n0)) return false;
+        const auto t0 = std::chrono::steady_clock::now();
+        ensure_nn_rows();  // (lists in ids form name slots of the image about to be replaced)
+        cloud_dev.upload_raw(c0, n0, stride, stream);
+        float lo[3], hi[3];
+        for (int a = 0; a < 3; ++a) plane_bounds(cloud_dev.stage.p + size_t(a) * n0, n0, lo[a], hi[a]);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (p.is_localization_mode) { map.become_empty(); map.is_first = true; }
+        if (!map.bulk_build(cloud_dev.x.p, cloud_dev.y.p, cloud_dev.z.p, n0, lo, hi)) return false;
+        map.is_first = false;
+        const auto t2 = std::chrono::steady_clock::now();
+        rc = FLS_OK;
+        if (p.is_localization_mode) {  // :134-138 kd-tree for GetFitnessScore, from the cloud already on the device
+            if (!fitness_builder.run(fitness_grid, cloud_dev.x.p, cloud_dev.y.p, cloud_dev.z.p, n0, 1.0f, 1, false, stream))
+                rc = fitness_grid.build(cloud_from(c0, n0, stride), 1.0f, stream);
+            FLS_HIP(hipStreamSynchronize(stream));
+            have_fitness_grid = (rc == FLS_OK);
+        }
+        if (host_timing) {
+            const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+            std::fprintf(stderr, "[fls host] device map build: %zu points into %zu voxels: stage+upload %.3f ms, keys+sort+scans %.3f ms, pool+cells+points %.3f ms, "
+                         "fitness grid %.3f ms, total %.3f ms\n", n0, map.dev_n_alive, ms(t0, t1), map.build_ms[0], map.build_ms[1], ms(t2, std::chrono::steady_clock::now()),
+                         ms(t0, std::chrono::steady_clock::now()));
+        }
+        return true;
     }
 
     // the decision launch (ivox_add_decide_kernel): codes + world points of the resident scan; while the device holds the map it also counts
@@ -144,9 +199,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         fls_status rc = FLS_OK;
         if (!(from_resident_scan && !map.is_first)) { ensure_nn_rows(); map.to_mirror(); }  // every other branch works on the host mirror
         if (map.is_first) {
+            const auto tm0 = std::chrono::steady_clock::now();
             rc = ivox.add_points(planar_cloud.data(), planar_cloud.size());
             if (rc != FLS_OK) return rc;
             map.is_first = false;
+            if (host_timing)
+                std::fprintf(stderr, "[fls host] host map build: AddPoints of %zu points into %zu voxels %.3f ms\n", planar_cloud.size(), ivox.n_alive,
+                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count());
         } else if (from_resident_scan) {
             // :79-131 on the device (the cloud is the scan just matched, still resident): decision code + world point
             // per source point; the host only walks the codes to build the two insertion lists in index order.
@@ -179,6 +238,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
                     // path below replays the batch on the host mirror
                     map.fall_back(v);
                 }
+                map.to_mirror();   // (an ImageOnly map -- bulk-built, device update not allowed -- has no mirror yet)
                 h_code.resize(n);  // (host copies only on this path: the device applied nothing)
                 h_pw.resize(n);
                 FLS_HIP(hipMemcpyAsync(h_code.data(), d_code.p, n, hipMemcpyDeviceToHost, stream));
@@ -249,8 +309,11 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
                              map.image.cell_upd.size());
         }
         if (p.is_localization_mode) {  // :134-138 kd-tree for GetFitnessScore
+            const auto tf0 = std::chrono::steady_clock::now();
             rc = fitness_grid.build(planar_cloud, 1.0f, stream);
             have_fitness_grid = (rc == FLS_OK);
+            if (host_timing)
+                std::fprintf(stderr, "[fls host] host fitness grid %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf0).count());
         }
         return rc;
     }

@@ -164,7 +164,9 @@ fls_status fls_map_import(fls_handle h, const void* blob, size_t n_bytes);
  * *_on_device != 0 -- e.g. the data_ptr of the CUDA tensor an RCCL broadcast works on -- or host memory (pinned for speed; gloo).  The exporter
  * keeps its map.  The importer becomes a READ-ONLY REPLICA, like a member of fls_replicas_*: fls_match / fls_match_batch with update_map == 0;
  * fls_map_import or a replica refresh makes it an ordinary handle again.  Header and contents are validated on import (sizes against n_bytes,
- * every cell inside the point array): FLS_ERR_INVALID otherwise.  Only the iVox kind has such an image (others: 0 / FLS_ERR_STATE). */
+ * every cell inside the point array): FLS_ERR_INVALID otherwise.  Only the iVox kind has such an image (others: 0 / FLS_ERR_STATE).
+ * Two builds of one cloud give FUNCTIONALLY equal flat images, not byte-equal ones: brick indices follow the order in which the bricks were
+ * created (on the device: whichever thread claimed the directory entry first), and no result depends on them.                        */
 size_t fls_map_image_bytes(fls_handle h);
 fls_status fls_map_image_export(fls_handle h, void* dst, size_t cap_bytes, int dst_on_device);
 fls_status fls_map_image_import(fls_handle h, const void* src, size_t n_bytes, int src_on_device);
@@ -262,7 +264,13 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
 /* fls_map_size: slot 0 = map points (voxels for NDT), 1 = corner map (LoamFull), 102 = occupied voxels (iVox); slots >= 100 are
  * introspection counters of the device-side map update that the tests and bench.py read (device batches applied 103 / 109, refused
  * 104 / 110, voxels evicted inside device batches 117, of which re-created by a later point of the same batch 126, refusals by
- * reason 119-121, ...): see map_size() of the matcher in csrc/matcher_p2plane_ivox.hpp / matcher_ndt.hpp.  Not part of the drop-in. */
+ * reason 119-121, ...): see map_size() of the matcher in csrc/matcher_p2plane_ivox.hpp / matcher_ndt.hpp.  Not part of the drop-in.
+ * iVox, a whole cloud into the empty map (the first fls_add_cloud_to_local_map of a mapping handle, every one of a localization handle;
+ * IvoxMap::counter in csrc/ivox_map.hpp): 140 = built on the device, 141 = declined to the sequential host path (FLS_IVOX_DEVICE_BUILD=0
+ * counts here and in no reason slot; an empty cloud counts nowhere), declines by reason: 142 = more points than the device sort takes,
+ * 143 = as many voxels as the LRU capacity (the insert evicts), 144 = a point outside the key range or not finite (the call returns
+ * FLS_ERR_RANGE), 145 = brick pool over its byte budget, 146 = hash-table form (FLS_IVOX_DENSE=0); 147 = host mirrors reconstructed from a
+ * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).                      */
 size_t fls_map_size(fls_handle h, int slot);
 
 /* ---- measurement hooks ----------------------------------------------------------------------------
