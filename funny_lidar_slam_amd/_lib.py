@@ -46,6 +46,11 @@ BATCH_IVOX_SYMBOLS = ["fls_batch_ivox_revision", "fls_match_batch_shared_ivox", 
 # every symbol include/fls_debug_linalg.h declares (FLS_DEBUG_LINALG_REVISION 1): test hooks of csrc/linalg_dev.hpp / wave_solve.hpp
 DEBUG_LINALG_SYMBOLS = ["fls_debug_linalg_revision", "fls_debug_plane_fit_5x3", "fls_debug_svd3", "fls_debug_lu6", "fls_debug_so3", "fls_debug_wave_sum"]
 
+# every symbol include/fls_debug_fit.h declares (FLS_DEBUG_FIT_REVISION 1): test hooks of the stages of the fit launch
+DEBUG_FIT_SYMBOLS = ["fls_debug_fit_revision", "fls_debug_plane_residual", "fls_debug_line_residual", "fls_debug_icp_point_rows", "fls_debug_rank1_mfma",
+                     "fls_debug_rank1_dpp", "fls_debug_rank1x3_mfma", "fls_debug_reduce_partials", "fls_debug_fanin", "fls_debug_last_system"]
+DEBUG_TICKET_WORDS = 320  # FLS_DEBUG_TICKET_WORDS
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -363,6 +368,24 @@ def lib():
         L.fls_debug_so3.argtypes = [C.c_int, dp, dp, C.c_int, dp, dp, dp]
         L.fls_debug_wave_sum.restype = C.c_int
         L.fls_debug_wave_sum.argtypes = [C.c_int, dp, C.c_int, dp]
+        if hasattr(L, "fls_debug_fit_revision"):  # (as fls_batch_ivox_revision above)
+            u32p = C.POINTER(C.c_uint32)
+            L.fls_debug_fit_revision.restype = C.c_int
+            L.fls_debug_fit_revision.argtypes = []
+            for f in (L.fls_debug_plane_residual, L.fls_debug_line_residual):
+                f.restype = C.c_int
+                f.argtypes = [C.c_int, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp]
+            L.fls_debug_icp_point_rows.restype = C.c_int
+            L.fls_debug_icp_point_rows.argtypes = [C.c_int, dp, dp, dp, C.c_int, dp, dp, dp]
+            for f in (L.fls_debug_rank1_mfma, L.fls_debug_rank1_dpp, L.fls_debug_rank1x3_mfma):
+                f.restype = C.c_int
+                f.argtypes = [C.c_int, dp, dp, dp, C.c_int, dp]
+            L.fls_debug_reduce_partials.restype = C.c_int
+            L.fls_debug_reduce_partials.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp]
+            L.fls_debug_fanin.restype = C.c_int
+            L.fls_debug_fanin.argtypes = [C.c_int, C.c_int, C.c_int, dp, u32p, u32p]
+            L.fls_debug_last_system.restype = C.c_int
+            L.fls_debug_last_system.argtypes = [hp, dp, dp]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

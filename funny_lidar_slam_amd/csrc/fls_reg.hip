@@ -12,10 +12,12 @@
 #include "replicas.hpp"
 #include "keyframes.hpp"
 #include "kernels_debug_linalg.hpp"
+#include "kernels_debug_fit.hpp"
 #include "../../include/fls_keyframes.h"
 #include "../../include/fls_batch.h"
 #include "../../include/fls_batch_ivox.h"
 #include "../../include/fls_debug_linalg.h"
+#include "../../include/fls_debug_fit.h"
 #include <new>
 
 using namespace fls;
@@ -424,6 +426,110 @@ fls_status fls_debug_so3(int device_id, const double* v, const double* R, int n,
 fls_status fls_debug_wave_sum(int device_id, const double* v, int n, double* total) {
     return debug_linalg_run(device_id, n, {{v, 64}}, {{total, 1}}, [&](const double* const* in, double* const* out) {
         hipLaunchKernelGGL(debug_wave_sum_kernel, dim3(unsigned(n)), dim3(64), 0, nullptr, in[0], n, out[0]);
+    });
+}
+
+// ---- test hooks of the stages of the fit launch (include/fls_debug_fit.h, kernels_debug_fit.hpp) ----------------------------------------
+int fls_debug_fit_revision(void) { return FLS_DEBUG_FIT_REVISION; }
+
+fls_status fls_debug_plane_residual(int device_id, const double* nn, const double* ps, const double* pt, const double* T, const double* gate, int n,
+                                    double* valid, double* J, double* d) {
+    return debug_linalg_run(device_id, n, {{nn, 15}, {ps, 3}, {pt, 3}, {T, 16}, {gate, 1}}, {{valid, 1}, {J, 6}, {d, 1}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_residual_kernel<false>, debug_linalg_lanes(n), dim3(kDebugFitBlock), 0, nullptr, in[0], in[1], in[2], in[3], in[4], n, out[0], out[1], out[2]);
+    });
+}
+
+fls_status fls_debug_line_residual(int device_id, const double* nn, const double* ps, const double* pt, const double* T, const double* gate, int n,
+                                   double* valid, double* J, double* d) {
+    return debug_linalg_run(device_id, n, {{nn, 15}, {ps, 3}, {pt, 3}, {T, 16}, {gate, 1}}, {{valid, 1}, {J, 6}, {d, 1}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_residual_kernel<true>, debug_linalg_lanes(n), dim3(kDebugFitBlock), 0, nullptr, in[0], in[1], in[2], in[3], in[4], n, out[0], out[1], out[2]);
+    });
+}
+
+fls_status fls_debug_icp_point_rows(int device_id, const double* T, const double* p, const double* m, int n, double* J, double* e, double* res) {
+    return debug_linalg_run(device_id, n, {{T, 16}, {p, 3}, {m, 3}}, {{J, 18}, {e, 3}, {res, 1}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_icp_point_rows_kernel, debug_linalg_lanes(n), dim3(kDebugFitBlock), 0, nullptr, in[0], in[1], in[2], n, out[0], out[1], out[2]);
+    });
+}
+
+fls_status fls_debug_rank1_mfma(int device_id, const double* contrib, const double* J, const double* r, int n, double* row) {
+    return debug_linalg_run(device_id, n, {{contrib, 64}, {J, 64 * 6}, {r, 64}}, {{row, 32}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_rank1_kernel<0>, dim3(unsigned((n + 3) / 4)), dim3(256), 0, nullptr, in[0], in[1], in[2], n, out[0]);
+    });
+}
+
+fls_status fls_debug_rank1_dpp(int device_id, const double* contrib, const double* J, const double* r, int n, double* row) {
+    return debug_linalg_run(device_id, n, {{contrib, 64}, {J, 64 * 6}, {r, 64}}, {{row, 32}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_rank1_kernel<1>, dim3(unsigned((n + 3) / 4)), dim3(256), 0, nullptr, in[0], in[1], in[2], n, out[0]);
+    });
+}
+
+fls_status fls_debug_rank1x3_mfma(int device_id, const double* contrib, const double* J, const double* e, int n, double* row) {
+    return debug_linalg_run(device_id, n, {{contrib, 64}, {J, 64 * 18}, {e, 64 * 3}}, {{row, 32}}, [&](const double* const* in, double* const* out) {
+        hipLaunchKernelGGL(debug_rank1_kernel<2>, dim3(unsigned((n + 3) / 4)), dim3(256), 0, nullptr, in[0], in[1], in[2], n, out[0]);
+    });
+}
+
+fls_status fls_debug_reduce_partials(int device_id, int variant, const double* rows, int nrows, double* tot) {
+    if (!rows || !tot || nrows < 0 || variant < 0 || variant > 3) return FLS_ERR_INVALID;
+    if (nrows == 0) return FLS_OK;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(device_id));
+        // one trip of NaN rows behind the caller's: a load past nrows shows in the totals instead of leaving the allocation
+        const size_t pad = size_t(32) * 32;
+        std::vector<double> h((size_t(nrows) + pad) * kPartialStride, std::numeric_limits<double>::quiet_NaN());
+        std::memcpy(h.data(), rows, size_t(nrows) * kPartialStride * sizeof(double));
+        DevBuf<double> drows, dtot;
+        drows.reserve(h.size()); dtot.reserve(32);
+        FLS_HIP(hipMemcpy(drows.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        const double* r = drows.p;
+        if (variant == 0) hipLaunchKernelGGL((debug_reduce_partials_kernel<256, true, 32, LuTailSmem>), dim3(1), dim3(256), 0, nullptr, r, nrows, dtot.p);
+        else if (variant == 1) hipLaunchKernelGGL((debug_reduce_partials_kernel<512, true, 16, LoamTailSmem>), dim3(1), dim3(512), 0, nullptr, r, nrows, dtot.p);
+        else if (variant == 2) hipLaunchKernelGGL((debug_reduce_partials_kernel<512, true, 32, LuTailSmem>), dim3(1), dim3(512), 0, nullptr, r, nrows, dtot.p);
+        else hipLaunchKernelGGL((debug_reduce_partials_kernel<1024, false, 16, LoamTailSmem>), dim3(1), dim3(1024), 0, nullptr, r, nrows, dtot.p);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipMemcpy(tot, dtot.p, 32 * sizeof(double), hipMemcpyDeviceToHost));
+        return FLS_OK;
+    });
+}
+
+fls_status fls_debug_fanin(int device_id, int nblocks, int shards, double* tot, uint32_t* last, uint32_t* ticket) {
+    static_assert(FLS_DEBUG_TICKET_WORDS == kTicketWords && kPartialStride == 32, "fls_debug_fit.h states the layout");
+    if (!tot || !last || !ticket || nblocks < 1 || nblocks > 65535 || shards < 1) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(device_id));
+        DevBuf<double> dpart, dtot;
+        DevBuf<unsigned> dticket, dlast;
+        const size_t pad = size_t(32) * 8;  // (NaN rows behind the last one, as in fls_debug_reduce_partials)
+        std::vector<double> h((size_t(nblocks) + pad) * kPartialStride, std::numeric_limits<double>::quiet_NaN());
+        std::fill(h.begin(), h.begin() + size_t(nblocks) * kPartialStride, 0.0);
+        dpart.reserve(h.size()); dtot.reserve(64); dticket.reserve(kTicketWords); dlast.reserve(2);
+        FLS_HIP(hipMemcpy(dpart.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        const std::vector<double> canary(64, 7.0);
+        FLS_HIP(hipMemcpy(dtot.p, canary.data(), 64 * sizeof(double), hipMemcpyHostToDevice));
+        FLS_HIP(hipMemset(dticket.p, 0, kTicketWords * sizeof(unsigned)));
+        FLS_HIP(hipMemset(dlast.p, 0, 2 * sizeof(unsigned)));
+        for (int k = 0; k < 2; ++k) {
+            hipLaunchKernelGGL(debug_fanin_kernel, dim3(unsigned(nblocks)), dim3(256), 0, nullptr, dpart.p, dticket.p, shards, double(k + 1), 1000.0 * k, dlast.p + k,
+                               dtot.p + 32 * k);
+            FLS_HIP(hipGetLastError());
+        }
+        FLS_HIP(hipMemcpy(tot, dtot.p, 64 * sizeof(double), hipMemcpyDeviceToHost));
+        FLS_HIP(hipMemcpy(last, dlast.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
+        FLS_HIP(hipMemcpy(ticket, dticket.p, kTicketWords * sizeof(unsigned), hipMemcpyDeviceToHost));
+        return FLS_OK;
+    });
+}
+
+fls_status fls_debug_last_system(fls_handle h, double* H36, double* g6) {
+    if (!h || !H36 || !g6) return FLS_ERR_INVALID;
+    if (!h->d_state.p) return FLS_ERR_STATE;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        FLS_HIP(hipStreamSynchronize(h->stream));
+        FLS_HIP(hipMemcpy(H36, reinterpret_cast<const char*>(h->d_state.p) + offsetof(GnState, H), 36 * sizeof(double), hipMemcpyDeviceToHost));
+        FLS_HIP(hipMemcpy(g6, reinterpret_cast<const char*>(h->d_state.p) + offsetof(GnState, g), 6 * sizeof(double), hipMemcpyDeviceToHost));
+        return FLS_OK;
     });
 }
 

@@ -101,6 +101,10 @@ void flo_set_instrumentation(void* h, int on);
 void flo_set_tie_break_by_id(int on);
 /* last Match's per-iteration H (36, col-major) and g (6) for reduction-tolerance tests */
 int flo_get_last_system(void* h, double* H36, double* g6);
+/* next to it: the sums of the ABSOLUTE values of the terms that H and g were summed from (LOAM family: |J_a J_b|, |J_a r| per point; IcpOptimized:
+ * per row of each point's Jacobian; IncrementalNDT: the per-point terms), the scale of a summation-order bound.  Returns the number of terms per
+ * entry.  Filled only while instrumentation is on (the default). */
+uint64_t flo_get_last_abs_system(void* h, double* absH36, double* absg6);
 size_t flo_map_size(void* h, int slot); /* points (iVox / kd maps) or voxels (NDT) */
 size_t flo_map_voxels(void* h);
 void flo_set_ivox_capacity(void* h, size_t cap); /* test hook for the LRU eviction rule */
@@ -160,6 +164,10 @@ void flo_fullpiv_qr_solve_6(const double A_colmajor[36], const double b[6], doub
 void flo_lu_inverse_6(const double A_colmajor[36], double inv[36], double* det);
 void flo_inverse3(const double A[9], double inv[9]);
 void flo_svd3(const double A[9], double U[9], double S[3], double V[9]);
+/* the point-to-plane / point-to-line residual lambdas of the LOAM family on caller-supplied neighbours, n systems: nn[n][5][3], ps[n][3] (source point),
+ * pt[n][3] (transformed point), T[n][16], gate[n] (plane threshold / line ratio) -> valid[n], J[n][6], d[n] (left alone where the lambda returns early) */
+void flo_plane_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d);
+void flo_line_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d);
 int flo_knn_bruteforce(const float* map_xyz, size_t m, const float* q, int k, int32_t* idx, float* d2);
 int flo_kdtree_knn(const float* map_xyz, size_t m, const float* queries, size_t nq, int k, int32_t* idx, float* d2);
 

@@ -46,6 +46,11 @@ struct MatcherBase {
     flo_counters counters{};
     std::vector<IterLog> log;
     double last_H[36]{}, last_g[6]{};
+    // sums of the absolute values of the terms last_H / last_g were summed from, and how many terms each entry has (flo_get_last_abs_system: the
+    // scale of a summation-order error bound); filled only while `instrument` is on, in loops of their own: the sums above keep their bits
+    double last_absH[36]{}, last_absg[6]{};
+    uint64_t last_terms = 0;
+    void AbsReset() { std::memset(last_absH, 0, sizeof(last_absH)); std::memset(last_absg, 0, sizeof(last_absg)); last_terms = 0; }
     bool instrument = true;  // traffic / tie counters of the kNN stage (flo_set_instrumentation: off for timing runs)
     // per query: the neighbour list it holds now was written by a search that met an exact distance tie (nearest two, or across the K / K + 1
     // boundary) -- the rows whose slot order / membership libstdc++'s introselect decides.  Sticky like the list itself (Q15).  Kinds
@@ -112,6 +117,12 @@ static inline void fill_rank1(PerPoint& pp, const double J[6], double r) {
         for (int a = 0; a < 6; ++a) pp.H[a + b * 6] = J[a] * J[b];
     for (int a = 0; a < 6; ++a) pp.g[a] = (-J[a]) * r;
     pp.res = r;
+}
+
+static inline void abs_rank1(MatcherBase& m, const PerPoint& pp) {
+    for (int k = 0; k < 36; ++k) m.last_absH[k] += std::fabs(pp.H[k]);
+    for (int k = 0; k < 6; ++k) m.last_absg[k] += std::fabs(pp.g[k]);
+    m.last_terms++;
 }
 
 // LOAM-family Gauss-Newton tail: dx = fullPivQR(H).solve(g); left update; stop rule.
@@ -292,6 +303,10 @@ struct P2PlaneIvox final : MatcherBase {
                 overall_res += coeffs[i].res;
             }
             std::memcpy(last_H, H, sizeof(H)); std::memcpy(last_g, g, sizeof(g));
+            if (instrument) {
+                AbsReset();
+                for (size_t i = 0; i < number_planar_point; ++i) if (flags[i]) abs_rank1(*this, coeffs[i]);
+            }
             const bool stop = loam_update(T_, H, g, p.rotation_converge_thres, p.position_converge_thres, st, stats.last_dx);
             stats.iterations = int(it) + 1;
             Log(T_, int(n_valid), overall_res);
@@ -415,6 +430,23 @@ struct IcpOptimized final : MatcherBase {
                 total_res += norm3(&err[3 * i]);
             }
             std::memcpy(last_H, H, sizeof(H)); std::memcpy(last_g, B, sizeof(B));
+            if (instrument) {  // the three rows of each point: |J_ra J_rb| and |J_ra e_r|, with J = [I | -R hat(o)] rebuilt as above
+                AbsReset();
+                for (size_t i = 0; i < n; ++i) {
+                    if (!eff[i]) continue;
+                    const double o[3] = {double(source[i].x), double(source[i].y), double(source[i].z)};
+                    double R[9], hat[9], RH[9], J[18];
+                    for (int j = 0; j < 3; ++j) for (int r = 0; r < 3; ++r) R[r + j * 3] = Tt[r + j * 4];
+                    so3_hat(o, hat);
+                    mat3_mul(R, hat, RH);
+                    for (int j = 0; j < 3; ++j) for (int r = 0; r < 3; ++r) { J[r + j * 3] = (r == j) ? 1.0 : 0.0; J[r + (j + 3) * 3] = -RH[r + j * 3]; }
+                    for (int r = 0; r < 3; ++r) {
+                        for (int b = 0; b < 6; ++b) for (int a = 0; a < 6; ++a) last_absH[a + b * 6] += std::fabs(J[r + a * 3] * J[r + b * 3]);
+                        for (int a = 0; a < 6; ++a) last_absg[a] += std::fabs(J[r + a * 3] * err[3 * i + size_t(r)]);
+                        last_terms++;
+                    }
+                }
+            }
             stats.iterations = int(it) + 1; stats.n_valid = effective; stats.sum_res = total_res;
             PartialPivLU<6> lu;
             lu.compute(H);
@@ -665,6 +697,25 @@ struct IncNdt final : MatcherBase {
                     b[a] += ((-JtI[a + 0 * 6]) * e[0] + (-JtI[a + 1 * 6]) * e[1]) + (-JtI[a + 2 * 6]) * e[2];
             }
             std::memcpy(last_H, H, sizeof(H)); std::memcpy(last_g, b, sizeof(b));
+            if (instrument) {  // the per-point terms, formed as above
+                AbsReset();
+                for (size_t ri = 0; ri < total; ++ri) {
+                    if (!eff7[ri]) continue;
+                    const double* e = &err[ri * 3];
+                    const double* I = &infov[ri * 9];
+                    const double* J = &jac[ri * 18];
+                    double JtI[18];
+                    for (int c = 0; c < 3; ++c)
+                        for (int a = 0; a < 6; ++a)
+                            JtI[a + c * 6] = (J[0 + a * 3] * I[0 + c * 3] + J[1 + a * 3] * I[1 + c * 3]) + J[2 + a * 3] * I[2 + c * 3];
+                    for (int bb = 0; bb < 6; ++bb)
+                        for (int a = 0; a < 6; ++a)
+                            last_absH[a + bb * 6] += std::fabs((JtI[a + 0 * 6] * J[0 + bb * 3] + JtI[a + 1 * 6] * J[1 + bb * 3]) + JtI[a + 2 * 6] * J[2 + bb * 3]);
+                    for (int a = 0; a < 6; ++a)
+                        last_absg[a] += std::fabs(((-JtI[a + 0 * 6]) * e[0] + (-JtI[a + 1 * 6]) * e[1]) + (-JtI[a + 2 * 6]) * e[2]);
+                    last_terms++;
+                }
+            }
             stats.iterations = it + 1; stats.n_valid = effective; stats.sum_res = total_res; stats.n_source = int(n);
             if (effective < p.ndt_min_effective_pts) {
                 std::memcpy(T, pose, sizeof(pose));
@@ -862,6 +913,11 @@ struct LoamFull final : MatcherBase {
             sum_features(corner, H, g, nvc, rc);  // :347-372: corners first, then planars
             sum_features(planar, H, g, nvp, rp);
             std::memcpy(last_H, H, sizeof(H)); std::memcpy(last_g, g, sizeof(g));
+            if (instrument) {
+                AbsReset();
+                for (const FeatureSet* f : {&corner, &planar})
+                    for (size_t i = 0; i < f->flags.size(); ++i) if (f->flags[i]) abs_rank1(*this, f->coeffs[i]);
+            }
             const bool stop = loam_update(T_, H, g, p.rotation_converge_thres, p.position_converge_thres, st, stats.last_dx);
             stats.iterations = int(it) + 1;
             Log(T_, int(nvp), rp);
@@ -954,6 +1010,10 @@ struct P2PlaneKd final : MatcherBase {  // loam_point_to_plane_kdtree.h
             PlanerMatch(planar_source);
             sum_features(planar, H, g, nv, res);
             std::memcpy(last_H, H, sizeof(H)); std::memcpy(last_g, g, sizeof(g));
+            if (instrument) {
+                AbsReset();
+                for (size_t i = 0; i < planar.flags.size(); ++i) if (planar.flags[i]) abs_rank1(*this, planar.coeffs[i]);
+            }
             const bool stop = loam_update(T_, H, g, p.rotation_converge_thres, p.position_converge_thres, st, stats.last_dx);
             stats.iterations = int(it) + 1;
             Log(T_, int(nv), res);
@@ -1049,6 +1109,12 @@ int flo_get_last_system(void* h, double* H36, double* g6) {
     std::memcpy(H36, m->last_H, sizeof(m->last_H));
     std::memcpy(g6, m->last_g, sizeof(m->last_g));
     return 0;
+}
+uint64_t flo_get_last_abs_system(void* h, double* absH36, double* absg6) {
+    auto* m = static_cast<MatcherBase*>(h);
+    std::memcpy(absH36, m->last_absH, sizeof(m->last_absH));
+    std::memcpy(absg6, m->last_absg, sizeof(m->last_absg));
+    return m->last_terms;
 }
 void flo_set_instrumentation(void* h, int on) { static_cast<MatcherBase*>(h)->instrument = on != 0; }
 void flo_set_tie_break_by_id(int on) { flo::tie_break_by_id() = on != 0; }
@@ -1204,6 +1270,22 @@ void flo_lu_inverse_6(const double A[36], double inv[36], double* det) {
     *det = lu.determinant();
 }
 void flo_inverse3(const double A[9], double inv[9]) { inverse3(A, inv); }
+// the per-point residual lambdas on caller-supplied neighbours, n systems: nn[n][5][3], ps[n][3], pt[n][3] floats, T[n][16], gate[n]
+// (plane threshold / line ratio) -> valid[n], J[n][6], d[n]; J and d are left alone where the lambda returned early
+void flo_plane_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d) {
+    for (size_t s = 0; s < n; ++s) {
+        P4 q[5];
+        for (int j = 0; j < 5; ++j) q[j] = P4{nn[s * 15 + j * 3], nn[s * 15 + j * 3 + 1], nn[s * 15 + j * 3 + 2], 0.f};
+        valid[s] = plane_residual(q, P4{ps[s * 3], ps[s * 3 + 1], ps[s * 3 + 2], 0.f}, P4{pt[s * 3], pt[s * 3 + 1], pt[s * 3 + 2], 0.f}, T + s * 16, gate[s], J + s * 6, d[s]) ? 1 : 0;
+    }
+}
+void flo_line_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d) {
+    for (size_t s = 0; s < n; ++s) {
+        P4 q[5];
+        for (int j = 0; j < 5; ++j) q[j] = P4{nn[s * 15 + j * 3], nn[s * 15 + j * 3 + 1], nn[s * 15 + j * 3 + 2], 0.f};
+        valid[s] = line_residual(q, P4{ps[s * 3], ps[s * 3 + 1], ps[s * 3 + 2], 0.f}, P4{pt[s * 3], pt[s * 3 + 1], pt[s * 3 + 2], 0.f}, T + s * 16, gate[s], J + s * 6, d[s]) ? 1 : 0;
+    }
+}
 void flo_svd3(const double A[9], double U[9], double S[3], double V[9]) { jacobi_svd3(A, U, S, V); }
 int flo_knn_bruteforce(const float* map, size_t m, const float* q, int k, int32_t* idx, float* d2) {
     std::vector<KdTree::Hit> all(m);

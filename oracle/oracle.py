@@ -176,6 +176,12 @@ def lib():
         L.flo_set_tie_break_by_id.restype = None
         L.flo_set_tie_break_by_id.argtypes = [C.c_int]
         L.flo_get_last_system.argtypes = [C.c_void_p, dp, dp]
+        L.flo_get_last_abs_system.restype = C.c_uint64
+        L.flo_get_last_abs_system.argtypes = [C.c_void_p, dp, dp]
+        L.flo_plane_residual.restype = None
+        L.flo_plane_residual.argtypes = [fp, fp, fp, dp, dp, C.c_size_t, bp, dp, dp]
+        L.flo_line_residual.restype = None
+        L.flo_line_residual.argtypes = [fp, fp, fp, dp, dp, C.c_size_t, bp, dp, dp]
         L.flo_map_size.restype = C.c_size_t
         L.flo_map_size.argtypes = [C.c_void_p, C.c_int]
         L.flo_map_voxels.restype = C.c_size_t
@@ -334,6 +340,12 @@ class OracleMatcher:
         lib().flo_get_last_system(self._h, H.ctypes.data_as(C.POINTER(C.c_double)), g.ctypes.data_as(C.POINTER(C.c_double)))
         return H.reshape(6, 6, order="F"), g
 
+    def last_abs_system(self):
+        """(sum of |terms| of H (6, 6), of g (6,), terms per entry) of the last iteration: flo_get_last_abs_system"""
+        H = np.zeros(36); g = np.zeros(6)
+        n = lib().flo_get_last_abs_system(self._h, H.ctypes.data_as(C.POINTER(C.c_double)), g.ctypes.data_as(C.POINTER(C.c_double)))
+        return H.reshape(6, 6, order="F"), g, int(n)
+
     def map_size(self, slot=0):
         return int(lib().flo_map_size(self._h, slot))
 
@@ -402,6 +414,26 @@ def lu_inverse_6(A):
     a, pa = _f64(np.asarray(A, dtype=np.float64).reshape(-1, order="F")); inv = np.zeros(36); det = C.c_double()
     lib().flo_lu_inverse_6(pa, inv.ctypes.data_as(C.POINTER(C.c_double)), C.byref(det))
     return inv.reshape(6, 6, order="F"), det.value
+
+
+def _residual(fn, nn, ps, pt, T, gate):
+    nn_, pn = _f32(np.asarray(nn).reshape(-1, 15)); ps_, pp = _f32(ps); pt_, pq = _f32(pt); T_, pT = _f64(T); g_, pg = _f64(gate)
+    n = nn_.shape[0]
+    assert ps_.shape == (n, 3) and pt_.shape == (n, 3) and T_.shape == (n, 16) and g_.shape == (n,)
+    valid = np.zeros(n, np.uint8); J = np.full((n, 6), 7.0); d = np.full(n, 7.0)
+    fn(pn, pp, pq, pT, pg, n, valid.ctypes.data_as(C.POINTER(C.c_uint8)), J.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_double)))
+    return valid.astype(bool), J, d
+
+
+def plane_residual(nn, ps, pt, T, thres):
+    """the point-to-plane lambda on n systems: nn (n, 5, 3), ps / pt (n, 3), T (n, 16) column-major, thres (n,) -> valid (n,) bool, J (n, 6), d_abs (n,);
+    J and d_abs hold 7.0 where the lambda returned early"""
+    return _residual(lib().flo_plane_residual, nn, ps, pt, T, thres)
+
+
+def line_residual(nn, ps, pt, T, ratio):
+    """the point-to-line lambda, same shapes: -> valid, J, dist"""
+    return _residual(lib().flo_line_residual, nn, ps, pt, T, ratio)
 
 
 def inverse3(A):

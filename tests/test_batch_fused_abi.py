@@ -32,7 +32,7 @@ def test_existing_abi_is_untouched(built):
     L = _lib.lib()
     assert L.fls_abi_revision() == 9 and L.fls_abi_version() == 1
     assert set(_lib.EXPORTED_SYMBOLS) == _declared("fls_reg.h") | _declared("fls_features.h")
-    others = _lib.EXPORTED_SYMBOLS + _lib.PREPROCESS_SYMBOLS + _lib.INGEST_SYMBOLS + _lib.KEYFRAMES_SYMBOLS + _lib.DEBUG_LINALG_SYMBOLS
+    others = _lib.EXPORTED_SYMBOLS + _lib.PREPROCESS_SYMBOLS + _lib.INGEST_SYMBOLS + _lib.KEYFRAMES_SYMBOLS + _lib.DEBUG_LINALG_SYMBOLS + _lib.DEBUG_FIT_SYMBOLS
     assert not set(_lib.BATCH_SYMBOLS) & set(others)
     assert len(_lib.EXPORTED_SYMBOLS) == 44
     assert "#define FLS_ABI_REVISION 9" in open(os.path.join(ROOT, "include", "fls_reg.h")).read()

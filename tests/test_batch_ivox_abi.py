@@ -36,7 +36,7 @@ def test_existing_abi_and_the_fused_batch_header_are_untouched(built):
     assert len(_lib.EXPORTED_SYMBOLS) == 44
     assert _lib.BATCH_SYMBOLS == ["fls_batch_revision", "fls_match_batch_fused", "fls_batch_stat"]
     assert set(_lib.BATCH_SYMBOLS) == _declared("fls_batch.h") and L.fls_batch_revision() == 1
-    others = (_lib.EXPORTED_SYMBOLS + _lib.PREPROCESS_SYMBOLS + _lib.INGEST_SYMBOLS + _lib.KEYFRAMES_SYMBOLS + _lib.DEBUG_LINALG_SYMBOLS +
+    others = (_lib.EXPORTED_SYMBOLS + _lib.PREPROCESS_SYMBOLS + _lib.INGEST_SYMBOLS + _lib.KEYFRAMES_SYMBOLS + _lib.DEBUG_LINALG_SYMBOLS + _lib.DEBUG_FIT_SYMBOLS +
               _lib.BATCH_SYMBOLS)
     assert not set(_lib.BATCH_IVOX_SYMBOLS) & set(others)
     assert "#define FLS_ABI_REVISION 9" in open(os.path.join(ROOT, "include", "fls_reg.h")).read()
