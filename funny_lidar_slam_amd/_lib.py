@@ -51,6 +51,9 @@ DEBUG_FIT_SYMBOLS = ["fls_debug_fit_revision", "fls_debug_plane_residual", "fls_
                      "fls_debug_rank1_dpp", "fls_debug_rank1x3_mfma", "fls_debug_reduce_partials", "fls_debug_fanin", "fls_debug_last_system"]
 DEBUG_TICKET_WORDS = 320  # FLS_DEBUG_TICKET_WORDS
 
+# every symbol include/fls_debug_ndt.h declares (FLS_DEBUG_NDT_REVISION 1): test read-out of the NDT voxel map
+DEBUG_NDT_SYMBOLS = ["fls_debug_ndt_revision", "fls_debug_ndt_voxels"]
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -386,6 +389,11 @@ def lib():
             L.fls_debug_fanin.argtypes = [C.c_int, C.c_int, C.c_int, dp, u32p, u32p]
             L.fls_debug_last_system.restype = C.c_int
             L.fls_debug_last_system.argtypes = [hp, dp, dp]
+        if hasattr(L, "fls_debug_ndt_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_debug_ndt_revision.restype = C.c_int
+            L.fls_debug_ndt_revision.argtypes = []
+            L.fls_debug_ndt_voxels.restype = C.c_int
+            L.fls_debug_ndt_voxels.argtypes = [hp, C.c_size_t, ip, ip, ip, bp, bp, dp, dp, dp, C.POINTER(C.c_size_t)]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

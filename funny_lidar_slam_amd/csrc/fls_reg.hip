@@ -18,6 +18,7 @@
 #include "../../include/fls_batch_ivox.h"
 #include "../../include/fls_debug_linalg.h"
 #include "../../include/fls_debug_fit.h"
+#include "../../include/fls_debug_ndt.h"
 #include <new>
 
 using namespace fls;
@@ -518,6 +519,21 @@ fls_status fls_debug_fanin(int device_id, int nblocks, int shards, double* tot, 
         FLS_HIP(hipMemcpy(last, dlast.p, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));
         FLS_HIP(hipMemcpy(ticket, dticket.p, kTicketWords * sizeof(unsigned), hipMemcpyDeviceToHost));
         return FLS_OK;
+    });
+}
+
+// ---- test read-out of the NDT voxel map (include/fls_debug_ndt.h) ----------------------------------------------------------------------
+int fls_debug_ndt_revision(void) { return FLS_DEBUG_NDT_REVISION; }
+
+fls_status fls_debug_ndt_voxels(fls_handle h, size_t cap, int32_t* keys, int32_t* vid, int32_t* num_points, uint8_t* estimated, uint8_t* pending,
+                                double* mu, double* sigma, double* info, size_t* n) {
+    if (!h || !n || h->kind != FLS_INCREMENTAL_NDT) return FLS_ERR_INVALID;
+    if (cap && (!keys || !vid || !num_points || !estimated || !pending || !mu || !sigma || !info)) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status {
+        NdtMatcher& m = *static_cast<NdtMatcher*>(h);
+        if (m.device_mode) FLS_HIP(hipSetDevice(h->device));
+        *n = m.dump_voxels(cap, NdtMatcher::VoxelDump{keys, vid, num_points, estimated, pending, mu, sigma, info});
+        return cap < *n ? FLS_ERR_NOMEM : FLS_OK;
     });
 }
 

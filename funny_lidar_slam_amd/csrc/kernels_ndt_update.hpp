@@ -2,9 +2,10 @@
 //
 // Reference: incremental_ndt.h:182-227 (per point: key = cast<int>(p * inv_voxel_size); new voxel -> push_front + capacity
 // check, known voxel -> append + splice to the front; then UpdateVoxel of every touched voxel, :130-179).  This file covers the
-// mapping-mode steady state: flag_first_scan == false, with the LRU evictions a batch causes (ndt_evict_select).  Anything
-// else (first scan, localization mode, evictions that would reach voxels of the batch itself, a key out of range) is refused without side effects and runs
-// through the exact sequential host code (matcher_ndt.hpp), which first downloads the device state.
+// mapping-mode steady state (flag_first_scan == false, ndt_upd_voxel) and the first-scan rule of UpdateVoxel (:131-143,
+// ndt_upd_voxel_first: the first cloud of a handle and every reload of a localization handle), both with the LRU evictions a batch
+// causes (ndt_evict_select).  Anything else (evictions that would reach voxels of the batch itself, a key out of range) is refused
+// without side effects and runs through the exact sequential host code (matcher_ndt.hpp), which first downloads the device state.
 //
 // How the sequential semantics are recovered from a parallel pass:
 //   * a voxel's points are consumed in cloud order: the {row, point} pairs are sorted by row with the stable radix sort of
@@ -26,7 +27,7 @@ namespace fls {
 
 constexpr unsigned kNdtNewBit = 0x80000000u;  // HashEntry.begin of an EMPTY or freshly claimed entry: 2^31 | (2^31 - 1 - first index)
 constexpr int kNdtCarry = 8;                  // unconsumed points kept per voxel between scans (min_points <= kNdtCarry)
-constexpr unsigned kNdtOk = 0u, kNdtNeedHost = 1u;
+constexpr unsigned kNdtOk = 0u, kNdtNeedHost = 1u, kNdtOutOfRange = 2u;  // status bits (kNdtOutOfRange: set beside kNdtNeedHost, tells the host why)
 constexpr unsigned long long kNdtTombKey = ~0ull - 1ull;  // table entry of an evicted voxel: probes walk past it (never equal to a packed key, not EMPTY)
 constexpr unsigned long long kNdtDeadKey = ~0ull - 2ull;  // r.key of an evicted row
 
@@ -74,7 +75,7 @@ ndt_upd_locate(const float* __restrict__ x, const float* __restrict__ y, const f
     if (i >= n) return;
     const double f0 = (double)x[i] * inv_voxel, f1 = (double)y[i] * inv_voxel, f2 = (double)z[i] * inv_voxel;
     if (!(fabs(f0) < (double)kKeyLimit) || !(fabs(f1) < (double)kKeyLimit) || !(fabs(f2) < (double)kKeyLimit)) {
-        atomicOr(&st->status, kNdtNeedHost);  // FLS_ERR_RANGE on the host path: all-or-nothing
+        atomicOr(&st->status, kNdtNeedHost | kNdtOutOfRange);  // FLS_ERR_RANGE on the host path: all-or-nothing
         slot_h[i] = 0xffffffffu;
         return;
     }
@@ -279,6 +280,8 @@ ndt_upd_create(const float* __restrict__ x, const float* __restrict__ y, const f
     r.vid[row] = st->next_vid + (int)rank;
     r.stamp[row] = 0ull;
     r.touch[row] = ndt_touch_word(st->seq, (unsigned)i);
+    for (int a = 0; a < 3; ++a) r.mu[3 * (size_t)row + a] = 0.0;  // VoxelData's initialisers (:79-81): a single-point first-scan voxel keeps this sigma
+    for (int a = 0; a < 9; ++a) { r.sigma[9 * (size_t)row + a] = 0.0; r.info[9 * (size_t)row + a] = 0.0; }
     table[h].begin = row;
     table[h].count = 0u;  // not estimated yet: ndt_kernel skips it
 }
@@ -380,6 +383,83 @@ ndt_upd_voxel(const unsigned* __restrict__ key, const unsigned* __restrict__ val
         r.num_points[row] = np + npts;
     }
     r.carry_cnt[row] = 0;
+}
+
+// hm::ndt_mean_cov over one segment's points val[0, len): the same two serial chains, term by term in cloud order.  The points are reached
+// through val[], so every trip first issues kNdtSegLoads index loads, then the 3 kNdtSegLoads coordinate loads they address, and only then
+// feeds the chain: the dependent-load latency is paid once per trip instead of once per point (a segment holds well over a hundred points
+// when a 0.2 m leaf fills 1 m voxels).  A short last trip re-reads the segment's last point and leaves it out of the sums.
+constexpr int kNdtSegLoads = 8;
+__device__ inline void ndt_segment_mean_cov(const unsigned* __restrict__ val, const int len, const float* __restrict__ x, const float* __restrict__ y,
+                                            const float* __restrict__ z, double* mean, double* cov) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int k0 = 0; k0 < len; k0 += kNdtSegLoads) {
+        unsigned p[kNdtSegLoads];
+        float fx[kNdtSegLoads], fy[kNdtSegLoads], fz[kNdtSegLoads];
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j) p[j] = val[min(k0 + j, len - 1)];
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j) { fx[j] = x[p[j]]; fy[j] = y[p[j]]; fz[j] = z[p[j]]; }
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j)
+            if (k0 + j < len) { s0 += (double)fx[j]; s1 += (double)fy[j]; s2 += (double)fz[j]; }
+    }
+    mean[0] = s0 / double(len); mean[1] = s1 / double(len); mean[2] = s2 / double(len);
+    double c[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < len; k0 += kNdtSegLoads) {
+        unsigned p[kNdtSegLoads];
+        float fx[kNdtSegLoads], fy[kNdtSegLoads], fz[kNdtSegLoads];
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j) p[j] = val[min(k0 + j, len - 1)];
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j) { fx[j] = x[p[j]]; fy[j] = y[p[j]]; fz[j] = z[p[j]]; }
+#pragma unroll
+        for (int j = 0; j < kNdtSegLoads; ++j)
+            if (k0 + j < len) {
+                const double v[3] = {(double)fx[j] - mean[0], (double)fy[j] - mean[1], (double)fz[j] - mean[2]};
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) c[a + b * 3] += v[a] * v[b];
+            }
+    }
+    for (int k = 0; k < 9; ++k) cov[k] = c[k] / double(len - 1);
+}
+
+// one thread per touched voxel (segment head of the sorted pairs): UpdateVoxel with flag_first_scan set, incremental_ndt.h:131-143 -- the
+// first cloud of a handle and every reload of a localization handle.  Statistics from the batch's points of the voxel alone, no min / max
+// gates (the first-scan test comes before them), nothing is carried over.  The sums are serial chains whose order bit identity with the
+// host fixes, so a segment is one thread's; the parallelism is the number of voxels.
+__global__ void __launch_bounds__(64)
+ndt_upd_voxel_first(const unsigned* __restrict__ key, const unsigned* __restrict__ val, const int n, const float* __restrict__ x,
+                    const float* __restrict__ y, const float* __restrict__ z, const NdtRows r, HashEntry* __restrict__ table,
+                    NdtUpdState* __restrict__ st) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= n || !st->apply) return;
+    const unsigned row = key[e];
+    if (e > 0 && key[e - 1] == row) return;
+    int len = 1;
+    while (e + len < n && key[e + len] == row) ++len;
+    atomicAdd(&st->touched, 1u);
+    r.stamp[row] = st->epoch + (unsigned long long)val[e + len - 1] + 1ull;
+    if (!r.estimated[row]) r.num_points[row] += len;  // (:73-75; 1 at creation)
+    double* const mu = r.mu + 3 * (size_t)row;
+    double* const info = r.info + 9 * (size_t)row;
+    if (len > 1) {
+        double m[3], s[9], inf[9];
+        ndt_segment_mean_cov(val + e, len, x, y, z, m, s);
+        hm::ndt_regularised_info(s, inf);
+        double* const sigma = r.sigma + 9 * (size_t)row;
+        for (int a = 0; a < 3; ++a) mu[a] = m[a];
+        for (int a = 0; a < 9; ++a) { sigma[a] = s[a]; info[a] = inf[a]; }
+    } else {  // :136-137 (sigma stays: zero in a new voxel, the previous estimate in an old one)
+        const unsigned p = val[e];
+        mu[0] = (double)x[p]; mu[1] = (double)y[p]; mu[2] = (double)z[p];
+        for (int k = 0; k < 9; ++k) info[k] = ((k % 4 == 0) ? 1.0 : 0.0) * 1.0e2;
+    }
+    r.estimated[row] = 1;
+    r.carry_cnt[row] = 0;
+    table[r.hslot[row]].count = 1u;  // visible to ndt_kernel from the next Match on
 }
 
 __global__ void ndt_upd_commit(NdtUpdState* __restrict__ st, const unsigned n) {

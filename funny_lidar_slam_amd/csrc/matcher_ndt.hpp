@@ -1,7 +1,8 @@
 // matcher_ndt.hpp -- host side of FLS_INCREMENTAL_NDT, the replacement of IncrementalNDT
 // (include/registration/incremental_ndt.h:16-383).
-//   AddCloudToLocalMap :182-227  voxel insert with LRU eviction + UpdateVoxel (:130-179) on the host;
-//                                the estimated voxels are flattened into a device hash table
+//   AddCloudToLocalMap :182-227  voxel insert with LRU eviction + UpdateVoxel (:130-179): on the device (kernels_ndt_update.hpp) -- a whole
+//                                cloud through add_cloud_build (first-scan rule), later scans as incremental batches -- and on the host
+//                                for whatever the device declines: there the estimated voxels are flattened into a device hash table
 //                                {key -> slot} with mu[slot], info[slot] in FP64.
 //   Match              :229-337  device-resident loop: ndt_lanes_kernel (7-voxel Mahalanobis scoring,
 //                                FP64, the Gauss-Newton tail in its last workgroup; mode 1).
@@ -88,6 +89,8 @@ struct NdtMatcher final : fls_matcher {
         init_tickets(d_ticket);
         if (const char* e = std::getenv("FLS_NDT_DEVICE_UPDATE")) allow_device_update = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_NDT_DEVICE_SLACK")) { const long c = std::atol(e); if (c >= 0) device_slack = size_t(c); }
+        if (const char* e = std::getenv("FLS_NDT_DEVICE_BUILD")) allow_device_build = std::atoi(e) != 0;
+        if (!allow_device_update) allow_device_build = false;  // a handle told to stay on the host stays there
         inv_voxel = 1.0 / p.ndt_voxel_size;
         return FLS_OK;
     }
@@ -252,8 +255,11 @@ struct NdtMatcher final : fls_matcher {
 
     // ---- device map update (kernels_ndt_update.hpp): the image holds EVERY alive voxel (table count = "estimated"), the
     // per-voxel bookkeeping lives in device rows, the host mirror (pool / LRU list / key map) is stale until
-    // sync_host_from_device().  Entered after a host-path update in mapping mode, left for good by the first refused batch.
+    // sync_host_from_device().  Entered by the first cloud of a handle, from nothing (add_cloud_build: no mirror is uploaded), or from the
+    // mirror after a host-path update (enter_device_mode); left by a refused batch or build and entered again eight host-path updates later.
+    // A localization handle stays in it across its reloads.
     bool allow_device_update = true;  // FLS_NDT_DEVICE_UPDATE
+    bool allow_device_build = true;   // FLS_NDT_DEVICE_BUILD (off with FLS_NDT_DEVICE_UPDATE=0 as well)
     size_t device_slack = 65536;      // FLS_NDT_DEVICE_SLACK: spare table entries / rows allocated ahead (test hook: small values force growth)
     bool device_mode = false, device_left = false;
     unsigned host_updates_since_left = 0;  // device mode is re-entered after a refusal once eight host-path updates went by (hysteresis)
@@ -290,9 +296,36 @@ struct NdtMatcher final : fls_matcher {
     bool can_enter_device_mode() const {
         // after a refusal (device_left) the handle comes back once eight host-path updates went by: a scan that left the key range or
         // an eviction the device could not order exactly is an episode, not a reason to stay on the 2 ms host path for good
-        const bool left = device_left && host_updates_since_left < 8;
-        return allow_device_update && !left && !device_mode && !owner && !p.is_localization_mode && !flag_first_scan &&
-               p.ndt_min_points_in_voxel <= kNdtCarry && p.ndt_min_points_in_voxel >= 0 && p.ndt_capacity > 2;
+        // (a localization handle keeps flag_first_scan: every reload of it is a build, so it comes back only where builds run)
+        const bool kind_ok = p.is_localization_mode ? allow_device_build && build_filter_ok() : !flag_first_scan;
+        return allow_device_update && !staying_on_host() && !device_mode && !owner && kind_ok && device_rows_fit();
+    }
+    bool staying_on_host() const { return device_left && host_updates_since_left < 8; }
+    bool device_rows_fit() const { return p.ndt_min_points_in_voxel <= kNdtCarry && p.ndt_min_points_in_voxel >= 0 && p.ndt_capacity > 2; }
+    // the build filters on the device and needs the host filter's bits: the exact-order form of the device VoxelGrid
+    static bool build_filter_ok() { return device_voxelgrid_mode() == 1; }
+    // an empty image: the table seeded on the device, rows for a first cloud of n filtered points, nothing uploaded
+    void enter_device_empty(const size_t n) {
+        const size_t ahead = device_slack ? n / 2 + device_slack : 0;  // slack 0 (test hook): nothing ahead
+        const unsigned ts = GridImage::table_size_for(n + ahead);
+        mask = ts - 1;
+        d_table.reserve(ts);
+        hipLaunchKernelGGL(ndt_table_fill_kernel, dim3((ts + 255) / 256), dim3(256), 0, stream, d_table.p, ts);
+        reserve_rows(n + ahead, false);
+        FLS_HIP(hipMemsetAsync(r_touch.p, 0, r_touch.cap * sizeof(unsigned long long), stream));
+        dev_rows = dev_alive = dev_entries = 0;
+        dev_table = ts;
+        dev_next_vid = next_vid;
+        dev_epoch = 1;
+        d_upd.reserve(1);
+        h_upd.reserve(2);
+        edit_table.clear(); edit_rows.clear(); evicted_image_keys.clear(); changed_idx.clear(); free_rows.clear();
+        device_mode = true;
+    }
+    // a first cloud the device refused: the empty image is dropped, the (empty) mirror is what it was
+    void leave_device_empty() {
+        device_mode = false;
+        have_map = false;
     }
     // uploads the whole host mirror as rows (LRU order: row 0 = least recently touched) + a table holding every alive voxel
     void enter_device_mode(size_t batch_hint) {
@@ -351,7 +384,8 @@ struct NdtMatcher final : fls_matcher {
         DevBuf<HashEntry> nt;
         nt.reserve(ts);
         hipLaunchKernelGGL(ndt_table_fill_kernel, dim3((ts + 255) / 256), dim3(256), 0, stream, nt.p, ts);
-        hipLaunchKernelGGL(ndt_table_rehash_kernel, dim3(unsigned((dev_rows + 255) / 256)), dim3(256), 0, stream, nt.p, ts - 1, rows_dev(), unsigned(dev_rows));
+        if (dev_rows)  // (an image that is still empty has nothing to re-hash)
+            hipLaunchKernelGGL(ndt_table_rehash_kernel, dim3(unsigned((dev_rows + 255) / 256)), dim3(256), 0, stream, nt.p, ts - 1, rows_dev(), unsigned(dev_rows));
         FLS_HIP(hipStreamSynchronize(stream));
         std::swap(d_table.p, nt.p);
         std::swap(d_table.cap, nt.cap);
@@ -369,9 +403,12 @@ struct NdtMatcher final : fls_matcher {
         FLS_HIP(hipMemcpyAsync(u_cloud.p, u_stage.p, 3 * n * sizeof(float), hipMemcpyHostToDevice, stream));
         return device_add_cloud_dev(u_cloud.p, u_cloud.p + n, u_cloud.p + 2 * n, n);
     }
-    // the filtered world cloud already on the device (x, y, z of n points, cloud order)
-    bool device_add_cloud_dev(const float* x, const float* y, const float* z, const size_t n) {
+    // the filtered world cloud already on the device (x, y, z of n points, cloud order).  first_rule: UpdateVoxel with flag_first_scan set
+    // (a build: counted in slots 150 and 107, never in 109 / 110); refused_status says why a refused call was refused.
+    unsigned refused_status = 0;
+    bool device_add_cloud_dev(const float* x, const float* y, const float* z, const size_t n, const bool first_rule = false) {
         if (n == 0) return true;
+        refused_status = 0;
         if (n > size_t(kVgMaxBlocks) * kVgTile) return false;
         if ((dev_entries + n) * 2 + 2 > dev_table) grow_table_device(dev_alive + n);
         if (dev_rows + n > row_cap) { reserve_rows(device_slack ? dev_rows + dev_rows / 2 + 2 * n : dev_rows + n, true); ++row_growths; }
@@ -417,20 +454,28 @@ struct NdtMatcher final : fls_matcher {
         hipLaunchKernelGGL(ndt_upd_rowkeys, dim3(unsigned(nb1)), dim3(256), 0, stream, ni, (const HashEntry*)d_table.p, (const unsigned*)u_slot.p, u_sort.k0, u_sort.v0,
                            (const NdtUpdState*)d_upd.p);
         u_sort.run(DevicePairSort::passes_for((unsigned long long)(dev_rows + n)), stream);
-        hipLaunchKernelGGL(ndt_upd_voxel, dim3(unsigned((ni + 63) / 64)), dim3(64), 0, stream, (const unsigned*)u_sort.k0, (const unsigned*)u_sort.v0, ni, x, y, z, R,
-                           d_table.p, d_upd.p, int(p.ndt_min_points_in_voxel), int(p.ndt_max_points_in_voxel));
+        if (first_rule)
+            hipLaunchKernelGGL(ndt_upd_voxel_first, dim3(unsigned((ni + 63) / 64)), dim3(64), 0, stream, (const unsigned*)u_sort.k0, (const unsigned*)u_sort.v0, ni, x, y, z,
+                               R, d_table.p, d_upd.p);
+        else
+            hipLaunchKernelGGL(ndt_upd_voxel, dim3(unsigned((ni + 63) / 64)), dim3(64), 0, stream, (const unsigned*)u_sort.k0, (const unsigned*)u_sort.v0, ni, x, y, z, R,
+                               d_table.p, d_upd.p, int(p.ndt_min_points_in_voxel), int(p.ndt_max_points_in_voxel));
         hipLaunchKernelGGL(ndt_upd_commit, dim3(1), dim3(1), 0, stream, d_upd.p, unsigned(n));
         FLS_HIP(hipMemcpyAsync(&h_upd.p[1], d_upd.p, sizeof(NdtUpdState), hipMemcpyDeviceToHost, stream));
         FLS_HIP(hipStreamSynchronize(stream));
         FLS_HIP(hipGetLastError());
         const NdtUpdState& o = h_upd.p[1];
-        if (!o.apply) { ++refused_batches; return false; }
+        if (!o.apply) {
+            refused_status = o.status;
+            if (!first_rule) ++refused_batches;
+            return false;
+        }
         dev_entries += size_t(o.n_rows) - dev_rows - o.recreated;  // one table entry per created voxel (an evicted voxel's entry stays as a tombstone, a re-created voxel reuses its own)
         dev_rows = o.n_rows; dev_alive = o.n_alive; dev_next_vid = o.next_vid; dev_epoch = o.epoch;
         last_touched = o.touched;
         device_evictions += o.evict;
         device_recreated += o.recreated;
-        ++device_batches;
+        if (first_rule) { ++device_builds; ++full_rebuilds; } else ++device_batches;
         // retired rows pile up at the capacity (hundreds per scan): drop them through the host mirror now and then
         if (dev_rows - dev_alive > std::max<size_t>(2 * dev_alive, 262144)) compact_device_rows(n);
         return true;
@@ -511,6 +556,74 @@ struct NdtMatcher final : fls_matcher {
         if (can_enter_device_mode()) enter_device_mode(batch_hint);
     }
 
+    // ---- the map built from a whole cloud on the device: the first cloud of a handle (flag_first_scan still set, nothing in the map) and
+    // every reload of a localization handle, which keeps the flag (:222-223).  The raw cloud goes up once, the device VoxelGrid filters it
+    // (bit-identical to the host filter), the update chain runs on the filter's output with the first-scan rule (ndt_upd_voxel_first) and,
+    // in localization mode, the fitness grid is built from the same device cloud -- after the batch has been applied.  A decline leaves the
+    // handle as it was and the host path runs the call (it also answers FLS_ERR_RANGE).  Slots 150-155.
+    unsigned long long device_builds = 0, builds_declined = 0;
+    enum { kWhyPoints = 0, kWhyEvictions, kWhyRange, kWhyParams, kWhyCount };
+    unsigned long long declined_why[kWhyCount] = {0, 0, 0, 0};
+    int left_why = kWhyEvictions;  // why the handle left device mode: what the declines of the eight host-path calls behind it count as
+    DevScan build_raw;
+    DeviceGridBuilder fitness_builder;
+    std::vector<float> build_tmp;
+    bool is_build_call() const { return !owner && (p.is_localization_mode || (flag_first_scan && !device_mode && n_alive == 0)); }
+    bool decline_build(const int why) {
+        ++builds_declined;
+        if (why >= 0) ++declined_why[why];
+        if (why >= 0 && device_mode) left_why = why;  // (the host path is about to take the image back to the mirror)
+        return false;
+    }
+    // true: applied (FLS_OK); false: declined, nothing changed
+    bool add_cloud_build(const float* c0, const size_t n0, const int stride) {
+        if (n0 == 0 || c0 == nullptr) return false;  // (counted nowhere)
+        if (!allow_device_build) return decline_build(-1);
+        if (!device_rows_fit() || !build_filter_ok()) return decline_build(kWhyParams);
+        if (n0 > size_t(kVgMaxBlocks) * kVgTile) return decline_build(kWhyPoints);
+        if (staying_on_host()) return decline_build(left_why);
+        const auto t0 = std::chrono::steady_clock::now();
+        build_raw.upload_raw(c0, n0, stride, stream, true);
+        const float *fx = nullptr, *fy = nullptr, *fz = nullptr;  // the cloud the map takes, on the device
+        size_t n = 0;
+        if (map_vg.run(build_raw.x.p, build_raw.y.p, build_raw.z.p, build_raw.xyz.p + 3 * n0, n0, p.source_cloud_filter_size, stream)) {
+            fx = map_vg.ox(); fy = map_vg.oy(); fz = map_vg.oz();
+            n = map_vg.n_out;
+        } else {
+            const unsigned vs = map_vg.vmb_host ? map_vg.vmb_host->status : unsigned(kVgOk);
+            if (vs == kVgNoFinitePoint || vs == kVgNonFinitePoints) return decline_build(kWhyRange);
+            if (vs != kVgLeafTooSmall) return decline_build(kWhyPoints);  // (the exact sort gave up)
+            // PCL's "leaf size too small" (an extent of more than INT_MAX leaves, every point finite): the filter hands the cloud on as it came
+            fx = build_raw.x.p; fy = build_raw.y.p; fz = build_raw.z.p;
+            n = n0;
+        }
+        if (n == 0) return decline_build(kWhyPoints);
+        const auto t1 = std::chrono::steady_clock::now();
+        const bool from_nothing = !device_mode && n_alive == 0;
+        if (from_nothing) enter_device_empty(n);
+        else if (!device_mode) enter_device_mode(n);  // (a populated mirror: a localization handle back from the host path)
+        if (!device_add_cloud_dev(fx, fy, fz, n, /*first_rule=*/true)) {
+            // (a populated image goes back to the mirror in add_cloud_impl, like a refused batch)
+            if (from_nothing) leave_device_empty();
+            return decline_build((refused_status & kNdtOutOfRange) ? kWhyRange : kWhyEvictions);
+        }
+        flag_first_scan = p.is_localization_mode ? true : false;  // :222-226
+        have_map = true;
+        const auto t2 = std::chrono::steady_clock::now();
+        if (p.is_localization_mode) {  // :188-190 kd-tree for GetFitnessScore, from the filtered cloud already on the device
+            if (fitness_builder.run(fitness_grid, fx, fy, fz, n, 1.0f, 1, false, stream)) have_fitness_grid = true;
+            else have_fitness_grid = fitness_grid.build(fx == build_raw.x.p ? cloud_from(c0, n0, stride) : map_vg.download(stream, build_tmp), 1.0f, stream) == FLS_OK;
+            FLS_HIP(hipStreamSynchronize(stream));
+        }
+        if (host_timing) {
+            const auto t3 = std::chrono::steady_clock::now();
+            auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+            std::fprintf(stderr, "[fls_reg] ndt map build (device): %zu -> %zu pts | upload + VoxelGrid %.3f ms | first-scan UpdateVoxel x%u %.3f ms | fitness grid %.3f ms (%zu voxels)\n",
+                         n0, n, ms(t0, t1), last_touched, ms(t1, t2), ms(t2, t3), dev_alive);
+        }
+        return true;
+    }
+
     fls_status add_cloud_impl(const std::vector<PtI>& cloud_world_full) {  // :182-227
         const auto t0 = std::chrono::steady_clock::now();
         const std::vector<PtI> cloud_world = voxel_grid(cloud_world_full, p.source_cloud_filter_size);
@@ -551,6 +664,8 @@ struct NdtMatcher final : fls_matcher {
                 v.pts.push_back(pe[0]); v.pts.push_back(pe[1]); v.pts.push_back(pe[2]);
                 v.estimated = false;
                 v.num_points = 1;
+                for (int a = 0; a < 3; ++a) v.mu[a] = 0.0;  // VoxelData's initialisers (:79-81): a recycled pool entry is a new voxel
+                for (int a = 0; a < 9; ++a) v.sigma[a] = v.info[a] = 0.0;
                 v.vid = next_vid++;
                 v.slot = -1;
                 v.dirty = false;
@@ -606,6 +721,7 @@ struct NdtMatcher final : fls_matcher {
     }
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
         if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
+        if (is_build_call() && add_cloud_build(c0, n0, stride)) return FLS_OK;  // the cloud goes in whole
         return add_cloud_impl(cloud_from(c0, n0, stride));
     }
     fls_status scan_upload(const float* s0, size_t n0, const float*, size_t, int stride) override {
@@ -725,7 +841,56 @@ struct NdtMatcher final : fls_matcher {
         if (slot == 126) return size_t(device_recreated);    // ... of which re-created by a later point of the same batch
         if (slot == 117) return size_t(device_evictions);    // voxels evicted by device batches / row compactions through the host mirror
         if (slot == 118) return size_t(device_compactions);
+        if (slot == 150) return size_t(device_builds);    // maps built from a whole cloud on the device / declined (host path), then why:
+        if (slot == 151) return size_t(builds_declined);  // too many points, evictions the device cannot order, range or non-finite, parameters
+        if (slot >= 152 && slot <= 155) return size_t(declined_why[slot - 152]);
         return alive();
+    }
+    // fls_debug_ndt_voxels (include/fls_debug_ndt.h): every alive voxel, most recently touched first -- the mirror's LRU list, or the device
+    // rows ordered by their stamps while the device holds the map.  Reads only: no counter, no state, device mode is not left.
+    // pending = the unconsumed points a device row would carry (a saturated voxel's list is never read again: 0).
+    struct VoxelDump { int32_t *keys, *vid, *num_points; uint8_t *estimated, *pending; double *mu, *sigma, *info; };
+    size_t dump_voxels(const size_t cap, const VoxelDump& o) {
+        const size_t na = alive();
+        if (cap < na || na == 0) return na;
+        size_t w = 0;
+        auto put = [&](const int kx, const int ky, const int kz, const int vid, const int np, const bool est, const size_t pend, const double* mu, const double* sg,
+                       const double* inf) {
+            o.keys[3 * w] = kx; o.keys[3 * w + 1] = ky; o.keys[3 * w + 2] = kz;
+            o.vid[w] = vid; o.num_points[w] = np; o.estimated[w] = est ? 1 : 0; o.pending[w] = uint8_t(pend);
+            std::memcpy(o.mu + 3 * w, mu, 3 * sizeof(double)); std::memcpy(o.sigma + 9 * w, sg, 9 * sizeof(double)); std::memcpy(o.info + 9 * w, inf, 9 * sizeof(double));
+            ++w;
+        };
+        if (!device_mode) {
+            for (int vi = lru_head; vi >= 0 && w < na; vi = pool[vi].next) {
+                const Voxel& v = pool[vi];
+                const size_t keep = (v.estimated && v.num_points > p.ndt_max_points_in_voxel) ? 0 : v.pts.size() / 3;
+                put(v.kx, v.ky, v.kz, v.vid, v.num_points, v.estimated, std::min<size_t>(keep, kNdtCarry), v.mu, v.sigma, v.info);
+            }
+            return w;
+        }
+        const size_t nr = dev_rows;
+        std::vector<unsigned long long> k(nr), st(nr);
+        std::vector<int> np(nr), vid(nr);
+        std::vector<unsigned char> est(nr), cc(nr);
+        std::vector<double> mu(nr * 3), sg(nr * 9), inf(nr * 9);
+        auto dn = [&](void* h, const void* d, size_t bytes) { if (bytes) FLS_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, stream)); };
+        dn(k.data(), r_key.p, nr * 8); dn(st.data(), r_stamp.p, nr * 8); dn(np.data(), r_np.p, nr * 4); dn(vid.data(), d_vid.p, nr * 4);
+        dn(est.data(), r_est.p, nr); dn(cc.data(), r_cc.p, nr);
+        dn(mu.data(), d_mu.p, mu.size() * 8); dn(sg.data(), d_sigma.p, sg.size() * 8); dn(inf.data(), d_info.p, inf.size() * 8);
+        FLS_HIP(hipStreamSynchronize(stream));
+        std::vector<size_t> order;
+        order.reserve(na);
+        for (size_t r = 0; r < nr; ++r) if (k[r] != kNdtDeadKey) order.push_back(r);
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return st[a] > st[b]; });  // stamps are unique
+        for (const size_t r : order) {
+            if (w == na) break;
+            int kx, ky, kz;
+            unpack_key(k[r], kx, ky, kz);
+            const bool saturated = est[r] && np[r] > p.ndt_max_points_in_voxel;
+            put(kx, ky, kz, vid[r], np[r], est[r] != 0, saturated ? 0 : cc[r], &mu[3 * r], &sg[9 * r], &inf[9 * r]);
+        }
+        return w;
     }
 };
 

@@ -294,6 +294,26 @@ class RegistrationInterface:
     def map_size(self, slot: int = 0) -> int:
         return int(_lib.lib().fls_map_size(self._h, slot))
 
+    def ndt_voxels(self) -> dict:
+        """fls_debug_ndt_voxels (IncrementalNDT): every alive voxel in LRU order, most recently touched first, as a dict of arrays --
+        keys (n, 3) int32, vid, num_points (n,) int32, estimated, pending (n,) uint8, mu (n, 3), sigma and info (n, 9) column-major."""
+        L = _lib.lib()
+        cnt = C.c_size_t(0)
+        rc = L.fls_debug_ndt_voxels(self._h, 0, None, None, None, None, None, None, None, None, C.byref(cnt))
+        if rc not in (_lib.FLS_OK, _lib.FLS_ERR_NOMEM):
+            raise FlsError(rc, "fls_debug_ndt_voxels")
+        n = int(cnt.value)
+        out = dict(keys=np.zeros((n, 3), np.int32), vid=np.zeros(n, np.int32), num_points=np.zeros(n, np.int32), estimated=np.zeros(n, np.uint8),
+                   pending=np.zeros(n, np.uint8), mu=np.zeros((n, 3)), sigma=np.zeros((n, 9)), info=np.zeros((n, 9)))
+        if n:
+            ip, bp, dp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+            rc = L.fls_debug_ndt_voxels(self._h, n, out["keys"].ctypes.data_as(ip), out["vid"].ctypes.data_as(ip), out["num_points"].ctypes.data_as(ip),
+                                        out["estimated"].ctypes.data_as(bp), out["pending"].ctypes.data_as(bp), out["mu"].ctypes.data_as(dp),
+                                        out["sigma"].ctypes.data_as(dp), out["info"].ctypes.data_as(dp), C.byref(cnt))
+            if rc != _lib.FLS_OK or int(cnt.value) != n:
+                raise FlsError(rc, "fls_debug_ndt_voxels")
+        return out
+
     def set_profiling(self, events: bool, counters: bool = False) -> None:
         _lib.lib().fls_set_profiling(self._h, (1 if events else 0) | (2 if counters else 0))
 
