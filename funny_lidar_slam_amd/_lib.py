@@ -54,6 +54,30 @@ DEBUG_TICKET_WORDS = 320  # FLS_DEBUG_TICKET_WORDS
 # every symbol include/fls_debug_ndt.h declares (FLS_DEBUG_NDT_REVISION 1): test read-out of the NDT voxel map
 DEBUG_NDT_SYMBOLS = ["fls_debug_ndt_revision", "fls_debug_ndt_voxels"]
 
+# every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
+# fls_map_image_* and the replica sets of fls_reg.h
+NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
+NDT_IMAGE_MAGIC, NDT_IMAGE_HEADER_BYTES, NDT_IMAGE_CARRY = b"FLSNDT01", 64, 8
+
+
+class NdtImageHeader(C.Structure):
+    """fls_ndt_image_header (include/fls_map_ndt.h)."""
+
+    _fields_ = [("magic", C.c_char * 8), ("revision", C.c_uint32), ("carry", C.c_uint32), ("total_bytes", C.c_uint64), ("n_voxels", C.c_uint64),
+                ("next_vid", C.c_int32), ("flag_first_scan", C.c_uint32), ("ndt_voxel_size_bits", C.c_uint64), ("ndt_min_points_in_voxel", C.c_int32),
+                ("ndt_max_points_in_voxel", C.c_int32), ("ndt_capacity", C.c_int32), ("reserved", C.c_uint32)]
+
+
+def ndt_image_layout(n: int) -> dict:
+    """byte offsets of the arrays of an image of n voxels (csrc/ndt_image.hpp::ndt_image_layout): every array starts on a 16-byte boundary"""
+    out, o = {}, NDT_IMAGE_HEADER_BYTES
+    for name, width in (("key", 8), ("num_points", 4), ("vid", 4), ("estimated", 1), ("pending", 1), ("points", NDT_IMAGE_CARRY * 24), ("mu", 24),
+                        ("sigma", 72), ("info", 72)):
+        out[name] = o
+        o = (o + n * width + 15) & ~15
+    out["total"] = o
+    return out
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -394,6 +418,9 @@ def lib():
             L.fls_debug_ndt_revision.argtypes = []
             L.fls_debug_ndt_voxels.restype = C.c_int
             L.fls_debug_ndt_voxels.argtypes = [hp, C.c_size_t, ip, ip, ip, bp, bp, dp, dp, dp, C.POINTER(C.c_size_t)]
+        if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_ndt_image_revision.restype = C.c_int
+            L.fls_ndt_image_revision.argtypes = []
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

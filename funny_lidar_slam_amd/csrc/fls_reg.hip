@@ -246,6 +246,9 @@ fls_status fls_map_import(fls_handle h, const void* blob, size_t n) {
     return guarded([&]() -> fls_status { FLS_HIP(hipSetDevice(h->device)); return h->map_import(blob, n); });
 }
 
+// ---- include/fls_map_ndt.h: the format fls_map_export / fls_map_image_export write for an FLS_INCREMENTAL_NDT handle ----
+int fls_ndt_image_revision(void) { return FLS_NDT_IMAGE_REVISION; }
+
 fls_status fls_replicas_create(fls_handle owner, const int* device_ids, int n_devices, fls_replicas_handle* out) {
     if (!out) return FLS_ERR_INVALID;
     *out = nullptr;

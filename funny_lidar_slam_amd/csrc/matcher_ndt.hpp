@@ -6,11 +6,14 @@
 //                                {key -> slot} with mu[slot], info[slot] in FP64.
 //   Match              :229-337  device-resident loop: ndt_lanes_kernel (7-voxel Mahalanobis scoring,
 //                                FP64, the Gauss-Newton tail in its last workgroup; mode 1).
+//   the map as it travels        one flat image (include/fls_map_ndt.h): map_export / map_import, map_image_*, replicate_from -- packed from the device
+//                                rows or from the mirror (ndt_image.hpp, which also holds the mirror itself: NdtMirror), the same bytes either way.
 #pragma once
 #include "matcher_base.hpp"
 #include "host_math.hpp"
 #include "device_voxelgrid.hpp"
 #include "kernels_ndt_update.hpp"
+#include "kernels_ndt_image.hpp"
 #include "kernels_knn.hpp"
 #include "fitness_host.hpp"
 #include <chrono>
@@ -18,40 +21,9 @@
 
 namespace fls {
 
-struct NdtMatcher final : fls_matcher {
-    struct Voxel {
-        int kx, ky, kz;
-        std::vector<double> pts;  // xyz triples waiting for the next estimate
-        double mu[3] = {0, 0, 0}, sigma[9] = {0}, info[9] = {0};
-        bool estimated = false;
-        int num_points = 0;
-        int vid = 0;
-        int prev = -1, next = -1;  // LRU list (head = most recently touched)
-        int slot = -1;             // row of the device image (estimated voxels only)
-        unsigned epoch = 0;        // last add_cloud call that touched it
-        bool dirty = false;        // mu / info changed in this call
-    };
-    // std::list + unordered_map of the reference (incremental_ndt.h:352-353) as a pool with an intrusive LRU list and an
-    // open-addressing key map: same sequence of creations, touches and evictions, no node allocation per point
-    std::vector<Voxel> pool;
-    std::vector<int> free_ix;
-    int lru_head = -1, lru_tail = -1;
-    size_t n_alive = 0;
-    FlatKeyMap grids;  // key -> pool index
+struct NdtMatcher final : fls_matcher, NdtMirror {
+    // the host mirror of the map (Voxel, pool, LRU list, key map): ndt_image.hpp's NdtMirror
     unsigned epoch = 0;
-    void lru_unlink(int v) {
-        Voxel& x = pool[v];
-        if (x.prev >= 0) pool[x.prev].next = x.next; else lru_head = x.next;
-        if (x.next >= 0) pool[x.next].prev = x.prev; else lru_tail = x.prev;
-        x.prev = x.next = -1;
-    }
-    void lru_push_front(int v) {
-        Voxel& x = pool[v];
-        x.prev = -1;
-        x.next = lru_head;
-        if (lru_head >= 0) pool[lru_head].prev = v; else lru_tail = v;
-        lru_head = v;
-    }
     bool flag_first_scan = true;
     int next_vid = 0;
     double inv_voxel = 1.0;
@@ -525,22 +497,11 @@ struct NdtMatcher final : fls_matcher {
         std::vector<size_t> order(nr);
         for (size_t i = 0; i < nr; ++i) order[i] = i;
         std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return st[a] < st[b]; });  // stamps are unique
-        pool.clear(); free_ix.clear(); grids.clear();
-        lru_head = lru_tail = -1;
-        n_alive = 0;
+        clear_mirror();
         pool.reserve(nr);
         for (const size_t r : order) {  // oldest first: every push_front leaves the most recent at the head
             if (k[r] == kNdtDeadKey) continue;  // evicted on the device
-            pool.emplace_back();
-            Voxel& v = pool.back();
-            unpack_key(k[r], v.kx, v.ky, v.kz);
-            v.pts.assign(carry.begin() + r * kNdtCarry * 3, carry.begin() + r * kNdtCarry * 3 + size_t(cc[r]) * 3);
-            std::memcpy(v.mu, &mu[3 * r], sizeof(v.mu)); std::memcpy(v.sigma, &sg[9 * r], sizeof(v.sigma)); std::memcpy(v.info, &inf[9 * r], sizeof(v.info));
-            v.estimated = est[r] != 0; v.num_points = np[r]; v.vid = vid[r];
-            const int vi = int(pool.size()) - 1;
-            lru_push_front(vi);
-            grids.insert(k[r], vi);
-            ++n_alive;
+            push_row(k[r], np[r], vid[r], est[r] != 0, cc[r], &carry[r * kNdtCarry * 3], &mu[3 * r], &sg[9 * r], &inf[9 * r]);
         }
         next_vid = dev_next_vid;
         device_mode = false;
@@ -555,6 +516,209 @@ struct NdtMatcher final : fls_matcher {
         ++device_compactions;
         if (can_enter_device_mode()) enter_device_mode(batch_hint);
     }
+
+    // ---- the map as one flat image (include/fls_map_ndt.h, ndt_image.hpp): fls_map_export / _import, fls_map_image_*, replica sets.  The bytes are
+    // a function of the map's logical state: the mirror walked from its LRU tail and the device rows sorted by their stamps give the same image.
+    // A device-mode export runs on the device and changes nothing (the stamp sort uses the eviction selection's scratch buffers); an import
+    // builds new rows and a new table beside the old ones, checks them, and swaps them in only then.  Slots 156-159.
+    unsigned long long image_exports_device = 0, image_exports_mirror = 0, image_imports_device = 0, image_imports_mirror = 0;
+    DevBuf<unsigned char> img_stage;      // the image on the device, where the caller's buffer is not device memory the kernels can use directly
+    PinnedBuf<unsigned char> img_pinned;  // the image (or its header) on its way between the mirror and device memory
+    DevBuf<unsigned> img_status;
+    PinnedBuf<unsigned> img_status_h;
+    NdtImageParams image_params() const { return NdtImageParams{p.ndt_voxel_size, p.ndt_min_points_in_voxel, p.ndt_max_points_in_voxel, p.ndt_capacity}; }
+    // a voxel may hold as many pending points as ndt_min_points_in_voxel: an image entry carries kNdtCarry of them, like a device row
+    bool image_fits() const { return !owner && p.ndt_min_points_in_voxel <= kNdtCarry; }
+    static bool kernel_aligned(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+    size_t map_image_bytes() override {
+        NdtImageLayout L;
+        return image_fits() && ndt_image_layout(alive(), L) ? L.total : 0;
+    }
+    fls_status map_image_export(void* dst, size_t cap, int dst_on_device) override {
+        NdtImageLayout L;
+        if (!image_fits() || !dst || !ndt_image_layout(alive(), L)) return FLS_ERR_STATE;
+        if (cap < L.total) return FLS_ERR_RANGE;
+        unsigned char* const out = static_cast<unsigned char*>(dst);
+        if (!device_mode) {  // from the mirror: lru_tail -> prev, as enter_device_mode walks it
+            unsigned char* const host = dst_on_device ? (img_pinned.reserve(L.total), img_pinned.p) : out;
+            ndt_image_from_mirror(*this, image_params(), next_vid, flag_first_scan, L, host);
+            if (dst_on_device) {
+                FLS_HIP(hipMemcpyAsync(out, host, L.total, hipMemcpyHostToDevice, stream));
+                FLS_HIP(hipStreamSynchronize(stream));
+            }
+            ++image_exports_mirror;
+            return FLS_OK;
+        }
+        const bool direct = dst_on_device && kernel_aligned(dst);
+        unsigned char* img = out;
+        if (!direct) { img_stage.reserve(L.total); img = img_stage.p; }
+        img_pinned.reserve(sizeof(fls_ndt_image_header));
+        const fls_ndt_image_header h = ndt_image_make_header(image_params(), L, dev_next_vid, flag_first_scan);
+        std::memcpy(img_pinned.p, &h, sizeof(h));
+        FLS_HIP(hipMemsetAsync(img, 0, L.total, stream));  // the padding between the arrays
+        FLS_HIP(hipMemcpyAsync(img, img_pinned.p, sizeof(h), hipMemcpyHostToDevice, stream));
+        if (L.n) {
+            // rows in LRU order, as the eviction selection orders them: stable radix sort by the low, then by the high word of the stamps, dead rows last
+            const unsigned nr = unsigned(dev_rows), nbr = (nr + 255u) / 256u;
+            const unsigned dead_hi = unsigned((dev_epoch + 2) >> 32) + 1u;
+            const NdtRows R = rows_dev();
+            ev_sort.prepare(dev_rows);
+            hipLaunchKernelGGL(ndt_evict_keys, dim3(nbr), dim3(256), 0, stream, R, nr, dead_hi, 0, (const unsigned*)nullptr, ev_sort.k0, ev_sort.v0);
+            ev_sort.run(4, stream);
+            hipLaunchKernelGGL(ndt_evict_keys, dim3(nbr), dim3(256), 0, stream, R, nr, dead_hi, 1, (const unsigned*)ev_sort.v0, ev_sort.k0, ev_sort.v0);
+            ev_sort.run(DevicePairSort::passes_for((unsigned long long)dead_hi), stream);
+            const unsigned long long lanes = (unsigned long long)L.n * kNdtImageLanesPerVoxel;
+            hipLaunchKernelGGL(ndt_image_pack_kernel, dim3(unsigned((lanes + 255ull) / 256ull)), dim3(256), 0, stream, R, (const unsigned*)ev_sort.v0,
+                               (unsigned long long)L.n, int(p.ndt_max_points_in_voxel), img, ndt_image_offsets(L));
+        }
+        if (!direct) FLS_HIP(hipMemcpyAsync(out, img, L.total, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        FLS_HIP(hipGetLastError());
+        ++image_exports_device;
+        return FLS_OK;
+    }
+    size_t map_export(void* blob, size_t cap) override {
+        const size_t need = map_image_bytes();
+        if (need && blob && cap >= need && map_image_export(blob, cap, 0) != FLS_OK) return 0;
+        return need;
+    }
+    // what an import leaves of the Match before it (as a replaced iVox map does)
+    void map_replaced() {
+        have_final = false;
+        log_n = 0;
+        log_stale = false;
+        have_fitness_grid = false;  // not in the image: the next AddCloudToLocalMap of a localization handle builds it
+    }
+    struct RowBufs {
+        DevBuf<unsigned long long> key, stamp, touch;
+        DevBuf<unsigned> hslot;
+        DevBuf<int> np, vid;
+        DevBuf<unsigned char> est, cc;
+        DevBuf<double> carry, mu, sigma, info;
+        DevBuf<HashEntry> table;
+        void reserve(const size_t rows, const size_t ts) {
+            key.reserve(rows); stamp.reserve(rows); touch.reserve(rows); hslot.reserve(rows); np.reserve(rows); vid.reserve(rows); est.reserve(rows); cc.reserve(rows);
+            carry.reserve(rows * kNdtCarry * 3); mu.reserve(rows * 3); sigma.reserve(rows * 9); info.reserve(rows * 9);
+            table.reserve(ts);
+        }
+        NdtRows rows() { return NdtRows{key.p, hslot.p, np.p, est.p, cc.p, carry.p, mu.p, sigma.p, info.p, vid.p, stamp.p, touch.p}; }
+    };
+    // the rows and the table an import fills and checks before the handle takes them; what it takes them for stays here for the next import
+    // (a replica-set refresh, a periodic re-broadcast): after the first one no import allocates
+    RowBufs img_rows;
+    template <class T> static void swap_buf(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+    fls_status map_image_import(const void* src, size_t n_bytes, int src_on_device) override {
+        if (owner || !src) return FLS_ERR_INVALID;  // a batch lane has no map of its own
+        if (!image_fits()) return FLS_ERR_STATE;
+        // (1) the header, on the host
+        unsigned char head[sizeof(fls_ndt_image_header)];
+        if (n_bytes < sizeof(head)) return FLS_ERR_INVALID;
+        if (src_on_device) FLS_HIP(hipMemcpy(head, src, sizeof(head), hipMemcpyDeviceToHost));
+        else std::memcpy(head, src, sizeof(head));
+        fls_ndt_image_header h;
+        NdtImageLayout L;
+        const fls_status hrc = ndt_image_check_header(head, n_bytes, image_params(), h, L);
+        if (hrc != FLS_OK) return hrc;
+        FLS_HIP(hipStreamSynchronize(stream));
+        const bool to_device = allow_device_update && device_rows_fit() && !staying_on_host();
+        const size_t n = L.n;
+        RowBufs& nb = img_rows;
+        unsigned ts = 0;
+        size_t cap_rows = 0;
+        const unsigned char* host_bytes = src_on_device ? nullptr : static_cast<const unsigned char*>(src);
+        if (n) {
+            // (2) the voxels, on the device: into rows and a table of their own
+            const unsigned char* img = static_cast<const unsigned char*>(src);
+            if (!(src_on_device && kernel_aligned(src))) {
+                img_stage.reserve(L.total);
+                FLS_HIP(hipMemcpyAsync(img_stage.p, src, L.total, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+                img = img_stage.p;
+            }
+            const size_t ahead = to_device ? (device_slack ? n / 2 + device_slack : 1) : 0;  // as enter_device_mode sizes them (no batch in sight)
+            ts = GridImage::table_size_for(n + ahead);
+            cap_rows = n + ahead;
+            nb.reserve(cap_rows, ts);
+            img_status.reserve(1);
+            img_status_h.reserve(1);
+            FLS_HIP(hipMemsetAsync(img_status.p, 0, sizeof(unsigned), stream));
+            FLS_HIP(hipMemsetAsync(nb.touch.p, 0, nb.touch.cap * sizeof(unsigned long long), stream));
+            const NdtRows R = nb.rows();
+            const unsigned long long lanes = (unsigned long long)n * kNdtImageLanesPerVoxel;
+            hipLaunchKernelGGL(ndt_table_fill_kernel, dim3((ts + 255) / 256), dim3(256), 0, stream, nb.table.p, ts);
+            hipLaunchKernelGGL(ndt_image_check_unpack_kernel, dim3(unsigned((lanes + 255ull) / 256ull)), dim3(256), 0, stream, img, ndt_image_offsets(L),
+                               (unsigned long long)n, int(p.ndt_max_points_in_voxel), int(h.next_vid), R, img_status.p);
+            hipLaunchKernelGGL(ndt_table_rehash_check_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, nb.table.p, ts - 1, R, unsigned(n), img_status.p);
+            FLS_HIP(hipMemcpyAsync(img_status_h.p, img_status.p, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+            if (!to_device && src_on_device) {  // the mirror is built from host memory
+                img_pinned.reserve(L.total);
+                FLS_HIP(hipMemcpyAsync(img_pinned.p, img, L.total, hipMemcpyDeviceToHost, stream));
+                host_bytes = img_pinned.p;
+            }
+            FLS_HIP(hipStreamSynchronize(stream));
+            FLS_HIP(hipGetLastError());
+            if (img_status_h.p[0] != 0u) return FLS_ERR_INVALID;  // (the handle is as it was)
+        }
+        // (3) the handle takes the image
+        FLS_HIP(hipDeviceSynchronize());  // launches of the batch lanes may still hold the old buffers
+        clear_mirror();
+        next_vid = h.next_vid;
+        flag_first_scan = h.flag_first_scan != 0u;
+        edit_table.clear(); edit_rows.clear(); evicted_image_keys.clear(); changed_idx.clear(); free_rows.clear();
+        map_replaced();
+        if (n == 0) {  // an empty handle: what it was before its first cloud
+            device_mode = false;
+            have_map = false;
+            ++(to_device ? image_imports_device : image_imports_mirror);
+            return FLS_OK;
+        }
+        if (to_device) {
+            swap_buf(r_key, nb.key); swap_buf(r_stamp, nb.stamp); swap_buf(r_touch, nb.touch); swap_buf(r_hslot, nb.hslot); swap_buf(r_np, nb.np);
+            swap_buf(d_vid, nb.vid); swap_buf(r_est, nb.est); swap_buf(r_cc, nb.cc); swap_buf(r_carry, nb.carry); swap_buf(d_mu, nb.mu);
+            swap_buf(d_sigma, nb.sigma); swap_buf(d_info, nb.info); swap_buf(d_table, nb.table);
+            row_cap = cap_rows;
+            mask = ts - 1;
+            dev_table = ts;
+            dev_rows = dev_alive = dev_entries = n;
+            dev_next_vid = h.next_vid;
+            dev_epoch = n + 1;
+            device_left = false;
+            d_upd.reserve(1);
+            h_upd.reserve(2);
+            have_map = true;
+            device_mode = true;
+            ++image_imports_device;
+            return FLS_OK;
+        }
+        ndt_mirror_from_image(*this, host_bytes, L);
+        device_mode = false;
+        have_map = false;
+        rebuild_image();  // the host-path image: estimated voxels only, rows in the mirror's order
+        ++image_imports_mirror;
+        return FLS_OK;
+    }
+    fls_status map_import(const void* blob, size_t n) override { return map_image_import(blob, n, 0); }
+    // replica sets: the owner's image, exported on its device, copied device to device and imported on this handle's device.  The replica is an
+    // ordinary handle holding the owner's map.
+    bool can_replicate() const override { return image_fits(); }
+    fls_status replicate_from(fls_matcher& o) override {
+        if (o.kind != kind || owner) return FLS_ERR_STATE;
+        NdtMatcher& src = static_cast<NdtMatcher&>(o);
+        FLS_HIP(hipSetDevice(src.device));
+        const fls_status prc = src.prepare_batch();  // image current, stream idle
+        if (prc != FLS_OK) return prc;
+        const size_t nbytes = src.map_image_bytes();
+        if (!nbytes) return FLS_ERR_STATE;
+        DevBuf<unsigned char>& out = src.replica_out;  // (kept by the owner: a refresh allocates nothing)
+        out.reserve(nbytes);
+        const fls_status erc = src.map_image_export(out.p, nbytes, 1);
+        if (erc != FLS_OK) return erc;
+        FLS_HIP(hipSetDevice(device));
+        if (src.device == device) return map_image_import(out.p, nbytes, 1);
+        replica_in.reserve(nbytes);
+        FLS_HIP(hipMemcpyPeer(replica_in.p, device, out.p, src.device, nbytes));
+        return map_image_import(replica_in.p, nbytes, 1);
+    }
+    DevBuf<unsigned char> replica_out, replica_in;  // the image of a replication on the owner's device / on the replica's
 
     // ---- the map built from a whole cloud on the device: the first cloud of a handle (flag_first_scan still set, nothing in the map) and
     // every reload of a localization handle, which keeps the flag (:222-223).  The raw cloud goes up once, the device VoxelGrid filters it
@@ -844,6 +1008,10 @@ struct NdtMatcher final : fls_matcher {
         if (slot == 150) return size_t(device_builds);    // maps built from a whole cloud on the device / declined (host path), then why:
         if (slot == 151) return size_t(builds_declined);  // too many points, evictions the device cannot order, range or non-finite, parameters
         if (slot >= 152 && slot <= 155) return size_t(declined_why[slot - 152]);
+        if (slot == 156) return size_t(image_exports_device);  // flat images (fls_map_ndt.h) exported on the device / from the mirror,
+        if (slot == 157) return size_t(image_exports_mirror);  // imported into device mode / through the mirror
+        if (slot == 158) return size_t(image_imports_device);
+        if (slot == 159) return size_t(image_imports_mirror);
         return alive();
     }
     // fls_debug_ndt_voxels (include/fls_debug_ndt.h): every alive voxel, most recently touched first -- the mirror's LRU list, or the device

@@ -259,7 +259,10 @@ class RegistrationInterface:
         return ids, cnt, valid
 
     def ExportMap(self) -> np.ndarray:
-        """fls_map_export: the map image as a self-contained byte blob (uint8 array), e.g. to broadcast it to other GPUs."""
+        """fls_map_export: the map image as a self-contained byte blob (uint8 array), e.g. to broadcast it to other GPUs or to checkpoint a
+        mapping session.  iVox and IncrementalNDT handles; an NDT handle returns the flat image of include/fls_map_ndt.h (the bytes
+        ExportMapImage writes), packed on the device when the device holds the map -- the handle stays as it is.  Raises for a kind without
+        an image and for an NDT handle with ndt_min_points_in_voxel > 8."""
         n = _lib.lib().fls_map_export(self._h, None, 0)
         if n == 0:
             raise FlsError(_lib.FLS_ERR_STATE, "fls_map_export (this kind has no exportable image)")
@@ -270,13 +273,16 @@ class RegistrationInterface:
         return blob
 
     def ImportMap(self, blob: np.ndarray) -> None:
+        """fls_map_import: this handle takes the exporter's map and continues exactly like it.  Validated before anything changes: a refused
+        blob (FLS_ERR_INVALID) leaves the handle as it was.  The state of the last Match is cleared; an imported NDT localization handle has
+        no fitness grid until its next AddCloudToLocalMap (GetFitnessScore raises FLS_ERR_STATE)."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         rc = _lib.lib().fls_map_import(self._h, blob.ctypes.data, blob.size)
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_map_import")
 
     def MapImageBytes(self) -> int:
-        """fls_map_image_bytes: size of the flat DEVICE image (0: this kind has none)."""
+        """fls_map_image_bytes: size of the flat DEVICE image (0: this kind has none; an NDT handle: the size of ExportMap's blob)."""
         return int(_lib.lib().fls_map_image_bytes(self._h))
 
     def ExportMapImage(self, ptr: int, nbytes: int, on_device: bool) -> None:
@@ -286,7 +292,8 @@ class RegistrationInterface:
             raise FlsError(rc, "fls_map_image_export")
 
     def ImportMapImage(self, ptr: int, nbytes: int, on_device: bool) -> None:
-        """fls_map_image_import: this handle becomes a read-only replica of the exporter's map."""
+        """fls_map_image_import: an iVox handle becomes a read-only replica of the exporter's map; an NDT handle takes the map as ImportMap
+        does (from host or device memory) and stays an ordinary handle."""
         rc = _lib.lib().fls_map_image_import(self._h, C.c_void_p(ptr), nbytes, 1 if on_device else 0)
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_map_image_import")
@@ -520,7 +527,8 @@ YAML_NCLT_LOC_KDTREE = dict(optimization_iter_num=8, point_to_planar_thres=0.1, 
 
 class ReplicaSet:
     """Native one-process multi-GPU form of BASELINE configs[4] (include/fls_reg.h: fls_replicas_*): the owner's map image
-    replicated per device, jobs block-partitioned over the devices, one host thread per device inside the library."""
+    replicated per device, jobs block-partitioned over the devices, one host thread per device inside the library.  The owner is an iVox
+    handle (read-only copies of its device image) or an IncrementalNDT handle (its flat image, include/fls_map_ndt.h, imported per device)."""
 
     def __init__(self, owner, device_ids):
         self._owner = owner  # keeps the owner handle alive

@@ -1,7 +1,7 @@
 /* ============================================================================
  * fls_debug_ndt.h -- test-only read-out of the voxel map of an FLS_INCREMENTAL_NDT handle (same shared library as fls_reg.h;
- * FLS_ABI_REVISION stays 9, this header has a revision of its own, like fls_debug_fit.h).  The NDT kind has no fls_map_export: this is
- * what lets a test compare the voxel statistics of two handles, or of a handle and the CPU oracle.
+ * FLS_ABI_REVISION stays 9, this header has a revision of its own, like fls_debug_fit.h).  This is what lets a test compare the voxel
+ * statistics of two handles, or of a handle and the CPU oracle, array by array (the map itself travels as the image of fls_map_ndt.h).
  * ==========================================================================*/
 #ifndef FLS_DEBUG_NDT_H
 #define FLS_DEBUG_NDT_H

@@ -155,8 +155,11 @@ fls_status fls_match_batch(fls_handle h, size_t n_jobs, const float* const* src0
 /* ---- map image export / import (BASELINE configs[4], SURVEY.md 8e: rank 0 builds the map, the image is broadcast, every
  * GPU imports it instead of re-inserting 1e6 points).  The blob is self-contained host memory (voxel keys in LRU order, the
  * points with their insertion ids, counters): import into a handle of the same kind created with the same parameters gives a
- * handle whose Match / AddCloudToLocalMap results are identical to the exporter's from then on.  FLS_P2PLANE_IVOX only
- * (other kinds: export returns 0, import FLS_ERR_STATE).  fls_map_export(h, NULL, 0) returns the size needed.            */
+ * handle whose Match / AddCloudToLocalMap results are identical to the exporter's from then on.  FLS_P2PLANE_IVOX and
+ * FLS_INCREMENTAL_NDT (other kinds: export returns 0, import FLS_ERR_STATE).  fls_map_export(h, NULL, 0) returns the size needed.
+ * The NDT blob is the flat image of fls_map_ndt.h (voxel statistics and pending points in LRU order; no Match state, no fitness grid:
+ * fls_get_fitness_score on an imported localization handle answers FLS_ERR_STATE until its next fls_add_cloud_to_local_map); a refused
+ * import (FLS_ERR_INVALID) leaves the handle as it was; a handle with ndt_min_points_in_voxel > 8 exports 0 bytes.                  */
 size_t fls_map_export(fls_handle h, void* blob, size_t cap_bytes);
 fls_status fls_map_import(fls_handle h, const void* blob, size_t n_bytes);
 /* The DEVICE image itself as one flat buffer (revision 6): what a torch.distributed rank broadcasts to the others in place of the blob above
@@ -164,7 +167,9 @@ fls_status fls_map_import(fls_handle h, const void* blob, size_t n_bytes);
  * *_on_device != 0 -- e.g. the data_ptr of the CUDA tensor an RCCL broadcast works on -- or host memory (pinned for speed; gloo).  The exporter
  * keeps its map.  The importer becomes a READ-ONLY REPLICA, like a member of fls_replicas_*: fls_match / fls_match_batch with update_map == 0;
  * fls_map_import or a replica refresh makes it an ordinary handle again.  Header and contents are validated on import (sizes against n_bytes,
- * every cell inside the point array): FLS_ERR_INVALID otherwise.  Only the iVox kind has such an image (others: 0 / FLS_ERR_STATE).
+ * every cell inside the point array): FLS_ERR_INVALID otherwise.  The iVox kind has such an image, and the NDT kind has the one of
+ * fls_map_ndt.h: the same bytes fls_map_export writes, packed on the device when the device holds the map; an NDT importer is an ORDINARY
+ * handle afterwards (it keeps mapping), not a read-only replica (others: 0 / FLS_ERR_STATE).
  * Two builds of one cloud give FUNCTIONALLY equal flat images, not byte-equal ones: brick indices follow the order in which the bricks were
  * created (on the device: whichever thread claimed the directory entry first), and no result depends on them.                        */
 size_t fls_map_image_bytes(fls_handle h);
@@ -182,7 +187,9 @@ fls_status fls_map_image_import(fls_handle h, const void* src, size_t n_bytes, i
  * one host thread per entry, `lanes` stream lanes per entry.  Every job still equals a fresh reference matcher holding the
  * owner's map, so the table is independent of the device list.  fls_replicas_refresh re-replicates after the owner's map
  * changed.  The owner must outlive the set and must not run a Match of its own while a batch is in flight.
- * FLS_P2PLANE_IVOX only (the kind with an exportable image); fls_replicas_import_ms: per entry, the last replication.      */
+ * FLS_P2PLANE_IVOX and FLS_INCREMENTAL_NDT (the kinds with an exportable image; an NDT replica takes the owner's flat image of
+ * fls_map_ndt.h, exported on the owner's device and copied device to device, and is an ordinary handle holding that map);
+ * fls_replicas_import_ms: per entry, the last replication.                                                                       */
 typedef struct fls_replicas* fls_replicas_handle;
 fls_status fls_replicas_create(fls_handle owner, const int* device_ids, int n_devices, fls_replicas_handle* out);
 fls_status fls_replicas_refresh(fls_replicas_handle r);
