@@ -78,6 +78,34 @@ def ndt_image_layout(n: int) -> dict:
     out["total"] = o
     return out
 
+# every symbol include/fls_map_kd.h declares (FLS_KD_IMAGE_REVISION 1): the flat image of the kd-tree kinds' local maps (ICP, LoamFull, P2PlaneKd),
+# moved by fls_map_export / _import, fls_map_image_* and the replica sets of fls_reg.h, and the fused batch over a replica set
+KD_IMAGE_SYMBOLS = ["fls_kd_image_revision", "fls_replicas_match_batch_fused"]
+KD_IMAGE_MAGIC, KD_IMAGE_HEADER_BYTES = b"FLSKDM01", 224
+
+
+class KdImageHeader(C.Structure):
+    """fls_kd_image_header (include/fls_map_kd.h)."""
+
+    _fields_ = [("magic", C.c_char * 8), ("revision", C.c_uint32), ("kind", C.c_uint32), ("total_bytes", C.c_uint64), ("n_maps", C.c_uint32),
+                ("is_localization_mode", C.c_uint32), ("filter_size_bits", C.c_uint32 * 2), ("local_size", C.c_uint32 * 2),
+                ("point_search_thres_bits", C.c_uint64), ("gate_init", C.c_uint32), ("reserved", C.c_uint32), ("gate_last_T", C.c_double * 16),
+                ("n_clouds", C.c_uint64 * 2), ("n_points", C.c_uint64 * 2)]
+
+
+def kd_image_layout(n_clouds, n_points) -> dict:
+    """byte offsets of the arrays of an image (csrc/kd_image.hpp::kd_image_layout): n_clouds / n_points per map (one entry, or two for LoamFull:
+    planar, corner); every array starts on a 16-byte boundary.  Returns {"sizes": [...], "rows": [...], "total": n}."""
+    out, o = {"sizes": [], "rows": []}, KD_IMAGE_HEADER_BYTES
+    for nc, npts in zip(n_clouds, n_points):
+        out["sizes"].append(o)
+        o = (o + 4 * int(nc) + 15) & ~15
+        out["rows"].append(o)
+        o = (o + 16 * int(npts) + 15) & ~15
+    out["total"] = o
+    return out
+
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -421,6 +449,11 @@ def lib():
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []
+        if hasattr(L, "fls_kd_image_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_kd_image_revision.restype = C.c_int
+            L.fls_kd_image_revision.argtypes = []
+            L.fls_replicas_match_batch_fused.restype = C.c_int
+            L.fls_replicas_match_batch_fused.argtypes = L.fls_replicas_match_batch.argtypes
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int

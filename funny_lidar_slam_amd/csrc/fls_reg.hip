@@ -19,6 +19,7 @@
 #include "../../include/fls_debug_linalg.h"
 #include "../../include/fls_debug_fit.h"
 #include "../../include/fls_debug_ndt.h"
+#include "../../include/fls_map_kd.h"
 #include <new>
 
 using namespace fls;
@@ -293,6 +294,16 @@ fls_status fls_replicas_match_batch(fls_replicas_handle r, size_t n_jobs, const 
     if (!r || stride < 3 || (n_jobs && (!src0 || !n0 || !T))) return FLS_ERR_INVALID;
     if ((src1 == nullptr) != (n1 == nullptr)) return FLS_ERR_INVALID;
     return guarded([&]() -> fls_status { return r->match_batch(n_jobs, src0, n0, src1, n1, stride, T, stats, status, lanes); });
+}
+
+// ---- include/fls_map_kd.h: the format fls_map_export / fls_map_image_export write for the kd-tree kinds, and the fused batch over a replica set ----
+int fls_kd_image_revision(void) { return FLS_KD_IMAGE_REVISION; }
+
+fls_status fls_replicas_match_batch_fused(fls_replicas_handle r, size_t n_jobs, const float* const* src0, const size_t* n0, const float* const* src1,
+                                          const size_t* n1, int stride, double* T, fls_stats* stats, int32_t* status, int slots) {
+    if (!r || stride < 3 || (n_jobs && (!src0 || !n0 || !T))) return FLS_ERR_INVALID;
+    if ((src1 == nullptr) != (n1 == nullptr)) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status { return r->match_batch(n_jobs, src0, n0, src1, n1, stride, T, stats, status, slots, true); });
 }
 
 int fls_replicas_import_ms(fls_replicas_handle r, double* ms, int cap) {

@@ -11,6 +11,8 @@
 #include "kernels_knn.hpp"
 #include "kernels_grid_coop.hpp"
 #include "fitness_host.hpp"
+#include "kd_image.hpp"
+#include "kernels_kd_image.hpp"
 
 namespace fls {
 
@@ -23,6 +25,251 @@ inline float cell_for_gate(double gate_sq) {  // smallest safe cell for a square
 }
 // workgroups of a search launch (eight lanes per query) over n queries: a multiple of 64, so that the kernels' XCD chunk re-map is a bijection
 inline unsigned knn_grid_blocks(size_t n) { return unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64); }
+
+// ---------------------------------------------------------------------------------------------
+// The local maps of one kd-tree handle as one flat image (include/fls_map_kd.h, kd_image.hpp): fls_map_export / _import, fls_map_image_*,
+// replica sets.  The image carries the deque(s) and the keyframe gate; the bytes are a function of the logical state, so the rings of a
+// device-path handle (packed by kd_image_pack_kernel) and the host deques of a host-path one give the same image.  An import checks the
+// whole image on the host, unpacks the rows into planes of its own (kept for the next import: a replica refresh allocates nothing after
+// the first), and only then swaps them into the handle and runs the kind's own rebuild.  The host deque is filled EAGERLY (it stays
+// authoritative for whatever the device declines, as after every push): one device-to-host copy when the source is device memory.
+// fls_map_size slots 160-163.
+struct KdMapImage {
+    unsigned long long exports_device = 0, exports_host = 0, imports_device = 0, imports_host = 0;
+    DevBuf<unsigned char> img_stage;      // the image on the device, where the caller's buffer is not device memory the kernels can use directly
+    PinnedBuf<unsigned char> img_pinned;  // header + sizes on their way up; the whole image on its way down
+    struct SpareRing { DevBuf<float> planes; size_t cap = 0; } spare[2];  // what an import unpacks into / what it took the handle's planes for
+    DevBuf<unsigned char> replica_out, replica_in;  // the image of a replication on the owner's device / on the replica's
+    static bool kernel_aligned(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
+    size_t counter(int slot) const { return size_t(slot == 160 ? exports_device : slot == 161 ? exports_host : slot == 162 ? imports_device : imports_host); }
+
+    static bool layout_of(KdLocalMap* const* maps, const int n_maps, KdImageLayout& L) {
+        const KdDeque* d[2] = {&maps[0]->clouds, n_maps > 1 ? &maps[1]->clouds : nullptr};
+        return kd_image_layout_of(d, n_maps, L);
+    }
+    // the rings hold what the deques hold, in planes a 16-byte access may walk
+    static bool rings_usable(KdLocalMap* const* maps, const KdImageLayout& L) {
+        unsigned long long quads = 0;
+        for (int m = 0; m < L.n_maps; ++m) {
+            const DeviceCloudRing& r = maps[m]->ring;
+            if (!maps[m]->on_device || r.size() != L.n_points[m] || r.sizes.size() != L.n_clouds[m]) return false;
+            if (L.n_points[m] && ((r.cap & 3u) != 0 || !kernel_aligned(r.planes.p) || r.tail > r.cap)) return false;
+            quads += (L.n_points[m] + 6) / 4;
+        }
+        return quads < 0x7fffffffull;
+    }
+    fls_status export_image(const KdImageParams& q, const KdImageGate& g, KdLocalMap* const* maps, void* dst, size_t cap, int dst_on_device, hipStream_t stream) {
+        KdImageLayout L;
+        if (!dst || !layout_of(maps, int(q.n_maps), L)) return FLS_ERR_STATE;
+        if (cap < L.total) return FLS_ERR_RANGE;
+        unsigned char* const out = static_cast<unsigned char*>(dst);
+        const KdDeque* d[2] = {&maps[0]->clouds, L.n_maps > 1 ? &maps[1]->clouds : nullptr};
+        FLS_HIP(hipStreamSynchronize(stream));
+        if (!rings_usable(maps, L)) {  // from the host deques
+            unsigned char* const host = dst_on_device ? (img_pinned.reserve(L.total), img_pinned.p) : out;
+            kd_image_from_deques(q, g, L, d, host);
+            if (dst_on_device) {
+                FLS_HIP(hipMemcpyAsync(out, host, L.total, hipMemcpyHostToDevice, stream));
+                FLS_HIP(hipStreamSynchronize(stream));
+            }
+            ++exports_host;
+            return FLS_OK;
+        }
+        const bool direct = dst_on_device && kernel_aligned(dst);
+        unsigned char* img = out;
+        if (!direct) { img_stage.reserve(L.total); img = img_stage.p; }
+        // header and sizes, with the padding behind them, from the host; the rows from the rings: together every byte of the image
+        const size_t meta0 = L.rows[0], meta1 = L.n_maps > 1 ? L.rows[1] - L.sizes[1] : 0;
+        img_pinned.reserve(meta0 + meta1);
+        unsigned char* const chunk[2] = {img_pinned.p, img_pinned.p + meta0};
+        kd_image_write_meta(q, g, L, d, chunk);
+        FLS_HIP(hipMemcpyAsync(img, chunk[0], meta0, hipMemcpyHostToDevice, stream));
+        if (meta1) FLS_HIP(hipMemcpyAsync(img + L.sizes[1], chunk[1], meta1, hipMemcpyHostToDevice, stream));
+        KdPackArgs a{};
+        unsigned quads = 0;
+        for (int m = 0; m < L.n_maps; ++m) {
+            const DeviceCloudRing& r = maps[m]->ring;
+            if (!L.n_points[m]) continue;
+            const size_t base = r.head & ~size_t(3);
+            const unsigned* pl = reinterpret_cast<const unsigned*>(r.planes.p);
+            KdPackMap& k = a.m[m];
+            k.x = pl + base; k.y = pl + r.cap + base; k.z = pl + 2 * r.cap + base; k.i = pl + 3 * r.cap + base;
+            k.rows = reinterpret_cast<uint4*>(img + L.rows[m]);
+            k.off = unsigned(r.head - base);
+            k.n = unsigned(L.n_points[m]);
+            k.quads = (k.off + k.n + 3u) / 4u;  // base + 4 * quads <= cap: cap is a multiple of 4 and tail <= cap
+            quads += k.quads;
+        }
+        if (quads) hipLaunchKernelGGL(kd_image_pack_kernel, dim3((quads + kKdImageBlock - 1) / kKdImageBlock), dim3(kKdImageBlock), 0, stream, a);
+        if (!direct) FLS_HIP(hipMemcpyAsync(out, img, L.total, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        FLS_HIP(hipGetLastError());
+        ++exports_device;
+        return FLS_OK;
+    }
+    // Everything of an import up to the kind's rebuild: FLS_OK = the deques, the rings and `gate` hold the image (`any_cloud`: it holds a
+    // cloud at all); anything else = the handle is as it was.
+    fls_status import_image(const KdImageParams& q, KdLocalMap* const* maps, const void* src, size_t n_bytes, int src_on_device, hipStream_t stream,
+                            hm::KeyframeGate& gate, bool& any_cloud) {
+        if (!src) return FLS_ERR_INVALID;
+        // (1) the header
+        unsigned char head[sizeof(fls_kd_image_header)];
+        if (n_bytes < sizeof(head)) return FLS_ERR_INVALID;
+        if (src_on_device) FLS_HIP(hipMemcpy(head, src, sizeof(head), hipMemcpyDeviceToHost));
+        else std::memcpy(head, src, sizeof(head));
+        fls_kd_image_header h;
+        KdImageLayout L;
+        const fls_status hrc = kd_image_check_header(head, n_bytes, q, h, L);
+        if (hrc != FLS_OK) return hrc;
+        // (2) the whole image in host memory: sizes and padding are checked there, and the host deques are filled from it
+        const unsigned char* host = static_cast<const unsigned char*>(src);
+        if (src_on_device) {
+            img_pinned.reserve(L.total);
+            FLS_HIP(hipMemcpyAsync(img_pinned.p, src, L.total, hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            host = img_pinned.p;
+        }
+        const fls_status brc = kd_image_check_body(host, L);
+        if (brc != FLS_OK) return brc;
+        // (3) the rows into planes of this importer's own
+        const bool on_device = maps[0]->on_device;
+        unsigned long long quads_all = 0;
+        for (int m = 0; m < L.n_maps; ++m) quads_all += (L.n_points[m] + 3) / 4;
+        if (on_device && quads_all >= 0x7fffffffull) return FLS_ERR_INVALID;  // (more points than a ring can hold)
+        if (on_device && quads_all) {
+            const unsigned char* img = static_cast<const unsigned char*>(src);
+            if (!(src_on_device && kernel_aligned(src))) {
+                img_stage.reserve(L.total);
+                FLS_HIP(hipMemcpyAsync(img_stage.p, src, L.total, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+                img = img_stage.p;
+            }
+            KdUnpackArgs a{};
+            unsigned quads = 0;
+            for (int m = 0; m < L.n_maps; ++m) {
+                const size_t n = L.n_points[m];
+                if (!n) continue;
+                SpareRing& sp = spare[m];
+                if (sp.cap < n || !sp.planes.p) {  // as DeviceCloudRing::make_room sizes a ring: 65,536 floats per plane, doubled until it fits
+                    size_t ncap = 65536;
+                    while (ncap < n) ncap *= 2;
+                    sp.planes.reserve(4 * ncap);
+                    sp.cap = ncap;
+                }
+                unsigned* pl = reinterpret_cast<unsigned*>(sp.planes.p);
+                KdUnpackMap& k = a.m[m];
+                k.rows = reinterpret_cast<const uint4*>(img + L.rows[m]);
+                k.x = pl; k.y = pl + sp.cap; k.z = pl + 2 * sp.cap; k.i = pl + 3 * sp.cap;
+                k.n = unsigned(n);
+                k.quads = unsigned((n + 3) / 4);  // 4 * quads <= cap: cap is a multiple of 4
+                quads += k.quads;
+            }
+            hipLaunchKernelGGL(kd_image_unpack_kernel, dim3((quads + kKdImageBlock - 1) / kKdImageBlock), dim3(kKdImageBlock), 0, stream, a);
+            FLS_HIP(hipStreamSynchronize(stream));
+            FLS_HIP(hipGetLastError());
+        }
+        // (4) the handle takes the image
+        FLS_HIP(hipDeviceSynchronize());  // launches of the batch lanes may still read the old grid
+        any_cloud = false;
+        for (int m = 0; m < L.n_maps; ++m) {
+            KdLocalMap& km = *maps[m];
+            kd_deque_from_image(host, L, m, km.clouds);
+            any_cloud = any_cloud || L.n_clouds[m] != 0;
+            if (!on_device) continue;
+            DeviceCloudRing& r = km.ring;
+            if (L.n_points[m]) {
+                std::swap(r.planes.p, spare[m].planes.p);
+                std::swap(r.planes.cap, spare[m].planes.cap);
+                std::swap(r.cap, spare[m].cap);
+            }
+            r.head = 0;
+            r.tail = L.n_points[m];
+            r.sizes.clear();
+            for (const auto& c : km.clouds) r.sizes.push_back(c.size());
+        }
+        const KdImageGate g = kd_gate_from_header(h);
+        gate = hm::KeyframeGate();
+        gate.init = g.init;
+        std::memcpy(gate.last_T, g.last_T, sizeof(gate.last_T));
+        ++(on_device ? imports_device : imports_host);
+        return FLS_OK;
+    }
+    // a handle without a cloud: what it was before its first one
+    static void reset_map(KdLocalMap& km) { km.local.clear(); km.n = 0; }
+};
+inline KdImageGate kd_gate_of(const hm::KeyframeGate& gate) {
+    KdImageGate g;
+    g.init = gate.init;
+    if (g.init) std::memcpy(g.last_T, gate.last_T, sizeof(g.last_T));
+    return g;
+}
+// what the three kinds share of the image calls (M: the matcher; it supplies image_maps(), rebuild_maps() and map_replaced())
+template <class M>
+struct KdImageCalls {
+    static size_t bytes(M& s) {
+        if (s.owner) return 0;
+        KdImageLayout L;
+        KdLocalMap* maps[2];
+        s.image_maps(maps);
+        return KdMapImage::layout_of(maps, int(kd_image_params(s.kind, s.p).n_maps), L) ? L.total : 0;
+    }
+    static fls_status export_to(M& s, void* dst, size_t cap, int on_device) {
+        if (s.owner) return FLS_ERR_STATE;
+        KdLocalMap* maps[2];
+        s.image_maps(maps);
+        return s.image.export_image(kd_image_params(s.kind, s.p), kd_gate_of(s.gate), maps, dst, cap, on_device, s.stream);
+    }
+    static size_t export_blob(M& s, void* blob, size_t cap) {
+        const size_t need = bytes(s);
+        if (need && blob && cap >= need && export_to(s, blob, cap, 0) != FLS_OK) return 0;
+        return need;
+    }
+    static fls_status import_from(M& s, const void* src, size_t n_bytes, int on_device) {
+        if (s.owner) return FLS_ERR_INVALID;  // a batch lane has no map of its own
+        KdLocalMap* maps[2];
+        s.image_maps(maps);
+        bool any_cloud = false;
+        const fls_status rc = s.image.import_image(kd_image_params(s.kind, s.p), maps, src, n_bytes, on_device, s.stream, s.gate, any_cloud);
+        if (rc != FLS_OK) return rc;
+        s.map_replaced();
+        s.log_n = 0;
+        s.log_stale = false;
+        if (!any_cloud) {
+            for (int m = 0; m < int(kd_image_params(s.kind, s.p).n_maps); ++m) KdMapImage::reset_map(*maps[m]);
+            s.have_map = false;
+            return FLS_OK;
+        }
+        return s.rebuild_maps();
+    }
+    // replica sets: the owner's image, exported on its device, copied device to device and imported on this handle's device
+    static fls_status replicate(M& s, fls_matcher& o) {
+        if (o.kind != s.kind || s.owner) return FLS_ERR_STATE;
+        M& src = static_cast<M&>(o);
+        FLS_HIP(hipSetDevice(src.device));
+        const fls_status prc = src.prepare_batch();  // map current, stream idle
+        if (prc != FLS_OK) return prc;
+        const size_t nbytes = bytes(src);
+        if (!nbytes) return FLS_ERR_STATE;
+        DevBuf<unsigned char>& out = src.image.replica_out;  // (kept by the owner: a refresh allocates nothing)
+        out.reserve(nbytes);
+        const fls_status erc = export_to(src, out.p, nbytes, 1);
+        if (erc != FLS_OK) return erc;
+        FLS_HIP(hipSetDevice(s.device));
+        if (src.device == s.device) return import_from(s, out.p, nbytes, 1);
+        s.image.replica_in.reserve(nbytes);
+        FLS_HIP(hipMemcpyPeer(s.image.replica_in.p, s.device, out.p, src.device, nbytes));
+        return import_from(s, s.image.replica_in.p, nbytes, 1);
+    }
+};
+// the overrides of fls_matcher every kd kind spells the same way
+#define FLS_KD_IMAGE_OVERRIDES(M)                                                                                                              \
+    KdMapImage image;                                                                                                                          \
+    size_t map_image_bytes() override { return KdImageCalls<M>::bytes(*this); }                                                                \
+    fls_status map_image_export(void* dst, size_t cap, int on_device) override { return KdImageCalls<M>::export_to(*this, dst, cap, on_device); } \
+    fls_status map_image_import(const void* src, size_t n, int on_device) override { return KdImageCalls<M>::import_from(*this, src, n, on_device); } \
+    size_t map_export(void* blob, size_t cap) override { return KdImageCalls<M>::export_blob(*this, blob, cap); }                              \
+    fls_status map_import(const void* blob, size_t n) override { return KdImageCalls<M>::import_from(*this, blob, n, 0); }                     \
+    bool can_replicate() const override { return !owner && have_map; }                                                                         \
+    fls_status replicate_from(fls_matcher& o) override { return KdImageCalls<M>::replicate(*this, o); }
 
 // ---------------------------------------------------------------------------------------------
 struct IcpMatcher final : fls_matcher {
@@ -54,12 +301,19 @@ struct IcpMatcher final : fls_matcher {
     fls_status add_cloud_impl(const std::vector<PtI>& new_cloud) {  // :165-189
         if (p.is_localization_mode) map.reset_to(new_cloud, stream);
         else { map.push(new_cloud, stream); map.trim(p.local_map_size); }
+        return rebuild_maps();
+    }
+    fls_status rebuild_maps() {  // (a keyframe update and an image import)
         // gate-sized cells here: the ICP scan starts far from the map (1-NN often beyond half the gate in the early
         // iterations), the two-stage search would run its second stage for most queries (measured 25 vs 13.5 us / launch)
         const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, cell_for_gate(p.point_search_thres), 1, stream);  // Q13: always filtered
         have_map = rc == FLS_OK;
         return rc;
     }
+    // ---- the map as one flat image (include/fls_map_kd.h) ----
+    void image_maps(KdLocalMap** m) { m[0] = &map; m[1] = nullptr; }
+    void map_replaced() { have_final = false; }  // fls_get_fitness_score answers FLS_ERR_STATE until the next Match
+    FLS_KD_IMAGE_OVERRIDES(IcpMatcher)
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
         if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
         return add_cloud_impl(cloud_from(c0, n0, stride));
@@ -218,6 +472,7 @@ struct IcpMatcher final : fls_matcher {
         if (slot == 105) return size_t(src_filter.device_runs);  // source filters run on the device / on the host
         if (slot == 106) return size_t(src_filter.host_runs);
         if (slot >= 114 && slot <= 116) return map.counter(slot);
+        if (slot >= 160 && slot <= 163) return image.counter(slot);
         return map.n;
     }
 };
@@ -294,6 +549,9 @@ struct LoamFullMatcher final : fls_matcher {
         map_planar.push(planar_cloud, stream);
         map_planar.trim(p.local_planar_size);
         map_corner.trim(p.local_corner_size);
+        return rebuild_maps();
+    }
+    fls_status rebuild_maps() {  // (a keyframe update and an image import)
         // half-gate cells + the two-stage kernel; the VoxelGrid only once the deque holds more than 5 frames (:92-100)
         const float cs = 0.5f * cell_for_gate(p.point_search_thres);
         fls_status rc = map_planar.rebuild(map_planar.clouds.size() > 5, p.planar_voxel_filter_size, cs, kGridRings, stream);
@@ -302,6 +560,10 @@ struct LoamFullMatcher final : fls_matcher {
         have_map = rc == FLS_OK;  // (the corner rebuild's status alone)
         return rc;
     }
+    // ---- the maps as one flat image (include/fls_map_kd.h): planar first, then corner ----
+    void image_maps(KdLocalMap** m) { m[0] = &map_planar; m[1] = &map_corner; }
+    void map_replaced() {}
+    FLS_KD_IMAGE_OVERRIDES(LoamFullMatcher)
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
         if (c1 == nullptr && n1 != 0) return FLS_ERR_INVALID;  // CHECK_EQ(cloud_list.size(), 2) :66
         return add_cloud_impl(cloud_from(c0, n0, stride), c1 ? cloud_from(c1, n1, stride) : std::vector<PtI>());
@@ -371,6 +633,7 @@ struct LoamFullMatcher final : fls_matcher {
     }
     size_t map_size(int slot) const override {
         if (slot >= 114 && slot <= 116) return map_planar.counter(slot) + map_corner.counter(slot);
+        if (slot >= 160 && slot <= 163) return image.counter(slot);
         return slot == 1 ? map_corner.n : map_planar.n;
     }
 };
@@ -396,11 +659,18 @@ struct P2PlaneKdMatcher final : fls_matcher {
     fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud) {  // :56-79
         if (p.is_localization_mode) map.reset_to(planar_cloud, stream);
         else { map.push(planar_cloud, stream); map.trim(p.local_map_size); }
+        return rebuild_maps();
+    }
+    fls_status rebuild_maps() {  // (a keyframe update and an image import)
         // un-gated 5-NN: ring search with a cell of two map leaves (>= 1 point per leaf after VoxelGrid)
         const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, std::max(2.0f * p.map_cloud_filter_size, 0.5f), 1, stream);
         have_map = rc == FLS_OK;
         return rc;
     }
+    // ---- the map as one flat image (include/fls_map_kd.h) ----
+    void image_maps(KdLocalMap** m) { m[0] = &map; m[1] = nullptr; }
+    void map_replaced() { have_final = false; }
+    FLS_KD_IMAGE_OVERRIDES(P2PlaneKdMatcher)
     fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
         if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
         return add_cloud_impl(cloud_from(c0, n0, stride));
@@ -456,6 +726,7 @@ struct P2PlaneKdMatcher final : fls_matcher {
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override { return planar.fetch(stream, ids, cnt, valid, cap); }
     size_t map_size(int slot) const override {
         if (slot >= 114 && slot <= 116) return map.counter(slot);
+        if (slot >= 160 && slot <= 163) return image.counter(slot);
         return map.n;
     }
 };

@@ -9,6 +9,7 @@
 // torch.distributed (one process per GPU, bench.py --gpus N) remains the multi-process form of the same sharding.
 #pragma once
 #include "../../include/fls_reg.h"
+#include "../../include/fls_batch.h"
 #include "matcher_base.hpp"
 #include <algorithm>
 #include <chrono>
@@ -87,8 +88,9 @@ struct fls_replicas {
         end = begin + base + (rank < extra ? 1 : 0);
     }
 
+    // fused: fls_match_batch_fused per entry (include/fls_map_kd.h: fls_replicas_match_batch_fused), `lanes` = its slots
     fls_status match_batch(size_t n_jobs, const float* const* src0, const size_t* n0, const float* const* src1, const size_t* n1, int stride, double* T,
-                           fls_stats* stats, int32_t* status, int lanes) {
+                           fls_stats* stats, int32_t* status, int lanes, bool fused = false) {
         const size_t world = handles.size();
         std::vector<fls_status> rc(world, FLS_OK);
         fls::Threads th;
@@ -97,7 +99,7 @@ struct fls_replicas {
             block(n_jobs, world, r, b, e);
             if (b == e) continue;
             th.start([&, r, b, e] {
-                rc[r] = fls_match_batch(handles[r], e - b, src0 + b, n0 + b, src1 ? src1 + b : nullptr, n1 ? n1 + b : nullptr, stride, T + 16 * b, stats ? stats + b : nullptr,
+                rc[r] = (fused ? fls_match_batch_fused : fls_match_batch)(handles[r], e - b, src0 + b, n0 + b, src1 ? src1 + b : nullptr, n1 ? n1 + b : nullptr, stride, T + 16 * b, stats ? stats + b : nullptr,
                                         status ? status + b : nullptr, lanes);
             });
         }

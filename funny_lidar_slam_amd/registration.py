@@ -260,9 +260,10 @@ class RegistrationInterface:
 
     def ExportMap(self) -> np.ndarray:
         """fls_map_export: the map image as a self-contained byte blob (uint8 array), e.g. to broadcast it to other GPUs or to checkpoint a
-        mapping session.  iVox and IncrementalNDT handles; an NDT handle returns the flat image of include/fls_map_ndt.h (the bytes
-        ExportMapImage writes), packed on the device when the device holds the map -- the handle stays as it is.  Raises for a kind without
-        an image and for an NDT handle with ndt_min_points_in_voxel > 8."""
+        mapping session.  Every kind; the kd-tree kinds (IcpOptimized, LoamFull, LoamPointToPlaneKdtree) return the flat image of
+        include/fls_map_kd.h (the deque of keyframe clouds and the keyframe gate), an NDT handle returns the flat image of include/fls_map_ndt.h (the bytes
+        ExportMapImage writes), packed on the device when the device holds the map -- the handle stays as it is.  Raises for an NDT handle
+        with ndt_min_points_in_voxel > 8."""
         n = _lib.lib().fls_map_export(self._h, None, 0)
         if n == 0:
             raise FlsError(_lib.FLS_ERR_STATE, "fls_map_export (this kind has no exportable image)")
@@ -293,7 +294,7 @@ class RegistrationInterface:
 
     def ImportMapImage(self, ptr: int, nbytes: int, on_device: bool) -> None:
         """fls_map_image_import: an iVox handle becomes a read-only replica of the exporter's map; an NDT handle takes the map as ImportMap
-        does (from host or device memory) and stays an ordinary handle."""
+        does (from host or device memory) and stays an ordinary handle, and so does a handle of a kd-tree kind (include/fls_map_kd.h)."""
         rc = _lib.lib().fls_map_image_import(self._h, C.c_void_p(ptr), nbytes, 1 if on_device else 0)
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_map_image_import")
@@ -528,7 +529,8 @@ YAML_NCLT_LOC_KDTREE = dict(optimization_iter_num=8, point_to_planar_thres=0.1, 
 class ReplicaSet:
     """Native one-process multi-GPU form of BASELINE configs[4] (include/fls_reg.h: fls_replicas_*): the owner's map image
     replicated per device, jobs block-partitioned over the devices, one host thread per device inside the library.  The owner is an iVox
-    handle (read-only copies of its device image) or an IncrementalNDT handle (its flat image, include/fls_map_ndt.h, imported per device)."""
+    handle (read-only copies of its device image), an IncrementalNDT handle (its flat image, include/fls_map_ndt.h, imported per device) or a
+    handle of a kd-tree kind that holds a map (its flat image, include/fls_map_kd.h, imported per device)."""
 
     def __init__(self, owner, device_ids):
         self._owner = owner  # keeps the owner handle alive
@@ -562,5 +564,15 @@ class ReplicaSet:
         rc = _lib.lib().fls_replicas_match_batch(self._r, n, p0s, n0s, p1s, n1s, stride, Tf.ctypes.data_as(C.POINTER(C.c_double)), stats, status, int(lanes))
         if rc < 0:
             raise FlsError(rc, "fls_replicas_match_batch")
+        T = Tf.reshape(n, 4, 4).transpose(0, 2, 1).copy()
+        return [status[j] == _lib.FLS_OK for j in range(n)], T, list(stats)
+
+    def MatchBatchFused(self, clusters, T_inits, slots: int = 8):
+        """fls_replicas_match_batch_fused (include/fls_map_kd.h): the same block partition, fls_match_batch_fused per entry -- the shared
+        iteration launches of an IcpOptimized owner on every device of the set; a kind without a fused form runs as MatchBatch(lanes=slots)."""
+        n, keep, p0s, n0s, p1s, n1s, stride, Tf, stats, status = self._owner._batch_args(clusters, T_inits)
+        rc = _lib.lib().fls_replicas_match_batch_fused(self._r, n, p0s, n0s, p1s, n1s, stride, Tf.ctypes.data_as(C.POINTER(C.c_double)), stats, status, int(slots))
+        if rc < 0:
+            raise FlsError(rc, "fls_replicas_match_batch_fused")
         T = Tf.reshape(n, 4, 4).transpose(0, 2, 1).copy()
         return [status[j] == _lib.FLS_OK for j in range(n)], T, list(stats)

@@ -155,8 +155,11 @@ fls_status fls_match_batch(fls_handle h, size_t n_jobs, const float* const* src0
 /* ---- map image export / import (BASELINE configs[4], SURVEY.md 8e: rank 0 builds the map, the image is broadcast, every
  * GPU imports it instead of re-inserting 1e6 points).  The blob is self-contained host memory (voxel keys in LRU order, the
  * points with their insertion ids, counters): import into a handle of the same kind created with the same parameters gives a
- * handle whose Match / AddCloudToLocalMap results are identical to the exporter's from then on.  FLS_P2PLANE_IVOX and
- * FLS_INCREMENTAL_NDT (other kinds: export returns 0, import FLS_ERR_STATE).  fls_map_export(h, NULL, 0) returns the size needed.
+ * handle whose Match / AddCloudToLocalMap results are identical to the exporter's from then on.  Every kind has an image:
+ * FLS_P2PLANE_IVOX its own blob, FLS_INCREMENTAL_NDT the flat image of fls_map_ndt.h, the kd-tree kinds (FLS_ICP_OPTIMIZED, FLS_LOAM_FULL,
+ * FLS_P2PLANE_KDTREE) the flat image of fls_map_kd.h: the deque of keyframe clouds and the keyframe gate, from which the importer rebuilds
+ * filter and search grid (no Match state: fls_get_fitness_score answers FLS_ERR_STATE until the importer's next Match).
+ * fls_map_export(h, NULL, 0) returns the size needed.
  * The NDT blob is the flat image of fls_map_ndt.h (voxel statistics and pending points in LRU order; no Match state, no fitness grid:
  * fls_get_fitness_score on an imported localization handle answers FLS_ERR_STATE until its next fls_add_cloud_to_local_map); a refused
  * import (FLS_ERR_INVALID) leaves the handle as it was; a handle with ndt_min_points_in_voxel > 8 exports 0 bytes.                  */
@@ -169,7 +172,8 @@ fls_status fls_map_import(fls_handle h, const void* blob, size_t n_bytes);
  * fls_map_import or a replica refresh makes it an ordinary handle again.  Header and contents are validated on import (sizes against n_bytes,
  * every cell inside the point array): FLS_ERR_INVALID otherwise.  The iVox kind has such an image, and the NDT kind has the one of
  * fls_map_ndt.h: the same bytes fls_map_export writes, packed on the device when the device holds the map; an NDT importer is an ORDINARY
- * handle afterwards (it keeps mapping), not a read-only replica (others: 0 / FLS_ERR_STATE).
+ * handle afterwards (it keeps mapping), not a read-only replica.  The kd-tree kinds have the image of fls_map_kd.h in the same way: the
+ * bytes fls_map_export writes, packed on the device when the deque lives there, and an importer that is an ordinary handle.
  * Two builds of one cloud give FUNCTIONALLY equal flat images, not byte-equal ones: brick indices follow the order in which the bricks were
  * created (on the device: whichever thread claimed the directory entry first), and no result depends on them.                        */
 size_t fls_map_image_bytes(fls_handle h);
@@ -188,7 +192,9 @@ fls_status fls_map_image_import(fls_handle h, const void* src, size_t n_bytes, i
  * owner's map, so the table is independent of the device list.  fls_replicas_refresh re-replicates after the owner's map
  * changed.  The owner must outlive the set and must not run a Match of its own while a batch is in flight.
  * FLS_P2PLANE_IVOX and FLS_INCREMENTAL_NDT (the kinds with an exportable image; an NDT replica takes the owner's flat image of
- * fls_map_ndt.h, exported on the owner's device and copied device to device, and is an ordinary handle holding that map);
+ * fls_map_ndt.h, exported on the owner's device and copied device to device, and is an ordinary handle holding that map), and the
+ * kd-tree kinds once the owner holds a map (fls_map_kd.h, same shape; an owner without a map: FLS_ERR_STATE; fls_map_kd.h also declares
+ * fls_replicas_match_batch_fused, the fused batch of fls_batch.h over a set);
  * fls_replicas_import_ms: per entry, the last replication.                                                                       */
 typedef struct fls_replicas* fls_replicas_handle;
 fls_status fls_replicas_create(fls_handle owner, const int* device_ids, int n_devices, fls_replicas_handle* out);
@@ -277,7 +283,9 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
  * counts here and in no reason slot; an empty cloud counts nowhere), declines by reason: 142 = more points than the device sort takes,
  * 143 = as many voxels as the LRU capacity (the insert evicts), 144 = a point outside the key range or not finite (the call returns
  * FLS_ERR_RANGE), 145 = brick pool over its byte budget, 146 = hash-table form (FLS_IVOX_DENSE=0); 147 = host mirrors reconstructed from a
- * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).                      */
+ * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).
+ * The kd-tree kinds, flat images (fls_map_kd.h; KdMapImage in csrc/matchers_kd.hpp): 160 = exports packed on the device, 161 = exports
+ * written by the host from the deque, 162 = imports unpacked on the device, 163 = imports through the host deque alone.                  */
 size_t fls_map_size(fls_handle h, int slot);
 
 /* ---- measurement hooks ----------------------------------------------------------------------------
