@@ -37,6 +37,11 @@ INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_prepr
 KEYFRAMES_SYMBOLS = ["fls_keyframes_revision", "fls_keyframes_create", "fls_keyframes_destroy", "fls_keyframes_add", "fls_keyframes_add_preprocessed",
                      "fls_keyframes_count", "fls_keyframes_get", "fls_keyframes_merge", "fls_keyframes_loop_match", "fls_keyframes_stat"]
 
+# every symbol include/fls_localmap.h declares (FLS_LOCALMAP_REVISION 1)
+LOCALMAP_SYMBOLS = ["fls_localmap_revision", "fls_localmap_create", "fls_localmap_destroy", "fls_localmap_set_global", "fls_localmap_crop",
+                    "fls_localmap_split", "fls_localmap_add_tile", "fls_localmap_tiles", "fls_localmap_get_tile", "fls_localmap_load_tiles",
+                    "fls_localmap_reset", "fls_localmap_get_local", "fls_add_localmap_to_local_map", "fls_localmap_stat"]
+
 # every symbol include/fls_batch.h declares (FLS_BATCH_REVISION 1)
 BATCH_SYMBOLS = ["fls_batch_revision", "fls_match_batch_fused", "fls_batch_stat"]
 
@@ -398,6 +403,35 @@ def lib():
         L.fls_keyframes_loop_match.argtypes = [hp, ip, dp, C.c_size_t, ip, dp, C.c_size_t, dp, fp, C.c_void_p]
         L.fls_keyframes_stat.restype = C.c_size_t
         L.fls_keyframes_stat.argtypes = [hp, C.c_int]
+        if hasattr(L, "fls_localmap_revision"):  # (as fls_batch_ivox_revision below)
+            L.fls_localmap_revision.restype = C.c_int
+            L.fls_localmap_revision.argtypes = []
+            L.fls_localmap_create.restype = C.c_int
+            L.fls_localmap_create.argtypes = [C.c_int, C.POINTER(hp)]
+            L.fls_localmap_destroy.restype = None
+            L.fls_localmap_destroy.argtypes = [hp]
+            L.fls_localmap_set_global.restype = C.c_int
+            L.fls_localmap_set_global.argtypes = [hp, fp, C.c_size_t, C.c_int, C.c_float, szp]
+            L.fls_localmap_crop.restype = C.c_int
+            L.fls_localmap_crop.argtypes = [hp, dp, C.c_int, C.POINTER(C.c_int), szp]
+            L.fls_localmap_split.restype = C.c_int
+            L.fls_localmap_split.argtypes = [hp, C.c_double, szp]
+            L.fls_localmap_add_tile.restype = C.c_int
+            L.fls_localmap_add_tile.argtypes = [hp, C.c_double, C.c_int32, C.c_int32, fp, C.c_size_t, C.c_int]
+            L.fls_localmap_tiles.restype = C.c_int
+            L.fls_localmap_tiles.argtypes = [hp, ip, C.POINTER(C.c_uint32), C.c_size_t, szp]
+            L.fls_localmap_get_tile.restype = C.c_int
+            L.fls_localmap_get_tile.argtypes = [hp, C.c_int32, C.c_int32, C.c_float, fp, C.c_size_t, szp]
+            L.fls_localmap_load_tiles.restype = C.c_int
+            L.fls_localmap_load_tiles.argtypes = [hp, dp, C.c_float, C.POINTER(C.c_int), szp]
+            L.fls_localmap_reset.restype = C.c_int
+            L.fls_localmap_reset.argtypes = [hp]
+            L.fls_localmap_get_local.restype = C.c_int
+            L.fls_localmap_get_local.argtypes = [hp, fp, C.c_size_t, szp]
+            L.fls_add_localmap_to_local_map.restype = C.c_int
+            L.fls_add_localmap_to_local_map.argtypes = [hp, hp]
+            L.fls_localmap_stat.restype = C.c_size_t
+            L.fls_localmap_stat.argtypes = [hp, C.c_int]
         L.fls_batch_revision.restype = C.c_int
         L.fls_batch_revision.argtypes = []
         L.fls_match_batch_fused.restype = C.c_int

@@ -11,9 +11,11 @@
 #include "loop_closure.hpp"
 #include "replicas.hpp"
 #include "keyframes.hpp"
+#include "localmap.hpp"
 #include "kernels_debug_linalg.hpp"
 #include "kernels_debug_fit.hpp"
 #include "../../include/fls_keyframes.h"
+#include "../../include/fls_localmap.h"
 #include "../../include/fls_batch.h"
 #include "../../include/fls_batch_ivox.h"
 #include "../../include/fls_debug_linalg.h"
@@ -1007,6 +1009,128 @@ fls_status fls_keyframes_loop_match(fls_keyframes_handle h, const int32_t* src_i
 }
 
 size_t fls_keyframes_stat(fls_keyframes_handle h, int slot) {
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    return h->stat(slot);
+}
+
+}  // extern "C"
+
+// ---- the device local-map source (include/fls_localmap.h) ------------------------------------------------------------------------
+namespace {
+bool lm_grid_ok(double g) { return std::isfinite(g) && g > 0.0; }
+bool lm_pose_ok(const double* T) { return T && std::isfinite(T[12]) && std::isfinite(T[13]) && std::isfinite(T[14]); }
+}  // namespace
+
+extern "C" {
+
+int fls_localmap_revision(void) { return FLS_LOCALMAP_REVISION; }
+
+fls_status fls_localmap_create(int device_id, fls_localmap_handle* out) {
+    if (!out) return FLS_ERR_INVALID;
+    *out = nullptr;
+    return kf_guarded([&]() -> fls_status {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device_id < 0 || device_id >= n) return FLS_ERR_DEVICE;
+        hipDeviceProp_t prop;
+        FLS_HIP(hipGetDeviceProperties(&prop, device_id));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLS_ERR_DEVICE;
+        std::unique_ptr<fls_localmap> s(new fls_localmap());
+        s->device = device_id;
+        s->init();
+        *out = s.release();
+        return FLS_OK;
+    });
+}
+
+void fls_localmap_destroy(fls_localmap_handle h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;
+}
+
+fls_status fls_localmap_set_global(fls_localmap_handle h, const float* pts, size_t n, int stride, float leaf, size_t* n_stored) {
+    if (!h || (!pts && n) || stride < 3 || !kf_leaf_ok(leaf) || n > kLmMaxPoints) return FLS_ERR_INVALID;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->set_global(pts, n, stride, leaf, n_stored);
+    });
+}
+
+fls_status fls_localmap_crop(fls_localmap_handle h, const double pose[16], int force, int* updated, size_t* n_local) {
+    if (!h || !updated || !n_local || !lm_pose_ok(pose)) return FLS_ERR_INVALID;
+    if (!h->global) return FLS_ERR_STATE;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->crop(pose, force, updated, n_local);
+    });
+}
+
+fls_status fls_localmap_split(fls_localmap_handle h, double grid_size, size_t* n_tiles) {
+    if (!h || !n_tiles || !lm_grid_ok(grid_size)) return FLS_ERR_INVALID;
+    if (!h->global) return FLS_ERR_STATE;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->split(grid_size, n_tiles);
+    });
+}
+
+fls_status fls_localmap_add_tile(fls_localmap_handle h, double grid_size, int32_t gx, int32_t gy, const float* pts, size_t n, int stride) {
+    if (!h || (!pts && n) || stride < 3 || !lm_grid_ok(grid_size) || n > kLmMaxPoints || (h->grid_size != 0.0 && h->grid_size != grid_size)) return FLS_ERR_INVALID;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->add_tile(grid_size, gx, gy, pts, n, stride);
+    });
+}
+
+fls_status fls_localmap_tiles(fls_localmap_handle h, int32_t* gxgy, uint32_t* counts, size_t cap, size_t* n_tiles) {
+    if (!h || !n_tiles || (cap && (!gxgy || !counts))) return FLS_ERR_INVALID;
+    return h->list_tiles(gxgy, counts, cap, n_tiles);
+}
+
+fls_status fls_localmap_get_tile(fls_localmap_handle h, int32_t gx, int32_t gy, float leaf, float* out, size_t cap, size_t* n_out) {
+    if (!h || !n_out || (cap && !out) || !kf_leaf_ok(leaf) || !h->tiles.count(LmTileKey{gx, gy})) return FLS_ERR_INVALID;
+    *n_out = 0;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->get_tile(gx, gy, leaf, out, cap, n_out);
+    });
+}
+
+fls_status fls_localmap_load_tiles(fls_localmap_handle h, const double pose[16], float leaf, int* updated, size_t* n_local) {
+    if (!h || !updated || !n_local || !lm_pose_ok(pose) || !kf_leaf_ok(leaf)) return FLS_ERR_INVALID;
+    if (h->tiles.empty()) return FLS_ERR_STATE;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->load_tiles(pose, leaf, updated, n_local);
+    });
+}
+
+fls_status fls_localmap_reset(fls_localmap_handle h) {
+    if (!h) return FLS_ERR_INVALID;
+    h->reset();
+    return FLS_OK;
+}
+
+fls_status fls_localmap_get_local(fls_localmap_handle h, float* out, size_t cap, size_t* n_out) {
+    if (!h || !n_out || (cap && !out)) return FLS_ERR_INVALID;
+    *n_out = 0;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(h->device));
+        return h->get_local(out, cap, n_out);
+    });
+}
+
+fls_status fls_add_localmap_to_local_map(fls_handle m, fls_localmap_handle h) {
+    if (!m || !h || m->device != h->device) return FLS_ERR_INVALID;
+    if (h->n_local == 0) return FLS_ERR_STATE;
+    return kf_guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(m->device));
+        return h->add_to(*m);
+    });
+}
+
+size_t fls_localmap_stat(fls_localmap_handle h, int slot) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     return h->stat(slot);

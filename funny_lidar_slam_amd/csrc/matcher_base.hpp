@@ -7,6 +7,7 @@
 #include "host_maps.hpp"
 #include "kernels_handoff.hpp"
 #include "kernels_p2plane.hpp"  // kTicketWords
+#include <functional>
 #include <memory>
 #include <thread>
 #if defined(__SSE__)
@@ -62,6 +63,15 @@ struct fls_matcher {
         if (mb_host) (void)hipHostFree(mb_host);
     }
     virtual fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) = 0;
+    // fls_add_localmap_to_local_map: what add_cloud(rows of `c`, 4 floats each) would leave, from a cloud that lies on this device as x | y | z |
+    // intensity planes (the caller has ordered this handle's stream behind the producer).  rows(): the same cloud on the host, fetched when a
+    // path needs it.  *took_planes: a device builder read the planes; otherwise the host entry point ran (default: every kind without one).
+    using HostRows = std::function<const std::vector<fls::PtI>&()>;
+    virtual fls_status add_cloud_device(const fls::HandoffCloud&, const HostRows& rows, bool* took_planes) {
+        *took_planes = false;
+        const std::vector<fls::PtI>& r = rows();
+        return add_cloud(r.empty() ? nullptr : &r[0].x, r.size(), nullptr, 0, 4);
+    }
     virtual fls_status scan_upload(const float* s0, size_t n0, const float* s1, size_t n1, int stride) = 0;
     // fls_match's upload: the Match follows at once, so a kind may leave the scan in its pinned staging buffer and let the first
     // iteration's kernels read it from there (default: the ordinary upload)

@@ -742,15 +742,26 @@ struct NdtMatcher final : fls_matcher, NdtMirror {
     // true: applied (FLS_OK); false: declined, nothing changed
     bool add_cloud_build(const float* c0, const size_t n0, const int stride) {
         if (n0 == 0 || c0 == nullptr) return false;  // (counted nowhere)
+        if (!build_admits(n0)) return false;
+        const auto t0 = std::chrono::steady_clock::now();
+        build_raw.upload_raw(c0, n0, stride, stream, true);
+        return build_core(build_raw.x.p, build_raw.y.p, build_raw.z.p, build_raw.xyz.p + 3 * n0, n0, [&] { return cloud_from(c0, n0, stride); }, t0);
+    }
+    // what add_cloud_build can say before the cloud is touched (a decline is counted)
+    bool build_admits(const size_t n0) {
         if (!allow_device_build) return decline_build(-1);
         if (!device_rows_fit() || !build_filter_ok()) return decline_build(kWhyParams);
         if (n0 > size_t(kVgMaxBlocks) * kVgTile) return decline_build(kWhyPoints);
         if (staying_on_host()) return decline_build(left_why);
-        const auto t0 = std::chrono::steady_clock::now();
-        build_raw.upload_raw(c0, n0, stride, stream, true);
+        return true;
+    }
+    // the build itself, from the raw cloud's x | y | z | intensity on the device; host_cloud(): the same cloud on the host (a fitness-grid fallback)
+    template <class HostCloud>
+    bool build_core(const float* rx, const float* ry, const float* rz, const float* ri, const size_t n0, HostCloud&& host_cloud,
+                    const std::chrono::steady_clock::time_point t0) {
         const float *fx = nullptr, *fy = nullptr, *fz = nullptr;  // the cloud the map takes, on the device
         size_t n = 0;
-        if (map_vg.run(build_raw.x.p, build_raw.y.p, build_raw.z.p, build_raw.xyz.p + 3 * n0, n0, p.source_cloud_filter_size, stream)) {
+        if (map_vg.run(rx, ry, rz, ri, n0, p.source_cloud_filter_size, stream)) {
             fx = map_vg.ox(); fy = map_vg.oy(); fz = map_vg.oz();
             n = map_vg.n_out;
         } else {
@@ -758,7 +769,7 @@ struct NdtMatcher final : fls_matcher, NdtMirror {
             if (vs == kVgNoFinitePoint || vs == kVgNonFinitePoints) return decline_build(kWhyRange);
             if (vs != kVgLeafTooSmall) return decline_build(kWhyPoints);  // (the exact sort gave up)
             // PCL's "leaf size too small" (an extent of more than INT_MAX leaves, every point finite): the filter hands the cloud on as it came
-            fx = build_raw.x.p; fy = build_raw.y.p; fz = build_raw.z.p;
+            fx = rx; fy = ry; fz = rz;
             n = n0;
         }
         if (n == 0) return decline_build(kWhyPoints);
@@ -776,7 +787,7 @@ struct NdtMatcher final : fls_matcher, NdtMirror {
         const auto t2 = std::chrono::steady_clock::now();
         if (p.is_localization_mode) {  // :188-190 kd-tree for GetFitnessScore, from the filtered cloud already on the device
             if (fitness_builder.run(fitness_grid, fx, fy, fz, n, 1.0f, 1, false, stream)) have_fitness_grid = true;
-            else have_fitness_grid = fitness_grid.build(fx == build_raw.x.p ? cloud_from(c0, n0, stride) : map_vg.download(stream, build_tmp), 1.0f, stream) == FLS_OK;
+            else have_fitness_grid = fitness_grid.build(fx == rx ? host_cloud() : map_vg.download(stream, build_tmp), 1.0f, stream) == FLS_OK;
             FLS_HIP(hipStreamSynchronize(stream));
         }
         if (host_timing) {
@@ -887,6 +898,15 @@ struct NdtMatcher final : fls_matcher, NdtMirror {
         if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
         if (is_build_call() && add_cloud_build(c0, n0, stride)) return FLS_OK;  // the cloud goes in whole
         return add_cloud_impl(cloud_from(c0, n0, stride));
+    }
+    // add_cloud from a cloud on the device: the same decisions, the build reads the planes where they lie
+    fls_status add_cloud_device(const HandoffCloud& c, const HostRows& rows, bool* took_planes) override {
+        *took_planes = false;
+        if (is_build_call() && c.n != 0 && build_admits(c.n) && build_core(c.x, c.y, c.z, c.in, c.n, rows, std::chrono::steady_clock::now())) {
+            *took_planes = true;
+            return FLS_OK;
+        }
+        return add_cloud_impl(rows());
     }
     fls_status scan_upload(const float* s0, size_t n0, const float*, size_t, int stride) override {
         src_filter.filter(s0, n0, stride, p.source_cloud_filter_size, stream, scan, source);  // :232

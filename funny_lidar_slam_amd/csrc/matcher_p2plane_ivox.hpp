@@ -16,6 +16,7 @@
 #include "kernels_ivox_coop.hpp"
 #include "kernels_ivox_update.hpp"
 #include "ivox_map.hpp"
+#include "kernels_localmap.hpp"
 #include "fitness_host.hpp"
 #include <thread>
 #include <chrono>
@@ -118,6 +119,20 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         const std::vector<PtI> cloud = cloud_from(c0, n0, stride);
         return add_cloud_impl(cloud);
     }
+    // add_cloud from a cloud on the device: the same decisions, the bounds by a device reduction (equal to plane_bounds: min and max of the same floats)
+    DeviceBounds cloud_bounds;
+    fls_status add_cloud_device(const HandoffCloud& c, const HostRows& rows, bool* took_planes) override {
+        *took_planes = false;
+        if (!map.is_replica() && (p.is_localization_mode || map.is_first) && c.n != 0 && bulk_admits(c.n)) {
+            const auto t0 = std::chrono::steady_clock::now();
+            ensure_nn_rows();
+            float lo[3], hi[3];
+            cloud_bounds.run(c.x, c.y, c.z, c.n, stream, lo, hi);
+            fls_status rc = FLS_OK;
+            if (bulk_core(c.x, c.y, c.z, c.n, lo, hi, rows, rc, t0)) { *took_planes = true; return rc; }
+        }
+        return add_cloud_impl(rows());
+    }
     // coordinate bounds of the staged cloud per axis, NaN ignored (an infinite coordinate shows: the build declines on it)
     static void plane_bounds(const float* v, const size_t n, float& lo, float& hi) {
         float mn = std::numeric_limits<float>::infinity(), mx = -mn;
@@ -139,22 +154,32 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     // false: declined (IvoxMap counts why; an empty cloud and a map that is not blank count nowhere), the host path runs as ever.
     bool add_cloud_bulk(const float* c0, const size_t n0, const int stride, fls_status& rc) {
         if (n0 == 0 || c0 == nullptr) return false;
-        if (!p.is_localization_mode && !map.is_blank()) return false;  // (an imported map with is_first set: the cloud joins what is there)
-        if (!map.bulk_build_applies(n0)) return false;
+        if (!bulk_admits(n0)) return false;
         const auto t0 = std::chrono::steady_clock::now();
         ensure_nn_rows();  // (lists in ids form name slots of the image about to be replaced)
         cloud_dev.upload_raw(c0, n0, stride, stream);
         float lo[3], hi[3];
         for (int a = 0; a < 3; ++a) plane_bounds(cloud_dev.stage.p + size_t(a) * n0, n0, lo[a], hi[a]);
+        return bulk_core(cloud_dev.x.p, cloud_dev.y.p, cloud_dev.z.p, n0, lo, hi, [&] { return cloud_from(c0, n0, stride); }, rc, t0);
+    }
+    // what add_cloud_bulk can say before the cloud is touched (a decline is counted by IvoxMap)
+    bool bulk_admits(const size_t n0) {
+        if (!p.is_localization_mode && !map.is_blank()) return false;  // (an imported map with is_first set: the cloud joins what is there)
+        return map.bulk_build_applies(n0);
+    }
+    // the build itself, from x | y | z on the device with their bounds; host_cloud(): the same cloud on the host (the fitness grid's fallback)
+    template <class HostCloud>
+    bool bulk_core(const float* x, const float* y, const float* z, const size_t n0, const float (&lo)[3], const float (&hi)[3], HostCloud&& host_cloud,
+                   fls_status& rc, const std::chrono::steady_clock::time_point t0) {
         const auto t1 = std::chrono::steady_clock::now();
         if (p.is_localization_mode) { map.become_empty(); map.is_first = true; }
-        if (!map.bulk_build(cloud_dev.x.p, cloud_dev.y.p, cloud_dev.z.p, n0, lo, hi)) return false;
+        if (!map.bulk_build(x, y, z, n0, lo, hi)) return false;
         map.is_first = false;
         const auto t2 = std::chrono::steady_clock::now();
         rc = FLS_OK;
         if (p.is_localization_mode) {  // :134-138 kd-tree for GetFitnessScore, from the cloud already on the device
-            if (!fitness_builder.run(fitness_grid, cloud_dev.x.p, cloud_dev.y.p, cloud_dev.z.p, n0, 1.0f, 1, false, stream))
-                rc = fitness_grid.build(cloud_from(c0, n0, stride), 1.0f, stream);
+            if (!fitness_builder.run(fitness_grid, x, y, z, n0, 1.0f, 1, false, stream))
+                rc = fitness_grid.build(host_cloud(), 1.0f, stream);
             FLS_HIP(hipStreamSynchronize(stream));
             have_fitness_grid = (rc == FLS_OK);
         }
