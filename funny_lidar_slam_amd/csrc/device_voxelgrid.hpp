@@ -8,6 +8,8 @@
 #include "kernels_exactsort.hpp"
 #include "kernels_voxelgrid_plan.hpp"
 #include "kernels_gridbuild.hpp"
+#include "kernels_kd_push.hpp"
+#include "kd_lazy_deque.hpp"
 #include "matcher_base.hpp"
 #include <atomic>
 #include <cstdlib>
@@ -516,11 +518,45 @@ struct DeviceCloudRing {
         tail += n;
         sizes.push_back(n);
     }
+    // The same append for clouds that already lie on this device (kernels_kd_push.hpp): n_rings (1 or 2) rings take one cloud each in ONE
+    // launch on `s`, transformed on the way as `a.mode` says (the caller fills a.mode / a.R / a.t / a.T; the maps are filled here).  Nothing
+    // waits for the launch: whatever reads the rings next is queued behind it on the same stream.  make_room runs unchanged.
+    // false: a ring cannot take its cloud (its live points + the cloud would pass the 2^31 - 1 floats the 32-bit point counts of the
+    // ring's kernels can address) -- nothing has changed, the caller pushes through the host.
+    struct DeviceCloud { const float *x, *y, *z, *in; size_t n; };
+    static constexpr size_t kMaxPoints = 0x7fffffffu;
+    static bool push_back_device(DeviceCloudRing* const* rings, const DeviceCloud* src, const int n_rings, KdPushArgs a, hipStream_t s) {
+        size_t total = 0;
+        for (int r = 0; r < n_rings; ++r) {
+            if (src[r].n > kMaxPoints || rings[r]->size() > kMaxPoints - src[r].n) return false;
+            total += src[r].n;
+        }
+        if (total > kMaxPoints) return false;
+        a.m[0] = a.m[1] = KdPushMap{};
+        for (int r = 0; r < n_rings; ++r) {
+            DeviceCloudRing& g = *rings[r];
+            const size_t n = src[r].n;
+            g.make_room(n, s);  // tail + n <= cap from here on: the launch below writes floats tail .. tail + n of every plane
+            if (!n) continue;
+            float* const at = g.planes.p + g.tail;
+            a.m[r] = KdPushMap{src[r].x, src[r].y, src[r].z, reinterpret_cast<const unsigned*>(src[r].in), at, at + g.cap, at + 2 * g.cap,
+                               reinterpret_cast<unsigned*>(at + 3 * g.cap), unsigned(n)};
+        }
+        if (total) {
+            hipLaunchKernelGGL(kd_push_kernel, dim3(unsigned((total + kKdPushBlock - 1) / kKdPushBlock)), dim3(kKdPushBlock), 0, s, a);
+            FLS_HIP(hipGetLastError());
+        }
+        for (int r = 0; r < n_rings; ++r) {
+            rings[r]->tail += src[r].n;
+            rings[r]->sizes.push_back(src[r].n);
+        }
+        return true;
+    }
 };
 
 // Map maintenance of one kd-tree kind on the device: the cell-grid build and the deque + map-side pcl::VoxelGrid (bit-identical to
-// the reference's since round 4: kernels_exactsort.hpp; FLS_DEVICE_VOXELGRID=0 = the host filter).  The host deque stays
-// authoritative: whatever the device declines is redone by the host path.
+// the reference's since round 4: kernels_exactsort.hpp; FLS_DEVICE_VOXELGRID=0 = the host filter).  Whatever the device
+// declines is redone by the host path, on the host deque (KdLocalMap::host_clouds fetches what a device push left in the ring alone).
 struct KdMapDevice {
     bool grid_on_device = true;  // FLS_DEVICE_GRID_BUILD=0: host std::sort + bucket loop + upload (A/B)
     bool vg_on_device = true;    // FLS_DEVICE_VOXELGRID=0: the host filter
@@ -528,10 +564,13 @@ struct KdMapDevice {
     DeviceVoxelGrid vg;
     PinnedBuf<float> stage;
     DevBuf<float> xyz;
+    bool push_on_device = true;  // FLS_KD_DEVICE_PUSH=0: a keyframe goes through the host (download, host transform, upload) as every other push
     unsigned long long device_filters = 0, host_filters = 0;
     void init() {
         if (const char* e = std::getenv("FLS_DEVICE_GRID_BUILD")) grid_on_device = std::atoi(e) != 0;
         vg_on_device = device_voxelgrid_mode() != 0;
+        if (const char* e = std::getenv("FLS_KD_DEVICE_PUSH")) push_on_device = std::atoi(e) != 0;
+        push_on_device = push_on_device && vg_on_device && grid_on_device;  // (no ring without the other two)
     }
     // grid over a HOST cloud (the exact host filter's output, or an unfiltered cloud)
     fls_status build_from_host(CellGridImage& grid, const std::vector<PtI>& cloud, float cell, hipStream_t s, int rings = 1) {
@@ -570,44 +609,92 @@ struct KdMapDevice {
 // loam_full_kdtree.h:65-104, loam_point_to_plane_kdtree.h:56-79) and what the Match searches, the cell grid over [the VoxelGrid of] the
 // concatenated deque.  The owner pushes / trims as its reference does and calls rebuild() at the same moments; cell size and search depth are
 // the owner's.  With `on_device` the deque is mirrored in a DeviceCloudRing and filter + grid build never leave the device.
+//
+// The host deque is LAZY (kd_lazy_deque.hpp): a keyframe pushed on the device (push_device) exists in the ring alone until something reads
+// the host deque -- host_clouds(), the one accessor: a rebuild the device declined, an export through the host -- which first copies what is
+// missing out of the ring.  Count and sizes (deque.size(), deque.sizes) are read without a download.
 struct KdLocalMap {
-    std::deque<std::vector<PtI>> clouds;
+    KdLazyDeque deque;        // the reference's deque; host copies of the clouds a host push or an import brought, or a fetch
     DeviceCloudRing ring;     // the deque's clouds back to back on the device (device path only)
     std::vector<PtI> local;   // the map cloud on the host: what the host path built, empty after a device rebuild
     CellGridImage grid;
     KdMapDevice dev;
     size_t n = 0;             // points of the local map, whichever path built it (fls_map_size)
     bool on_device = false;   // the deque is mirrored on the device: FLS_DEVICE_VOXELGRID != 0 and FLS_DEVICE_GRID_BUILD != 0
+    bool rebuild_declined = false;  // the last rebuild(): the handle is on the device path and the device declined
+    PinnedBuf<unsigned> fetch_stage;  // x | y | z | i of the run being fetched
+    unsigned long long device_pushes = 0, host_pushes = 0, fetched = 0;
     void init() {
         dev.init();
         on_device = dev.vg_on_device && dev.grid_on_device;
     }
     void push(const std::vector<PtI>& cloud, hipStream_t s) {
-        clouds.push_back(cloud);
-        if (on_device) ring.push_back(cloud, s);
+        deque.push_host(cloud);
+        if (on_device) { ring.push_back(cloud, s); ++host_pushes; }
     }
-    void trim(size_t max_clouds) {
-        if (clouds.size() <= max_clouds) return;
-        clouds.pop_front();
-        if (on_device) ring.pop_front();
+    bool can_push_device() const { return on_device && dev.push_on_device; }
+    // A keyframe from clouds that lie on this device, one per map of `maps` (LoamFull: two), in one launch (DeviceCloudRing::push_back_device).
+    // false: not on the device-push path, or a ring cannot take its cloud -- every map is as it was and the caller pushes through the host.
+    static bool push_device(KdLocalMap* const* maps, const DeviceCloudRing::DeviceCloud* src, const int n_maps, const KdPushArgs& a, hipStream_t s) {
+        DeviceCloudRing* rings[2] = {nullptr, nullptr};
+        for (int m = 0; m < n_maps; ++m) {
+            if (!maps[m]->can_push_device()) return false;
+            rings[m] = &maps[m]->ring;
+        }
+        if (!DeviceCloudRing::push_back_device(rings, src, n_maps, a, s)) return false;
+        for (int m = 0; m < n_maps; ++m) { maps[m]->deque.push_device(src[m].n); ++maps[m]->device_pushes; }
+        return true;
+    }
+    void trim(size_t max_clouds) {  // (whether or not the cloud that leaves was ever fetched)
+        if (deque.trim(max_clouds) && on_device) ring.pop_front();
     }
     void reset_to(const std::vector<PtI>& cloud, hipStream_t s) {  // localization mode: the map is the last cloud alone
-        clouds.clear();
+        deque.clear();
         ring.clear();
         push(cloud, s);
+    }
+    // an import: the image's deque, every cloud present on the host (the caller has put the rows into the ring's planes)
+    void replace_deque(KdDeque&& all) {
+        deque.assign(std::move(all));
+        if (!on_device) return;
+        ring.sizes.clear();
+        for (const size_t sz : deque.sizes) ring.sizes.push_back(sz);
+    }
+    // THE reader of the host deque: whatever the host does not hold is fetched from the ring first, run by run (four copies and one wait each)
+    const KdDeque& host_clouds(hipStream_t s) {
+        if (deque.complete()) return deque.clouds;
+        for (const KdLazyDeque::Run& r : deque.missing_runs()) {
+            if (r.n_points) {
+                fetch_stage.reserve(4 * r.n_points);
+                for (int a = 0; a < 4; ++a)
+                    FLS_HIP(hipMemcpyAsync(fetch_stage.p + size_t(a) * r.n_points, ring.planes.p + size_t(a) * ring.cap + ring.head + r.offset, r.n_points * sizeof(float),
+                                           hipMemcpyDeviceToHost, s));
+                FLS_HIP(hipStreamSynchronize(s));
+            }
+            const unsigned* q = fetch_stage.p;
+            deque.fill(r, q, q + r.n_points, q + 2 * r.n_points, q + 3 * r.n_points);
+            fetched += r.n_clouds;
+        }
+        return deque.clouds;
     }
     // local map = [VoxelGrid(leaf) of] the concatenated deque, then the grid (cells of `cell`, searched `rings` deep): on the device, or on
     // the host for whatever the device declines
     fls_status rebuild(bool filter, float leaf, float cell, int rings, hipStream_t s) {
+        rebuild_declined = false;
         if (on_device && dev.filter_and_build(grid, ring, filter, leaf, cell, rings, n, s)) { local.clear(); return FLS_OK; }
+        rebuild_declined = on_device;
         local.clear();
-        for (const auto& c : clouds) local.insert(local.end(), c.begin(), c.end());
+        for (const auto& c : host_clouds(s)) local.insert(local.end(), c.begin(), c.end());
         if (filter) { local = voxel_grid(local, leaf); ++dev.host_filters; }
         n = local.size();
         return dev.build_from_host(grid, local, cell, s, rings);
     }
-    // fls_map_size slots 114 / 115 / 116: cell grids built on the device / map updates filtered on the device / ... filtered on the host
-    size_t counter(int slot) const { return size_t(slot == 114 ? dev.builder.builds : slot == 115 ? dev.device_filters : dev.host_filters); }
+    // fls_map_size slots 114 / 115 / 116: cell grids built on the device / map updates filtered on the device / ... filtered on the host;
+    // 164 / 165 / 166: clouds pushed on the device / pushed through the host while a ring exists / fetched to the host lazily
+    size_t counter(int slot) const {
+        return size_t(slot == 114 ? dev.builder.builds : slot == 115 ? dev.device_filters : slot == 116 ? dev.host_filters : slot == 164 ? device_pushes
+                      : slot == 165 ? host_pushes : fetched);
+    }
 };
 
 // the source-scan filter of the kd-tree / NDT matchers (icp_optimized.h:57, incremental_ndt.h:232): on the device (default), the

@@ -138,33 +138,53 @@ inline fls_status kd_image_check_body(const unsigned char* img, const KdImageLay
 }
 
 using KdDeque = std::deque<std::vector<PtI>>;
+using KdSizes = std::deque<size_t>;  // the points of every cloud of a deque: all the layout, the header and the sizes array need of it
 
 // the layout of the image of `maps[0 .. n_maps)`; false: too large for the format (a cloud of 2^32 points) or for a size_t
-inline bool kd_image_layout_of(const KdDeque* const* maps, const int n_maps, KdImageLayout& L) {
+inline bool kd_image_layout_of(const KdSizes* const* maps, const int n_maps, KdImageLayout& L) {
     uint64_t nc[2] = {0, 0}, np[2] = {0, 0};
     for (int m = 0; m < n_maps && m < 2; ++m) {
         nc[m] = maps[m]->size();
-        for (const auto& c : *maps[m]) {
-            if (c.size() > 0xffffffffull) return false;
-            np[m] += c.size();
+        for (const size_t s : *maps[m]) {
+            if (s > 0xffffffffull) return false;
+            np[m] += s;
         }
     }
     return kd_image_layout(n_maps, nc, np, L);
 }
 // Header + sizes of every map, with the padding behind them, and nothing of the rows: what the device export writes from the host.
 // chunk[0] receives the image bytes [0, rows[0]): the header and map 0's sizes; chunk[1] the bytes [sizes[1], rows[1]): map 1's sizes
-inline void kd_image_write_meta(const KdImageParams& q, const KdImageGate& g, const KdImageLayout& L, const KdDeque* const* maps, unsigned char* const* chunk) {
+inline void kd_image_write_meta(const KdImageParams& q, const KdImageGate& g, const KdImageLayout& L, const KdSizes* const* maps, unsigned char* const* chunk) {
     const fls_kd_image_header h = kd_image_make_header(q, g, L);
     std::memcpy(chunk[0], &h, sizeof(h));
     for (int m = 0; m < L.n_maps; ++m) {
         unsigned char* const at = m == 0 ? chunk[0] + L.sizes[0] : chunk[1];
         std::memset(at, 0, L.rows[m] - L.sizes[m]);
         size_t c = 0;
-        for (const auto& cloud : *maps[m]) {
-            const uint32_t s = uint32_t(cloud.size());
+        for (const size_t n : *maps[m]) {
+            const uint32_t s = uint32_t(n);
             std::memcpy(at + 4 * c++, &s, 4);
         }
     }
+}
+// the same two from the deques themselves
+struct KdSizesOf {
+    KdSizes s[2];
+    const KdSizes* p[2] = {&s[0], &s[1]};
+    KdSizesOf(const KdDeque* const* maps, const int n_maps) {
+        for (int m = 0; m < n_maps && m < 2; ++m)
+            for (const auto& c : *maps[m]) s[m].push_back(c.size());
+    }
+    KdSizesOf(const KdSizesOf&) = delete;
+    KdSizesOf& operator=(const KdSizesOf&) = delete;
+};
+inline bool kd_image_layout_of(const KdDeque* const* maps, const int n_maps, KdImageLayout& L) {
+    const KdSizesOf s(maps, n_maps);
+    return kd_image_layout_of(s.p, n_maps, L);
+}
+inline void kd_image_write_meta(const KdImageParams& q, const KdImageGate& g, const KdImageLayout& L, const KdDeque* const* maps, unsigned char* const* chunk) {
+    const KdSizesOf s(maps, L.n_maps);
+    kd_image_write_meta(q, g, L, s.p, chunk);
 }
 // deque -> image.  dst holds L.total bytes; every one of them is written
 inline void kd_image_from_deques(const KdImageParams& q, const KdImageGate& g, const KdImageLayout& L, const KdDeque* const* maps, unsigned char* dst) {

@@ -457,10 +457,12 @@ struct DevScan {
     // attach_device: the scan was written on the device (x | y | z | intensity); the pinned staging copy / `host` are fetched only
     // when a map update or a declined device path reads them
     bool stage_stale = false, host_stale = false;
+    bool dev_intensity = false;  // the scan's intensity plane lies on the device, at xyz.p + 3 n (an attached scan; an upload sends x | y | z)
     void attach_device(const HandoffCloud& c, hipStream_t s, bool want_host) {
         n = c.n;
         host.clear();
         stage_stale = n != 0;
+        dev_intensity = n != 0;
         host_stale = want_host && n != 0;
         if (n == 0) return;
         xyz.reserve(4 * n);
@@ -510,6 +512,7 @@ struct DevScan {
         n = count;
         host.clear();
         stage_stale = host_stale = false;
+        dev_intensity = false;
         if (n == 0) return;
         stage.reserve(4 * n);
         float* sx = stage.p; float* sy = stage.p + n; float* sz = stage.p + 2 * n; float* si = stage.p + 3 * n;
@@ -551,6 +554,7 @@ struct DevScan {
         host = c;
         n = c.size();
         stage_stale = host_stale = false;
+        dev_intensity = false;
         if (n == 0) return;
         stage.reserve(3 * n);
         for (size_t i = 0; i < n; ++i) { stage.p[i] = c[i].x; stage.p[n + i] = c[i].y; stage.p[2 * n + i] = c[i].z; }

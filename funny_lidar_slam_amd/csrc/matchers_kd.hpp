@@ -31,8 +31,9 @@ inline unsigned knn_grid_blocks(size_t n) { return unsigned((((n * 8 + 255) / 25
 // replica sets.  The image carries the deque(s) and the keyframe gate; the bytes are a function of the logical state, so the rings of a
 // device-path handle (packed by kd_image_pack_kernel) and the host deques of a host-path one give the same image.  An import checks the
 // whole image on the host, unpacks the rows into planes of its own (kept for the next import: a replica refresh allocates nothing after
-// the first), and only then swaps them into the handle and runs the kind's own rebuild.  The host deque is filled EAGERLY (it stays
-// authoritative for whatever the device declines, as after every push): one device-to-host copy when the source is device memory.
+// the first), and only then swaps them into the handle and runs the kind's own rebuild.  An import fills the host deque EAGERLY (every cloud
+// present, as after a host push; a keyframe pushed on the device has no host copy until something reads one, KdLocalMap::host_clouds): one
+// device-to-host copy when the source is device memory.  An export from the rings reads sizes alone and fetches nothing.
 // fls_map_size slots 160-163.
 struct KdMapImage {
     unsigned long long exports_device = 0, exports_host = 0, imports_device = 0, imports_host = 0;
@@ -43,8 +44,9 @@ struct KdMapImage {
     static bool kernel_aligned(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
     size_t counter(int slot) const { return size_t(slot == 160 ? exports_device : slot == 161 ? exports_host : slot == 162 ? imports_device : imports_host); }
 
+    // (layout, header and sizes need the clouds' sizes alone: no host copy is fetched for them)
     static bool layout_of(KdLocalMap* const* maps, const int n_maps, KdImageLayout& L) {
-        const KdDeque* d[2] = {&maps[0]->clouds, n_maps > 1 ? &maps[1]->clouds : nullptr};
+        const KdSizes* d[2] = {&maps[0]->deque.sizes, n_maps > 1 ? &maps[1]->deque.sizes : nullptr};
         return kd_image_layout_of(d, n_maps, L);
     }
     // the rings hold what the deques hold, in planes a 16-byte access may walk
@@ -63,11 +65,12 @@ struct KdMapImage {
         if (!dst || !layout_of(maps, int(q.n_maps), L)) return FLS_ERR_STATE;
         if (cap < L.total) return FLS_ERR_RANGE;
         unsigned char* const out = static_cast<unsigned char*>(dst);
-        const KdDeque* d[2] = {&maps[0]->clouds, L.n_maps > 1 ? &maps[1]->clouds : nullptr};
+        const KdSizes* d[2] = {&maps[0]->deque.sizes, L.n_maps > 1 ? &maps[1]->deque.sizes : nullptr};
         FLS_HIP(hipStreamSynchronize(stream));
-        if (!rings_usable(maps, L)) {  // from the host deques
+        if (!rings_usable(maps, L)) {  // from the host deques (fetched from the rings where a device push left them there alone)
             unsigned char* const host = dst_on_device ? (img_pinned.reserve(L.total), img_pinned.p) : out;
-            kd_image_from_deques(q, g, L, d, host);
+            const KdDeque* hd[2] = {&maps[0]->host_clouds(stream), L.n_maps > 1 ? &maps[1]->host_clouds(stream) : nullptr};
+            kd_image_from_deques(q, g, L, hd, host);
             if (dst_on_device) {
                 FLS_HIP(hipMemcpyAsync(out, host, L.total, hipMemcpyHostToDevice, stream));
                 FLS_HIP(hipStreamSynchronize(stream));
@@ -172,19 +175,20 @@ struct KdMapImage {
         any_cloud = false;
         for (int m = 0; m < L.n_maps; ++m) {
             KdLocalMap& km = *maps[m];
-            kd_deque_from_image(host, L, m, km.clouds);
+            KdDeque all;
+            kd_deque_from_image(host, L, m, all);
             any_cloud = any_cloud || L.n_clouds[m] != 0;
-            if (!on_device) continue;
-            DeviceCloudRing& r = km.ring;
-            if (L.n_points[m]) {
-                std::swap(r.planes.p, spare[m].planes.p);
-                std::swap(r.planes.cap, spare[m].planes.cap);
-                std::swap(r.cap, spare[m].cap);
+            if (on_device) {
+                DeviceCloudRing& r = km.ring;
+                if (L.n_points[m]) {
+                    std::swap(r.planes.p, spare[m].planes.p);
+                    std::swap(r.planes.cap, spare[m].planes.cap);
+                    std::swap(r.cap, spare[m].cap);
+                }
+                r.head = 0;
+                r.tail = L.n_points[m];
             }
-            r.head = 0;
-            r.tail = L.n_points[m];
-            r.sizes.clear();
-            for (const auto& c : km.clouds) r.sizes.push_back(c.size());
+            km.replace_deque(std::move(all));  // (every cloud present on the host; the ring's sizes follow)
         }
         const KdImageGate g = kd_gate_from_header(h);
         gate = hm::KeyframeGate();
@@ -270,6 +274,46 @@ struct KdImageCalls {
     fls_status map_import(const void* blob, size_t n) override { return KdImageCalls<M>::import_from(*this, blob, n, 0); }                     \
     bool can_replicate() const override { return !owner && have_map; }                                                                         \
     fls_status replicate_from(fls_matcher& o) override { return KdImageCalls<M>::replicate(*this, o); }
+
+// ---------------------------------------------------------------------------------------------
+// A keyframe pushed on the device (KdLocalMap::push_device, kernels_kd_push.hpp): the transform as the kernel takes it, and the intensity
+// plane of scans whose intensities never went to the device.
+inline KdPushArgs kd_push_xform_f(const double* T) {  // hm::xform_cloud_f's casts
+    KdPushArgs a{};
+    a.mode = kKdPushXformF;
+    for (int j = 0; j < 3; ++j) for (int i = 0; i < 3; ++i) a.R[i + j * 3] = float(T[i + j * 4]);
+    for (int i = 0; i < 3; ++i) a.t[i] = float(T[12 + i]);
+    return a;
+}
+inline KdPushArgs kd_push_xform_d(const double* T) {  // hm::xform_cloud_d
+    KdPushArgs a{};
+    a.mode = kKdPushXformD;
+    std::memcpy(a.T, T, sizeof(a.T));
+    return a;
+}
+// DevScan::upload sends x | y | z; the intensities a keyframe carries into the deque are gathered from the scans' host copies into pinned
+// memory and copied up as one plane (cloud 0's, then cloud 1's) when a keyframe is taken, and only then: a Match without one pays nothing.
+struct KdPushIntensity {
+    PinnedBuf<float> h;
+    DevBuf<float> d;
+    hipEvent_t copied = nullptr;  // the last copy has read `h`
+    ~KdPushIntensity() { if (copied) (void)hipEventDestroy(copied); }
+    const float* upload(const std::vector<PtI>* const* clouds, const int n_clouds, hipStream_t s) {
+        size_t total = 0;
+        for (int c = 0; c < n_clouds; ++c) total += clouds[c]->size();
+        if (!total) return nullptr;
+        if (copied) FLS_HIP(hipEventSynchronize(copied));  // (long over: a rebuild has waited for the stream since)
+        else FLS_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        h.reserve(total);
+        d.reserve(total);
+        size_t at = 0;
+        for (int c = 0; c < n_clouds; ++c)
+            for (const PtI& q : *clouds[c]) std::memcpy(h.p + at++, &q.i, sizeof(float));
+        FLS_HIP(hipMemcpyAsync(d.p, h.p, total * sizeof(float), hipMemcpyHostToDevice, s));
+        FLS_HIP(hipEventRecord(copied, s));
+        return d.p;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 struct IcpMatcher final : fls_matcher {
@@ -387,12 +431,29 @@ struct IcpMatcher final : fls_matcher {
         // switch, as in the reference; update_map == 0 (this ABI's "registration only" switch) skips the whole statement,
         // so such a call leaves the keyframe gate alone
         if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {
-            src_filter.materialize(stream, source);
-            const fls_status arc = add_cloud_impl(hm::xform_cloud_f(source, final_T));
+            fls_status arc;
+            if (push_keyframe_device()) {  // the mapping branch of add_cloud_impl, the push on the device
+                map.trim(p.local_map_size);
+                arc = rebuild_maps();
+                if (map.rebuild_declined) ++push_declines;
+            } else {
+                src_filter.materialize(stream, source);
+                arc = add_cloud_impl(hm::xform_cloud_f(source, final_T));
+            }
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
         }
         if (out) *out = stats;
         return rc;
+    }
+    // the filtered scan the Match just used, still on the device (the source filter's output planes), into the ring at final_T; false: the
+    // host filter ran, or the map cannot take a device push -- nothing has changed
+    unsigned long long push_declines = 0;  // device rebuilds declined after a device push (fls_map_size slot 167)
+    bool push_keyframe_device() {
+        if (!src_filter.resident || !map.can_push_device()) return false;
+        const DeviceVoxelGrid& vg = src_filter.vg;
+        const DeviceCloudRing::DeviceCloud src{vg.ox(), vg.oy(), vg.oz(), vg.oi(), vg.n_out};
+        KdLocalMap* maps[1] = {&map};
+        return KdLocalMap::push_device(maps, &src, 1, kd_push_xform_f(final_T), stream);
     }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         MatchPlan m;
@@ -471,8 +532,9 @@ struct IcpMatcher final : fls_matcher {
     size_t map_size(int slot) const override {
         if (slot == 105) return size_t(src_filter.device_runs);  // source filters run on the device / on the host
         if (slot == 106) return size_t(src_filter.host_runs);
-        if (slot >= 114 && slot <= 116) return map.counter(slot);
+        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map.counter(slot);
         if (slot >= 160 && slot <= 163) return image.counter(slot);
+        if (slot == 167) return size_t(push_declines);
         return map.n;
     }
 };
@@ -554,9 +616,9 @@ struct LoamFullMatcher final : fls_matcher {
     fls_status rebuild_maps() {  // (a keyframe update and an image import)
         // half-gate cells + the two-stage kernel; the VoxelGrid only once the deque holds more than 5 frames (:92-100)
         const float cs = 0.5f * cell_for_gate(p.point_search_thres);
-        fls_status rc = map_planar.rebuild(map_planar.clouds.size() > 5, p.planar_voxel_filter_size, cs, kGridRings, stream);
+        fls_status rc = map_planar.rebuild(map_planar.deque.size() > 5, p.planar_voxel_filter_size, cs, kGridRings, stream);
         if (rc != FLS_OK) return rc;
-        rc = map_corner.rebuild(map_corner.clouds.size() > 5, p.corner_voxel_filter_size, cs, kGridRings, stream);
+        rc = map_corner.rebuild(map_corner.deque.size() > 5, p.corner_voxel_filter_size, cs, kGridRings, stream);
         have_map = rc == FLS_OK;  // (the corner rebuild's status alone)
         return rc;
     }
@@ -619,11 +681,34 @@ struct LoamFullMatcher final : fls_matcher {
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (update_map && !owner && has_converge && gate.need(mb.T, p.dist_thre_add_cloud, p.rot_thre_add_cloud)) {  // :185-193 (no localization switch)
-            const fls_status arc = add_cloud_impl(hm::xform_cloud_d(planar.scan.host, mb.T), hm::xform_cloud_d(corner.scan.host, mb.T));
+            fls_status arc;
+            if (push_keyframe_device(mb.T)) {  // add_cloud_impl, both pushes in one launch on the device
+                map_planar.trim(p.local_planar_size);
+                map_corner.trim(p.local_corner_size);
+                map_planar.rebuild_declined = map_corner.rebuild_declined = false;
+                arc = rebuild_maps();
+                if (map_planar.rebuild_declined || map_corner.rebuild_declined) ++push_declines;
+            } else {
+                arc = add_cloud_impl(hm::xform_cloud_d(planar.scan.host, mb.T), hm::xform_cloud_d(corner.scan.host, mb.T));
+            }
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
         }
         if (out) *out = stats;
         return rc;
+    }
+    // both feature scans, still on the device, into their rings at the pose the Match found; their intensities go up first (one plane for
+    // both).  false: the maps cannot take a device push -- nothing has changed
+    KdPushIntensity push_i;
+    unsigned long long push_declines = 0;  // keyframes after whose device push a device rebuild was declined (fls_map_size slot 167)
+    bool push_keyframe_device(const double* T) {
+        if (!map_planar.can_push_device() || !map_corner.can_push_device()) return false;
+        const DevScan &ps = planar.scan, &cs = corner.scan;
+        if (ps.host.size() != ps.n || cs.host.size() != cs.n) return false;
+        const std::vector<PtI>* clouds[2] = {&ps.host, &cs.host};
+        const float* in = push_i.upload(clouds, 2, stream);
+        const DeviceCloudRing::DeviceCloud src[2] = {{ps.x.p, ps.y.p, ps.z.p, in, ps.n}, {cs.x.p, cs.y.p, cs.z.p, in + ps.n, cs.n}};
+        KdLocalMap* maps[2] = {&map_planar, &map_corner};
+        return KdLocalMap::push_device(maps, src, 2, kd_push_xform_d(T), stream);
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
@@ -632,8 +717,9 @@ struct LoamFullMatcher final : fls_matcher {
         return (slot == 1 ? corner : planar).fetch(stream, ids, cnt, valid, cap);
     }
     size_t map_size(int slot) const override {
-        if (slot >= 114 && slot <= 116) return map_planar.counter(slot) + map_corner.counter(slot);
+        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map_planar.counter(slot) + map_corner.counter(slot);  // (clouds: two per keyframe)
         if (slot >= 160 && slot <= 163) return image.counter(slot);
+        if (slot == 167) return size_t(push_declines);
         return slot == 1 ? map_corner.n : map_planar.n;
     }
 };
@@ -710,12 +796,34 @@ struct P2PlaneKdMatcher final : fls_matcher {
         stats.converged = has_converge ? 1 : 0;
         fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
         if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {  // :145-149
-            planar.scan.fetch_host(stream);  // (an attached scan is fetched only here)
-            const fls_status arc = add_cloud_impl(hm::xform_cloud_f(planar.scan.host, final_T));
+            fls_status arc;
+            if (push_keyframe_device()) {  // the mapping branch of add_cloud_impl, the push on the device
+                map.trim(p.local_map_size);
+                arc = rebuild_maps();
+                if (map.rebuild_declined) ++push_declines;
+            } else {
+                planar.scan.fetch_host(stream);  // (an attached scan is fetched only here)
+                arc = add_cloud_impl(hm::xform_cloud_f(planar.scan.host, final_T));
+            }
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
         }
         if (out) *out = stats;
         return rc;
+    }
+    // the scan, still on the device, into the ring at final_T.  Intensity: the fourth plane of an attached scan; of an uploaded one the
+    // host copy's, sent up here.  false: the map cannot take a device push -- nothing has changed
+    KdPushIntensity push_i;
+    unsigned long long push_declines = 0;  // device rebuilds declined after a device push (fls_map_size slot 167)
+    bool push_keyframe_device() {
+        if (!map.can_push_device()) return false;
+        const DevScan& sc = planar.scan;
+        const float* in = nullptr;
+        if (sc.dev_intensity) in = sc.xyz.p + 3 * sc.n;
+        else if (sc.host.size() == sc.n) { const std::vector<PtI>* clouds[1] = {&sc.host}; in = push_i.upload(clouds, 1, stream); }
+        else return false;
+        const DeviceCloudRing::DeviceCloud src{sc.x.p, sc.y.p, sc.z.p, in, sc.n};
+        KdLocalMap* maps[1] = {&map};
+        return KdLocalMap::push_device(maps, &src, 1, kd_push_xform_f(final_T), stream);
     }
     void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
@@ -725,8 +833,9 @@ struct P2PlaneKdMatcher final : fls_matcher {
     }
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override { return planar.fetch(stream, ids, cnt, valid, cap); }
     size_t map_size(int slot) const override {
-        if (slot >= 114 && slot <= 116) return map.counter(slot);
+        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map.counter(slot);
         if (slot >= 160 && slot <= 163) return image.counter(slot);
+        if (slot == 167) return size_t(push_declines);
         return map.n;
     }
 };

@@ -285,7 +285,13 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
  * FLS_ERR_RANGE), 145 = brick pool over its byte budget, 146 = hash-table form (FLS_IVOX_DENSE=0); 147 = host mirrors reconstructed from a
  * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).
  * The kd-tree kinds, flat images (fls_map_kd.h; KdMapImage in csrc/matchers_kd.hpp): 160 = exports packed on the device, 161 = exports
- * written by the host from the deque, 162 = imports unpacked on the device, 163 = imports through the host deque alone.                  */
+ * written by the host from the deque, 162 = imports unpacked on the device, 163 = imports through the host deque alone.
+ * The kd-tree kinds, keyframes (KdLocalMap in csrc/device_voxelgrid.hpp; LoamFull: both deques together, so two clouds per keyframe in
+ * 164-166): 164 = clouds a Match pushed into the device deque on the device (the scan it just used, transformed there; FLS_KD_DEVICE_PUSH=0
+ * restores the push through the host, FLS_DEVICE_VOXELGRID=0 / FLS_DEVICE_GRID_BUILD=0 imply it), 165 = clouds pushed through the host while
+ * a device deque exists (fls_add_cloud_to_local_map, a host-filtered ICP source, the switch), 166 = clouds whose host copy was fetched from
+ * the device deque because something read it (a rebuild the device declined, an export written by the host), 167 = keyframes pushed on
+ * the device whose map rebuild the device then declined (the host rebuilt, on the fetched deque).                                          */
 size_t fls_map_size(fls_handle h, int slot);
 
 /* ---- measurement hooks ----------------------------------------------------------------------------
