@@ -111,6 +111,25 @@ def kd_image_layout(n_clouds, n_points) -> dict:
     return out
 
 
+# every symbol include/fls_map_ivox.h declares (FLS_IVOX_BLOB_REVISION 1): the FLSIVOX1 blob of fls_map_export / fls_map_import for the iVox kind,
+# packed from and built into the device image without the host mirror
+IVOX_BLOB_SYMBOLS = ["fls_ivox_blob_revision", "fls_ivox_map_bytes", "fls_ivox_map_export", "fls_ivox_map_import"]
+IVOX_BLOB_MAGIC, IVOX_BLOB_VERSION, IVOX_BLOB_HEADER_BYTES, IVOX_BLOB_VOXEL_BYTES, IVOX_BLOB_POINT_BYTES = b"FLSIVOX1", 1, 56, 16, 16
+
+
+class IvoxBlobHeader(C.Structure):
+    """fls_ivox_blob_header (include/fls_map_ivox.h)."""
+
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("kind", C.c_uint32), ("resolution", C.c_float), ("is_first", C.c_uint32),
+                ("capacity", C.c_uint64), ("n_voxels", C.c_uint64), ("n_points", C.c_uint64), ("next_id", C.c_int64)]
+
+
+class IvoxBlobVoxel(C.Structure):
+    """fls_ivox_blob_voxel (include/fls_map_ivox.h)."""
+
+    _fields_ = [("key", C.c_uint64), ("count", C.c_uint32), ("pad", C.c_uint32)]
+
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -321,6 +340,14 @@ def lib():
         L.fls_map_export.argtypes = [hp, C.c_void_p, C.c_size_t]
         L.fls_map_import.restype = C.c_int
         L.fls_map_import.argtypes = [hp, C.c_void_p, C.c_size_t]
+        L.fls_ivox_blob_revision.restype = C.c_uint
+        L.fls_ivox_blob_revision.argtypes = []
+        L.fls_ivox_map_bytes.restype = C.c_size_t
+        L.fls_ivox_map_bytes.argtypes = [hp]
+        L.fls_ivox_map_export.restype = C.c_int
+        L.fls_ivox_map_export.argtypes = [hp, C.c_void_p, C.c_size_t, C.c_int]
+        L.fls_ivox_map_import.restype = C.c_int
+        L.fls_ivox_map_import.argtypes = [hp, C.c_void_p, C.c_size_t, C.c_int]
         L.fls_loop_match.restype = C.c_int
         L.fls_loop_match.argtypes = [C.c_int, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float),
                                      C.c_void_p]

@@ -249,6 +249,26 @@ fls_status fls_map_import(fls_handle h, const void* blob, size_t n) {
     return guarded([&]() -> fls_status { FLS_HIP(hipSetDevice(h->device)); return h->map_import(blob, n); });
 }
 
+// ---- include/fls_map_ivox.h: the blob of fls_map_export / fls_map_import for an FLS_P2PLANE_IVOX handle, packed and built on the device ----
+unsigned fls_ivox_blob_revision(void) { return FLS_IVOX_BLOB_REVISION; }
+
+size_t fls_ivox_map_bytes(fls_handle h) {
+    if (!h) return 0;
+    size_t n = 0;
+    (void)guarded([&]() -> fls_status { n = h->ivox_blob_bytes(); return FLS_OK; });
+    return n;
+}
+
+fls_status fls_ivox_map_export(fls_handle h, void* dst, size_t cap_bytes, int dst_on_device) {
+    if (!h || !dst) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status { FLS_HIP(hipSetDevice(h->device)); return h->ivox_blob_export(dst, cap_bytes, dst_on_device); });
+}
+
+fls_status fls_ivox_map_import(fls_handle h, const void* src, size_t n_bytes, int src_on_device) {
+    if (!h || !src) return FLS_ERR_INVALID;
+    return guarded([&]() -> fls_status { FLS_HIP(hipSetDevice(h->device)); return h->ivox_blob_import(src, n_bytes, src_on_device); });
+}
+
 // ---- include/fls_map_ndt.h: the format fls_map_export / fls_map_image_export write for an FLS_INCREMENTAL_NDT handle ----
 int fls_ndt_image_revision(void) { return FLS_NDT_IMAGE_REVISION; }
 

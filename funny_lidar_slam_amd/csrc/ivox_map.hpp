@@ -2,11 +2,13 @@
 // uses it (InitIVox :53-58, the AddPoints side of AddCloudToLocalMap :60-139).  Host mirror (HostIvox) + device image (IvoxImage) + the rule
 // which of the two is the map (State; diagram in DESIGN.md 3), the device-side AddPoints (enqueue_update / await_update) and the ways a
 // map travels (blob, replica, flat image).  A whole cloud going into an EMPTY map is built on the device (bulk_build, kernels_ivox_build.hpp):
-// the image then is the map and the mirror is only reconstructed when something asks for it.  Everything is queued on the one stream given to init().
+// the image then is the map and the mirror is only reconstructed when something asks for it.  The blob is also packed from and built into the image
+// on the device (export_blob_to / import_blob_from, kernels_ivox_blob.hpp).  Everything is queued on the one stream given to init().
 #pragma once
 #include "ivox_image.hpp"
 #include "device_voxelgrid.hpp"
 #include "kernels_ivox_build.hpp"
+#include "kernels_ivox_blob.hpp"
 #include <chrono>
 #include <algorithm>
 
@@ -47,7 +49,11 @@ struct IvoxMap {
     enum class BuildDecline { None = 0, TooMany, Capacity, Range, Budget, NotDense, SwitchedOff };
     size_t n_bulk_builds = 0, n_bulk_declined = 0, n_bulk_decline_reason[7] = {}, n_lazy_mirrors = 0;
     BuildDecline last_decline = BuildDecline::None;
-    bool mirror_pending = false;  // the map came from a bulk build and its mirror has not been reconstructed yet
+    bool mirror_pending = false;  // the map came from a bulk build (or a blob built on the device) and its mirror has not been reconstructed yet
+    // map_size slots 168-175: the blob packed / built on the device (include/fls_map_ivox.h)
+    bool allow_device_image = true;  // FLS_IVOX_DEVICE_IMAGE=0: export_blob_to / import_blob_from take the host path (A/B)
+    enum class BlobDecline { None = 0, SwitchedOff, Size, Range, Budget, NotDense };
+    size_t n_blob_exports_device = 0, n_blob_exports_host = 0, n_blob_imports_device = 0, n_blob_imports_declined = 0, n_blob_decline_reason[6] = {};
     double build_ms[3] = {0, 0, 0};  // FLS_HOST_TIMING: keys + sort + scans up to the mailbox | pool set-up + cells + points | total
     // ---- device-side AddPoints: persistent state, the mailbox its commit kernel writes, the counts mirrored from it ----
     DevBuf<IvoxUpdState> d_upd_state;
@@ -73,6 +79,10 @@ struct IvoxMap {
     IvbMailbox* bb_mb_host = nullptr;
     IvbMailbox* bb_mb_dev = nullptr;
     unsigned bb_seq = 0;
+    // the blob on the device: staging (shifted by 8 bytes: every record 16-byte aligned), the report of the checks, prefixes of the counts
+    DevBuf<uint4> d_blob;
+    DevBuf<IvblReport> d_blob_rep;
+    DevBuf<unsigned> bl_lsrc, bl_bt;
 
     ~IvoxMap() {
         if (stream) (void)hipStreamSynchronize(stream);  // (the owner destroys the stream after its members)
@@ -84,6 +94,7 @@ struct IvoxMap {
         if (const char* e = std::getenv("FLS_IVOX_DENSE")) use_dense = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_UPDATE")) allow_device_map = std::atoi(e) != 0;
         if (const char* e = std::getenv("FLS_IVOX_DEVICE_BUILD")) allow_device_build = std::atoi(e) != 0;
+        if (const char* e = std::getenv("FLS_IVOX_DEVICE_IMAGE")) allow_device_image = std::atoi(e) != 0;
         d_upd_state.reserve(1);
         FLS_HIP(hipHostMalloc((void**)&upd_mb_host, sizeof(IvoxUpdMailbox), hipHostMallocMapped));
         std::memset(upd_mb_host, 0, sizeof(IvoxUpdMailbox));
@@ -203,6 +214,66 @@ struct IvoxMap {
         return true;
     }
     bool is_blank() const { return state == State::MirrorUnbuilt && ivox.n_alive == 0 && ivox.next_id == 0; }
+    // The image's arrays sized and cleared for V voxels in `used` slots, and the voxels' cells written by `launch_cells` (ivb_cells, or ivbl_cells
+    // for the voxels of a blob) -- shared by bulk_build and import_blob_device.  Point array: the growth room build_from_ivox reserves.  Brick pool:
+    // its rule too -- three times the voxels' own bricks as a first guess, room for as many bricks again once they are all there, never over the
+    // byte budget (the host path then takes the hash-table form).  false: over the budget, the stream idle.  true: the cells launch that passed
+    // is complete, IvoxUpdState is set.
+    struct BuiltPool { size_t dir_size = 0, n_bricks_cap = 0, n_bricks_made = 0; };
+    template <class LaunchCells>
+    bool build_brick_pool(const size_t own, const size_t used, const size_t n_points, const size_t V, const int next_id, const unsigned long long stamp_base, BuiltPool& out,
+                          LaunchCells&& launch_cells) {
+        image.d_pts.reserve(used + used / 2 + (size_t(1) << 16));
+        size_t cap_guess = std::max<size_t>(image.n_bricks_cap, 256), ds = 0, n_bricks_made = 0;
+        while (cap_guess < 3 * own) cap_guess *= 2;
+        for (;;) {
+            if (cap_guess * IvoxImage::kPoolBrickBytes > IvoxImage::brick_budget_bytes()) {
+                FLS_HIP(hipStreamSynchronize(stream));
+                return false;
+            }
+            ds = 4096;
+            while (ds < 4 * cap_guess) ds <<= 1;
+            const size_t ncell = cap_guess * kBrickStride;
+            image.d_dir.reserve(ds); image.d_brick_key.reserve(cap_guess); image.d_cells.reserve(ncell); image.d_nbr.reserve(cap_guess * 32);
+            image.d_cap_log2.reserve(ncell); image.d_stamp.reserve(ncell); image.d_pend.reserve(ncell); image.d_rank_mm.reserve(ncell);
+            FLS_HIP(hipMemsetAsync(image.d_dir.p, 0xff, ds * sizeof(HashEntry), stream));  // every entry {kEmptyKey, kBrickPending, -}
+            FLS_HIP(hipMemsetAsync(image.d_cells.p, 0, ncell * sizeof(uint2), stream));
+            FLS_HIP(hipMemsetAsync(image.d_nbr.p, 0xff, cap_guess * 32 * sizeof(unsigned), stream));
+            FLS_HIP(hipMemsetAsync(image.d_cap_log2.p, 0, ncell, stream));
+            FLS_HIP(hipMemsetAsync(image.d_stamp.p, 0, ncell * sizeof(unsigned long long), stream));
+            FLS_HIP(hipMemsetAsync(image.d_pend.p, 0, ncell * sizeof(unsigned), stream));
+            FLS_HIP(hipMemsetAsync(image.d_rank_mm.p, 0xff, ncell * sizeof(unsigned), stream));
+            IvoxUpdState st{};
+            st.n_points = n_points; st.used = used; st.garbage = 0; st.stamp_base = stamp_base;
+            st.pts_capacity = image.d_pts.cap; st.n_alive = unsigned(V); st.lru_capacity = unsigned(std::min<size_t>(ivox.capacity, 0xffffffffu));
+            st.next_id = next_id; st.n_bricks = 0u; st.status = kUpdOk;
+            FLS_HIP(hipMemcpyAsync(d_upd_state.p, &st, sizeof(st), hipMemcpyHostToDevice, stream));
+            const IvoxUpdArrays a{image.d_cells.p, image.d_pts.p, image.d_cap_log2.p, image.d_stamp.p, image.d_pend.p, image.d_rank_mm.p,
+                                  image.d_dir.p, unsigned(ds - 1), unsigned(cap_guess), image.d_brick_key.p, image.d_nbr.p, ivox.inv_resolution};
+            launch_cells(a);
+            FLS_HIP(hipGetLastError());
+            FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            n_bricks_made = st.n_bricks;
+            if (!(st.status & kUpdArrayFull) && 2 * n_bricks_made <= cap_guess) break;
+            cap_guess = std::max(cap_guess * 2, 2 * n_bricks_made);  // (a refused launch counted every brick it wanted)
+        }
+        out = BuiltPool{ds, cap_guess, n_bricks_made};
+        return true;
+    }
+    // -> Device where enter_device() would go there, else ImageOnly.  Pre: build_brick_pool passed, the points are in their regions, the stream idle.
+    void adopt_built_image(const BuiltPool& pool, const size_t used, const size_t n_points, const size_t V, const unsigned long long stamp_base) {
+        image.want_hash = false; image.have_bricks = true;
+        image.table.clear(); image.mask = 0;
+        image.brick_index.clear(); image.brick_keys.clear(); image.dir.clear(); image.dir_dirty = false;  // (no host copy of the directory: to_mirror downloads it)
+        image.dir_mask = unsigned(pool.dir_size - 1); image.n_bricks_cap = pool.n_bricks_cap; image.meta_cells = pool.n_bricks_cap * kBrickStride;
+        image.cell_upd.clear(); image.pt_upd.clear();
+        image.used = used; image.garbage = 0; image.n_pts_live = n_points;
+        dev_n_points = n_points; dev_n_alive = V; dev_n_bricks = pool.n_bricks_made;
+        stamp_bound = stamp_base;
+        mirror_pending = true;
+        state = device_update_allowed() ? State::Device : State::ImageOnly;
+    }
     // -> Device where enter_device() would go there, else ImageOnly.  Pre: is_blank(), bulk_build_applies(n), n > 0; x | y | z the cloud on the
     // device, lo / hi its coordinate bounds over the points that are not NaN (round() is monotone: the extreme keys come from the extreme
     // coordinates).  false: declined (counted), nothing the host path relies on was changed.  One host wait inside (the mailbox of ivb_report),
@@ -260,59 +331,19 @@ struct IvoxMap {
         if (bb_mb_host->flag != 0u) return decline_build(BuildDecline::Range);
         const size_t V = bb_mb_host->n_voxels, own = bb_mb_host->own_bricks, used = size_t(bb_mb_host->used);
         if (V >= ivox.capacity) return decline_build(BuildDecline::Capacity);  // (evict_tail fires when n_alive >= capacity after a creation)
-        // point array: the growth room build_from_ivox reserves.  Brick pool: its rule too -- three times the voxels' own bricks as a first guess,
-        // room for as many bricks again once they are all there, never over the byte budget (the host path then takes the hash-table form)
-        image.d_pts.reserve(used + used / 2 + (size_t(1) << 16));
-        size_t cap_guess = std::max<size_t>(image.n_bricks_cap, 256), ds = 0, n_bricks_made = 0;
-        while (cap_guess < 3 * own) cap_guess *= 2;
-        for (;;) {
-            if (cap_guess * IvoxImage::kPoolBrickBytes > IvoxImage::brick_budget_bytes()) {
-                FLS_HIP(hipStreamSynchronize(stream));
-                return decline_build(BuildDecline::Budget);
-            }
-            ds = 4096;
-            while (ds < 4 * cap_guess) ds <<= 1;
-            const size_t ncell = cap_guess * kBrickStride;
-            image.d_dir.reserve(ds); image.d_brick_key.reserve(cap_guess); image.d_cells.reserve(ncell); image.d_nbr.reserve(cap_guess * 32);
-            image.d_cap_log2.reserve(ncell); image.d_stamp.reserve(ncell); image.d_pend.reserve(ncell); image.d_rank_mm.reserve(ncell);
-            FLS_HIP(hipMemsetAsync(image.d_dir.p, 0xff, ds * sizeof(HashEntry), stream));  // every entry {kEmptyKey, kBrickPending, -}
-            FLS_HIP(hipMemsetAsync(image.d_cells.p, 0, ncell * sizeof(uint2), stream));
-            FLS_HIP(hipMemsetAsync(image.d_nbr.p, 0xff, cap_guess * 32 * sizeof(unsigned), stream));
-            FLS_HIP(hipMemsetAsync(image.d_cap_log2.p, 0, ncell, stream));
-            FLS_HIP(hipMemsetAsync(image.d_stamp.p, 0, ncell * sizeof(unsigned long long), stream));
-            FLS_HIP(hipMemsetAsync(image.d_pend.p, 0, ncell * sizeof(unsigned), stream));
-            FLS_HIP(hipMemsetAsync(image.d_rank_mm.p, 0xff, ncell * sizeof(unsigned), stream));
-            IvoxUpdState st{};
-            st.n_points = n; st.used = used; st.garbage = 0; st.stamp_base = n;  // (stamps are 1 .. n: index of the last member + 1)
-            st.pts_capacity = image.d_pts.cap; st.n_alive = unsigned(V); st.lru_capacity = unsigned(std::min<size_t>(ivox.capacity, 0xffffffffu));
-            st.next_id = int(n); st.n_bricks = 0u; st.status = kUpdOk;
-            FLS_HIP(hipMemcpyAsync(d_upd_state.p, &st, sizeof(st), hipMemcpyHostToDevice, stream));
-            const IvoxUpdArrays a{image.d_cells.p, image.d_pts.p, image.d_cap_log2.p, image.d_stamp.p, image.d_pend.p, image.d_rank_mm.p,
-                                  image.d_dir.p, unsigned(ds - 1), unsigned(cap_guess), image.d_brick_key.p, image.d_nbr.p, ivox.inv_resolution};
-            hipLaunchKernelGGL(ivb_cells, g, t, 0, stream, (const unsigned long long*)bb_vkey.p, order, (const unsigned*)bb_first.p, unsigned(V), (const unsigned*)bb_lcap.p,
-                               (const unsigned*)btcs, a, d_upd_state.p, bb_vbegin.p);
-            FLS_HIP(hipGetLastError());
-            FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipStreamSynchronize(stream));
-            n_bricks_made = st.n_bricks;
-            if (!(st.status & kUpdArrayFull) && 2 * n_bricks_made <= cap_guess) break;
-            cap_guess = std::max(cap_guess * 2, 2 * n_bricks_made);  // (a refused launch counted every brick it wanted)
-        }
+        BuiltPool pool;
+        // (stamps are 1 .. n: index of the last member + 1)
+        if (!build_brick_pool(own, used, n, V, /*next_id=*/int(n), /*stamp_base=*/n, pool, [&](const IvoxUpdArrays& a) {
+                hipLaunchKernelGGL(ivb_cells, g, t, 0, stream, (const unsigned long long*)bb_vkey.p, order, (const unsigned*)bb_first.p, unsigned(V), (const unsigned*)bb_lcap.p,
+                                   (const unsigned*)btcs, a, d_upd_state.p, bb_vbegin.p);
+            }))
+            return decline_build(BuildDecline::Budget);
         // (ivb_points reads the region begins ivb_cells writes: queued behind the launch that passed)
         hipLaunchKernelGGL(ivb_points, g, t, 0, stream, x, y, z, order, ni, (const unsigned*)bb_vidx.p, (const unsigned*)bb_first.p, (const unsigned*)bb_vbegin.p, image.d_pts.p,
                            (unsigned long long)image.d_pts.cap);
         FLS_HIP(hipGetLastError());
         FLS_HIP(hipStreamSynchronize(stream));
-        image.want_hash = false; image.have_bricks = true;
-        image.table.clear(); image.mask = 0;
-        image.brick_index.clear(); image.brick_keys.clear(); image.dir.clear(); image.dir_dirty = false;  // (no host copy of the directory: to_mirror downloads it)
-        image.dir_mask = unsigned(ds - 1); image.n_bricks_cap = cap_guess; image.meta_cells = cap_guess * kBrickStride;
-        image.cell_upd.clear(); image.pt_upd.clear();
-        image.used = used; image.garbage = 0; image.n_pts_live = n;
-        dev_n_points = n; dev_n_alive = V; dev_n_bricks = n_bricks_made;
-        stamp_bound = n;
-        mirror_pending = true;
-        state = device_update_allowed() ? State::Device : State::ImageOnly;
+        adopt_built_image(pool, used, n, V, /*stamp_base=*/n);
         ++n_bulk_builds;
         last_decline = BuildDecline::None;
         const auto t2 = clock::now();
@@ -444,15 +475,8 @@ struct IvoxMap {
 
     // ---- map export / import (fls_reg.h): header, voxels from the LRU tail (oldest) to the head {key, count}, then the
     // points {x, y, z, id} of the voxels in the same order
-    struct BlobHeader {
-        char magic[8];
-        unsigned version, kind;
-        float resolution;
-        unsigned is_first;
-        unsigned long long capacity, n_voxels, n_points;
-        long long next_id;
-    };
-    struct BlobVoxel { unsigned long long key; unsigned count, pad; };
+    using BlobHeader = fls_ivox_blob_header;  // (include/fls_map_ivox.h documents the layout)
+    using BlobVoxel = fls_ivox_blob_voxel;
     // Pre: not a Replica.  A Device map passes through the mirror and goes back to the device.
     size_t export_blob(void* blob, size_t cap) {
         const bool was_device = on_device();
@@ -462,7 +486,7 @@ struct IvoxMap {
             char* w = static_cast<char*>(blob);
             BlobHeader hd{};
             std::memcpy(hd.magic, "FLSIVOX1", 8);
-            hd.version = 1; hd.kind = kind; hd.resolution = ivox.resolution; hd.is_first = is_first ? 1u : 0u;
+            hd.version = FLS_IVOX_BLOB_VERSION; hd.kind = kind; hd.resolution = ivox.resolution; hd.is_first = is_first ? 1u : 0u;
             hd.capacity = ivox.capacity; hd.n_voxels = ivox.n_alive; hd.n_points = ivox.n_points; hd.next_id = ivox.next_id;
             std::memcpy(w, &hd, sizeof(hd));
             BlobVoxel* bv = reinterpret_cast<BlobVoxel*>(w + sizeof(hd));
@@ -480,18 +504,10 @@ struct IvoxMap {
     }
     // Any state -> an ordinary map holding the blob's voxels (refreshed: MirrorCurrent or Device).  An invalid blob leaves the map as it was.
     fls_status import_blob(const void* blob, size_t n) {
-        if (n < sizeof(BlobHeader)) return FLS_ERR_INVALID;
         const char* r = static_cast<const char*>(blob);
         BlobHeader hd;
-        std::memcpy(&hd, r, sizeof(hd));
-        if (std::memcmp(hd.magic, "FLSIVOX1", 8) != 0 || hd.version != 1 || hd.kind != kind) return FLS_ERR_INVALID;
-        // the header is untrusted (it may come off a broadcast): bound both counts by the payload BEFORE multiplying (no u64 wrap),
-        // the resolution must be this map's, every voxel non-empty and unique, the counts must add up in 64 bits
-        static_assert(sizeof(BlobVoxel) == 16 && sizeof(Pt4) == 16, "blob records");
-        const unsigned long long payload = (unsigned long long)(n - sizeof(BlobHeader)) / 16ull;
-        if ((n - sizeof(BlobHeader)) % 16u != 0 || hd.n_voxels > payload || hd.n_points > payload || hd.n_voxels + hd.n_points != payload) return FLS_ERR_INVALID;
-        if (!(hd.resolution > 0.f) || !std::isfinite(hd.resolution) || hd.resolution != ivox.resolution) return FLS_ERR_INVALID;
-        if (hd.n_voxels > hd.n_points || hd.next_id < 0 || (unsigned long long)hd.next_id < hd.n_points) return FLS_ERR_INVALID;
+        // the header is untrusted (ivox_blob_check_header), and so are the records: every voxel non-empty and unique, the counts must add up in 64 bits
+        if (ivox_blob_check_header(blob, n, kind, ivox.resolution, hd) != FLS_OK) return FLS_ERR_INVALID;
         const BlobVoxel* bv = reinterpret_cast<const BlobVoxel*>(r + sizeof(hd));
         const Pt4* bp = reinterpret_cast<const Pt4*>(r + sizeof(hd) + hd.n_voxels * sizeof(BlobVoxel));
         std::vector<HostIvox::ImageVoxel> vox(size_t(hd.n_voxels));
@@ -512,6 +528,173 @@ struct IvoxMap {
         load_mirror(vox, bp, size_t(hd.n_points), int(hd.next_id));  // (the resolution is the blob's: checked equal above)
         is_first = hd.is_first != 0;
         refresh();
+        return FLS_OK;
+    }
+
+    // ---- the same blob at device speed (include/fls_map_ivox.h; kernels_ivox_blob.hpp): packed from the image and built into it without the mirror.
+    // `dst` / `src`: memory of this map's device (on_device) or host memory.  The kernels work in d_blob, where the blob starts 8 bytes behind a
+    // 16-byte boundary so that its records (behind the 56-byte header) are 16-byte aligned; one copy moves it to or from the caller's memory.
+    static constexpr size_t kBlobSortMax = size_t(kVgMaxBlocks) * kVgTile;  // records the radix sort takes
+    size_t blob_bytes() const {  // (from the counts the host holds: no mirror, no download)
+        return sizeof(BlobHeader) + ((image_is_map() ? dev_n_alive : ivox.n_alive) + (image_is_map() ? dev_n_points : ivox.n_points)) * 16;
+    }
+    char* blob_staging(const size_t n_bytes) {
+        d_blob.reserve(n_bytes / 16 + 2);
+        return reinterpret_cast<char*>(d_blob.p) + 8;
+    }
+    // Pre: not a Replica; a queued update chain settled (Match returns with it collected).  A Device / ImageOnly map stays in its state.
+    fls_status export_blob_to(void* dst, const size_t cap, const bool dst_on_device) {
+        if (!dst) return FLS_ERR_INVALID;
+        if (image_is_map() && allow_device_image && dev_n_alive <= kBlobSortMax) return export_blob_device(dst, cap, dst_on_device);
+        const size_t need = blob_bytes();
+        if (cap < need) return FLS_ERR_RANGE;
+        if (!dst_on_device) {
+            if (export_blob(dst, cap) != need) return FLS_ERR_STATE;
+        } else {
+            std::vector<char> host(need);
+            if (export_blob(host.data(), need) != need) return FLS_ERR_STATE;
+            FLS_HIP(hipMemcpy(dst, host.data(), need, hipMemcpyHostToDevice));
+        }
+        ++n_blob_exports_host;
+        return FLS_OK;
+    }
+    fls_status export_blob_device(void* dst, const size_t cap, const bool dst_on_device) {
+        FLS_HIP(hipStreamSynchronize(stream));
+        IvoxUpdState st{};
+        FLS_HIP(hipMemcpyAsync(&st, d_upd_state.p, sizeof(st), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        const size_t V = st.n_alive, P = size_t(st.n_points), need = sizeof(BlobHeader) + (V + P) * 16;
+        if (V != dev_n_alive || P != dev_n_points) throw std::runtime_error("iVox image: the device state does not match the counts the host holds");
+        if (cap < need) return FLS_ERR_RANGE;
+        char* const base = blob_staging(need);
+        BlobHeader hd{};
+        std::memcpy(hd.magic, FLS_IVOX_BLOB_MAGIC, 8);
+        hd.version = FLS_IVOX_BLOB_VERSION; hd.kind = kind; hd.resolution = ivox.resolution; hd.is_first = is_first ? 1u : 0u;
+        hd.capacity = ivox.capacity; hd.n_voxels = V; hd.n_points = P; hd.next_id = st.next_id;
+        FLS_HIP(hipMemcpyAsync(base, &hd, sizeof(hd), hipMemcpyHostToDevice, stream));
+        if (V) {
+            const unsigned n = unsigned(V), nblk = (n + kIvbBlock - 1) / kIvbBlock;
+            const size_t nb = std::min<size_t>(st.n_bricks, image.n_bricks_cap), ncell = nb * kBrickStride;
+            const dim3 g{nblk, 1u, 1u}, t{unsigned(kIvbBlock), 1u, 1u};
+            image.d_alive_rec.reserve(V);
+            d_blob_rep.reserve(1); bl_lsrc.reserve(V); bl_bt.reserve(size_t(2) * nblk + 1);
+            FLS_HIP(hipMemsetAsync(d_blob_rep.p, 0, sizeof(IvblReport), stream));
+            FLS_HIP(hipMemsetAsync(image.d_alive_rec.p, 0, V * sizeof(IvoxAliveRec), stream));  // (a record the listing does not fill packs nothing: the totals below catch it)
+            if (ncell)
+                hipLaunchKernelGGL(ivox_list_alive_kernel, dim3(unsigned((ncell + 255) / 256)), dim3(256), 0, stream, (const uint2*)image.d_cells.p,
+                                   (const unsigned long long*)image.d_brick_key.p, unsigned(ncell), (const unsigned char*)image.d_cap_log2.p,
+                                   (const unsigned long long*)image.d_stamp.p, image.d_alive_rec.p, &d_blob_rep.p->n_listed, n);
+            // oldest first: the 64-bit stamps in two stable rounds, low word first (as the eviction selection sorts them); every stamp <= stamp_base
+            const IvoxAliveRec* const rec = image.d_alive_rec.p;
+            bb_sort.prepare(V);
+            hipLaunchKernelGGL(ivbx_stamp_keys, g, t, 0, stream, rec, n, bb_sort.k0, bb_sort.v0);
+            bb_sort.run(DevicePairSort::passes_for(std::min<unsigned long long>(st.stamp_base, 0xffffffffull)), stream);
+            if (st.stamp_base >> 32) {
+                hipLaunchKernelGGL(ivbx_stamp_hi, g, t, 0, stream, rec, (const unsigned*)bb_sort.v0, n, bb_sort.k0);
+                bb_sort.run(DevicePairSort::passes_for(st.stamp_base >> 32), stream);
+            }
+            const unsigned* const order = bb_sort.v0;
+            hipLaunchKernelGGL(ivbx_counts, g, t, 0, stream, rec, order, n, bl_lsrc.p, bl_bt.p, d_blob_rep.p);
+            hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)bl_bt.p, bl_bt.p + nblk, int(nblk), (unsigned*)nullptr);
+            hipLaunchKernelGGL(ivbx_pack, dim3(unsigned((V * kIvblLanes + kIvbBlock - 1) / kIvbBlock)), t, 0, stream, rec, order, n, (const unsigned*)bl_lsrc.p,
+                               (const unsigned*)(bl_bt.p + nblk), (const float4*)image.d_pts.p, (unsigned long long)image.d_pts.cap,
+                               reinterpret_cast<ulonglong2*>(base + sizeof(BlobHeader)), reinterpret_cast<float4*>(base + sizeof(BlobHeader) + V * 16), (unsigned long long)P);
+            FLS_HIP(hipGetLastError());
+            IvblReport rep{};
+            FLS_HIP(hipMemcpyAsync(&rep, d_blob_rep.p, sizeof(rep), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            if (rep.n_listed != n || rep.count_sum != P) throw std::runtime_error("iVox image: the alive-voxel or point count of the device state does not match its cells");
+        }
+        FLS_HIP(hipMemcpyAsync(dst, base, need, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        ++n_blob_exports_device;
+        return FLS_OK;
+    }
+    // Any state -> an ordinary map holding the blob's voxels: Device / ImageOnly without a mirror where the device builds it, else what import_blob
+    // leaves.  An invalid blob leaves the map as it was.
+    fls_status import_blob_from(const void* src, const size_t n, const bool src_on_device) {
+        if (!src || n < sizeof(BlobHeader)) return FLS_ERR_INVALID;
+        unsigned char head[sizeof(BlobHeader)];
+        FLS_HIP(hipMemcpy(head, src, sizeof(head), src_on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+        BlobHeader hd;
+        const fls_status hrc = ivox_blob_check_header(head, n, kind, ivox.resolution, hd);
+        if (hrc != FLS_OK) return hrc;
+        BlobDecline why = BlobDecline::None;
+        if (!allow_device_image) why = BlobDecline::SwitchedOff;
+        else if (!use_dense) why = BlobDecline::NotDense;
+        else if (hd.n_voxels == 0 || hd.n_voxels >= ivox.capacity || hd.n_voxels > kBlobSortMax || hd.n_points > kBlobSortMax) why = BlobDecline::Size;
+        if (why == BlobDecline::None) {
+            const fls_status rc = import_blob_device(src, n, src_on_device, hd, why);
+            if (why == BlobDecline::None) return rc;
+        }
+        ++n_blob_imports_declined;
+        ++n_blob_decline_reason[int(why)];
+        if (!src_on_device) return import_blob(src, n);
+        std::vector<char> host(n);
+        FLS_HIP(hipMemcpy(host.data(), src, n, hipMemcpyDeviceToHost));
+        return import_blob(host.data(), n);
+    }
+    // The closed form of "a blob into an EMPTY map"  on the device.  `why` set: declined, the host path answers (the map is as it
+    // was, or empty where the brick pool went over its budget -- import_blob starts from an empty map anyway).
+    fls_status import_blob_device(const void* src, const size_t n, const bool src_on_device, const BlobHeader& hd, BlobDecline& why) {
+        const size_t V = size_t(hd.n_voxels), P = size_t(hd.n_points);
+        const unsigned nv = unsigned(V), nblk = (nv + kIvbBlock - 1) / kIvbBlock;
+        const dim3 g{nblk, 1u, 1u}, t{unsigned(kIvbBlock), 1u, 1u};
+        FLS_HIP(hipStreamSynchronize(stream));  // (the staging buffer and the scratch are free)
+        char* const base = blob_staging(n);
+        FLS_HIP(hipMemcpyAsync(base, src, n, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+        const ulonglong2* const vox = reinterpret_cast<const ulonglong2*>(base + sizeof(BlobHeader));
+        const float4* const rows = reinterpret_cast<const float4*>(base + sizeof(BlobHeader) + V * 16);
+        // ---- checks: nothing of the map changes before they have all passed ----
+        d_blob_rep.reserve(1); bl_lsrc.reserve(V); bl_bt.reserve(size_t(2) * nblk + 1);
+        IvblReport rep{};
+        for (int a = 0; a < 3; ++a) { rep.bmin[a] = INT_MAX; rep.bmax[a] = INT_MIN; }
+        FLS_HIP(hipMemcpyAsync(d_blob_rep.p, &rep, sizeof(rep), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(ivbl_check, g, t, 0, stream, vox, nv, (unsigned long long)P, bl_lsrc.p, bl_bt.p, d_blob_rep.p);
+        hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)bl_bt.p, bl_bt.p + nblk, int(nblk), (unsigned*)nullptr);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipMemcpyAsync(&rep, d_blob_rep.p, sizeof(rep), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        if ((rep.flag & (kIvblZeroCount | kIvblBadCount)) || rep.count_sum != P) return FLS_ERR_INVALID;
+        if (rep.flag & kIvblBadKey) { why = BlobDecline::Range; return FLS_OK; }
+        const IvoxBrickExtent ext = ivox_brick_extent(rep.bmin, rep.bmax);
+        const IvbExtent e{{ext.bmin[0], ext.bmin[1], ext.bmin[2]}, ext.bits[0], ext.bits[1]};
+        const int key_bits = ext.key_bits();
+        const bool wide = key_bits > 32;
+        bb_sort.prepare(V);
+        if (wide) bb_khi.reserve(V);
+        bb_lcap.reserve(V); bb_vbegin.reserve(V); bb_btc.reserve(size_t(2) * nblk + 1);
+        unsigned* const btcs = bb_btc.p + nblk;  // scanned capacities
+        hipLaunchKernelGGL(ivbl_keys, g, t, 0, stream, vox, nv, e, bb_sort.k0, wide ? bb_khi.p : (unsigned*)nullptr, bb_sort.v0);
+        bb_sort.run((std::min(key_bits, 32) + 7) / 8, stream);
+        if (wide) {  // two stable rounds, low word first
+            hipLaunchKernelGGL(ivb_gather_hi, g, t, 0, stream, (const unsigned*)bb_khi.p, (const unsigned*)bb_sort.v0, int(nv), bb_sort.k0);
+            bb_sort.run((key_bits - 32 + 7) / 8, stream);
+        }
+        const unsigned* const order = bb_sort.v0;
+        hipLaunchKernelGGL(ivbl_layout, g, t, 0, stream, vox, order, nv, bb_lcap.p, bb_btc.p, d_blob_rep.p);
+        hipLaunchKernelGGL(vg_scan, dim3(1), dim3(kVgScanBlock), 0, stream, (const unsigned*)bb_btc.p, btcs, int(nblk), &d_blob_rep.p->used);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipMemcpyAsync(&rep, d_blob_rep.p, sizeof(rep), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        if (rep.flag & kIvblDuplicate) return FLS_ERR_INVALID;
+        // ---- the build: bulk_build's pool and cells, the voxels and their stamps (blob position + 1) given ----
+        const size_t used = rep.used;
+        become_empty();
+        BuiltPool pool;
+        if (!build_brick_pool(rep.own_bricks, used, P, V, int(hd.next_id), /*stamp_base=*/V, pool, [&](const IvoxUpdArrays& a) {
+                hipLaunchKernelGGL(ivbl_cells, g, t, 0, stream, vox, order, nv, (const unsigned*)bb_lcap.p, (const unsigned*)btcs, a, d_upd_state.p, bb_vbegin.p);
+            })) {
+            why = BlobDecline::Budget;
+            return FLS_OK;
+        }
+        hipLaunchKernelGGL(ivbl_points, dim3(unsigned((V * kIvblLanes + kIvbBlock - 1) / kIvbBlock)), t, 0, stream, vox, rows, nv, (unsigned long long)P,
+                           (const unsigned*)bl_lsrc.p, (const unsigned*)(bl_bt.p + nblk), (const unsigned*)bb_vbegin.p, image.d_pts.p, (unsigned long long)image.d_pts.cap);
+        FLS_HIP(hipGetLastError());
+        FLS_HIP(hipStreamSynchronize(stream));
+        adopt_built_image(pool, used, P, V, /*stamp_base=*/V);
+        is_first = hd.is_first != 0;
+        ++n_blob_imports_device;
         return FLS_OK;
     }
 
@@ -576,7 +759,7 @@ struct IvoxMap {
     size_t counter(int slot) const {
         switch (slot) {
             case 100: return n_incremental;          // image updates applied as scatter lists
-            case 101: return n_full_rebuilds + n_bulk_builds;  // full builds of the image: re-flatten + upload from the mirror, or built on the device (slot 140 says how many of them)
+            case 101: return n_full_rebuilds + n_bulk_builds + n_blob_imports_device;  // full builds of the image: re-flatten + upload from the mirror, or built on the device (slots 140 and 170 say how many of them)
             case 102: return image_is_map() ? dev_n_alive : ivox.n_alive;  // occupied voxels (of a bulk-built map: without building the mirror)
             case 103: return n_device_updates;       // ... by the device-side AddPoints
             case 104: return n_host_fallbacks;       // batches the device refused (replayed on the host)
@@ -598,6 +781,14 @@ struct IvoxMap {
             case 145: return n_bulk_decline_reason[int(BuildDecline::Budget)];    // a brick pool over its byte budget /
             case 146: return n_bulk_decline_reason[int(BuildDecline::NotDense)];  // the hash-table form (FLS_IVOX_DENSE=0, or the budget exceeded earlier)
             case 147: return n_lazy_mirrors;         // mirrors reconstructed from a bulk-built image (to_mirror)
+            case 168: return n_blob_exports_device;  // include/fls_map_ivox.h: blobs packed on the device / written by the host writer
+            case 169: return n_blob_exports_host;
+            case 170: return n_blob_imports_device;  // blobs built into the image on the device / declined to import_blob (FLS_IVOX_DEVICE_IMAGE=0 counts here and in no reason slot)
+            case 171: return n_blob_imports_declined;
+            case 172: return n_blob_decline_reason[int(BlobDecline::Size)];      // declines by reason: empty, n_voxels >= capacity, more than the sort takes /
+            case 173: return n_blob_decline_reason[int(BlobDecline::Range)];     // a key outside the key range or with reserved bits /
+            case 174: return n_blob_decline_reason[int(BlobDecline::Budget)];    // a brick pool over its byte budget /
+            case 175: return n_blob_decline_reason[int(BlobDecline::NotDense)];  // the hash-table form
             default: return image_is_map() ? dev_n_points : ivox.n_points;
         }
     }

@@ -10,7 +10,7 @@
 //   ivb_voxels   <n>   voxel index per sorted position, first position per voxel
 //   ivb_caps     <n>   per voxel: count, region capacity, block-local prefix + block totals        -> vg_scan over the totals
 //   ivb_report   <1>   {flag, V, used, own bricks} to the host-mapped mailbox: the one host wait (declines, point array and brick pool sizes)
-//   ivb_cells    <n>   per voxel: its bricks found or created (brick_find_or_create), cell record + halo mirrors, capacity, stamp
+//   ivb_cells    <n>   per voxel: its bricks found or created (brick_find_or_create), cell record + halo mirrors, capacity, stamp (ivb_cell_write)
 //   ivb_points   <n>   points into their regions, slack filled
 // The per-position launches are sized by n (the host does not know V before the mailbox); threads beyond V leave at once.
 #pragma once
@@ -110,19 +110,13 @@ __global__ void ivb_report(const unsigned* __restrict__ flag, const unsigned* __
     __hip_atomic_store(&mb->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// voxel v: its own brick and the neighbours whose halo mirrors it exist from here on (created empty if need be: the pool is pre-zeroed);
-// its cell record {begin, count} in the primary cell and the mirrors; region capacity; LRU stamp = index of its last member + 1.  A full
-// pool or directory raises kUpdArrayFull in the state (the host grows the pool and runs the launch again).
-__global__ void __launch_bounds__(kIvbBlock)
-ivb_cells(const unsigned long long* __restrict__ vkey, const unsigned* __restrict__ order, const unsigned* __restrict__ first, const unsigned n_voxels,
-          const unsigned* __restrict__ lcap, const unsigned* __restrict__ btcs /* scanned */, const IvoxUpdArrays a, IvoxUpdState* __restrict__ st,
-          unsigned* __restrict__ vbegin) {
-    const unsigned v = blockIdx.x * kIvbBlock + threadIdx.x;
-    if (v >= n_voxels) return;
-    const unsigned f = first[v], cnt = first[v + 1u] - f, begin = btcs[blockIdx.x] + lcap[v];
-    vbegin[v] = begin;
+// one voxel: its own brick and the neighbours whose halo mirrors it exist from here on (created empty if need be: the pool is pre-zeroed);
+// its cell record {begin, count} in the primary cell and the mirrors; region capacity; LRU stamp.  A full pool or directory raises
+// kUpdArrayFull in the state (the host grows the pool and runs the launch again).
+__device__ __forceinline__ void ivb_cell_write(const IvoxUpdArrays& a, IvoxUpdState* __restrict__ st, const unsigned long long key, const unsigned begin,
+                                               const unsigned cnt, const unsigned long long stamp) {
     int kx, ky, kz;
-    unpack_key(vkey[order[f]], kx, ky, kz);
+    unpack_key(key, kx, ky, kz);
     const int bx = kx >> kBrickLog, by = ky >> kBrickLog, bz = kz >> kBrickLog;
     const int lx = kx & (kBrickSide - 1), ly = ky & (kBrickSide - 1), lz = kz & (kBrickSide - 1);
     const unsigned bi = brick_find_or_create(a, st, bx, by, bz);
@@ -139,7 +133,19 @@ ivb_cells(const unsigned long long* __restrict__ vkey, const unsigned* __restric
     a.cells[cell] = rec;
     brick_write_mirrors(a, cell, rec);
     a.cap_log2[cell] = (unsigned char)upd_log2(upd_cap_for(cnt));
-    a.stamp[cell] = (unsigned long long)order[f + cnt - 1u] + 1ull;  // (stable sort: the last member of the segment is the last inserted)
+    a.stamp[cell] = stamp;
+}
+// voxel v of the sorted cloud: LRU stamp = index of its last member + 1 (the voxels of a blob bring their own counts and stamps:
+// kernels_ivox_blob.hpp's ivbl_cells)
+__global__ void __launch_bounds__(kIvbBlock)
+ivb_cells(const unsigned long long* __restrict__ vkey, const unsigned* __restrict__ order, const unsigned* __restrict__ first, const unsigned n_voxels,
+          const unsigned* __restrict__ lcap, const unsigned* __restrict__ btcs /* scanned */, const IvoxUpdArrays a, IvoxUpdState* __restrict__ st,
+          unsigned* __restrict__ vbegin) {
+    const unsigned v = blockIdx.x * kIvbBlock + threadIdx.x;
+    if (v >= n_voxels) return;
+    const unsigned f = first[v], cnt = first[v + 1u] - f, begin = btcs[blockIdx.x] + lcap[v];
+    vbegin[v] = begin;
+    ivb_cell_write(a, st, vkey[order[f]], begin, cnt, (unsigned long long)order[f + cnt - 1u] + 1ull);  // (stable sort: the last member of the segment is the last inserted)
 }
 
 // sorted position j -> its slot; the first member of a voxel also fills the region's slack

@@ -91,6 +91,10 @@ struct fls_matcher {
     virtual size_t map_image_bytes() { return 0; }
     virtual fls_status map_image_export(void*, size_t, int /*buffer on this handle's device*/) { return FLS_ERR_STATE; }
     virtual fls_status map_image_import(const void*, size_t, int) { return FLS_ERR_STATE; }
+    // the iVox blob at device speed (include/fls_map_ivox.h): 0 / FLS_ERR_STATE: not an iVox handle
+    virtual size_t ivox_blob_bytes() { return 0; }
+    virtual fls_status ivox_blob_export(void*, size_t, int /*buffer on this handle's device*/) { return FLS_ERR_STATE; }
+    virtual fls_status ivox_blob_import(const void*, size_t, int) { return FLS_ERR_STATE; }
     // fls_replicas_*: this handle becomes a READ-ONLY copy of `owner`'s device map image (device to device, no host mirror): it serves
     // fls_match_batch (and fls_match with update_map == 0) and nothing else until fls_map_import makes it an ordinary handle again (fls_add_cloud_to_local_map is refused: FLS_ERR_STATE)
     virtual bool can_replicate() const { return false; }

@@ -584,6 +584,15 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     size_t map_export(void* blob, size_t cap) override { return borrowed || map.is_replica() ? 0 : map.export_blob(blob, cap); }
     fls_status map_replaced(const fls_status rc) { if (rc == FLS_OK) reset_match_state(); return rc; }
     fls_status map_import(const void* blob, size_t n) override { return borrowed ? FLS_ERR_INVALID : map_replaced(map.import_blob(blob, n)); }
+    // the same blob packed from / built into the device image (include/fls_map_ivox.h): a Match returns with its update chain collected, so
+    // the image is settled; the map's own calls wait for the stream
+    size_t ivox_blob_bytes() override { return borrowed || map.is_replica() ? 0 : map.blob_bytes(); }
+    fls_status ivox_blob_export(void* dst, size_t cap, int on_device) override {
+        return borrowed || map.is_replica() ? FLS_ERR_STATE : map.export_blob_to(dst, cap, on_device != 0);
+    }
+    fls_status ivox_blob_import(const void* src, size_t n, int on_device) override {
+        return borrowed ? FLS_ERR_INVALID : map_replaced(map.import_blob_from(src, n, on_device != 0));
+    }
     bool can_replicate() const override { return !borrowed; }
     fls_status replicate_from(fls_matcher& o) override {
         if (borrowed || o.kind != kind) return FLS_ERR_INVALID;

@@ -299,6 +299,25 @@ class RegistrationInterface:
         if rc != _lib.FLS_OK:
             raise FlsError(rc, "fls_map_image_import")
 
+    def MapBlobBytes(self) -> int:
+        """fls_ivox_map_bytes (include/fls_map_ivox.h): size of ExportMap's blob of an iVox handle now, from counts the host holds (0: another
+        kind, a read-only replica)."""
+        return int(_lib.lib().fls_ivox_map_bytes(self._h))
+
+    def ExportMapBlob(self, ptr: int, nbytes: int, on_device: bool) -> None:
+        """fls_ivox_map_export into caller memory (`ptr`: device memory of this handle's device, or host memory): the bytes of ExportMap,
+        packed on the device where the device image is the map -- no host mirror is built, the handle stays in its state."""
+        rc = _lib.lib().fls_ivox_map_export(self._h, C.c_void_p(ptr), nbytes, 1 if on_device else 0)
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_ivox_map_export")
+
+    def ImportMapBlob(self, ptr: int, nbytes: int, on_device: bool) -> None:
+        """fls_ivox_map_import: what ImportMap does with the same blob, from host or device memory, the map built on the device (an ordinary
+        handle that goes on mapping, not a replica).  A refused blob (FLS_ERR_INVALID) leaves the handle as it was."""
+        rc = _lib.lib().fls_ivox_map_import(self._h, C.c_void_p(ptr), nbytes, 1 if on_device else 0)
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_ivox_map_import")
+
     def map_size(self, slot: int = 0) -> int:
         return int(_lib.lib().fls_map_size(self._h, slot))
 

@@ -284,6 +284,8 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
  * 143 = as many voxels as the LRU capacity (the insert evicts), 144 = a point outside the key range or not finite (the call returns
  * FLS_ERR_RANGE), 145 = brick pool over its byte budget, 146 = hash-table form (FLS_IVOX_DENSE=0); 147 = host mirrors reconstructed from a
  * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).
+ * iVox, the blob packed and built on the device (fls_map_ivox.h documents the slots): 168 / 169 = exports packed on the device / written by
+ * the host, 170 / 171 = imports built on the device / declined to fls_map_import's path, 172-175 = declines by reason.
  * The kd-tree kinds, flat images (fls_map_kd.h; KdMapImage in csrc/matchers_kd.hpp): 160 = exports packed on the device, 161 = exports
  * written by the host from the deque, 162 = imports unpacked on the device, 163 = imports through the host deque alone.
  * The kd-tree kinds, keyframes (KdLocalMap in csrc/device_voxelgrid.hpp; LoamFull: both deques together, so two clouds per keyframe in
