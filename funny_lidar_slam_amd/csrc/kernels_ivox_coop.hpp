@@ -501,23 +501,41 @@ p2plane_fit_solve_body(FLS_P2P_FIT_SMEM_PARAMS, const N nrows, const float* __re
     const int ii = i < n ? i : 0;
     const int cb = nn_cnt[ii];
     const int cnt = cb & 7;
+    const float px = sx[ii], py = sy[ii], pz = sz[ii];
+    const unsigned char stale = FIRST ? (unsigned char)0 : flag[ii];  // the first kNN launch of a Match cleared the flags
     float4 nn[5];
+    // A neighbour's load stays where it is written, beside its address: left alone, the compiler merges the loads of the forms below into one load
+    // of a merged address and moves it into the fit's block, away from the address arithmetic, where the three words of a point then take three
+    // 64-bit addresses of their own (13 loads and 12 additions for 5 loads).  An empty statement that reads and writes the fetched words holds it.
+    // (after the five loads of a form, so that they are in flight together; a point as the four registers its load fills, so that no word is moved)
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    auto hold = [&]() {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            f32x4 v = {nn[j].x, nn[j].y, nn[j].z, nn[j].w};
+            asm volatile("" : "+v"(v));
+            nn[j] = make_float4(v.x, v.y, v.z, v.w);
+        }
+    };
     if (nn_ids) {  // uniform: lists in ids form unless a point's count byte says rows (bit 7)
         const uint4 i4 = *reinterpret_cast<const uint4*>(nn_ids + (size_t)ii * 8);
         const unsigned i5 = nn_ids[(size_t)ii * 8 + 4];
         const unsigned sl[5] = {i4.x, i4.y, i4.z, i4.w, i5};
         const bool rows_form = (cb & 0x80) != 0;
+        if (__ballot(rows_form) == 0ull) {  // the wave's lists are all ids (every wave of a Match that moves no map slot): no per-lane choice of address
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float4* src = rows_form ? nn_pts + (size_t)ii * 5 + j : map_pts + (sl[j] < n_slots ? sl[j] : 0u);
-            nn[j] = *src;
+            for (int j = 0; j < 5; ++j) nn[j] = map_pts[sl[j] < n_slots ? sl[j] : 0u];
+            hold();
+        } else {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) nn[j] = *(rows_form ? nn_pts + (size_t)ii * 5 + j : map_pts + (sl[j] < n_slots ? sl[j] : 0u));
+            hold();
         }
     } else {
 #pragma unroll
         for (int j = 0; j < 5; ++j) nn[j] = nn_pts[(size_t)ii * 5 + j];
+        hold();
     }
-    const float px = sx[ii], py = sy[ii], pz = sz[ii];
-    const unsigned char stale = FIRST ? (unsigned char)0 : flag[ii];  // the first kNN launch of a Match cleared the flags
     if (done) return;
 #ifdef FLS_TIMING
     const long long t_begin = (long long)__builtin_readcyclecounter();
@@ -531,19 +549,23 @@ p2plane_fit_solve_body(FLS_P2P_FIT_SMEM_PARAMS, const N nrows, const float* __re
         Jst[(size_t)6 * n + i] = res;
         flag[i] = 1;
     };
-    if (i < n) {
+    {
+        // One straight path through the fit for the whole wave: a lane past the scan's end or with a short list computes on what its clamped loads
+        // brought and its result is dropped (nothing below traps, and no lane's arithmetic depends on another's); only a wave with no point to fit at all
+        // -- the waves past the end of the last workgroup -- skips it.
+        const bool want = i < n && cnt == 5;
         bool valid_now = false;
-        if (cnt == 5) {
+        if (__ballot(want) != 0ull) {
             const double x = px, y = py, z = pz;
             const float ptx = (float)(((T44[0] * x + T44[4] * y) + T44[8] * z) + T44[12]);
             const float pty = (float)(((T44[1] * x + T44[5] * y) + T44[9] * z) + T44[13]);
             const float ptz = (float)(((T44[2] * x + T44[6] * y) + T44[10] * z) + T44[14]);
-            valid_now = plane_residual_dev(nn, px, py, pz, ptx, pty, ptz, T44, plane_thres, J, res);
+            valid_now = plane_residual_dev(nn, px, py, pz, ptx, pty, ptz, T44, plane_thres, J, res) && want;
         }
         if (valid_now) {
             fresh = true;
             contrib = true;
-        } else if (stale) {  // Q1: stale contribution of an earlier iteration
+        } else if (i < n && stale) {  // Q1: stale contribution of an earlier iteration
 #pragma unroll
             for (int a = 0; a < 6; ++a) J[a] = Jst[(size_t)a * n + i];
             res = Jst[(size_t)6 * n + i];

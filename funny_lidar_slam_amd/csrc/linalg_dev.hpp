@@ -28,6 +28,9 @@ namespace fls {
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void swap_d(double& a, double& b) { const double t = a; a = b; b = t; }
 __device__ __forceinline__ void swap_i(int& a, int& b) { const int t = a; a = b; b = t; }
+// exchange where `ex`, as two selects
+__device__ __forceinline__ void cswap_d(const bool ex, double& a, double& b) { const double ta = a, tb = b; a = ex ? tb : ta; b = ex ? ta : tb; }
+__device__ __forceinline__ void cswap_i(const bool ex, int& a, int& b) { const int ta = a, tb = b; a = ex ? tb : ta; b = ex ? ta : tb; }
 
 __device__ __forceinline__ void plane_fit_5x3(const double (&A)[3][5], double (&x)[3]) {
     double q[3][5];
@@ -59,15 +62,17 @@ __device__ __forceinline__ void plane_fit_5x3(const double (&A)[3][5], double (&
         for (int j = k + 1; j < 3; ++j)
             if (nu[j] > bv) { bv = nu[j]; big = j; }
         if (nzp == 3 && bv * bv < threshold_helper * double(5 - k)) nzp = k;
+        // the exchange as selects, not as a guarded block of 22-30 moves: no branch, no exec-mask arithmetic, and the perm[] words become predicates
+        // (a wave whose lanes all keep their pivot column no longer skips the work: DESIGN.md section 4 has the executed counts)
 #pragma unroll
-        for (int j = k + 1; j < 3; ++j)
-            if (big == j) {
+        for (int j = k + 1; j < 3; ++j) {
+            const bool ex = big == j;
 #pragma unroll
-                for (int r = 0; r < 5; ++r) swap_d(q[k][r], q[j][r]);
-                swap_d(nu[k], nu[j]);
-                swap_d(nd[k], nd[j]);
-                swap_i(perm[k], perm[j]);
-            }
+            for (int r = 0; r < 5; ++r) cswap_d(ex, q[k][r], q[j][r]);
+            cswap_d(ex, nu[k], nu[j]);
+            cswap_d(ex, nd[k], nd[j]);
+            cswap_i(ex, perm[k], perm[j]);
+        }
         // Householder on column k, rows k..4
         double tail = 0.0;
 #pragma unroll
@@ -89,10 +94,11 @@ __device__ __forceinline__ void plane_fit_5x3(const double (&A)[3][5], double (&
         }
         q[k][k] = beta;
         hc[k] = tau;
-        // apply to the trailing columns
+        // apply to the trailing columns: one guarded block for both of them (tau == 0 only where the tail vanished: a wave without such a lane runs
+        // it whole, a wave of such lanes skips it)
+        if (tau != 0.0) {
 #pragma unroll
-        for (int j = k + 1; j < 3; ++j) {
-            if (tau != 0.0) {
+            for (int j = k + 1; j < 3; ++j) {
                 double tmp = 0.0;
 #pragma unroll
                 for (int r = k + 1; r < 5; ++r) tmp += q[k][r] * q[j][r];
@@ -102,25 +108,24 @@ __device__ __forceinline__ void plane_fit_5x3(const double (&A)[3][5], double (&
                 for (int r = k + 1; r < 5; ++r) q[j][r] -= (tau * q[k][r]) * tmp;
             }
         }
-        // LAPACK-style column-norm down-dating
+        // LAPACK-style column-norm down-dating, one straight path: both sides of the reference's test end in a square root, so the argument is selected
+        // and the root taken once; a lane whose nu[j] is zero computes on and keeps what it had (a discarded IEEE result changes nothing)
 #pragma unroll
         for (int j = k + 1; j < 3; ++j) {
-            if (nu[j] != 0.0) {
-                double temp = fabs(q[j][k]) / nu[j];
-                temp = (1.0 + temp) * (1.0 - temp);
-                temp = temp < 0.0 ? 0.0 : temp;
-                const double rr = nu[j] / nd[j];
-                const double temp2 = temp * (rr * rr);
-                if (temp2 <= downdate_thr) {
-                    double s = 0.0;
+            const bool nz = nu[j] != 0.0;
+            double temp = fabs(q[j][k]) / nu[j];
+            temp = (1.0 + temp) * (1.0 - temp);
+            temp = temp < 0.0 ? 0.0 : temp;
+            const double rr = nu[j] / nd[j];
+            const double temp2 = temp * (rr * rr);
+            const bool renorm = temp2 <= downdate_thr;
+            double s = 0.0;
 #pragma unroll
-                    for (int r = k + 1; r < 5; ++r) s += q[j][r] * q[j][r];
-                    nd[j] = sqrt(s);
-                    nu[j] = nd[j];
-                } else {
-                    nu[j] *= sqrt(temp);
-                }
-            }
+            for (int r = k + 1; r < 5; ++r) s += q[j][r] * q[j][r];
+            const double root = sqrt(renorm ? s : temp);
+            const double scaled = nu[j] * root;
+            nd[j] = (nz && renorm) ? root : nd[j];
+            nu[j] = nz ? (renorm ? root : scaled) : nu[j];
         }
     }
     // c = Q^T b, b = -1
@@ -146,13 +151,10 @@ __device__ __forceinline__ void plane_fit_5x3(const double (&A)[3][5], double (&
             for (int r = 0; r < i; ++r) c[r] -= c[i] * q[i][r];
         }
     }
+    // x[perm[i]] = c[i] (zero past the rank); perm is a permutation, so the entry that is neither perm[0] nor perm[1] is perm[2]
+    const double xp[3] = {0 < nzp ? c[0] : 0.0, 1 < nzp ? c[1] : 0.0, 2 < nzp ? c[2] : 0.0};
 #pragma unroll
-    for (int j = 0; j < 3; ++j) x[j] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (perm[i] == j) x[j] = (i < nzp) ? c[i] : 0.0;
+    for (int j = 0; j < 3; ++j) x[j] = perm[0] == j ? xp[0] : (perm[1] == j ? xp[1] : xp[2]);
 }
 
 // ---------------------------------------------------------------------------------------------
