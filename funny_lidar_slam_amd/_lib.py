@@ -59,6 +59,10 @@ DEBUG_TICKET_WORDS = 320  # FLS_DEBUG_TICKET_WORDS
 # every symbol include/fls_debug_ndt.h declares (FLS_DEBUG_NDT_REVISION 1): test read-out of the NDT voxel map
 DEBUG_NDT_SYMBOLS = ["fls_debug_ndt_revision", "fls_debug_ndt_voxels"]
 
+# every symbol include/fls_debug_loop.h declares (FLS_DEBUG_LOOP_REVISION 1): test hooks of the stages of the loop-closure matcher
+DEBUG_LOOP_SYMBOLS = ["fls_debug_loop_revision", "fls_debug_loop_ndt", "fls_debug_loop_gicp_cov", "fls_debug_loop_gicp_corr", "fls_debug_loop_gicp_fdf",
+                      "fls_debug_loop_fitness"]
+
 # every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
 # fls_map_image_* and the replica sets of fls_reg.h
 NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
@@ -507,6 +511,20 @@ def lib():
             L.fls_debug_ndt_revision.argtypes = []
             L.fls_debug_ndt_voxels.restype = C.c_int
             L.fls_debug_ndt_voxels.argtypes = [hp, C.c_size_t, ip, ip, ip, bp, bp, dp, dp, dp, C.POINTER(C.c_size_t)]
+        if hasattr(L, "fls_debug_loop_revision"):  # (as fls_batch_ivox_revision above)
+            i64p = C.POINTER(C.c_int64)
+            L.fls_debug_loop_revision.restype = C.c_int
+            L.fls_debug_loop_revision.argtypes = []
+            L.fls_debug_loop_ndt.restype = C.c_int
+            L.fls_debug_loop_ndt.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_float, dp, C.c_int, dp, dp, dp, i64p, ip, ip]
+            L.fls_debug_loop_gicp_cov.restype = C.c_int
+            L.fls_debug_loop_gicp_cov.argtypes = [C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, dp]
+            L.fls_debug_loop_gicp_corr.restype = C.c_int
+            L.fls_debug_loop_gicp_corr.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, fp, dp, dp, dp, C.c_double, C.c_int, ip, dp]
+            L.fls_debug_loop_gicp_fdf.restype = C.c_int
+            L.fls_debug_loop_gicp_fdf.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, dp, ip, dp, C.c_int, dp]
+            L.fls_debug_loop_fitness.restype = C.c_int
+            L.fls_debug_loop_fitness.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, dp, i64p]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

@@ -146,6 +146,9 @@ float flo_loop_match(const float* src, size_t ns, const float* tgt, size_t nt, i
 /* pieces: NDT score / gradient / Hessian at pose vector p (x, y, z, rx, ry, rz) for the clouds AS GIVEN (leaf Gaussians at `resolution`) */
 int flo_ndt_derivatives(const float* src, size_t ns, const float* tgt, size_t nt, int stride_floats, float resolution, const double p[6], double* score,
                         double grad[6], double hess[36]);
+/* the same, and the number of (point, leaf) pairs that contributed to the sums (pairs may be NULL) */
+int flo_ndt_derivatives_pairs(const float* src, size_t ns, const float* tgt, size_t nt, int stride_floats, float resolution, const double p[6], double* score,
+                              double grad[6], double hess[36], int64_t* pairs);
 size_t flo_ndt_leaves(const float* tgt, size_t nt, int stride_floats, float resolution, int32_t* idx, int32_t* nr, double* mean3, double* icov9,
                       float* centroid3, size_t cap);
 void flo_gicp_covariances(const float* c, size_t n, int stride_floats, int k, double eps, double* out9);

@@ -283,6 +283,7 @@ struct Ndt {
     double j_ang[8][3], h_ang[15][3];
     M4f final_transformation = m4f_identity();
     NdtStats stats;
+    long long pairs = 0;  // (point, leaf) pairs that contributed to the last derivatives() call
 
     void set_target(const Cloud& target) { cells.build(target, resolution); }
 
@@ -325,6 +326,7 @@ struct Ndt {
         for (int i = 0; i < 6; ++i) grad[i] = 0.0;
         if (with_hessian) for (int i = 0; i < 36; ++i) hess[i] = 0.0;
         double score = 0.0;
+        pairs = 0;
         angle_derivatives(p, with_hessian);
         std::vector<int> nb;
         ++stats.evaluations;
@@ -382,6 +384,7 @@ struct Ndt {
                             hess[i + 6 * j] += e_x * ((-gauss_d2 * xcg[i] * xcg[j] + t2) + t3);
                         }
                 score += score_inc;
+                ++pairs;
             }
         }
         return score;

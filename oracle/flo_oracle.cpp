@@ -1204,6 +1204,10 @@ float flo_loop_match(const float* src, size_t ns, const float* tgt, size_t nt, i
 }
 int flo_ndt_derivatives(const float* src, size_t ns, const float* tgt, size_t nt, int stride, float resolution, const double p[6], double* score,
                         double grad[6], double hess[36]) {
+    return flo_ndt_derivatives_pairs(src, ns, tgt, nt, stride, resolution, p, score, grad, hess, nullptr);
+}
+int flo_ndt_derivatives_pairs(const float* src, size_t ns, const float* tgt, size_t nt, int stride, float resolution, const double p[6], double* score,
+                              double grad[6], double hess[36], int64_t* pairs) {
     loop::Ndt ndt;
     ndt.resolution = resolution;
     const Cloud s = make_cloud(src, ns, stride), t = make_cloud(tgt, nt, stride);
@@ -1214,6 +1218,7 @@ int flo_ndt_derivatives(const float* src, size_t ns, const float* tgt, size_t nt
     ndt.gauss_d1 = -std::log(c1 + c2) - d3;
     ndt.gauss_d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / ndt.gauss_d1);
     *score = ndt.derivatives(grad, hess, loop::pose_from_p(p), p, true);
+    if (pairs) *pairs = int64_t(ndt.pairs);
     return 0;
 }
 size_t flo_ndt_leaves(const float* tgt, size_t nt, int stride, float resolution, int32_t* idx, int32_t* nr, double* mean3, double* icov9, float* centroid3,

@@ -195,6 +195,7 @@ def lib():
         L.flo_loop_match.restype = C.c_float
         L.flo_loop_match.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.c_int, dp, C.POINTER(LoopStats)]
         L.flo_ndt_derivatives.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.c_int, C.c_float, dp, dp, dp, dp]
+        L.flo_ndt_derivatives_pairs.argtypes = L.flo_ndt_derivatives.argtypes + [C.POINTER(C.c_int64)]
         L.flo_ndt_leaves.restype = C.c_size_t
         L.flo_ndt_leaves.argtypes = [fp, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp, dp, fp, C.c_size_t]
         L.flo_gicp_covariances.restype = None
@@ -483,6 +484,19 @@ def ndt_derivatives(source, target, resolution, p):
     if rc != 0:
         raise RuntimeError("flo_ndt_derivatives: no leaf with >= 6 points")
     return score.value, g, H.reshape(6, 6, order="F")
+
+
+def ndt_derivatives_pairs(source, target, resolution, p):
+    """ndt_derivatives and the number of (point, leaf) pairs that contributed; a target without a leaf of 6 points gives zeros, not an error"""
+    a, pa, na, sa = _cloud(source)
+    b, pb, nb, sb = _cloud(target)
+    p = np.ascontiguousarray(p, np.float64)
+    score = C.c_double(); pairs = C.c_int64()
+    g = np.zeros(6); H = np.zeros(36)
+    rc = lib().flo_ndt_derivatives_pairs(pa, na, pb, nb, sa, resolution, _dp(p), C.byref(score), _dp(g), _dp(H), C.byref(pairs))
+    if rc != 0:
+        return 0.0, np.zeros(6), np.zeros((6, 6)), 0
+    return score.value, g, H.reshape(6, 6, order="F"), pairs.value
 
 
 def ndt_leaves(target, resolution):
