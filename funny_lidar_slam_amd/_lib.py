@@ -63,6 +63,9 @@ DEBUG_NDT_SYMBOLS = ["fls_debug_ndt_revision", "fls_debug_ndt_voxels"]
 DEBUG_LOOP_SYMBOLS = ["fls_debug_loop_revision", "fls_debug_loop_ndt", "fls_debug_loop_gicp_cov", "fls_debug_loop_gicp_corr", "fls_debug_loop_gicp_fdf",
                       "fls_debug_loop_fitness"]
 
+# every symbol include/fls_debug_knn.h declares (FLS_DEBUG_KNN_REVISION 1): test hooks of the cooperative grid k-NN kernels of the kd-tree kinds
+DEBUG_KNN_SYMBOLS = ["fls_debug_knn_revision", "fls_debug_grid_knn5", "fls_debug_grid_knn5_dual", "fls_debug_icp_knn1"]
+
 # every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
 # fls_map_image_* and the replica sets of fls_reg.h
 NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
@@ -525,6 +528,16 @@ def lib():
             L.fls_debug_loop_gicp_fdf.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, dp, ip, dp, C.c_int, dp]
             L.fls_debug_loop_fitness.restype = C.c_int
             L.fls_debug_loop_fitness.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, dp, i64p]
+        if hasattr(L, "fls_debug_knn_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_debug_knn_revision.restype = C.c_int
+            L.fls_debug_knn_revision.argtypes = []
+            L.fls_debug_grid_knn5.restype = C.c_int
+            L.fls_debug_grid_knn5.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, dp, C.c_int, fp, bp, fp, ip]
+            L.fls_debug_grid_knn5_dual.restype = C.c_int
+            L.fls_debug_grid_knn5_dual.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, C.c_int, fp, C.c_int, C.c_float, C.c_int,
+                                                   C.c_float, C.c_int, dp, C.c_int, fp, bp, fp, ip, fp, bp, fp, ip]
+            L.fls_debug_icp_knn1.restype = C.c_int
+            L.fls_debug_icp_knn1.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_double, dp, C.c_int, ip, bp, ip]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

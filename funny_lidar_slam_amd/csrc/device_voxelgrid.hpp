@@ -414,13 +414,13 @@ struct DeviceGridBuilder {
         FLS_HIP(hipStreamSynchronize(s));
         const VgHeader& hh = h_hdr.p[1];
         if (hh.n_bad != 0u || hh.mn[0] == 0xffffffffu) { ++declined; return false; }
-        const float inv = 1.0f / cell_size;
+        const double inv = 1.0 / double(cell_size);
         CgWindow w;
         w.inv_cell = inv;
         int mn[3], mx[3];
-        for (int a = 0; a < 3; ++a) {  // floorf(p * inv) is monotone in p: the extreme cells come from the extreme coordinates
-            const float lo = std::floor(vg_unord(hh.mn[a]) * inv), hi = std::floor(vg_unord(hh.mx[a]) * inv);
-            if (!(std::fabs(lo) < float(kKeyLimit) && std::fabs(hi) < float(kKeyLimit))) { ++declined; return false; }
+        for (int a = 0; a < 3; ++a) {  // floor(double(p) * inv), cg_keys' expression, is monotone in p: the extreme cells come from the extreme coordinates
+            const double lo = std::floor(double(vg_unord(hh.mn[a])) * inv), hi = std::floor(double(vg_unord(hh.mx[a])) * inv);
+            if (!(std::fabs(lo) < double(kKeyLimit) && std::fabs(hi) < double(kKeyLimit))) { ++declined; return false; }
             mn[a] = int(lo); mx[a] = int(hi);
         }
         size_t nc = 1;

@@ -489,10 +489,12 @@ inline std::vector<PtI> voxel_grid_strided(const float* p, size_t n, int stride,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Exact-kNN cell grid over a flat cloud: cell = floor(p * inv_cell), ids = index in the cloud.
+// Exact-kNN cell grid over a flat cloud: cell = floor(double(p) * inv_cell) with inv_cell = 1.0 / double(cell) -- the expression the search
+// kernels file their queries with (kernels_knn.hpp: the exactness argument needs ONE filing function) --, ids = index in the cloud.
 // ---------------------------------------------------------------------------------------------
 struct CellGridImage : GridImage {
-    float cell = 1.0f, inv_cell = 1.0f;
+    float cell = 1.0f;
+    double inv_cell = 1.0;
     int rings = 1;  // 2: the cell is half the gate radius, the search covers the 5x5x5 block in two stages
     size_t n_cells = 0;
     DevBuf<float4> d_by_id;  // optional: the cloud in its own order (see CellGridDev::by_id)
@@ -507,12 +509,12 @@ struct CellGridImage : GridImage {
             FLS_HIP(hipStreamSynchronize(s));
         }
         cell = cell_size;
-        inv_cell = 1.0f / cell_size;
+        inv_cell = 1.0 / double(cell_size);
         const size_t n = cloud.size();
         std::vector<std::pair<unsigned long long, unsigned>> kv(n);
         for (size_t i = 0; i < n; ++i) {
-            const float fx = std::floor(cloud[i].x * inv_cell), fy = std::floor(cloud[i].y * inv_cell), fz = std::floor(cloud[i].z * inv_cell);
-            if (!(std::fabs(fx) < float(kKeyLimit) && std::fabs(fy) < float(kKeyLimit) && std::fabs(fz) < float(kKeyLimit))) return FLS_ERR_RANGE;
+            const double fx = std::floor(double(cloud[i].x) * inv_cell), fy = std::floor(double(cloud[i].y) * inv_cell), fz = std::floor(double(cloud[i].z) * inv_cell);
+            if (!(std::fabs(fx) < double(kKeyLimit) && std::fabs(fy) < double(kKeyLimit) && std::fabs(fz) < double(kKeyLimit))) return FLS_ERR_RANGE;
             kv[i] = {pack_key(int(fx), int(fy), int(fz)), unsigned(i)};
         }
         pooled_sort_total_order(kv.data(), kv.data() + n);  // (cell key, index) pairs: a total order

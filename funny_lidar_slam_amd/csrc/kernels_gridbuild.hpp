@@ -8,7 +8,8 @@
 // here and in packed-key order on the host path: the ORDER OF THE BUCKETS in the point array is the one thing that differs, and
 // nothing reads it -- every selection key of the search kernels carries the MAP INDEX as its tie-breaker, not the slot.
 //
-//   cg_keys     cell of every point (floorf(p * inv_cell) in float, like the host build) -> linear window index, value = point index
+//   cg_keys     cell of every point (floor(double(p) * inv_cell), inv_cell = 1.0 / double(cell): the host build's expression and the one the
+//               search kernels file their queries with) -> linear window index, value = point index
 //   (vg_hist / vg_scan_rows / vg_scatter: ceil(bits / 8) radix passes)
 //   cg_fill     points gathered into sorted order; the head of every run writes its cell's `begin`
 //   cg_count    the tail of every run writes its cell's `count`
@@ -20,7 +21,7 @@
 namespace fls {
 
 struct CgWindow {
-    float inv_cell;
+    double inv_cell;
     int ox, oy, oz, nx, ny, nz;
 };
 
@@ -30,7 +31,7 @@ cg_keys(const float* __restrict__ x, const float* __restrict__ y, const float* _
     const int i = blockIdx.x * kVgBlock + threadIdx.x;
     if (i >= n) return;
     // the host decided the window from the finite bounds of these very points: every cell index is inside it
-    const int cx = (int)floorf(x[i] * w.inv_cell) - w.ox, cy = (int)floorf(y[i] * w.inv_cell) - w.oy, cz = (int)floorf(z[i] * w.inv_cell) - w.oz;
+    const int cx = (int)floor((double)x[i] * w.inv_cell) - w.ox, cy = (int)floor((double)y[i] * w.inv_cell) - w.oy, cz = (int)floor((double)z[i] * w.inv_cell) - w.oz;
     key[i] = (unsigned)((cz * w.ny + cy) * w.nx + cx);
     val[i] = (unsigned)i;
 }

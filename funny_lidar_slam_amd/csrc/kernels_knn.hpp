@@ -1,7 +1,12 @@
 // kernels_knn.hpp -- exact k-NN on a uniform hash grid (the GPU stand-in for the reference's
 // pcl::KdTreeFLANN) and the residual kernels built on it.   gfx950 only.
 //
-// Exactness (SURVEY.md 0 note 3): cells are floor(double(p) * inv_cell) per axis.  After scanning
+// Exactness (SURVEY.md 0 note 3): cells are floor(double(p) * inv_cell) per axis, inv_cell = 1.0 / double(cell), for the queries here AND for the
+// map points in both grid builders (host_maps.hpp CellGridImage::build, kernels_gridbuild.hpp cg_keys).  The argument needs ONE monotone filing
+// function: two floats less than a cell apart then lie at most one cell index apart (their products differ by less than 1 - 5e-6 under the
+// 1e-5 margin below, the rounding errors stay under 2^-32).  Filing map points with floorf(p * (1.0f / cell)) in float breaks this from
+// |p| ~ 100 cells on: next to a cell face the point lands one cell off and a certified list lacks a closer point
+// (tests/test_gpu_knn_stages.py, boundary_filing).  After scanning
 // every cell whose Chebyshev cell distance to the query cell is <= rho, every map point within
 // Euclidean distance rho*cell of the query has been seen.  The search stops when
 //   (a) K points are held and the K-th d2 <= (rho*cell)^2 (nothing unseen can beat it), or

@@ -28,7 +28,7 @@ def test_debug_loop_symbols_exported_declared_and_listed(built):
     assert "#define FLS_DEBUG_LOOP_REVISION 1" in src and L.fls_debug_loop_revision() == 1
     others = (_lib.EXPORTED_SYMBOLS + _lib.PREPROCESS_SYMBOLS + _lib.INGEST_SYMBOLS + _lib.KEYFRAMES_SYMBOLS + _lib.LOCALMAP_SYMBOLS + _lib.BATCH_SYMBOLS +
               _lib.BATCH_IVOX_SYMBOLS + _lib.DEBUG_LINALG_SYMBOLS + _lib.DEBUG_FIT_SYMBOLS + _lib.DEBUG_NDT_SYMBOLS + _lib.NDT_IMAGE_SYMBOLS + _lib.KD_IMAGE_SYMBOLS +
-              _lib.IVOX_BLOB_SYMBOLS)
+              _lib.IVOX_BLOB_SYMBOLS + _lib.DEBUG_KNN_SYMBOLS)
     assert not set(_lib.DEBUG_LOOP_SYMBOLS) & set(others)
     dpp = C.CDLL(os.path.join(os.path.dirname(_lib.LIB_PATH), "libfls_reg_dpp.so"))
     for s in declared:
