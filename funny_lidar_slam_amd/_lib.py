@@ -30,6 +30,11 @@ PREPROCESS_SYMBOLS = [
     "fls_features_project_deskew",
 ] + HANDOFF_SYMBOLS
 
+# every symbol include/fls_features_device.h declares (FLS_FEATURES_DEVICE_REVISION 1): the feature clouds kept on the device, LoamFull attach
+FEATURES_DEVICE_SYMBOLS = ["fls_features_device_revision", "fls_features_keep_on_device", "fls_features_get_host_bytes", "fls_features_stat",
+                           "fls_scan_attach_features"]
+FEAT_STAT_DEVICE_GATHERS, FEAT_STAT_DEVICE_FILTERS, FEAT_STAT_FILTER_DECLINES, FEAT_STAT_LAZY_DOWNLOADS = range(4)
+
 # every symbol include/fls_ingest.h declares (FLS_INGEST_REVISION 1)
 INGEST_SYMBOLS = ["fls_ingest_revision", "fls_ingest_default_layout", "fls_preprocess_scan_driver", "fls_features_project_driver"]
 
@@ -406,6 +411,17 @@ def lib():
         L.fls_features_project_deskew.restype = C.c_int
         L.fls_features_project_deskew.argtypes = [hp, C.c_void_p, C.c_size_t, C.POINTER(RawLayout), C.c_uint64, u64p, dp, C.c_size_t, dp,
                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        if hasattr(L, "fls_features_device_revision"):  # (as fls_batch_ivox_revision below)
+            L.fls_features_device_revision.restype = C.c_int
+            L.fls_features_device_revision.argtypes = []
+            L.fls_features_keep_on_device.restype = C.c_int
+            L.fls_features_keep_on_device.argtypes = [hp, C.c_int]
+            L.fls_features_get_host_bytes.restype = C.c_int
+            L.fls_features_get_host_bytes.argtypes = [hp, u64p]
+            L.fls_features_stat.restype = C.c_size_t
+            L.fls_features_stat.argtypes = [hp, C.c_int]
+            L.fls_scan_attach_features.restype = C.c_int
+            L.fls_scan_attach_features.argtypes = [hp, hp, C.c_int]
         L.fls_ingest_revision.restype = C.c_int
         L.fls_ingest_revision.argtypes = []
         L.fls_ingest_default_layout.restype = C.c_int

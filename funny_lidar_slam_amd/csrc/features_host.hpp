@@ -3,7 +3,10 @@
 #pragma once
 #include "host_maps.hpp"
 #include "kernels_features.hpp"
+#include "kernels_features_gather.hpp"
+#include "device_voxelgrid.hpp"
 #include "../../include/fls_features.h"
+#include "../../include/fls_features_device.h"
 #include <limits>
 #include <memory>
 
@@ -37,7 +40,48 @@ struct fls_features {
     std::vector<int> h_cidx, h_ccnt, h_pidx, h_pcnt;
     std::shared_ptr<fls::DeskewScratch> deskew;  // created by the first fls_features_project_deskew
 
+    // ---- include/fls_features_device.h: the arrays stay on the device, fls_features_get fetches what it is asked for ----
+    bool resident = false;       // fls_features_keep_on_device
+    uint64_t d2h_bytes = 0;      // device -> host copies on behalf of the last frame so far
+    size_t stats[4] = {0, 0, 0, 0};  // FLS_FEAT_STAT_*
+    // One class's clouds on the device: the gathered planes (row stride cap), the compacted indices, and the filtered cloud -- the
+    // VoxelGrid's own output planes, or `up` where the device declined and the host filter's result went up again.
+    struct ResidentCloud {
+        fls::DevBuf<float> planes;  // x | y | z | intensity, row stride cap
+        fls::DevBuf<int> idx;
+        fls::DevBuf<float> up;      // x | y | z | intensity of the host-filtered cloud, row stride n_f
+        fls::DeviceVoxelGrid vg;
+        size_t cap = 0, n = 0, n_f = 0;
+        bool filter_on_device = false;
+        bool stale = false, stale_idx = false, stale_f = false;  // the host copy has not been downloaded yet
+        fls::HandoffCloud cloud() const {
+            fls::HandoffCloud c;
+            c.x = planes.p; c.y = planes.p + cap; c.z = planes.p + 2 * cap; c.in = planes.p + 3 * cap; c.n = n;
+            return c;
+        }
+        fls::HandoffCloud filtered() const {
+            fls::HandoffCloud c;
+            if (filter_on_device) { c.x = vg.ox(); c.y = vg.oy(); c.z = vg.oz(); c.in = vg.oi(); }
+            else { c.x = up.p; c.y = up.p + n_f; c.z = up.p + 2 * n_f; c.in = up.p + 3 * n_f; }
+            c.n = n_f;
+            return c;
+        }
+    };
+    ResidentCloud rc_corner, rc_planar;
+    fls::DevBuf<int> d_tot;
+    int h_tot[2] = {0, 0};
+    bool stale_ordered = false, stale_depth = false, stale_col = false, stale_rows = false;
+    std::vector<float> tmp;
+    // hand-off (fls_scan_attach_features): ready = "everything queued on this stream so far", recorded per attach and waited for by the
+    // matcher's stream; consumed[k] = a matcher's copy kernels have read this handle's buffers, waited for by the next projection
+    hipEvent_t ev_ready = nullptr;
+    std::vector<hipEvent_t> consumed;
+    size_t n_consumed = 0;
+
     ~fls_features() {
+        for (size_t k = 0; k < n_consumed; ++k) (void)hipEventSynchronize(consumed[k]);  // (the buffers below are still being read)
+        for (auto e : consumed) if (e) (void)hipEventDestroy(e);
+        if (ev_ready) (void)hipEventDestroy(ev_ready);
         for (auto e : ev) if (e) (void)hipEventDestroy(e);
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     }
@@ -57,6 +101,8 @@ struct fls_features {
         FLS_HIP(hipSetDevice(device));
         FLS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         for (auto& e : ev) FLS_HIP(hipEventCreate(&e));
+        FLS_HIP(hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming));
+        d_tot.reserve(2);
         const size_t cells = size_t(pd.rows) * size_t(pd.cols);
         d_owner.reserve(cells);
         d_row_count.reserve(size_t(pd.rows)); d_row_start.reserve(size_t(pd.rows)); d_row_end.reserve(size_t(pd.rows));
@@ -75,7 +121,7 @@ struct fls_features {
             return FLS_ERR_INVALID;
         layout = fls::RawLayoutDev{L.stride_bytes, L.xyz_offset, L.intensity_offset, L.ring_offset};
         n_raw = n;
-        projected = extracted = false;
+        begin_projection();
         const size_t cells = size_t(pd.rows) * size_t(pd.cols);
         d_raw.reserve(std::max<size_t>(n * L.stride_bytes, 16));
         FLS_HIP(hipEventRecord(ev[0], stream));
@@ -88,20 +134,57 @@ struct fls_features {
         hipLaunchKernelGGL(fls::feat_compact_kernel, dim3(unsigned(pd.rows)), dim3(256), 0, stream, d_raw.p, layout, d_owner.p, pd, d_row_count.p,
                            d_ordered.p, d_depth.p, d_col.p, d_raw_index.p, d_valid.p, d_row_start.p, d_row_end.p, d_n.p);
         FLS_HIP(hipGetLastError());
+        return finish_projection(n_ordered);
+    }
+
+    // a matcher may still be copying the previous frame's clouds out of this handle's buffers: whatever is queued next waits for that
+    void wait_consumers() {
+        for (size_t k = 0; k < n_consumed; ++k) FLS_HIP(hipStreamWaitEvent(stream, consumed[k], 0));
+        n_consumed = 0;
+    }
+    hipEvent_t next_consumed_event() {
+        if (n_consumed == consumed.size()) {
+            hipEvent_t e = nullptr;
+            FLS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            consumed.push_back(e);
+        }
+        return consumed[n_consumed++];
+    }
+    // the start of every projection: no array of the previous frame is current any more
+    void begin_projection() {
+        projected = extracted = false;
+        have_raw_index = have_intro = false;
+        stale_ordered = stale_depth = stale_col = stale_rows = false;
+        d2h_bytes = 0;
+        wait_consumers();
+    }
+
+    // behind the launches of a projection (all three forms): the read-back.  Default: N and the ring indices, then the ordered cloud,
+    // depths and columns.  Resident: N alone.
+    fls_status finish_projection(size_t* n_ordered) {
         FLS_HIP(hipEventRecord(ev[1], stream));
         FLS_HIP(hipMemcpyAsync(&N, d_n.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        row_start.resize(size_t(pd.rows)); row_end.resize(size_t(pd.rows));
-        FLS_HIP(hipMemcpyAsync(row_start.data(), d_row_start.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, stream));
-        FLS_HIP(hipMemcpyAsync(row_end.data(), d_row_end.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        d2h_bytes += sizeof(int);
+        const size_t rows = size_t(pd.rows);
+        if (!resident) {
+            row_start.resize(rows); row_end.resize(rows);
+            FLS_HIP(hipMemcpyAsync(row_start.data(), d_row_start.p, rows * sizeof(int), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipMemcpyAsync(row_end.data(), d_row_end.p, rows * sizeof(int), hipMemcpyDeviceToHost, stream));
+            d2h_bytes += 2 * rows * sizeof(int);
+        }
         FLS_HIP(hipStreamSynchronize(stream));
         const size_t m = size_t(N);
-        ordered.resize(m); depth.resize(m); col.resize(m);
-        have_raw_index = have_intro = false;
-        if (m) {
-            FLS_HIP(hipMemcpyAsync(ordered.data(), d_ordered.p, m * sizeof(float4), hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipMemcpyAsync(depth.data(), d_depth.p, m * sizeof(float), hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipMemcpyAsync(col.data(), d_col.p, m * sizeof(int), hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipStreamSynchronize(stream));
+        if (resident) {
+            stale_ordered = stale_depth = stale_col = stale_rows = true;
+        } else {
+            ordered.resize(m); depth.resize(m); col.resize(m);
+            if (m) {
+                FLS_HIP(hipMemcpyAsync(ordered.data(), d_ordered.p, m * sizeof(float4), hipMemcpyDeviceToHost, stream));
+                FLS_HIP(hipMemcpyAsync(depth.data(), d_depth.p, m * sizeof(float), hipMemcpyDeviceToHost, stream));
+                FLS_HIP(hipMemcpyAsync(col.data(), d_col.p, m * sizeof(int), hipMemcpyDeviceToHost, stream));
+                FLS_HIP(hipStreamSynchronize(stream));
+                d2h_bytes += m * (sizeof(float4) + sizeof(float) + sizeof(int));
+            }
         }
         float ms = 0.f;
         FLS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -116,6 +199,14 @@ struct fls_features {
         const size_t m = size_t(N);
         have_intro = false;
         corner_idx.clear(); planar_idx.clear(); corner.clear(); planar.clear(); corner_f.clear(); planar_f.clear();
+        // no cloud of an earlier extraction is pending on the device any more, whichever mode made it (a handle switched back to the default
+        // must not fetch the resident frame's clouds over the ones computed below)
+        for (ResidentCloud* c : {&rc_corner, &rc_planar}) {
+            c->n = c->n_f = 0;
+            c->filter_on_device = false;
+            c->stale = c->stale_idx = c->stale_f = false;
+        }
+        if (resident) return extract_resident(n_corner, n_planar);
         if (N >= 12) {
             const size_t rows = size_t(pd.rows);
             h_cidx.resize(rows * 120); h_ccnt.resize(rows); h_pidx.resize(rows * size_t(pd.cols + 6)); h_pcnt.resize(rows);
@@ -132,6 +223,7 @@ struct fls_features {
             FLS_HIP(hipMemcpyAsync(h_cidx.data(), d_corner_idx.p, h_cidx.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipMemcpyAsync(h_pidx.data(), d_planar_idx.p, h_pidx.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipStreamSynchronize(stream));
+            d2h_bytes += (2 * rows + h_cidx.size() + h_pidx.size()) * sizeof(int);
             float ms = 0.f;
             FLS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
             extract_ms = ms;
@@ -155,6 +247,146 @@ struct fls_features {
         return FLS_OK;
     }
 
+    // fls_features_extract with the arrays kept on the device: the same two launches, then the gather (kernels_features_gather.hpp), ONE
+    // wait for the two sizes, then the two VoxelGrid filters on the gathered planes
+    fls_status extract_resident(size_t* n_corner, size_t* n_planar) {
+        const size_t m = size_t(N), rows = size_t(pd.rows);
+        wait_consumers();  // (an extraction repeated without a projection writes the same buffers)
+        if (N >= 12) {
+            rc_corner.cap = rows * size_t(fls::kFeatCornerStride);
+            rc_planar.cap = rows * size_t(pd.cols + 6);
+            for (ResidentCloud* c : {&rc_corner, &rc_planar}) { c->planes.reserve(4 * c->cap); c->idx.reserve(c->cap); }
+            FLS_HIP(hipEventRecord(ev[2], stream));
+            hipLaunchKernelGGL(fls::feat_valid_rough_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, stream, d_n.p, d_depth.p, d_col.p, d_rough.p,
+                               d_valid.p);
+            FLS_HIP(hipMemcpyAsync(d_valid_pre.p, d_valid.p, m, hipMemcpyDeviceToDevice, stream));  // snapshot before SelectFeatures edits the flags
+            hipLaunchKernelGGL(fls::feat_select_kernel, dim3(unsigned(pd.rows)), dim3(fls::kFeatSelectThreads), 0, stream, d_n.p, pd, d_row_start.p, d_row_end.p, d_rough.p,
+                               d_col.p, d_valid.p, d_is_corner.p, d_corner_idx.p, d_corner_cnt.p, d_planar_idx.p, d_planar_cnt.p);
+            const auto side = [](const fls::DevBuf<int>& idx, const fls::DevBuf<int>& cnt, int stride, ResidentCloud& c) {
+                return fls::FeatGatherSide{idx.p, cnt.p, stride, c.planes.p, c.planes.p + c.cap, c.planes.p + 2 * c.cap, c.planes.p + 3 * c.cap, c.idx.p};
+            };
+            hipLaunchKernelGGL(fls::feat_gather_kernel, dim3(unsigned(pd.rows)), dim3(fls::kFeatGatherThreads), 0, stream, d_n.p, d_ordered.p, pd.rows,
+                               side(d_corner_idx, d_corner_cnt, fls::kFeatCornerStride, rc_corner), side(d_planar_idx, d_planar_cnt, pd.cols + 6, rc_planar),
+                               d_tot.p);
+            FLS_HIP(hipGetLastError());
+            FLS_HIP(hipEventRecord(ev[3], stream));
+            FLS_HIP(hipMemcpyAsync(h_tot, d_tot.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            d2h_bytes += 2 * sizeof(int);
+            float ms = 0.f;
+            FLS_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+            extract_ms = ms;
+            ++stats[FLS_FEAT_STAT_DEVICE_GATHERS];
+            rc_corner.n = std::min(size_t(std::max(h_tot[0], 0)), rc_corner.cap);
+            rc_planar.n = std::min(size_t(std::max(h_tot[1], 0)), rc_planar.cap);
+            for (ResidentCloud* c : {&rc_corner, &rc_planar}) c->stale = c->stale_idx = c->n != 0;
+            filter_resident(rc_corner, corner, corner_f, p.corner_voxel_filter_size);  // preprocessing.cpp:234-235
+            filter_resident(rc_planar, planar, planar_f, p.planar_voxel_filter_size);  // :236-237
+        }
+        extracted = true;
+        if (n_corner) *n_corner = rc_corner.n;
+        if (n_planar) *n_planar = rc_planar.n;
+        return FLS_OK;
+    }
+    // VoxelGrid of one gathered cloud: on the device; where the device declines, the exact host filter on the downloaded cloud, its
+    // result uploaded again (x | y | z | intensity) so that fls_scan_attach_features still finds it in device memory
+    void filter_resident(ResidentCloud& c, std::vector<fls::PtI>& full, std::vector<fls::PtI>& filtered, const float leaf) {
+        if (!(leaf > 0.f) || c.n == 0) return;
+        if (fls::device_voxelgrid_mode() != 0 && c.vg.run(c.planes.p, c.planes.p + c.cap, c.planes.p + 2 * c.cap, c.planes.p + 3 * c.cap, c.n, leaf, stream)) {
+            c.filter_on_device = true;
+            c.n_f = c.vg.n_out;
+            c.stale_f = c.n_f != 0;
+            ++stats[FLS_FEAT_STAT_DEVICE_FILTERS];
+            return;
+        }
+        ++stats[FLS_FEAT_STAT_FILTER_DECLINES];
+        fetch_cloud(c, full);
+        filtered = fls::voxel_grid(full, leaf);
+        const size_t nf = c.n_f = filtered.size();
+        if (!nf) return;
+        tmp.resize(4 * nf);
+        for (size_t i = 0; i < nf; ++i) { tmp[i] = filtered[i].x; tmp[nf + i] = filtered[i].y; tmp[2 * nf + i] = filtered[i].z; tmp[3 * nf + i] = filtered[i].i; }
+        c.up.reserve(4 * nf);
+        FLS_HIP(hipMemcpyAsync(c.up.p, tmp.data(), 4 * nf * sizeof(float), hipMemcpyHostToDevice, stream));
+        FLS_HIP(hipStreamSynchronize(stream));  // (`tmp` is reused)
+    }
+
+    // ---- the lazy read-back of the resident mode: the host copy of one array made current ----
+    template <class T>
+    bool download(bool& stale, std::vector<T>& v, const T* dev, const size_t n) {
+        if (!stale) return false;
+        v.resize(n);
+        if (n) {
+            FLS_HIP(hipMemcpyAsync(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+        }
+        d2h_bytes += n * sizeof(T);
+        stale = false;
+        return true;
+    }
+    bool fetch_cloud(ResidentCloud& c, std::vector<fls::PtI>& out) {
+        if (!c.stale) return false;
+        const size_t n = c.n;
+        out.resize(n);
+        tmp.resize(4 * n);
+        for (int a = 0; a < 4; ++a)
+            FLS_HIP(hipMemcpyAsync(tmp.data() + size_t(a) * n, c.planes.p + size_t(a) * c.cap, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        FLS_HIP(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < n; ++i) out[i] = fls::PtI{tmp[i], tmp[n + i], tmp[2 * n + i], tmp[3 * n + i]};
+        d2h_bytes += 4 * n * sizeof(float);
+        c.stale = false;
+        return true;
+    }
+    bool fetch_filtered(ResidentCloud& c, std::vector<fls::PtI>& out) {
+        if (!c.stale_f) return false;
+        out = c.vg.download(stream, tmp);
+        d2h_bytes += out.size() * sizeof(fls::PtI);
+        c.stale_f = false;
+        return true;
+    }
+    void fetch_resident(int what) {
+        FLS_HIP(hipSetDevice(device));
+        const size_t m = size_t(N), rows = size_t(pd.rows);
+        bool did = false;
+        switch (what) {
+            case FLS_FEAT_ORDERED: did = download(stale_ordered, ordered, reinterpret_cast<const fls::Pt4*>(d_ordered.p), m); break;
+            case FLS_FEAT_DEPTH: did = download(stale_depth, depth, d_depth.p, m); break;
+            case FLS_FEAT_COL: did = download(stale_col, col, d_col.p, m); break;
+            case FLS_FEAT_ROW_START:
+            case FLS_FEAT_ROW_END: {
+                bool again = stale_rows;
+                did = download(stale_rows, row_start, d_row_start.p, rows);
+                download(again, row_end, d_row_end.p, rows);
+                break;
+            }
+            case FLS_FEAT_CORNER: did = fetch_cloud(rc_corner, corner); break;
+            case FLS_FEAT_PLANAR: did = fetch_cloud(rc_planar, planar); break;
+            case FLS_FEAT_CORNER_IDX: did = download(rc_corner.stale_idx, corner_idx, rc_corner.idx.p, rc_corner.n); break;
+            case FLS_FEAT_PLANAR_IDX: did = download(rc_planar.stale_idx, planar_idx, rc_planar.idx.p, rc_planar.n); break;
+            case FLS_FEAT_CORNER_FILTERED: did = fetch_filtered(rc_corner, corner_f); break;
+            case FLS_FEAT_PLANAR_FILTERED: did = fetch_filtered(rc_planar, planar_f); break;
+            default: break;
+        }
+        if (did) ++stats[FLS_FEAT_STAT_LAZY_DOWNLOADS];
+    }
+    // the element count of an array whose host copy is not current (a size query downloads nothing); false: the host copy is current
+    bool pending_size(int what, size_t& n) const {
+        switch (what) {
+            case FLS_FEAT_ORDERED: n = size_t(N); return stale_ordered;
+            case FLS_FEAT_DEPTH: n = size_t(N); return stale_depth;
+            case FLS_FEAT_COL: n = size_t(N); return stale_col;
+            case FLS_FEAT_ROW_START:
+            case FLS_FEAT_ROW_END: n = size_t(pd.rows); return stale_rows;
+            case FLS_FEAT_CORNER: n = rc_corner.n; return rc_corner.stale;
+            case FLS_FEAT_PLANAR: n = rc_planar.n; return rc_planar.stale;
+            case FLS_FEAT_CORNER_IDX: n = rc_corner.n; return rc_corner.stale_idx;
+            case FLS_FEAT_PLANAR_IDX: n = rc_planar.n; return rc_planar.stale_idx;
+            case FLS_FEAT_CORNER_FILTERED: n = rc_corner.n_f; return rc_corner.stale_f;
+            case FLS_FEAT_PLANAR_FILTERED: n = rc_planar.n_f; return rc_planar.stale_f;
+            default: return false;
+        }
+    }
+
     void fetch_raw_index() {
         if (have_raw_index) return;
         const size_t m = size_t(N);
@@ -163,6 +395,7 @@ struct fls_features {
             FLS_HIP(hipSetDevice(device));
             FLS_HIP(hipMemcpyAsync(raw_index.data(), d_raw_index.p, m * sizeof(int), hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipStreamSynchronize(stream));
+            d2h_bytes += m * sizeof(int);
         }
         have_raw_index = true;
     }
@@ -177,6 +410,7 @@ struct fls_features {
             FLS_HIP(hipMemcpyAsync(valid_post.data(), d_valid.p, m, hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipMemcpyAsync(is_corner.data(), d_is_corner.p, m, hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipStreamSynchronize(stream));
+            d2h_bytes += m * (sizeof(float) + 3);
         }
         have_intro = true;
     }
@@ -188,6 +422,11 @@ struct fls_features {
     size_t get(int what, void* out, size_t cap) {
         if (what == FLS_FEAT_RAW_INDEX) fetch_raw_index();
         if (what == FLS_FEAT_IS_CORNER || what == FLS_FEAT_ROUGHNESS || what == FLS_FEAT_VALID_PRE || what == FLS_FEAT_VALID_POST) fetch_intro();
+        size_t pending = 0;
+        if (pending_size(what, pending)) {  // (resident mode: the array still lies on the device alone)
+            if (!out) return pending;
+            fetch_resident(what);
+        }
         switch (what) {
             case FLS_FEAT_ORDERED: return copy_out(ordered, out, cap);
             case FLS_FEAT_DEPTH: return copy_out(depth, out, cap);

@@ -1102,6 +1102,53 @@ fls_status fls_features_get_time(fls_features_handle h, double* project_ms, doub
     return FLS_OK;
 }
 
+// ---- the feature clouds kept on the device and handed to the LoamFull kind (include/fls_features_device.h) ----------------------
+int fls_features_device_revision(void) { return FLS_FEATURES_DEVICE_REVISION; }
+
+fls_status fls_features_keep_on_device(fls_features_handle h, int on) {
+    if (!h) return FLS_ERR_INVALID;
+    const bool want = on != 0;
+    if (want != h->resident) {  // (no array of a projection made in the other mode is read in this one)
+        h->resident = want;
+        h->projected = h->extracted = false;
+    }
+    return FLS_OK;
+}
+
+fls_status fls_features_get_host_bytes(fls_features_handle h, uint64_t* d2h_bytes) {
+    if (!h || !d2h_bytes) return FLS_ERR_INVALID;
+    *d2h_bytes = h->d2h_bytes;
+    return FLS_OK;
+}
+
+size_t fls_features_stat(fls_features_handle h, int what) { return (h && what >= 0 && what < 4) ? h->stats[what] : 0; }
+
+fls_status fls_scan_attach_features(fls_handle m, fls_features_handle f, int filtered) {
+    if (!m || !f || m->device != f->device) return FLS_ERR_INVALID;
+    if (m->kind != FLS_LOAM_FULL || !f->extracted) return FLS_ERR_STATE;
+    if (filtered && (!(f->p.corner_voxel_filter_size > 0.f) || !(f->p.planar_voxel_filter_size > 0.f))) return FLS_ERR_STATE;
+    return guarded([&]() -> fls_status {
+        FLS_HIP(hipSetDevice(m->device));
+        if (!f->resident) {  // the clouds the default mode left on the host: the ordinary upload
+            const std::vector<PtI>& pl = filtered ? f->planar_f : f->planar;
+            const std::vector<PtI>& co = filtered ? f->corner_f : f->corner;
+            const fls_status rc = m->scan_upload(pl.empty() ? nullptr : &pl[0].x, pl.size(), co.empty() ? nullptr : &co[0].x, co.size(), 4);
+            FLS_HIP(hipStreamSynchronize(m->stream));
+            return rc;
+        }
+        const HandoffCloud pl = filtered ? f->rc_planar.filtered() : f->rc_planar.cloud();
+        const HandoffCloud co = filtered ? f->rc_corner.filtered() : f->rc_corner.cloud();
+        if (pl.n == 0 && co.n == 0) return m->scan_attach_features(pl, co);
+        // the copies wait for the extraction and the filters (and anything else queued on the front end's stream); the front end's next
+        // projection waits for the copies
+        FLS_HIP(hipEventRecord(f->ev_ready, f->stream));
+        FLS_HIP(hipStreamWaitEvent(m->stream, f->ev_ready, 0));
+        const fls_status rc = m->scan_attach_features(pl, co);
+        FLS_HIP(hipEventRecord(f->next_consumed_event(), m->stream));
+        return rc;
+    });
+}
+
 // ---- per-scan preprocessing: IMU de-skew, range gate, subsample, planar VoxelGrid (include/fls_preprocess.h) --------------------
 fls_status fls_preprocess_create(const fls_preprocess_params* params, int device_id, fls_preprocess_handle* out) {
     if (!out) return FLS_ERR_INVALID;

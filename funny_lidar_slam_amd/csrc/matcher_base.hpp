@@ -81,6 +81,9 @@ struct fls_matcher {
     // fls_scan_attach_preprocessed: what fls_scan_upload_raw(rows of `c`) would leave, from a cloud that already lies on this device.  The
     // copy kernel is queued on this handle's stream (the caller has ordered it behind the producer); host copies are fetched on demand.
     virtual fls_status scan_attach_device(const fls::HandoffCloud&) { return FLS_ERR_STATE; }
+    // fls_scan_attach_features: what fls_scan_upload(rows of `planar`, rows of `corner`) would leave, from the two feature clouds lying
+    // on this device (the LoamFull kind; same ordering contract as scan_attach_device)
+    virtual fls_status scan_attach_features(const fls::HandoffCloud& /*planar*/, const fls::HandoffCloud& /*corner*/) { return FLS_ERR_STATE; }
     virtual fls_status match_resident(double* T, int update_map, fls_stats* out) = 0;
     virtual fls_status fitness(float max_range, float* score) = 0;
     virtual int correspondences(int slot, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) = 0;

@@ -635,6 +635,11 @@ struct LoamFullMatcher final : fls_matcher {
         corner.scan.upload(s1 ? cloud_from(s1, n1, stride) : std::vector<PtI>(), stream);
         return FLS_OK;
     }
+    fls_status scan_attach_features(const HandoffCloud& planar_cloud, const HandoffCloud& corner_cloud) override {
+        planar.scan.attach_device(planar_cloud, stream, /*want_host=*/true);  // (a cloud of no points is attached as the empty scan)
+        corner.scan.attach_device(corner_cloud, stream, /*want_host=*/true);
+        return FLS_OK;
+    }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
         const size_t np = planar.scan.n, nc = corner.scan.n;
@@ -689,6 +694,8 @@ struct LoamFullMatcher final : fls_matcher {
                 arc = rebuild_maps();
                 if (map_planar.rebuild_declined || map_corner.rebuild_declined) ++push_declines;
             } else {
+                planar.scan.fetch_host(stream);  // (attached scans are fetched only here)
+                corner.scan.fetch_host(stream);
                 arc = add_cloud_impl(hm::xform_cloud_d(planar.scan.host, mb.T), hm::xform_cloud_d(corner.scan.host, mb.T));
             }
             if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
@@ -696,17 +703,25 @@ struct LoamFullMatcher final : fls_matcher {
         if (out) *out = stats;
         return rc;
     }
-    // both feature scans, still on the device, into their rings at the pose the Match found; their intensities go up first (one plane for
-    // both).  false: the maps cannot take a device push -- nothing has changed
+    // both feature scans, still on the device, into their rings at the pose the Match found.  Intensity: the fourth planes of attached
+    // scans (an empty scan needs none); of uploaded ones the host copies', sent up first (one plane for both).  false: the maps cannot
+    // take a device push -- nothing has changed
     KdPushIntensity push_i;
     unsigned long long push_declines = 0;  // keyframes after whose device push a device rebuild was declined (fls_map_size slot 167)
     bool push_keyframe_device(const double* T) {
         if (!map_planar.can_push_device() || !map_corner.can_push_device()) return false;
         const DevScan &ps = planar.scan, &cs = corner.scan;
-        if (ps.host.size() != ps.n || cs.host.size() != cs.n) return false;
-        const std::vector<PtI>* clouds[2] = {&ps.host, &cs.host};
-        const float* in = push_i.upload(clouds, 2, stream);
-        const DeviceCloudRing::DeviceCloud src[2] = {{ps.x.p, ps.y.p, ps.z.p, in, ps.n}, {cs.x.p, cs.y.p, cs.z.p, in + ps.n, cs.n}};
+        const float *in_p = nullptr, *in_c = nullptr;
+        if ((ps.dev_intensity || ps.n == 0) && (cs.dev_intensity || cs.n == 0) && (ps.dev_intensity || cs.dev_intensity)) {
+            if (ps.n) in_p = ps.xyz.p + 3 * ps.n;
+            if (cs.n) in_c = cs.xyz.p + 3 * cs.n;
+        } else {
+            if (ps.host.size() != ps.n || cs.host.size() != cs.n) return false;
+            const std::vector<PtI>* clouds[2] = {&ps.host, &cs.host};
+            in_p = push_i.upload(clouds, 2, stream);
+            in_c = in_p ? in_p + ps.n : nullptr;
+        }
+        const DeviceCloudRing::DeviceCloud src[2] = {{ps.x.p, ps.y.p, ps.z.p, in_p, ps.n}, {cs.x.p, cs.y.p, cs.z.p, in_c, cs.n}};
         KdLocalMap* maps[2] = {&map_planar, &map_corner};
         return KdLocalMap::push_device(maps, src, 2, kd_push_xform_d(T), stream);
     }

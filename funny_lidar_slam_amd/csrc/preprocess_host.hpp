@@ -585,7 +585,9 @@ inline fls_status features_project_driver(fls_features& f, const void* msg, size
     if (rc != FLS_OK) return rc;
     if (stamp_out) *stamp_out = f.deskew->stamp_out;
     f.deskew->fill_info(info);
-    return features_project_prepared(f, n_ordered, imu_status);
+    const fls_status prc = features_project_prepared(f, n_ordered, imu_status);
+    if (n) f.d2h_bytes += sizeof(fls::IngestMail);  // (the conversion's summary, read back before the projection)
+    return prc;
 }
 
 // after ds.prepare / ds.prepare_driver succeeded
@@ -594,8 +596,7 @@ inline fls_status features_project_prepared(fls_features& f, size_t* n_ordered, 
     const size_t n = ds.n;
     const fls::DeskewRawDev L{ds.L};
     if (imu_status) *imu_status = ds.imu_status;
-    f.projected = f.extracted = false;
-    f.have_raw_index = f.have_intro = false;
+    f.begin_projection();
     f.N = 0;
     f.ordered.clear(); f.depth.clear(); f.col.clear();
     if (n_ordered) *n_ordered = 0;
@@ -621,24 +622,5 @@ inline fls_status features_project_prepared(fls_features& f, size_t* n_ordered, 
         hipLaunchKernelGGL(fls::deskew_apply_kernel, dim3(unsigned((cells + 255) / 256)), dim3(256), 0, f.stream, f.d_n.p, f.d_raw_index.p, ds.d_corr.p,
                            f.d_ordered.p);
     FLS_HIP(hipGetLastError());
-    FLS_HIP(hipEventRecord(f.ev[1], f.stream));
-    FLS_HIP(hipMemcpyAsync(&f.N, f.d_n.p, sizeof(int), hipMemcpyDeviceToHost, f.stream));
-    f.row_start.resize(size_t(pd.rows)); f.row_end.resize(size_t(pd.rows));
-    FLS_HIP(hipMemcpyAsync(f.row_start.data(), f.d_row_start.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, f.stream));
-    FLS_HIP(hipMemcpyAsync(f.row_end.data(), f.d_row_end.p, size_t(pd.rows) * sizeof(int), hipMemcpyDeviceToHost, f.stream));
-    FLS_HIP(hipStreamSynchronize(f.stream));
-    const size_t m = size_t(f.N);
-    f.ordered.resize(m); f.depth.resize(m); f.col.resize(m);
-    if (m) {
-        FLS_HIP(hipMemcpyAsync(f.ordered.data(), f.d_ordered.p, m * sizeof(float4), hipMemcpyDeviceToHost, f.stream));
-        FLS_HIP(hipMemcpyAsync(f.depth.data(), f.d_depth.p, m * sizeof(float), hipMemcpyDeviceToHost, f.stream));
-        FLS_HIP(hipMemcpyAsync(f.col.data(), f.d_col.p, m * sizeof(int), hipMemcpyDeviceToHost, f.stream));
-        FLS_HIP(hipStreamSynchronize(f.stream));
-    }
-    float ms = 0.f;
-    FLS_HIP(hipEventElapsedTime(&ms, f.ev[0], f.ev[1]));
-    f.project_ms = ms;
-    f.projected = true;
-    if (n_ordered) *n_ordered = m;
-    return FLS_OK;
+    return f.finish_projection(n_ordered);  // (the read-back every projection shares)
 }

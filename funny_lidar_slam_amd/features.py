@@ -28,7 +28,7 @@ class FeatureFrontEnd:
     """One fls_features handle (projector + extractor state on one device)."""
 
     def __init__(self, lidar_horizontal_scan, lidar_vertical_scan, lidar_horizontal_resolution, min_distance, max_distance,
-                 corner_thres, planar_thres, corner_voxel_filter_size=0.0, planar_voxel_filter_size=0.0, device_id=0):
+                 corner_thres, planar_thres, corner_voxel_filter_size=0.0, planar_voxel_filter_size=0.0, device_id=0, keep_on_device=False):
         self.params = FeatureParams(C.sizeof(FeatureParams), lidar_vertical_scan, lidar_horizontal_scan, lidar_horizontal_resolution,
                                     min_distance, max_distance, corner_thres, planar_thres, corner_voxel_filter_size, planar_voxel_filter_size)
         self._h = C.c_void_p()
@@ -36,6 +36,30 @@ class FeatureFrontEnd:
         if rc != _lib.FLS_OK:
             self._h = C.c_void_p()
             raise FlsError(rc, "fls_features_create")
+        if keep_on_device:
+            self.keep_on_device(True)
+
+    # -- include/fls_features_device.h: the arrays stay on the device, `get` downloads what it is asked for ---------------
+    def keep_on_device(self, on: bool = True) -> None:
+        rc = _lib.lib().fls_features_keep_on_device(self._h, 1 if on else 0)
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_features_keep_on_device")
+
+    def attach_to(self, matcher, filtered: bool = True) -> int:
+        """The planar / corner clouds of the last extraction become `matcher`'s resident scans (a LoamFull handle); returns the status."""
+        return matcher.AttachFeatures(self, filtered)
+
+    def host_bytes(self) -> int:
+        """Bytes copied device -> host on behalf of the last frame so far (lazy downloads of `get` included)."""
+        n = C.c_uint64()
+        rc = _lib.lib().fls_features_get_host_bytes(self._h, C.byref(n))
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_features_get_host_bytes")
+        return int(n.value)
+
+    def stat(self) -> dict:
+        L = _lib.lib()
+        return {k: int(L.fls_features_stat(self._h, i)) for i, k in enumerate(("device_gathers", "device_filters", "filter_declines", "lazy_downloads"))}
 
     def project(self, raw: np.ndarray) -> int:
         raw = np.ascontiguousarray(raw)

@@ -204,6 +204,20 @@ class RegistrationInterface:
         what = ARRAYS[which][0] if which in ("ordered", "planar", "planar_filtered") else -1
         return int(_lib.lib().fls_scan_attach_preprocessed(self._h, getattr(pre, "_h", None), what))
 
+    def AttachFeatures(self, front, filtered: bool = True) -> int:
+        """fls_scan_attach_features (include/fls_features_device.h): the planar and corner clouds of `front`'s last extraction (a
+        features.FeatureFrontEnd; filtered: the VoxelGrid-filtered pair the reference hands to Match) become the resident scans of a
+        LoamFull handle -- the state UploadScan of those clouds would leave; device to device when `front` keeps its arrays there.
+        Returns the status (FLS_OK, or FLS_ERR_STATE / FLS_ERR_INVALID as the header lists them)."""
+        return int(_lib.lib().fls_scan_attach_features(self._h, getattr(front, "_h", None), 1 if filtered else 0))
+
+    def MatchFeatures(self, front, T: np.ndarray, update_map: bool = True, filtered: bool = True) -> bool:
+        """AttachFeatures + MatchResident: Match on the feature clouds of `front`'s last extraction."""
+        rc = self.AttachFeatures(front, filtered)
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_scan_attach_features")
+        return self.MatchResident(T, update_map)
+
     def MatchResident(self, T: np.ndarray, update_map: bool = False) -> bool:
         # hot in bench.py: one preallocated column-major pose buffer, no per-call ctypes object construction
         buf = getattr(self, "_Tbuf", None)

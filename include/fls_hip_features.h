@@ -8,9 +8,9 @@
 // the union of the two reference constructors (preprocessing.cpp:21-36).  Project() does not de-skew: hand over
 // corrected points, or raw points when the sensor did not move; the de-skewing projection is fls_features_project_deskew
 // (include/fls_preprocess.h).
-// Needs only <lidar/pointcloud_cluster.h> of the reference (for PointcloudCluster) and fls_features.h.
+// Needs only <lidar/pointcloud_cluster.h> of the reference (for PointcloudCluster), fls_features.h and fls_features_device.h.
 #pragma once
-#include "fls_features.h"
+#include "fls_features_device.h"
 
 #include <cstddef>
 #include <cstdio>
@@ -23,9 +23,12 @@ namespace loam {
 class HipFeatureFrontEnd {
 public:
     HipFeatureFrontEnd(int lidar_horizontal_scan, int lidar_vertical_scan, float lidar_horizontal_resolution, float min_distance,
-                       float max_distance, float corner_thr, float planar_thr, int device = 0) {
+                       float max_distance, float corner_thr, float planar_thr, int device = 0, float corner_voxel_filter_size = 0.f,
+                       float planar_voxel_filter_size = 0.f) {
         fls_feature_params p{};
         p.struct_size = sizeof(p);
+        p.corner_voxel_filter_size = corner_voxel_filter_size;  // (the two VoxelGrid filters of preprocessing.cpp:234-237; 0 = none)
+        p.planar_voxel_filter_size = planar_voxel_filter_size;
         p.lidar_vertical_scan = lidar_vertical_scan;
         p.lidar_horizontal_scan = lidar_horizontal_scan;
         p.lidar_horizontal_resolution = lidar_horizontal_resolution;
@@ -33,6 +36,7 @@ public:
         p.max_distance = max_distance;
         p.corner_thres = corner_thr;
         p.planar_thres = planar_thr;
+        filtered_ = corner_voxel_filter_size > 0.f && planar_voxel_filter_size > 0.f;
         const fls_status rc = fls_features_create(&p, device, &h_);
         if (rc != FLS_OK) {  // the reference CHECK-aborts on unset parameters (pointcloud_projector.cpp:23-29, feature_extractor.cpp:20-23)
             std::fprintf(stderr, "HipFeatureFrontEnd: fls_features_create failed: %s\n", fls_status_string(rc));
@@ -50,7 +54,8 @@ public:
         static const fls_point_layout lay{static_cast<uint32_t>(sizeof(RawPoint)), static_cast<uint32_t>(offsetof(RawPoint, x)),
                                           static_cast<uint32_t>(offsetof(RawPoint, intensity)), static_cast<uint32_t>(offsetof(RawPoint, ring))};
         size_t n = 0;
-        const fls_status rc = fls_features_project(h_, c.raw_cloud_.points.data(), c.raw_cloud_.points.size(), &lay, &n);
+        fls_status rc = fls_features_keep_on_device(h_, 0);  // (after a RunOnDevice: back to the default mode, every array downloaded eagerly)
+        if (rc == FLS_OK) rc = fls_features_project(h_, c.raw_cloud_.points.data(), c.raw_cloud_.points.size(), &lay, &n);
         if (rc != FLS_OK) { std::fprintf(stderr, "HipFeatureFrontEnd::Project: %s\n", fls_status_string(rc)); return false; }
         FetchCloud(FLS_FEAT_ORDERED, c.ordered_cloud_);
         // the reference keeps the two vectors at rows * cols entries (pointcloud_projector.cpp:37-44); the first N are live
@@ -76,6 +81,32 @@ public:
         return true;
     }
 
+    // Project() + ExtractFeatures() with every array left in device memory for HipRegistration::MatchFeatures
+    // (fls_hip_registration.h, include/fls_features_device.h): no cluster is filled; *n_corner / *n_planar are the cloud sizes.
+    // FillCluster() below delivers the clouds to callers that still need them on the host.  The handle stays in the resident mode until
+    // the next Project(), which restores the default; the two styles may alternate frame by frame.
+    template <class RawCloud>
+    bool RunOnDevice(const RawCloud& raw, size_t* n_corner = nullptr, size_t* n_planar = nullptr) {
+        using RawPoint = typename std::remove_const<typename std::remove_reference<decltype(raw.points[0])>::type>::type;
+        static const fls_point_layout lay{static_cast<uint32_t>(sizeof(RawPoint)), static_cast<uint32_t>(offsetof(RawPoint, x)),
+                                          static_cast<uint32_t>(offsetof(RawPoint, intensity)), static_cast<uint32_t>(offsetof(RawPoint, ring))};
+        size_t n = 0;
+        fls_status rc = fls_features_keep_on_device(h_, 1);
+        if (rc == FLS_OK) rc = fls_features_project(h_, raw.points.data(), raw.points.size(), &lay, &n);
+        if (rc == FLS_OK) rc = fls_features_extract(h_, n_corner, n_planar);
+        if (rc != FLS_OK) { std::fprintf(stderr, "HipFeatureFrontEnd::RunOnDevice: %s\n", fls_status_string(rc)); return false; }
+        return true;
+    }
+    // corner_cloud_ / planar_cloud_ of the last extraction (downloaded on first request after RunOnDevice)
+    template <class Cluster>
+    void FillCluster(Cluster& c) {
+        FetchCloud(FLS_FEAT_CORNER, c.corner_cloud_);
+        FetchCloud(FLS_FEAT_PLANAR, c.planar_cloud_);
+    }
+    fls_features_handle handle() const { return h_; }
+    // whether both VoxelGrid leaves are set: HipRegistration::MatchFeatures then attaches the filtered pair, as preprocessing.cpp does
+    bool filtered() const { return filtered_; }
+
 private:
     // library rows are packed {x, y, z, intensity}; pcl::PointXYZI is 32 bytes with the intensity in float 4
     template <class Cloud>
@@ -93,6 +124,7 @@ private:
         }
     }
     fls_features_handle h_ = nullptr;
+    bool filtered_ = false;
     std::vector<float> rows_;
 };
 

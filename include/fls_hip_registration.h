@@ -19,6 +19,7 @@
 #include "registration/registration_interface.h"
 #include "fls_reg.h"
 #include "fls_preprocess.h"
+#include "fls_features_device.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -158,6 +159,17 @@ public:
         fls_status rc = fls_scan_attach_preprocessed(handle_, pre.handle(), ordered ? FLS_PRE_ORDERED : pre.planar_what());
         if (rc == FLS_OK) rc = fls_match_resident(handle_, T.data(), /*update_map=*/1, &stats_);
         if (rc < 0) std::fprintf(stderr, "HipRegistration::MatchPreprocessed: %s\n", fls_status_string(rc));
+        return rc == FLS_OK;
+    }
+
+    // LoamFull: Match on the feature clouds a loam::HipFeatureFrontEnd (fls_hip_features.h) has just extracted with RunOnDevice, device
+    // to device (include/fls_features_device.h): the VoxelGrid-filtered pair where the front end has both leaves, else the unfiltered
+    // pair.  Any other kind: false.
+    template <class FrontEnd>
+    bool MatchFeatures(FrontEnd& front, Mat4d& T) {
+        fls_status rc = fls_scan_attach_features(handle_, front.handle(), front.filtered() ? 1 : 0);
+        if (rc == FLS_OK) rc = fls_match_resident(handle_, T.data(), /*update_map=*/1, &stats_);
+        if (rc < 0) std::fprintf(stderr, "HipRegistration::MatchFeatures: %s\n", fls_status_string(rc));
         return rc == FLS_OK;
     }
 
