@@ -49,7 +49,13 @@ def pinned_scenarios() -> list:
 
 def pinned_feature_cases() -> list:
     """Every feature case whose compiled-reference output has a committed record (tests/golden/ref_features_<name>.npz)."""
-    return list(FEATURE_CASES) + [f"ffuzz{s}" for s in FEATURE_FUZZ_SEEDS]
+    return list(FEATURE_CASES) + [f"ffuzz{s}" for s in FEATURE_FUZZ_SEEDS] + constructed_feature_cases()
+
+
+def constructed_feature_cases() -> list:
+    """The constructed frames of tests/feature_cases.py ("fc_<frame>") that the compiled reference can execute."""
+    from tests import feature_cases as FC
+    return [f"fc_{n}" for n in FC.FRAMES if n not in FC.NOT_FOR_REFERENCE]
 
 
 def _sha(*arrays) -> str:
@@ -338,6 +344,10 @@ FEATURE_FIELDS = ("ordered", "depth", "col", "row_start", "row_end", "corner", "
 
 def make_feature_case(name: str):
     from funny_lidar_slam_amd import synth
+    if name.startswith("fc_"):
+        from tests import feature_cases as FC
+        f = FC.frame(name[3:])
+        return f.raw, dict(f.params)
     if name.startswith("ffuzz"):
         # seeded random frame: either lidar model, poses up to 15 deg / 3 m off the scene's axes, thresholds and range gates away from the YAML's,
         # a random share of the returns dropped (ragged rows, rows that end up too short to extract from), driver order shuffled or not

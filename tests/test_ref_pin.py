@@ -106,6 +106,15 @@ def test_feature_oracle_equals_compiled_reference_fuzz(seed):
     refpin.assert_features_equal(refpin.ref_features_output(name), refpin.run_features("oracle", name, sort_mode=1), name)
 
 
+@pytest.mark.parametrize("name", refpin.constructed_feature_cases())
+def test_feature_oracle_equals_compiled_reference_constructed(name):
+    """The constructed frames of tests/feature_cases.py, on which the oracle judges the device kernels (tests/test_gpu_feature_stages.py): the cap,
+    the shared boundary element, column steps of 10 and 11, tied sectors, thresholds and range gates at equality, short rings, every column.
+    Every array bit for bit against the compiled reference, ties in libstdc++'s std::sort order (oracle sort_mode 1).  Left out: the frames of
+    feature_cases.NOT_FOR_REFERENCE (fewer than 12 ordered points: the reference reads outside its vectors, feature_extractor.cpp:50)."""
+    refpin.assert_features_equal(refpin.ref_features_output(name), refpin.run_features("oracle", name, sort_mode=1), name)
+
+
 @pytest.mark.parametrize("name", refpin.SCENARIOS)
 def test_oracle_equals_reference_golden(name):
     g = refpin.from_golden(np.load(os.path.join(GOLD, f"ref_{name}.npz")))
