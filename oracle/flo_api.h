@@ -112,6 +112,15 @@ void flo_set_ivox_capacity(void* h, size_t cap); /* test hook for the LRU evicti
 size_t flo_map_dump(void* h, int slot, float* xyz, size_t cap_points);
 /* NDT voxel dump: keys (n x 3 int32), mu (n x 3), info (n x 9 col-major), estimated (n) */
 size_t flo_ndt_dump(void* h, int32_t* keys, double* mu, double* info, uint8_t* est, int32_t* npts, size_t cap);
+/* The whole NDT map from an image in the layout of include/fls_map_ndt.h: data_ / grids_ (LRU order = entry order, oldest first), the voxel id counter
+ * and flag_first_scan.  The header's validity checks, all before anything changes: 0 = taken, -1 = refused (the oracle is as it was).  The state of the
+ * last Match and a localization handle's fitness tree are left alone. */
+int flo_ndt_import_image(void* h, const uint8_t* image, size_t n_bytes);
+/* Every alive voxel, OLDEST first (the image's order): keys (n x 3), vid, num_points, estimated, pending (count of waiting points), points (n x 8 x 3, zero
+ * beyond pending), mu (n x 3), sigma and info (n x 9 col-major).  A voxel beyond ndt_max_points_in_voxel is written with pending 0 and zero points.
+ * Returns the voxel count; fills at most cap entries. */
+size_t flo_ndt_dump_full(void* h, int32_t* keys, int32_t* vid, int32_t* npts, uint8_t* est, int32_t* pending, double* points, double* mu, double* sigma,
+                         double* info, size_t cap, int32_t* next_vid, int32_t* flag_first_scan);
 
 /* ---- LOAM feature front-end (src/loam/pointcloud_projector.cpp, src/loam/feature_extractor.cpp): see flo_features.h ---- */
 typedef struct flo_feat_params {

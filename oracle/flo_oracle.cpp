@@ -1145,6 +1145,110 @@ size_t flo_ndt_dump(void* h, int32_t* keys, double* mu, double* info, uint8_t* e
     return v.size();
 }
 
+// ---- the whole NDT map as an image in the layout of include/fls_map_ndt.h (restated here: the oracle shares no code with the product) ----
+namespace {
+constexpr int kImgCarry = 8;
+constexpr int kImgKeyLimit = (1 << 20) - 2;  // |key| bound per axis of the 21-bit packing
+struct NdtImgHeader {
+    char magic[8];
+    uint32_t revision, carry;
+    uint64_t total_bytes, n_voxels;
+    int32_t next_vid;
+    uint32_t flag_first_scan;
+    uint64_t voxel_size_bits;
+    int32_t min_points, max_points, capacity;
+    uint32_t reserved;
+};
+static_assert(sizeof(NdtImgHeader) == 64, "fls_ndt_image_header is 64 bytes");
+struct NdtImgLayout { size_t key, num_points, vid, estimated, pending, points, mu, sigma, info, total; };
+inline bool ndt_img_layout(uint64_t n64, NdtImgLayout& L) {
+    if (n64 > (uint64_t(1) << 40)) return false;
+    const size_t n = size_t(n64);
+    size_t o = sizeof(NdtImgHeader);
+    auto take = [&o](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~size_t(15); return at; };
+    L.key = take(n * 8); L.num_points = take(n * 4); L.vid = take(n * 4); L.estimated = take(n); L.pending = take(n);
+    L.points = take(n * kImgCarry * 24); L.mu = take(n * 24); L.sigma = take(n * 72); L.info = take(n * 72);
+    L.total = o;
+    return true;
+}
+inline int sext21(uint64_t f) { return int(uint32_t(f & 0x1FFFFFu) << 11) >> 11; }
+}  // namespace
+
+int flo_ndt_import_image(void* h, const uint8_t* img, size_t n_bytes) {
+    auto* m = dynamic_cast<IncNdt*>(static_cast<MatcherBase*>(h));
+    if (!m || !img || n_bytes < sizeof(NdtImgHeader)) return -1;
+    NdtImgHeader hd;
+    std::memcpy(&hd, img, sizeof(hd));
+    uint64_t vs_bits;
+    std::memcpy(&vs_bits, &m->p.ndt_voxel_size, 8);
+    NdtImgLayout L;
+    if (std::memcmp(hd.magic, "FLSNDT01", 8) != 0 || hd.revision != 1u || hd.carry != uint32_t(kImgCarry)) return -1;
+    if (hd.total_bytes != uint64_t(n_bytes) || hd.flag_first_scan > 1u || hd.reserved != 0u) return -1;
+    if (!ndt_img_layout(hd.n_voxels, L) || L.total != n_bytes) return -1;
+    if (hd.voxel_size_bits != vs_bits || hd.min_points != m->p.ndt_min_points_in_voxel || hd.max_points != m->p.ndt_max_points_in_voxel ||
+        hd.capacity != m->p.ndt_capacity)
+        return -1;
+    if (m->p.ndt_capacity <= 0 || hd.n_voxels >= uint64_t(m->p.ndt_capacity)) return -1;
+    if (hd.next_vid < 0 || uint64_t(hd.next_vid) < hd.n_voxels) return -1;
+    const size_t n = size_t(hd.n_voxels);
+    std::list<IncNdt::KD> data;
+    std::unordered_map<Key3, std::list<IncNdt::KD>::iterator, SpatialHash> grids;
+    for (size_t r = 0; r < n; ++r) {  // oldest first: every entry goes to the front
+        uint64_t key;
+        int32_t np, vid;
+        std::memcpy(&key, img + L.key + 8 * r, 8);
+        std::memcpy(&np, img + L.num_points + 4 * r, 4);
+        std::memcpy(&vid, img + L.vid + 4 * r, 4);
+        const uint8_t est = img[L.estimated + r], pend = img[L.pending + r];
+        const Key3 k{sext21(key >> 42), sext21(key >> 21), sext21(key)};
+        if ((key >> 63) != 0 || std::abs(k.x) >= kImgKeyLimit || std::abs(k.y) >= kImgKeyLimit || std::abs(k.z) >= kImgKeyLimit) return -1;
+        if (est > 1 || pend > kImgCarry || (pend > 0 && est == 1 && np > hd.max_points) || np < 0 || vid < 0 || vid >= hd.next_vid) return -1;
+        IncNdt::VoxelData v;
+        v.points.resize(size_t(pend) * 3);
+        if (pend) std::memcpy(v.points.data(), img + L.points + size_t(kImgCarry) * 24 * r, size_t(pend) * 24);
+        std::memcpy(v.mu, img + L.mu + 24 * r, 24);
+        std::memcpy(v.sigma, img + L.sigma + 72 * r, 72);
+        std::memcpy(v.info, img + L.info + 72 * r, 72);
+        if (est) {
+            for (double x : v.mu) if (!std::isfinite(x)) return -1;
+            for (double x : v.info) if (!std::isfinite(x)) return -1;
+        }
+        v.estimated = est != 0; v.num_points = np; v.vid = vid;
+        if (grids.count(k)) return -1;
+        data.emplace_front(k, v);
+        grids.insert({k, data.begin()});
+    }
+    m->data.swap(data);
+    m->grids.swap(grids);
+    m->next_vid = hd.next_vid;
+    m->flag_first_scan = hd.flag_first_scan != 0;
+    return 0;
+}
+
+size_t flo_ndt_dump_full(void* h, int32_t* keys, int32_t* vid, int32_t* npts, uint8_t* est, int32_t* pending, double* points, double* mu, double* sigma,
+                         double* info, size_t cap, int32_t* next_vid, int32_t* flag_first_scan) {
+    auto* m = dynamic_cast<IncNdt*>(static_cast<MatcherBase*>(h));
+    if (!m) return 0;
+    if (next_vid) *next_vid = m->next_vid;
+    if (flag_first_scan) *flag_first_scan = m->flag_first_scan ? 1 : 0;
+    size_t i = 0;
+    for (auto it = m->data.rbegin(); it != m->data.rend() && i < cap; ++it, ++i) {  // the list's back is the oldest voxel
+        const IncNdt::VoxelData& v = it->second;
+        keys[3 * i] = it->first.x; keys[3 * i + 1] = it->first.y; keys[3 * i + 2] = it->first.z;
+        vid[i] = v.vid; npts[i] = v.num_points; est[i] = v.estimated ? 1 : 0;
+        // a voxel beyond max_points never reads its list again: written without it
+        const bool beyond = v.estimated && v.num_points > m->p.ndt_max_points_in_voxel;
+        const size_t pend = beyond ? 0 : v.points.size() / 3;
+        pending[i] = int32_t(pend);
+        std::memset(points + size_t(kImgCarry) * 3 * i, 0, size_t(kImgCarry) * 24);
+        std::memcpy(points + size_t(kImgCarry) * 3 * i, v.points.data(), std::min<size_t>(pend, size_t(kImgCarry)) * 24);
+        std::memcpy(mu + 3 * i, v.mu, 24);
+        std::memcpy(sigma + 9 * i, v.sigma, 72);
+        std::memcpy(info + 9 * i, v.info, 72);
+    }
+    return m->data.size();
+}
+
 void* flo_feat_create(const flo_feat_params* p) {
     if (!p || p->struct_size != sizeof(flo_feat_params) || p->vertical_scan <= 0 || p->horizontal_scan <= 0) return nullptr;
     auto* s = new flo::FeatState();

@@ -192,6 +192,9 @@ def lib():
         L.flo_map_dump.argtypes = [C.c_void_p, C.c_int, fp, C.c_size_t]
         L.flo_ndt_dump.restype = C.c_size_t
         L.flo_ndt_dump.argtypes = [C.c_void_p, ip, dp, dp, bp, ip, C.c_size_t]
+        L.flo_ndt_import_image.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.flo_ndt_dump_full.restype = C.c_size_t
+        L.flo_ndt_dump_full.argtypes = [C.c_void_p, ip, ip, ip, bp, ip, dp, dp, dp, dp, C.c_size_t, ip, ip]
         L.flo_loop_match.restype = C.c_float
         L.flo_loop_match.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.c_int, dp, C.POINTER(LoopStats)]
         L.flo_ndt_derivatives.argtypes = [fp, C.c_size_t, fp, C.c_size_t, C.c_int, C.c_float, dp, dp, dp, dp]
@@ -370,6 +373,77 @@ class OracleMatcher:
                            info.ctypes.data_as(C.POINTER(C.c_double)), est.ctypes.data_as(C.POINTER(C.c_uint8)),
                            npts.ctypes.data_as(C.POINTER(C.c_int32)), n)
         return keys, mu, info.reshape(n, 3, 3).transpose(0, 2, 1).copy(), est, npts
+
+    def ndt_import_image(self, blob) -> bool:
+        """flo_ndt_import_image: the whole NDT map from an image (include/fls_map_ndt.h).  False: refused, the oracle is as it was."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        return lib().flo_ndt_import_image(self._h, blob.ctypes.data, blob.size) == 0
+
+    def ndt_dump_full(self) -> dict:
+        """flo_ndt_dump_full: every alive voxel, OLDEST first, as a dict of arrays -- keys (n, 3), vid, num_points, pending (n,) int32, estimated (n,)
+        uint8, points (n, 24), mu (n, 3), sigma and info (n, 9) column-major -- plus next_vid and flag_first_scan."""
+        n = self.map_size(0)
+        d = dict(keys=np.zeros((n, 3), np.int32), vid=np.zeros(n, np.int32), num_points=np.zeros(n, np.int32), estimated=np.zeros(n, np.uint8),
+                 pending=np.zeros(n, np.int32), points=np.zeros((n, NDT_IMAGE_CARRY * 3)), mu=np.zeros((n, 3)), sigma=np.zeros((n, 9)), info=np.zeros((n, 9)))
+        ip, bp, dp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        nv, ffs = C.c_int32(), C.c_int32()
+        m = lib().flo_ndt_dump_full(self._h, d["keys"].ctypes.data_as(ip), d["vid"].ctypes.data_as(ip), d["num_points"].ctypes.data_as(ip),
+                                    d["estimated"].ctypes.data_as(bp), d["pending"].ctypes.data_as(ip), d["points"].ctypes.data_as(dp),
+                                    d["mu"].ctypes.data_as(dp), d["sigma"].ctypes.data_as(dp), d["info"].ctypes.data_as(dp), n, C.byref(nv), C.byref(ffs))
+        assert m == n
+        d["next_vid"], d["flag_first_scan"] = int(nv.value), int(ffs.value)
+        return d
+
+    def ndt_image(self) -> np.ndarray:
+        """the map as the bytes of an image: ndt_encode_image of ndt_dump_full with this oracle's parameters"""
+        p = self.params
+        return ndt_encode_image(self.ndt_dump_full(), p.ndt_voxel_size, p.ndt_min_points_in_voxel, p.ndt_max_points_in_voxel, p.ndt_capacity)
+
+
+NDT_IMAGE_CARRY = 8
+NDT_KEY_LIMIT = (1 << 20) - 2
+
+
+def ndt_image_layout(n: int) -> dict:
+    """byte offsets of the arrays of an NDT image of n voxels (include/fls_map_ndt.h): a 64-byte header, every array on a 16-byte boundary"""
+    o, L = 64, {}
+    for name, width in (("key", 8), ("num_points", 4), ("vid", 4), ("estimated", 1), ("pending", 1), ("points", NDT_IMAGE_CARRY * 24), ("mu", 24),
+                        ("sigma", 72), ("info", 72)):
+        L[name] = o
+        o = (o + n * width + 15) & ~15
+    L["total"] = o
+    return L
+
+
+def ndt_pack_keys(keys) -> np.ndarray:
+    """(n, 3) voxel keys -> uint64 (n,): 21 bits per axis, x highest"""
+    k = (np.asarray(keys, np.int64).reshape(-1, 3) & 0x1FFFFF).astype(np.uint64)
+    return (k[:, 0] << np.uint64(42)) | (k[:, 1] << np.uint64(21)) | k[:, 2]
+
+
+def ndt_encode_image(d: dict, voxel_size: float, min_points: int, max_points: int, capacity: int) -> np.ndarray:
+    """A full dump (ndt_dump_full's dict, oldest voxel first; or one written by hand with the same entries) as image bytes.  The points beyond
+    `pending` must be zero, as the format asks; nothing else is checked here -- an importer does that."""
+    n = len(d["vid"])
+    L = ndt_image_layout(n)
+    blob = np.zeros(L["total"], np.uint8)
+    head = np.zeros(1, np.dtype([("magic", "S8"), ("revision", "<u4"), ("carry", "<u4"), ("total_bytes", "<u8"), ("n_voxels", "<u8"), ("next_vid", "<i4"),
+                                 ("flag_first_scan", "<u4"), ("voxel_size_bits", "<u8"), ("min_points", "<i4"), ("max_points", "<i4"), ("capacity", "<i4"),
+                                 ("reserved", "<u4")]))
+    assert head.itemsize == 64
+    head[0] = (b"FLSNDT01", 1, NDT_IMAGE_CARRY, L["total"], n, int(d["next_vid"]), int(d["flag_first_scan"]),
+               int(np.float64(voxel_size).view(np.uint64)), min_points, max_points, capacity, 0)
+    blob[:64] = head.view(np.uint8)
+    pend = np.asarray(d["pending"]).astype(np.int64)
+    assert ((pend >= 0) & (pend <= 255)).all()
+    pts = np.asarray(d["points"], np.float64).reshape(n, NDT_IMAGE_CARRY * 3)
+    assert not pts[np.arange(NDT_IMAGE_CARRY * 3)[None, :] >= 3 * np.minimum(pend, NDT_IMAGE_CARRY)[:, None]].any()
+    for name, arr in (("key", ndt_pack_keys(d["keys"])), ("num_points", np.asarray(d["num_points"], "<i4")), ("vid", np.asarray(d["vid"], "<i4")),
+                      ("estimated", np.asarray(d["estimated"], np.uint8)), ("pending", pend.astype(np.uint8)), ("points", pts),
+                      ("mu", np.asarray(d["mu"], np.float64)), ("sigma", np.asarray(d["sigma"], np.float64)), ("info", np.asarray(d["info"], np.float64))):
+        raw = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+        blob[L[name]:L[name] + raw.size] = raw
+    return blob
 
 
 def set_threads(n: int):
