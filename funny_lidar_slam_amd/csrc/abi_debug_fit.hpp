@@ -188,8 +188,8 @@ fls_status fls_debug_ndt_voxels(fls_handle h, size_t cap, int32_t* keys, int32_t
     if (cap && (!keys || !vid || !num_points || !estimated || !pending || !mu || !sigma || !info)) return FLS_ERR_INVALID;
     return guarded([&]() -> fls_status {
         NdtMatcher& m = *static_cast<NdtMatcher*>(h);
-        if (m.device_mode) FLS_HIP(hipSetDevice(h->device));  // (only a map that lives on the device is read from it; the host map needs none)
-        *n = m.dump_voxels(cap, NdtMatcher::VoxelDump{keys, vid, num_points, estimated, pending, mu, sigma, info});
+        if (m.map.on_device()) FLS_HIP(hipSetDevice(h->device));  // (only a map that lives on the device is read from it; the host map needs none)
+        *n = m.map.dump_voxels(cap, NdtMap::VoxelDump{keys, vid, num_points, estimated, pending, mu, sigma, info});
         return cap < *n ? FLS_ERR_NOMEM : FLS_OK;
     });
 }

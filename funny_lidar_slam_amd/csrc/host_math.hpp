@@ -149,7 +149,7 @@ __host__ __device__ inline bool ldlt_solve6(const double* H, const double* g, do
     return finite;  // a non-finite right-hand side goes through the exact solver as well
 }
 
-// ---- IncrementalNDT voxel statistics (incremental_ndt.h:91-179), shared by the host path (matcher_ndt.hpp) and the device
+// ---- IncrementalNDT voxel statistics (incremental_ndt.h:91-179), shared by the host path (ndt_image.hpp) and the device
 // map update (kernels_ndt_update.hpp): the same code, the same IEEE operation sequence on both sides ----
 template <class GetPt>
 __host__ __device__ inline void ndt_mean_cov(const int len, GetPt get, double* mean, double* cov) {  // ComputeMeanAndCov :91-110

@@ -1,10 +1,11 @@
 // ndt_image.hpp -- host side of the flat image of the NDT voxel map (include/fls_map_ndt.h): the array layout, the header checks an import
 // runs before it touches anything, and the host mirror of the map (pool + intrusive LRU list + key map, the replacement of the reference's
-// std::list + unordered_map, incremental_ndt.h:352-353) with its two conversions: mirror -> image and image rows -> mirror.  No HIP call in
-// here: tests/host/ndt_image_model_test.cpp runs all of it without a device.
+// std::list + unordered_map, incremental_ndt.h:352-353) with the host side of AddCloudToLocalMap (insert) and its two conversions: mirror ->
+// image and image rows -> mirror.  No HIP call in here: tests/host/ndt_image_model_test.cpp runs it without a device.
 #pragma once
 #include "../../include/fls_map_ndt.h"
-#include "host_maps.hpp"
+#include "host_math.hpp"
+#include <chrono>
 #include <cstring>
 #include <vector>
 
@@ -90,6 +91,10 @@ struct NdtMirror {
     int lru_head = -1, lru_tail = -1;
     size_t n_alive = 0;
     FlatKeyMap grids;  // key -> pool index
+    unsigned epoch = 0;
+    bool flag_first_scan = true;
+    int next_vid = 0;
+    std::vector<unsigned long long> evicted_image_keys;  // voxels evicted since the last image sync that had a row in the host-path image
     void lru_unlink(int v) {
         Voxel& x = pool[v];
         if (x.prev >= 0) pool[x.prev].next = x.next; else lru_head = x.next;
@@ -123,9 +128,97 @@ struct NdtMirror {
         ++n_alive;
     }
     // the pending points an image entry (or a device row) carries for v: none for a voxel beyond max_points, whose list is never read again
-    static size_t pending_of(const Voxel& v, const int max_points) {
-        const size_t keep = (v.estimated && v.num_points > max_points) ? 0 : v.pts.size() / 3;
-        return std::min<size_t>(keep, size_t(kNdtImageCarry));
+    // (`held`: the points waiting in the voxel, or a device row's carry count)
+    static size_t pending_of(const bool estimated, const int num_points, const size_t held, const int max_points) {
+        return std::min<size_t>((estimated && num_points > max_points) ? 0 : held, size_t(kNdtImageCarry));
+    }
+    static size_t pending_of(const Voxel& v, const int max_points) { return pending_of(v.estimated, v.num_points, v.pts.size() / 3, max_points); }
+
+    static void mean_cov(const std::vector<double>& pts, double* mean, double* cov) {  // ComputeMeanAndCov :91-110
+        const double* P = pts.data();
+        hm::ndt_mean_cov(int(pts.size() / 3), [P](int k, double* q) { q[0] = P[3 * k]; q[1] = P[3 * k + 1]; q[2] = P[3 * k + 2]; }, mean, cov);
+    }
+    void update_voxel(Voxel& v, const NdtImageParams& q) const {  // UpdateVoxel :130-179
+        if (flag_first_scan) {
+            if (v.pts.size() / 3 > 1u) { mean_cov(v.pts, v.mu, v.sigma); hm::ndt_regularised_info(v.sigma, v.info); }
+            else {
+                v.mu[0] = v.pts[0]; v.mu[1] = v.pts[1]; v.mu[2] = v.pts[2];
+                for (int k = 0; k < 9; ++k) v.info[k] = ((k % 4 == 0) ? 1.0 : 0.0) * 1.0e2;
+            }
+            v.estimated = v.dirty = true; v.pts.clear();
+            return;
+        }
+        if (v.estimated && v.num_points > q.max_points) return;
+        const int npts = int(v.pts.size() / 3);
+        if (!v.estimated && npts > q.min_points) {
+            mean_cov(v.pts, v.mu, v.sigma);
+            hm::ndt_regularised_info(v.sigma, v.info);
+            v.estimated = v.dirty = true; v.pts.clear();
+        } else if (v.estimated && npts > q.min_points) {
+            double cmu[3], cvar[9];
+            mean_cov(v.pts, cmu, cvar);
+            hm::ndt_merge(v.mu, v.sigma, v.info, v.num_points, cmu, cvar, npts);
+            v.num_points += npts;
+            v.dirty = true; v.pts.clear();
+        }
+    }
+    // AddCloudToLocalMap :192-221 on the mirror: the filtered world cloud (keys in range) point by point -- insert, LRU touch, eviction at the
+    // capacity -- then UpdateVoxel once per voxel the call touched.  Returns those voxels' pool indices; *t_inserted: the time between the two parts.
+    std::vector<int> insert(const std::vector<PtI>& cloud_world, const NdtImageParams& q, std::chrono::steady_clock::time_point* t_inserted = nullptr) {
+        const double inv_voxel = 1.0 / q.voxel_size;
+        ++epoch;
+        std::vector<int> touched;
+        touched.reserve(4096);
+        for (const PtI& pt : cloud_world) {
+            const double pe[3] = {double(pt.x), double(pt.y), double(pt.z)};
+            const int kx = int(pe[0] * inv_voxel), ky = int(pe[1] * inv_voxel), kz = int(pe[2] * inv_voxel);  // cast<int>: truncation (:195)
+            const unsigned long long key = pack_key(kx, ky, kz);
+            int vi = grids.find(key);
+            if (vi < 0) {
+                if (!free_ix.empty()) { vi = free_ix.back(); free_ix.pop_back(); }
+                else { vi = int(pool.size()); pool.emplace_back(); }
+                Voxel& v = pool[vi];
+                v.kx = kx; v.ky = ky; v.kz = kz;
+                v.pts.clear();
+                v.pts.push_back(pe[0]); v.pts.push_back(pe[1]); v.pts.push_back(pe[2]);
+                v.estimated = false; v.num_points = 1;
+                for (int a = 0; a < 3; ++a) v.mu[a] = 0.0;  // VoxelData's initialisers (:79-81): a recycled pool entry is a new voxel
+                for (int a = 0; a < 9; ++a) v.sigma[a] = v.info[a] = 0.0;
+                v.vid = next_vid++;
+                v.slot = -1; v.dirty = false; v.epoch = 0;
+                lru_push_front(vi); grids.insert(key, vi); ++n_alive;
+                if (n_alive >= size_t(q.capacity)) {  // :202-205
+                    const int b = lru_tail;
+                    Voxel& e = pool[b];
+                    const unsigned long long ek = pack_key(e.kx, e.ky, e.kz);
+                    grids.erase(ek);
+                    if (e.slot >= 0) evicted_image_keys.push_back(ek);
+                    e.slot = -1;
+                    e.epoch = 0;  // a voxel evicted within the call that touched it gets no UpdateVoxel (the reference would dereference a null entry)
+                    lru_unlink(b); free_ix.push_back(b); --n_alive;
+                    if (b == vi) continue;  // capacity 1: the new voxel itself
+                }
+            } else {
+                Voxel& v = pool[vi];
+                v.pts.push_back(pe[0]); v.pts.push_back(pe[1]); v.pts.push_back(pe[2]);
+                if (!v.estimated) v.num_points++;
+                if (lru_head != vi) { lru_unlink(vi); lru_push_front(vi); }
+            }
+            Voxel& v = pool[vi];
+            if (v.epoch != epoch) { v.epoch = epoch; touched.push_back(vi); }
+        }
+        if (t_inserted) *t_inserted = std::chrono::steady_clock::now();
+        size_t w = 0;
+        for (size_t k = 0; k < touched.size(); ++k) {
+            const int vi = touched[k];
+            if (pool[vi].epoch != epoch) continue;  // evicted after its touch
+            pool[vi].epoch = epoch + 0x40000000u;   // a pool entry re-created after an eviction appears twice: processed once
+            update_voxel(pool[vi], q);
+            touched[w++] = vi;
+        }
+        touched.resize(w);
+        for (int vi : touched) pool[vi].epoch = epoch;
+        return touched;
     }
 };
 

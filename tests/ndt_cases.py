@@ -7,7 +7,7 @@ backbone of well-separated estimated voxels with one point each, which keeps H c
 
 Histories (histories()): a start image (or none) + clouds handed to AddCloudToLocalMap one by one.  A mapping handle that imported an image with
 flag_first_scan = 0, or that has taken its first cloud, runs every cloud as a batch of UpdateVoxel (incremental_ndt.h:130-179; ndt_upd_voxel in
-csrc/kernels_ndt_update.hpp on the device, NdtMatcher::update_voxel on the host).  Every voxel of a history follows a script: points per batch.
+csrc/kernels_ndt_update.hpp on the device, NdtMirror::update_voxel on the host).  Every voxel of a history follows a script: points per batch.
 
 tests/test_ndt_cases.py shows on the oracle alone that every case is what it says; tests/test_gpu_ndt_stages.py runs them on the device."""
 import functools

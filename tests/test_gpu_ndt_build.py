@@ -1,4 +1,4 @@
-"""The NDT voxel map built from a whole cloud on the device (NdtMatcher::add_cloud_build, ndt_upd_voxel_first in kernels_ndt_update.hpp): the
+"""The NDT voxel map built from a whole cloud on the device (NdtMatcher::add_cloud_build -> NdtMap::build, ndt_upd_voxel_first in kernels_ndt_update.hpp): the
 first AddCloudToLocalMap of every handle and every reload of a localization handle.  Two handles per test: A created with
 FLS_NDT_DEVICE_BUILD=0 (host VoxelGrid, sequential insert, UpdateVoxel on one thread: the path every handle took before), B with the default.
 B must be indistinguishable from A: every array of ndt_voxels() (include/fls_debug_ndt.h) equal, LRU order included, and Matches bit for bit;

@@ -1,7 +1,7 @@
 """What AddCloudToLocalMap costs when the NDT map takes a whole cloud: the first insert of a mapping handle and every reload of a localization
 handle (FLS_INCREMENTAL_NDT).  A = FLS_NDT_DEVICE_BUILD=0 (host VoxelGrid, sequential insert + LRU, UpdateVoxel on one thread, image rebuild; a
 mapping handle then uploads the mirror to enter device mode: the only path before the device build existed), B = the default
-(NdtMatcher::add_cloud_build: device VoxelGrid + the update chain with ndt_upd_voxel_first, kernels_ndt_update.hpp).
+(NdtMatcher::add_cloud_build -> NdtMap::build: device VoxelGrid + the update chain with ndt_upd_voxel_first, kernels_ndt_update.hpp).
 
 Three clouds: the 1,000,000-point map of BASELINE configs[2], a 100,000-point cut of it (the points nearest the origin), one 64 x 1800 scan.
 Per cloud and scenario, A and B alternate in one process over warmup + rounds rounds: a localization pair reloads the same two handles (from the
