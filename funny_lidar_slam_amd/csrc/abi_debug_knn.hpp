@@ -22,7 +22,7 @@ struct DebugKnnSide {
     DevBuf<unsigned char> cnt, flag;
     DevBuf<float> kth;
     int nq = 0;
-    // the grid as KdLocalMap::rebuild makes it: on the device, else (or with host_grid) on the host
+    // the grid as KdLocalMap::rebuild (kd_map.hpp) makes it: on the device, else (or with host_grid) on the host
     fls_status prepare_grid(const float* m, int nm, const float* q, int n_query, int stride, float cell, int rings, bool host_grid) {
         const std::vector<PtI> mc = cloud_from(m, size_t(nm), stride), qc = cloud_from(q, size_t(n_query), stride);
         nq = n_query;

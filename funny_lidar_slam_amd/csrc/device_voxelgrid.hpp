@@ -8,8 +8,6 @@
 #include "kernels_exactsort.hpp"
 #include "kernels_voxelgrid_plan.hpp"
 #include "kernels_gridbuild.hpp"
-#include "kernels_kd_push.hpp"
-#include "kd_lazy_deque.hpp"
 #include "matcher_base.hpp"
 #include <atomic>
 #include <cstdlib>
@@ -454,246 +452,6 @@ struct DeviceGridBuilder {
         g.n_cells = 0;  // (not counted on this path)
         ++builds;
         return true;
-    }
-};
-
-// The local-map deque of the kd-tree kinds on the device (icp_optimized.h:173-184, loam_full_kdtree.h:70-91,
-// loam_point_to_plane_kdtree.h:60-71): the clouds of the deque live back to back in four SoA planes, so "concatenate the deque"
-// is a pointer + a length.  push_back appends (one host-to-device copy of the NEW cloud + a de-interleave kernel), pop_front
-// advances the head; the planes are re-packed when the tail reaches the end.  Only used by the opt-in device map filter.
-struct DeviceCloudRing {
-    DevBuf<float> planes;  // x | y | z | i, `cap` floats each
-    DevBuf<float4> rows;   // staging of the cloud being appended
-    PinnedBuf<float4> h_rows;
-    size_t cap = 0, head = 0, tail = 0;
-    std::deque<size_t> sizes;
-    const float* x() const { return planes.p + head; }
-    const float* y() const { return planes.p + cap + head; }
-    const float* z() const { return planes.p + 2 * cap + head; }
-    const float* in() const { return planes.p + 3 * cap + head; }
-    size_t size() const { return tail - head; }
-    void clear() { head = tail = 0; sizes.clear(); }
-    void pop_front() {
-        if (sizes.empty()) return;
-        head += sizes.front();
-        sizes.pop_front();
-        if (sizes.empty()) head = tail = 0;
-    }
-    void make_room(size_t extra, hipStream_t s) {
-        if (tail + extra <= cap) return;
-        const size_t live = tail - head;
-        size_t ncap = cap;
-        while (live + extra > ncap || ncap < 65536) ncap = ncap ? ncap * 2 : 65536;
-        if (ncap == cap && head >= live) {  // re-pack in place: source and destination do not overlap
-            for (int a = 0; a < 4 && live; ++a)
-                FLS_HIP(hipMemcpyAsync(planes.p + size_t(a) * cap, planes.p + size_t(a) * cap + head, live * sizeof(float), hipMemcpyDeviceToDevice, s));
-        } else {
-            if (ncap == cap) ncap *= 2;
-            DevBuf<float> np;
-            np.reserve(4 * ncap);
-            for (int a = 0; a < 4 && live; ++a)
-                FLS_HIP(hipMemcpyAsync(np.p + size_t(a) * ncap, planes.p + size_t(a) * cap + head, live * sizeof(float), hipMemcpyDeviceToDevice, s));
-            FLS_HIP(hipStreamSynchronize(s));  // the old planes are freed below
-            std::swap(planes.p, np.p);  // (np now owns the old planes and frees them)
-            std::swap(planes.cap, np.cap);
-            cap = ncap;
-        }
-        head = 0;
-        tail = live;
-    }
-    void push_back(const std::vector<PtI>& c, hipStream_t s) {
-        const size_t n = c.size();
-        make_room(n, s);
-        if (n) {
-            static_assert(sizeof(PtI) == sizeof(float4), "PtI rows are float4 rows");
-            h_rows.reserve(n);
-            rows.reserve(n);
-            std::memcpy(h_rows.p, c.data(), n * sizeof(PtI));
-            FLS_HIP(hipMemcpyAsync(rows.p, h_rows.p, n * sizeof(float4), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(soa_append, dim3(unsigned((n + kVgBlock - 1) / kVgBlock)), dim3(kVgBlock), 0, s, (const float4*)rows.p, int(n),
-                               planes.p + tail, planes.p + cap + tail, planes.p + 2 * cap + tail, planes.p + 3 * cap + tail);
-            FLS_HIP(hipGetLastError());
-            FLS_HIP(hipStreamSynchronize(s));  // the pinned staging rows are reused by the next push
-        }
-        tail += n;
-        sizes.push_back(n);
-    }
-    // The same append for clouds that already lie on this device (kernels_kd_push.hpp): n_rings (1 or 2) rings take one cloud each in ONE
-    // launch on `s`, transformed on the way as `a.mode` says (the caller fills a.mode / a.R / a.t / a.T; the maps are filled here).  Nothing
-    // waits for the launch: whatever reads the rings next is queued behind it on the same stream.  make_room runs unchanged.
-    // false: a ring cannot take its cloud (its live points + the cloud would pass the 2^31 - 1 floats the 32-bit point counts of the
-    // ring's kernels can address) -- nothing has changed, the caller pushes through the host.
-    struct DeviceCloud { const float *x, *y, *z, *in; size_t n; };
-    static constexpr size_t kMaxPoints = 0x7fffffffu;
-    static bool push_back_device(DeviceCloudRing* const* rings, const DeviceCloud* src, const int n_rings, KdPushArgs a, hipStream_t s) {
-        size_t total = 0;
-        for (int r = 0; r < n_rings; ++r) {
-            if (src[r].n > kMaxPoints || rings[r]->size() > kMaxPoints - src[r].n) return false;
-            total += src[r].n;
-        }
-        if (total > kMaxPoints) return false;
-        a.m[0] = a.m[1] = KdPushMap{};
-        for (int r = 0; r < n_rings; ++r) {
-            DeviceCloudRing& g = *rings[r];
-            const size_t n = src[r].n;
-            g.make_room(n, s);  // tail + n <= cap from here on: the launch below writes floats tail .. tail + n of every plane
-            if (!n) continue;
-            float* const at = g.planes.p + g.tail;
-            a.m[r] = KdPushMap{src[r].x, src[r].y, src[r].z, reinterpret_cast<const unsigned*>(src[r].in), at, at + g.cap, at + 2 * g.cap,
-                               reinterpret_cast<unsigned*>(at + 3 * g.cap), unsigned(n)};
-        }
-        if (total) {
-            hipLaunchKernelGGL(kd_push_kernel, dim3(unsigned((total + kKdPushBlock - 1) / kKdPushBlock)), dim3(kKdPushBlock), 0, s, a);
-            FLS_HIP(hipGetLastError());
-        }
-        for (int r = 0; r < n_rings; ++r) {
-            rings[r]->tail += src[r].n;
-            rings[r]->sizes.push_back(src[r].n);
-        }
-        return true;
-    }
-};
-
-// Map maintenance of one kd-tree kind on the device: the cell-grid build and the deque + map-side pcl::VoxelGrid (bit-identical to
-// the reference's since round 4: kernels_exactsort.hpp; FLS_DEVICE_VOXELGRID=0 = the host filter).  Whatever the device
-// declines is redone by the host path, on the host deque (KdLocalMap::host_clouds fetches what a device push left in the ring alone).
-struct KdMapDevice {
-    bool grid_on_device = true;  // FLS_DEVICE_GRID_BUILD=0: host std::sort + bucket loop + upload (A/B)
-    bool vg_on_device = true;    // FLS_DEVICE_VOXELGRID=0: the host filter
-    DeviceGridBuilder builder;
-    DeviceVoxelGrid vg;
-    PinnedBuf<float> stage;
-    DevBuf<float> xyz;
-    bool push_on_device = true;  // FLS_KD_DEVICE_PUSH=0: a keyframe goes through the host (download, host transform, upload) as every other push
-    unsigned long long device_filters = 0, host_filters = 0;
-    void init() {
-        if (const char* e = std::getenv("FLS_DEVICE_GRID_BUILD")) grid_on_device = std::atoi(e) != 0;
-        vg_on_device = device_voxelgrid_mode() != 0;
-        if (const char* e = std::getenv("FLS_KD_DEVICE_PUSH")) push_on_device = std::atoi(e) != 0;
-        push_on_device = push_on_device && vg_on_device && grid_on_device;  // (no ring without the other two)
-    }
-    // grid over a HOST cloud (the exact host filter's output, or an unfiltered cloud)
-    fls_status build_from_host(CellGridImage& grid, const std::vector<PtI>& cloud, float cell, hipStream_t s, int rings = 1) {
-        const size_t n = cloud.size();
-        if (grid_on_device && n != 0) {
-            stage.reserve(3 * n);
-            xyz.reserve(3 * n);
-            for (size_t i = 0; i < n; ++i) { stage.p[i] = cloud[i].x; stage.p[n + i] = cloud[i].y; stage.p[2 * n + i] = cloud[i].z; }
-            FLS_HIP(hipMemcpyAsync(xyz.p, stage.p, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-            if (builder.run(grid, xyz.p, xyz.p + n, xyz.p + 2 * n, n, cell, rings, false, s)) return FLS_OK;  // (run() synchronises: the staging is free)
-            FLS_HIP(hipStreamSynchronize(s));
-        }
-        return grid.build(cloud, cell, s, rings);
-    }
-    // local map = [VoxelGrid of] the concatenated deque, then the grid: all on the device.  false: declined, nothing changed.
-    bool filter_and_build(CellGridImage& grid, const DeviceCloudRing& ring, bool filter, float leaf, float cell, int rings, size_t& n_map,
-                          hipStream_t s) {
-        if (!vg_on_device || !grid_on_device) return false;
-        size_t n = ring.size();
-        if (n == 0) return false;
-        const float *x = ring.x(), *y = ring.y(), *z = ring.z();
-        if (filter) {
-            if (!vg.run(x, y, z, ring.in(), n, leaf, s)) return false;
-            x = vg.ox(); y = vg.oy(); z = vg.oz();
-            n = vg.n_out;
-            if (n == 0) return false;
-        }
-        if (!builder.run(grid, x, y, z, n, cell, rings, false, s)) return false;
-        n_map = n;
-        ++device_filters;
-        return true;
-    }
-};
-
-// The local map of one kd-tree kind (LoamFull: of one feature class): the reference's deque of clouds (AddCloudToLocalMap: icp_optimized.h:165-189,
-// loam_full_kdtree.h:65-104, loam_point_to_plane_kdtree.h:56-79) and what the Match searches, the cell grid over [the VoxelGrid of] the
-// concatenated deque.  The owner pushes / trims as its reference does and calls rebuild() at the same moments; cell size and search depth are
-// the owner's.  With `on_device` the deque is mirrored in a DeviceCloudRing and filter + grid build never leave the device.
-//
-// The host deque is LAZY (kd_lazy_deque.hpp): a keyframe pushed on the device (push_device) exists in the ring alone until something reads
-// the host deque -- host_clouds(), the one accessor: a rebuild the device declined, an export through the host -- which first copies what is
-// missing out of the ring.  Count and sizes (deque.size(), deque.sizes) are read without a download.
-struct KdLocalMap {
-    KdLazyDeque deque;        // the reference's deque; host copies of the clouds a host push or an import brought, or a fetch
-    DeviceCloudRing ring;     // the deque's clouds back to back on the device (device path only)
-    std::vector<PtI> local;   // the map cloud on the host: what the host path built, empty after a device rebuild
-    CellGridImage grid;
-    KdMapDevice dev;
-    size_t n = 0;             // points of the local map, whichever path built it (fls_map_size)
-    bool on_device = false;   // the deque is mirrored on the device: FLS_DEVICE_VOXELGRID != 0 and FLS_DEVICE_GRID_BUILD != 0
-    bool rebuild_declined = false;  // the last rebuild(): the handle is on the device path and the device declined
-    PinnedBuf<unsigned> fetch_stage;  // x | y | z | i of the run being fetched
-    unsigned long long device_pushes = 0, host_pushes = 0, fetched = 0;
-    void init() {
-        dev.init();
-        on_device = dev.vg_on_device && dev.grid_on_device;
-    }
-    void push(const std::vector<PtI>& cloud, hipStream_t s) {
-        deque.push_host(cloud);
-        if (on_device) { ring.push_back(cloud, s); ++host_pushes; }
-    }
-    bool can_push_device() const { return on_device && dev.push_on_device; }
-    // A keyframe from clouds that lie on this device, one per map of `maps` (LoamFull: two), in one launch (DeviceCloudRing::push_back_device).
-    // false: not on the device-push path, or a ring cannot take its cloud -- every map is as it was and the caller pushes through the host.
-    static bool push_device(KdLocalMap* const* maps, const DeviceCloudRing::DeviceCloud* src, const int n_maps, const KdPushArgs& a, hipStream_t s) {
-        DeviceCloudRing* rings[2] = {nullptr, nullptr};
-        for (int m = 0; m < n_maps; ++m) {
-            if (!maps[m]->can_push_device()) return false;
-            rings[m] = &maps[m]->ring;
-        }
-        if (!DeviceCloudRing::push_back_device(rings, src, n_maps, a, s)) return false;
-        for (int m = 0; m < n_maps; ++m) { maps[m]->deque.push_device(src[m].n); ++maps[m]->device_pushes; }
-        return true;
-    }
-    void trim(size_t max_clouds) {  // (whether or not the cloud that leaves was ever fetched)
-        if (deque.trim(max_clouds) && on_device) ring.pop_front();
-    }
-    void reset_to(const std::vector<PtI>& cloud, hipStream_t s) {  // localization mode: the map is the last cloud alone
-        deque.clear();
-        ring.clear();
-        push(cloud, s);
-    }
-    // an import: the image's deque, every cloud present on the host (the caller has put the rows into the ring's planes)
-    void replace_deque(KdDeque&& all) {
-        deque.assign(std::move(all));
-        if (!on_device) return;
-        ring.sizes.clear();
-        for (const size_t sz : deque.sizes) ring.sizes.push_back(sz);
-    }
-    // THE reader of the host deque: whatever the host does not hold is fetched from the ring first, run by run (four copies and one wait each)
-    const KdDeque& host_clouds(hipStream_t s) {
-        if (deque.complete()) return deque.clouds;
-        for (const KdLazyDeque::Run& r : deque.missing_runs()) {
-            if (r.n_points) {
-                fetch_stage.reserve(4 * r.n_points);
-                for (int a = 0; a < 4; ++a)
-                    FLS_HIP(hipMemcpyAsync(fetch_stage.p + size_t(a) * r.n_points, ring.planes.p + size_t(a) * ring.cap + ring.head + r.offset, r.n_points * sizeof(float),
-                                           hipMemcpyDeviceToHost, s));
-                FLS_HIP(hipStreamSynchronize(s));
-            }
-            const unsigned* q = fetch_stage.p;
-            deque.fill(r, q, q + r.n_points, q + 2 * r.n_points, q + 3 * r.n_points);
-            fetched += r.n_clouds;
-        }
-        return deque.clouds;
-    }
-    // local map = [VoxelGrid(leaf) of] the concatenated deque, then the grid (cells of `cell`, searched `rings` deep): on the device, or on
-    // the host for whatever the device declines
-    fls_status rebuild(bool filter, float leaf, float cell, int rings, hipStream_t s) {
-        rebuild_declined = false;
-        if (on_device && dev.filter_and_build(grid, ring, filter, leaf, cell, rings, n, s)) { local.clear(); return FLS_OK; }
-        rebuild_declined = on_device;
-        local.clear();
-        for (const auto& c : host_clouds(s)) local.insert(local.end(), c.begin(), c.end());
-        if (filter) { local = voxel_grid(local, leaf); ++dev.host_filters; }
-        n = local.size();
-        return dev.build_from_host(grid, local, cell, s, rings);
-    }
-    // fls_map_size slots 114 / 115 / 116: cell grids built on the device / map updates filtered on the device / ... filtered on the host;
-    // 164 / 165 / 166: clouds pushed on the device / pushed through the host while a ring exists / fetched to the host lazily
-    size_t counter(int slot) const {
-        return size_t(slot == 114 ? dev.builder.builds : slot == 115 ? dev.device_filters : slot == 116 ? dev.host_filters : slot == 164 ? device_pushes
-                      : slot == 165 ? host_pushes : fetched);
     }
 };
 

@@ -1,7 +1,7 @@
 // kd_image.hpp -- host side of the flat image of the kd-tree kinds' local maps (include/fls_map_kd.h): the layout arithmetic with its
 // overflow checks, the checks an import runs before it touches anything (header, sizes, padding), and the two conversions deque -> bytes
 // and bytes -> deque.  No HIP call in here: tests/host/kd_image_model_test.cpp runs all of it without a device.  A batch lane
-// (`owner != nullptr` in matchers_kd.hpp) never gets here: it exports 0 bytes and refuses every import with FLS_ERR_INVALID.
+// (`KdMatcher::owner != nullptr`, matchers_kd.hpp) never gets here: it exports 0 bytes and refuses every import with FLS_ERR_INVALID.
 #pragma once
 #include "../../include/fls_map_kd.h"
 #include "host_maps.hpp"

@@ -1,5 +1,5 @@
 // kd_lazy_deque.hpp -- the bookkeeping of the kd-tree kinds' host deque once a keyframe can be pushed on the device (kernels_kd_push.hpp):
-// the LOGICAL deque is what the reference's deque of clouds would be; the DeviceCloudRing (device_voxelgrid.hpp) holds all of it whenever
+// the LOGICAL deque is what the reference's deque of clouds would be; the DeviceCloudRing (kd_map.hpp) holds all of it whenever
 // the handle is on the device path, the host holds a subset of whole clouds.  A cloud pushed on the device has no host copy until something
 // reads the host deque (a rebuild the device declined, an export through the host); what is missing is then copied out of the ring's four
 // planes, run by run, and is bit for bit what a host push would have stored.  This header knows which clouds are present, which ring floats

@@ -1,5 +1,5 @@
 // kernels_kd_image.hpp -- the rows of the flat image of the kd-tree kinds' local maps (include/fls_map_kd.h, kd_image.hpp) written from and
-// read into the four SoA planes of a DeviceCloudRing (device_voxelgrid.hpp).
+// read into the four SoA planes of a DeviceCloudRing (kd_map.hpp).
 //   kd_image_pack_kernel    planes at head .. tail of one or two rings -> the float4 rows of one image, one launch
 //   kd_image_unpack_kernel  the rows of one or two maps -> planes that start at float 0 of a ring of the importer's own
 // Pure streaming, no arithmetic on the values (they move as 32-bit words: NaN payloads survive).  A lane serves four consecutive floats of

@@ -1,4 +1,4 @@
-// kernels_kd_push.hpp -- a keyframe of the kd-tree kinds pushed into the DeviceCloudRing (device_voxelgrid.hpp) without leaving the device:
+// kernels_kd_push.hpp -- a keyframe of the kd-tree kinds pushed into the DeviceCloudRing (kd_map.hpp) without leaving the device:
 // the cloud the Match just used lies on the device as x | y | z planes plus an intensity plane, the ring's four planes are its destination.
 //   kd_push_kernel  source planes of one or two clouds -> transformed points at the tails of one or two rings, one launch
 // The transform is spelled exactly as the host spells it (host_math.hpp), and the library is built with -ffp-contract=off, so the rows are

@@ -2,8 +2,9 @@
 //   IcpMatcher       <- IcpOptimized<double>            include/registration/icp_optimized.h
 //   LoamFullMatcher  <- LoamFull<double>                include/registration/loam_full_kdtree.h
 //   P2PlaneKdMatcher <- LoamPointToPlaneKdtree<double>  include/registration/loam_point_to_plane_kdtree.h
-// Map bookkeeping follows the reference's AddCloudToLocalMap (deque of clouds, VoxelGrid, rebuild): one KdLocalMap
-// (device_voxelgrid.hpp) per map, two for LoamFull; the kd-tree is replaced by an exact-kNN cell grid rebuilt at the same moments.
+// Map bookkeeping follows the reference's AddCloudToLocalMap (deque of clouds, VoxelGrid, rebuild): the handle's KdMaps (kd_map.hpp), one
+// KdLocalMap per map, two for LoamFull; the kd-tree is replaced by an exact-kNN cell grid rebuilt at the same moments.  This file keeps the
+// matchers: init checks, scan upload / attach, Match, fitness, correspondences, batch.
 #pragma once
 #include "matcher_base.hpp"
 #include "host_math.hpp"
@@ -11,8 +12,7 @@
 #include "kernels_knn.hpp"
 #include "kernels_grid_coop.hpp"
 #include "fitness_host.hpp"
-#include "kd_image.hpp"
-#include "kernels_kd_image.hpp"
+#include "kd_map.hpp"
 
 namespace fls {
 
@@ -27,306 +27,78 @@ inline float cell_for_gate(double gate_sq) {  // smallest safe cell for a square
 inline unsigned knn_grid_blocks(size_t n) { return unsigned((((n * 8 + 255) / 256) + 63) / 64 * 64); }
 
 // ---------------------------------------------------------------------------------------------
-// The local maps of one kd-tree handle as one flat image (include/fls_map_kd.h, kd_image.hpp): fls_map_export / _import, fls_map_image_*,
-// replica sets.  The image carries the deque(s) and the keyframe gate; the bytes are a function of the logical state, so the rings of a
-// device-path handle (packed by kd_image_pack_kernel) and the host deques of a host-path one give the same image.  An import checks the
-// whole image on the host, unpacks the rows into planes of its own (kept for the next import: a replica refresh allocates nothing after
-// the first), and only then swaps them into the handle and runs the kind's own rebuild.  An import fills the host deque EAGERLY (every cloud
-// present, as after a host push; a keyframe pushed on the device has no host copy until something reads one, KdLocalMap::host_clouds): one
-// device-to-host copy when the source is device memory.  An export from the rings reads sizes alone and fetches nothing.
-// fls_map_size slots 160-163.
-struct KdMapImage {
-    unsigned long long exports_device = 0, exports_host = 0, imports_device = 0, imports_host = 0;
-    DevBuf<unsigned char> img_stage;      // the image on the device, where the caller's buffer is not device memory the kernels can use directly
-    PinnedBuf<unsigned char> img_pinned;  // header + sizes on their way up; the whole image on its way down
-    struct SpareRing { DevBuf<float> planes; size_t cap = 0; } spare[2];  // what an import unpacks into / what it took the handle's planes for
-    DevBuf<unsigned char> replica_out, replica_in;  // the image of a replication on the owner's device / on the replica's
-    static bool kernel_aligned(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-    size_t counter(int slot) const { return size_t(slot == 160 ? exports_device : slot == 161 ? exports_host : slot == 162 ? imports_device : imports_host); }
+// What the three kinds share: the maps, a batch lane's view of its owner's, AddCloudToLocalMap, the image and replica calls, and the
+// keyframe update that ends a Match.  A kind supplies the scan(s) of that keyframe: on the device where they lie there, else on the host.
+struct KdMatcher : fls_matcher {
+    KdMaps maps;
+    const KdMatcher* owner = nullptr;  // batch lane: reads the owner's map grid(s)
+    double final_T[16]{};              // the last Match's pose (Icp, P2PlaneKd: what the fitness score is taken at; LoamFull keeps none)
+    bool have_final = false;
+    bool xform_double = false;         // a keyframe is moved as hm::xform_cloud_d does (LoamFull); false: hm::xform_cloud_f's casts
 
-    // (layout, header and sizes need the clouds' sizes alone: no host copy is fetched for them)
-    static bool layout_of(KdLocalMap* const* maps, const int n_maps, KdImageLayout& L) {
-        const KdSizes* d[2] = {&maps[0]->deque.sizes, n_maps > 1 ? &maps[1]->deque.sizes : nullptr};
-        return kd_image_layout_of(d, n_maps, L);
-    }
-    // the rings hold what the deques hold, in planes a 16-byte access may walk
-    static bool rings_usable(KdLocalMap* const* maps, const KdImageLayout& L) {
-        unsigned long long quads = 0;
-        for (int m = 0; m < L.n_maps; ++m) {
-            const DeviceCloudRing& r = maps[m]->ring;
-            if (!maps[m]->on_device || r.size() != L.n_points[m] || r.sizes.size() != L.n_clouds[m]) return false;
-            if (L.n_points[m] && ((r.cap & 3u) != 0 || !kernel_aligned(r.planes.p) || r.tail > r.cap)) return false;
-            quads += (L.n_points[m] + 6) / 4;
-        }
-        return quads < 0x7fffffffull;
-    }
-    fls_status export_image(const KdImageParams& q, const KdImageGate& g, KdLocalMap* const* maps, void* dst, size_t cap, int dst_on_device, hipStream_t stream) {
-        KdImageLayout L;
-        if (!dst || !layout_of(maps, int(q.n_maps), L)) return FLS_ERR_STATE;
-        if (cap < L.total) return FLS_ERR_RANGE;
-        unsigned char* const out = static_cast<unsigned char*>(dst);
-        const KdSizes* d[2] = {&maps[0]->deque.sizes, L.n_maps > 1 ? &maps[1]->deque.sizes : nullptr};
-        FLS_HIP(hipStreamSynchronize(stream));
-        if (!rings_usable(maps, L)) {  // from the host deques (fetched from the rings where a device push left them there alone)
-            unsigned char* const host = dst_on_device ? (img_pinned.reserve(L.total), img_pinned.p) : out;
-            const KdDeque* hd[2] = {&maps[0]->host_clouds(stream), L.n_maps > 1 ? &maps[1]->host_clouds(stream) : nullptr};
-            kd_image_from_deques(q, g, L, hd, host);
-            if (dst_on_device) {
-                FLS_HIP(hipMemcpyAsync(out, host, L.total, hipMemcpyHostToDevice, stream));
-                FLS_HIP(hipStreamSynchronize(stream));
-            }
-            ++exports_host;
-            return FLS_OK;
-        }
-        const bool direct = dst_on_device && kernel_aligned(dst);
-        unsigned char* img = out;
-        if (!direct) { img_stage.reserve(L.total); img = img_stage.p; }
-        // header and sizes, with the padding behind them, from the host; the rows from the rings: together every byte of the image
-        const size_t meta0 = L.rows[0], meta1 = L.n_maps > 1 ? L.rows[1] - L.sizes[1] : 0;
-        img_pinned.reserve(meta0 + meta1);
-        unsigned char* const chunk[2] = {img_pinned.p, img_pinned.p + meta0};
-        kd_image_write_meta(q, g, L, d, chunk);
-        FLS_HIP(hipMemcpyAsync(img, chunk[0], meta0, hipMemcpyHostToDevice, stream));
-        if (meta1) FLS_HIP(hipMemcpyAsync(img + L.sizes[1], chunk[1], meta1, hipMemcpyHostToDevice, stream));
-        KdPackArgs a{};
-        unsigned quads = 0;
-        for (int m = 0; m < L.n_maps; ++m) {
-            const DeviceCloudRing& r = maps[m]->ring;
-            if (!L.n_points[m]) continue;
-            const size_t base = r.head & ~size_t(3);
-            const unsigned* pl = reinterpret_cast<const unsigned*>(r.planes.p);
-            KdPackMap& k = a.m[m];
-            k.x = pl + base; k.y = pl + r.cap + base; k.z = pl + 2 * r.cap + base; k.i = pl + 3 * r.cap + base;
-            k.rows = reinterpret_cast<uint4*>(img + L.rows[m]);
-            k.off = unsigned(r.head - base);
-            k.n = unsigned(L.n_points[m]);
-            k.quads = (k.off + k.n + 3u) / 4u;  // base + 4 * quads <= cap: cap is a multiple of 4 and tail <= cap
-            quads += k.quads;
-        }
-        if (quads) hipLaunchKernelGGL(kd_image_pack_kernel, dim3((quads + kKdImageBlock - 1) / kKdImageBlock), dim3(kKdImageBlock), 0, stream, a);
-        if (!direct) FLS_HIP(hipMemcpyAsync(out, img, L.total, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-        FLS_HIP(hipStreamSynchronize(stream));
-        FLS_HIP(hipGetLastError());
-        ++exports_device;
-        return FLS_OK;
-    }
-    // Everything of an import up to the kind's rebuild: FLS_OK = the deques, the rings and `gate` hold the image (`any_cloud`: it holds a
-    // cloud at all); anything else = the handle is as it was.
-    fls_status import_image(const KdImageParams& q, KdLocalMap* const* maps, const void* src, size_t n_bytes, int src_on_device, hipStream_t stream,
-                            hm::KeyframeGate& gate, bool& any_cloud) {
-        if (!src) return FLS_ERR_INVALID;
-        // (1) the header
-        unsigned char head[sizeof(fls_kd_image_header)];
-        if (n_bytes < sizeof(head)) return FLS_ERR_INVALID;
-        if (src_on_device) FLS_HIP(hipMemcpy(head, src, sizeof(head), hipMemcpyDeviceToHost));
-        else std::memcpy(head, src, sizeof(head));
-        fls_kd_image_header h;
-        KdImageLayout L;
-        const fls_status hrc = kd_image_check_header(head, n_bytes, q, h, L);
-        if (hrc != FLS_OK) return hrc;
-        // (2) the whole image in host memory: sizes and padding are checked there, and the host deques are filled from it
-        const unsigned char* host = static_cast<const unsigned char*>(src);
-        if (src_on_device) {
-            img_pinned.reserve(L.total);
-            FLS_HIP(hipMemcpyAsync(img_pinned.p, src, L.total, hipMemcpyDeviceToHost, stream));
-            FLS_HIP(hipStreamSynchronize(stream));
-            host = img_pinned.p;
-        }
-        const fls_status brc = kd_image_check_body(host, L);
-        if (brc != FLS_OK) return brc;
-        // (3) the rows into planes of this importer's own
-        const bool on_device = maps[0]->on_device;
-        unsigned long long quads_all = 0;
-        for (int m = 0; m < L.n_maps; ++m) quads_all += (L.n_points[m] + 3) / 4;
-        if (on_device && quads_all >= 0x7fffffffull) return FLS_ERR_INVALID;  // (more points than a ring can hold)
-        if (on_device && quads_all) {
-            const unsigned char* img = static_cast<const unsigned char*>(src);
-            if (!(src_on_device && kernel_aligned(src))) {
-                img_stage.reserve(L.total);
-                FLS_HIP(hipMemcpyAsync(img_stage.p, src, L.total, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-                img = img_stage.p;
-            }
-            KdUnpackArgs a{};
-            unsigned quads = 0;
-            for (int m = 0; m < L.n_maps; ++m) {
-                const size_t n = L.n_points[m];
-                if (!n) continue;
-                SpareRing& sp = spare[m];
-                if (sp.cap < n || !sp.planes.p) {  // as DeviceCloudRing::make_room sizes a ring: 65,536 floats per plane, doubled until it fits
-                    size_t ncap = 65536;
-                    while (ncap < n) ncap *= 2;
-                    sp.planes.reserve(4 * ncap);
-                    sp.cap = ncap;
-                }
-                unsigned* pl = reinterpret_cast<unsigned*>(sp.planes.p);
-                KdUnpackMap& k = a.m[m];
-                k.rows = reinterpret_cast<const uint4*>(img + L.rows[m]);
-                k.x = pl; k.y = pl + sp.cap; k.z = pl + 2 * sp.cap; k.i = pl + 3 * sp.cap;
-                k.n = unsigned(n);
-                k.quads = unsigned((n + 3) / 4);  // 4 * quads <= cap: cap is a multiple of 4
-                quads += k.quads;
-            }
-            hipLaunchKernelGGL(kd_image_unpack_kernel, dim3((quads + kKdImageBlock - 1) / kKdImageBlock), dim3(kKdImageBlock), 0, stream, a);
-            FLS_HIP(hipStreamSynchronize(stream));
-            FLS_HIP(hipGetLastError());
-        }
-        // (4) the handle takes the image
-        FLS_HIP(hipDeviceSynchronize());  // launches of the batch lanes may still read the old grid
-        any_cloud = false;
-        for (int m = 0; m < L.n_maps; ++m) {
-            KdLocalMap& km = *maps[m];
-            KdDeque all;
-            kd_deque_from_image(host, L, m, all);
-            any_cloud = any_cloud || L.n_clouds[m] != 0;
-            if (on_device) {
-                DeviceCloudRing& r = km.ring;
-                if (L.n_points[m]) {
-                    std::swap(r.planes.p, spare[m].planes.p);
-                    std::swap(r.planes.cap, spare[m].planes.cap);
-                    std::swap(r.cap, spare[m].cap);
-                }
-                r.head = 0;
-                r.tail = L.n_points[m];
-            }
-            km.replace_deque(std::move(all));  // (every cloud present on the host; the ring's sizes follow)
-        }
-        const KdImageGate g = kd_gate_from_header(h);
-        gate = hm::KeyframeGate();
-        gate.init = g.init;
-        std::memcpy(gate.last_T, g.last_T, sizeof(gate.last_T));
-        ++(on_device ? imports_device : imports_host);
-        return FLS_OK;
-    }
-    // a handle without a cloud: what it was before its first one
-    static void reset_map(KdLocalMap& km) { km.local.clear(); km.n = 0; }
-};
-inline KdImageGate kd_gate_of(const hm::KeyframeGate& gate) {
-    KdImageGate g;
-    g.init = gate.init;
-    if (g.init) std::memcpy(g.last_T, gate.last_T, sizeof(g.last_T));
-    return g;
-}
-// what the three kinds share of the image calls (M: the matcher; it supplies image_maps(), rebuild_maps() and map_replaced())
-template <class M>
-struct KdImageCalls {
-    static size_t bytes(M& s) {
-        if (s.owner) return 0;
-        KdImageLayout L;
-        KdLocalMap* maps[2];
-        s.image_maps(maps);
-        return KdMapImage::layout_of(maps, int(kd_image_params(s.kind, s.p).n_maps), L) ? L.total : 0;
-    }
-    static fls_status export_to(M& s, void* dst, size_t cap, int on_device) {
-        if (s.owner) return FLS_ERR_STATE;
-        KdLocalMap* maps[2];
-        s.image_maps(maps);
-        return s.image.export_image(kd_image_params(s.kind, s.p), kd_gate_of(s.gate), maps, dst, cap, on_device, s.stream);
-    }
-    static size_t export_blob(M& s, void* blob, size_t cap) {
-        const size_t need = bytes(s);
-        if (need && blob && cap >= need && export_to(s, blob, cap, 0) != FLS_OK) return 0;
-        return need;
-    }
-    static fls_status import_from(M& s, const void* src, size_t n_bytes, int on_device) {
-        if (s.owner) return FLS_ERR_INVALID;  // a batch lane has no map of its own
-        KdLocalMap* maps[2];
-        s.image_maps(maps);
-        bool any_cloud = false;
-        const fls_status rc = s.image.import_image(kd_image_params(s.kind, s.p), maps, src, n_bytes, on_device, s.stream, s.gate, any_cloud);
-        if (rc != FLS_OK) return rc;
-        s.map_replaced();
-        s.log_n = 0;
-        s.log_stale = false;
-        if (!any_cloud) {
-            for (int m = 0; m < int(kd_image_params(s.kind, s.p).n_maps); ++m) KdMapImage::reset_map(*maps[m]);
-            s.have_map = false;
-            return FLS_OK;
-        }
-        return s.rebuild_maps();
-    }
-    // replica sets: the owner's image, exported on its device, copied device to device and imported on this handle's device
-    static fls_status replicate(M& s, fls_matcher& o) {
-        if (o.kind != s.kind || s.owner) return FLS_ERR_STATE;
-        M& src = static_cast<M&>(o);
-        FLS_HIP(hipSetDevice(src.device));
-        const fls_status prc = src.prepare_batch();  // map current, stream idle
-        if (prc != FLS_OK) return prc;
-        const size_t nbytes = bytes(src);
-        if (!nbytes) return FLS_ERR_STATE;
-        DevBuf<unsigned char>& out = src.image.replica_out;  // (kept by the owner: a refresh allocates nothing)
-        out.reserve(nbytes);
-        const fls_status erc = export_to(src, out.p, nbytes, 1);
-        if (erc != FLS_OK) return erc;
-        FLS_HIP(hipSetDevice(s.device));
-        if (src.device == s.device) return import_from(s, out.p, nbytes, 1);
-        s.image.replica_in.reserve(nbytes);
-        FLS_HIP(hipMemcpyPeer(s.image.replica_in.p, s.device, out.p, src.device, nbytes));
-        return import_from(s, s.image.replica_in.p, nbytes, 1);
-    }
-};
-// the overrides of fls_matcher every kd kind spells the same way
-#define FLS_KD_IMAGE_OVERRIDES(M)                                                                                                              \
-    KdMapImage image;                                                                                                                          \
-    size_t map_image_bytes() override { return KdImageCalls<M>::bytes(*this); }                                                                \
-    fls_status map_image_export(void* dst, size_t cap, int on_device) override { return KdImageCalls<M>::export_to(*this, dst, cap, on_device); } \
-    fls_status map_image_import(const void* src, size_t n, int on_device) override { return KdImageCalls<M>::import_from(*this, src, n, on_device); } \
-    size_t map_export(void* blob, size_t cap) override { return KdImageCalls<M>::export_blob(*this, blob, cap); }                              \
-    fls_status map_import(const void* blob, size_t n) override { return KdImageCalls<M>::import_from(*this, blob, n, 0); }                     \
-    bool can_replicate() const override { return !owner && have_map; }                                                                         \
-    fls_status replicate_from(fls_matcher& o) override { return KdImageCalls<M>::replicate(*this, o); }
+    const KdMaps& read_maps() const { return owner ? owner->maps : maps; }
+    bool map_ready() const { return owner ? owner->have_map : have_map; }
+    // src[m] for map m: the scan(s) the Match just used, still on the device, with their intensities.  false: not there -- nothing has changed
+    virtual bool keyframe_device(DeviceCloudRing::DeviceCloud* src) = 0;
+    virtual void keyframe_host(const std::vector<PtI>** clouds) = 0;  // the same on the host, fetched only here
 
-// ---------------------------------------------------------------------------------------------
-// A keyframe pushed on the device (KdLocalMap::push_device, kernels_kd_push.hpp): the transform as the kernel takes it, and the intensity
-// plane of scans whose intensities never went to the device.
-inline KdPushArgs kd_push_xform_f(const double* T) {  // hm::xform_cloud_f's casts
-    KdPushArgs a{};
-    a.mode = kKdPushXformF;
-    for (int j = 0; j < 3; ++j) for (int i = 0; i < 3; ++i) a.R[i + j * 3] = float(T[i + j * 4]);
-    for (int i = 0; i < 3; ++i) a.t[i] = float(T[12 + i]);
-    return a;
-}
-inline KdPushArgs kd_push_xform_d(const double* T) {  // hm::xform_cloud_d
-    KdPushArgs a{};
-    a.mode = kKdPushXformD;
-    std::memcpy(a.T, T, sizeof(a.T));
-    return a;
-}
-// DevScan::upload sends x | y | z; the intensities a keyframe carries into the deque are gathered from the scans' host copies into pinned
-// memory and copied up as one plane (cloud 0's, then cloud 1's) when a keyframe is taken, and only then: a Match without one pays nothing.
-struct KdPushIntensity {
-    PinnedBuf<float> h;
-    DevBuf<float> d;
-    hipEvent_t copied = nullptr;  // the last copy has read `h`
-    ~KdPushIntensity() { if (copied) (void)hipEventDestroy(copied); }
-    const float* upload(const std::vector<PtI>* const* clouds, const int n_clouds, hipStream_t s) {
-        size_t total = 0;
-        for (int c = 0; c < n_clouds; ++c) total += clouds[c]->size();
-        if (!total) return nullptr;
-        if (copied) FLS_HIP(hipEventSynchronize(copied));  // (long over: a rebuild has waited for the stream since)
-        else FLS_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
-        h.reserve(total);
-        d.reserve(total);
-        size_t at = 0;
-        for (int c = 0; c < n_clouds; ++c)
-            for (const PtI& q : *clouds[c]) std::memcpy(h.p + at++, &q.i, sizeof(float));
-        FLS_HIP(hipMemcpyAsync(d.p, h.p, total * sizeof(float), hipMemcpyHostToDevice, s));
-        FLS_HIP(hipEventRecord(copied, s));
-        return d.p;
+    fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
+        // one map: no second cloud; LoamFull: CHECK_EQ(cloud_list.size(), 2) loam_full_kdtree.h:66
+        if (maps.n_maps == 1 ? (c1 != nullptr && n1 != 0) : (c1 == nullptr && n1 != 0)) return FLS_ERR_INVALID;
+        const std::vector<PtI> clouds[2] = {cloud_from(c0, n0, stride), maps.n_maps > 1 && c1 ? cloud_from(c1, n1, stride) : std::vector<PtI>()};
+        return maps.add_host(clouds, have_map);
+    }
+    // The end of a Match.  icp_optimized.h:153 `has_converge_ && IsNeedAddCloud(T) && !is_localization_mode_` (loam_point_to_plane_kdtree.h:145-149;
+    // loam_full_kdtree.h:185-193 has no mode term): the gate (and its last_T) is evaluated before the mode switch, as in the reference;
+    // update_map == 0 (this ABI's "registration only" switch) skips the whole statement, so such a call leaves the keyframe gate alone.
+    // The keyframe is the mapping branch of AddCloudToLocalMap: pushed on the device (every map's cloud in one launch), else through the host.
+    fls_status finish_match(const double* T, const bool has_converge, const int update_map, fls_stats* out) {
+        stats.converged = has_converge ? 1 : 0;
+        fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
+        if (update_map && !owner && has_converge && maps.gate.need(T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !maps.localization) {
+            fls_status arc;
+            DeviceCloudRing::DeviceCloud src[2];
+            if (!(maps.can_push_device() && keyframe_device(src) &&
+                  maps.push_keyframe_device(src, xform_double ? kd_push_xform_d(T) : kd_push_xform_f(T), have_map, arc))) {
+                const std::vector<PtI>* at_sensor[2] = {nullptr, nullptr};
+                keyframe_host(at_sensor);
+                std::vector<PtI> clouds[2];
+                for (int m = 0; m < maps.n_maps; ++m) clouds[m] = xform_double ? hm::xform_cloud_d(*at_sensor[m], T) : hm::xform_cloud_f(*at_sensor[m], T);
+                arc = maps.add_host(clouds, have_map);
+            }
+            if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
+        }
+        if (out) *out = stats;
+        return rc;
+    }
+    void reset_job_state() override { maps.gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
+    // ---- the map(s) as one flat image (KdMaps::image_*): a batch lane has no map of its own ----
+    void map_replaced() { have_final = false; log_n = 0; log_stale = false; }  // fls_get_fitness_score answers FLS_ERR_STATE until the next Match
+    size_t map_image_bytes() override { return owner ? 0 : maps.image_bytes(); }
+    fls_status map_image_export(void* dst, size_t cap, int on_device) override { return owner ? FLS_ERR_STATE : maps.image_export(dst, cap, on_device); }
+    fls_status map_image_import(const void* src, size_t n, int on_device) override {
+        return owner ? FLS_ERR_INVALID : maps.image_import(src, n, on_device, have_map, [this] { map_replaced(); });
+    }
+    size_t map_export(void* blob, size_t cap) override { return owner ? 0 : maps.export_blob(blob, cap); }
+    fls_status map_import(const void* blob, size_t n) override { return map_image_import(blob, n, 0); }
+    bool can_replicate() const override { return !owner && have_map; }
+    fls_status replicate_from(fls_matcher& o) override {
+        if (o.kind != kind || owner) return FLS_ERR_STATE;
+        KdMatcher& src = static_cast<KdMatcher&>(o);
+        return maps.replicate_from(src.maps, [&src] { return src.prepare_batch(); }, have_map, [this] { map_replaced(); });
+    }
+    size_t map_size(int slot) const override {  // (any other slot: the map's points; LoamFull: slot 1 is the corner map)
+        return KdMaps::counts(slot) ? maps.counter(slot) : maps.map[maps.n_maps > 1 && slot == 1].n;
     }
 };
 
 // ---------------------------------------------------------------------------------------------
-struct IcpMatcher final : fls_matcher {
-    KdLocalMap map;
+struct IcpMatcher final : KdMatcher {
     std::vector<PtI> source;
     SourceFilter src_filter;
     DevBuf<unsigned> d_ticket;
-    const IcpMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
     DevScan scan;
     size_t raw_n = 0;
-    hm::KeyframeGate gate;
-    double final_T[16]{};
-    bool have_final = false;
     DevBuf<int> d_nn_id;
     DevBuf<unsigned char> d_eff;
 
@@ -338,29 +110,11 @@ struct IcpMatcher final : fls_matcher {
         if (!(p.point_search_thres > 0.0) || !(p.map_cloud_filter_size > 0.f) || !(p.source_cloud_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
         src_filter.init();
-        map.init();
+        // AddCloudToLocalMap :165-189, Q13: always filtered.  Gate-sized cells here: the ICP scan starts far from the map (1-NN often beyond half the
+        // gate in the early iterations), the two-stage search would run its second stage for most queries (measured 25 vs 13.5 us / launch)
+        maps.init(kind, p, device, stream, {{true, p.map_cloud_filter_size, cell_for_gate(p.point_search_thres), 1, p.local_map_size}});
         init_tickets(d_ticket);
         return FLS_OK;
-    }
-    fls_status add_cloud_impl(const std::vector<PtI>& new_cloud) {  // :165-189
-        if (p.is_localization_mode) map.reset_to(new_cloud, stream);
-        else { map.push(new_cloud, stream); map.trim(p.local_map_size); }
-        return rebuild_maps();
-    }
-    fls_status rebuild_maps() {  // (a keyframe update and an image import)
-        // gate-sized cells here: the ICP scan starts far from the map (1-NN often beyond half the gate in the early
-        // iterations), the two-stage search would run its second stage for most queries (measured 25 vs 13.5 us / launch)
-        const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, cell_for_gate(p.point_search_thres), 1, stream);  // Q13: always filtered
-        have_map = rc == FLS_OK;
-        return rc;
-    }
-    // ---- the map as one flat image (include/fls_map_kd.h) ----
-    void image_maps(KdLocalMap** m) { m[0] = &map; m[1] = nullptr; }
-    void map_replaced() { have_final = false; }  // fls_get_fitness_score answers FLS_ERR_STATE until the next Match
-    FLS_KD_IMAGE_OVERRIDES(IcpMatcher)
-    fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
-        if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
-        return add_cloud_impl(cloud_from(c0, n0, stride));
     }
     fls_status scan_upload(const float* s0, size_t n0, const float*, size_t, int stride) override {
         raw_n = n0;
@@ -390,14 +144,14 @@ struct IcpMatcher final : fls_matcher {
     fls_status match_prepare(const double* T, MatchPlan& m) {
         if (raw_n <= 10) return FLS_ERR_INVALID;  // CHECK_GT(ordered_cloud_.size(), 10u) :55
         if (src_filter.raw_pending) src_filter.refilter(stream, scan, source);  // :57, on the resident raw scan
-        if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
+        if (!map_ready()) return FLS_ERR_STATE;
         const size_t n = scan.n;
         stats = fls_stats{};
         stats.n_source = int(n);
         d_nn_id.reserve(std::max<size_t>(n, 1));
         d_eff.reserve(std::max<size_t>(n, 1));
         m.n = n;
-        m.cg = cell_dev(owner ? owner->map.grid : map.grid);
+        m.cg = cell_dev(read_maps().map[0].grid);
         m.rows = knn_grid_blocks(n);
         d_partials_b.reserve(size_t(std::max(m.rows, 1u)) * kPartialStride);
         std::memcpy(m.T0.m, T, sizeof(m.T0.m));
@@ -424,36 +178,18 @@ struct IcpMatcher final : fls_matcher {
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(final_T, mb.T, sizeof(final_T));
         have_final = true;
-        const bool has_converge = mb.converged != 0;  // Q10: false after max iterations
-        stats.converged = has_converge ? 1 : 0;
-        fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
-        // :153 `has_converge_ && IsNeedAddCloud(T) && !is_localization_mode_`: the gate (and its last_T) is evaluated before the mode
-        // switch, as in the reference; update_map == 0 (this ABI's "registration only" switch) skips the whole statement,
-        // so such a call leaves the keyframe gate alone
-        if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {
-            fls_status arc;
-            if (push_keyframe_device()) {  // the mapping branch of add_cloud_impl, the push on the device
-                map.trim(p.local_map_size);
-                arc = rebuild_maps();
-                if (map.rebuild_declined) ++push_declines;
-            } else {
-                src_filter.materialize(stream, source);
-                arc = add_cloud_impl(hm::xform_cloud_f(source, final_T));
-            }
-            if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
-        }
-        if (out) *out = stats;
-        return rc;
+        return finish_match(final_T, mb.converged != 0, update_map, out);  // Q10: not converged after max iterations
     }
-    // the filtered scan the Match just used, still on the device (the source filter's output planes), into the ring at final_T; false: the
-    // host filter ran, or the map cannot take a device push -- nothing has changed
-    unsigned long long push_declines = 0;  // device rebuilds declined after a device push (fls_map_size slot 167)
-    bool push_keyframe_device() {
-        if (!src_filter.resident || !map.can_push_device()) return false;
+    // the filtered scan the Match just used: the source filter's output planes while it is still on the device (false: the host filter ran)
+    bool keyframe_device(DeviceCloudRing::DeviceCloud* src) override {
+        if (!src_filter.resident) return false;
         const DeviceVoxelGrid& vg = src_filter.vg;
-        const DeviceCloudRing::DeviceCloud src{vg.ox(), vg.oy(), vg.oz(), vg.oi(), vg.n_out};
-        KdLocalMap* maps[1] = {&map};
-        return KdLocalMap::push_device(maps, &src, 1, kd_push_xform_f(final_T), stream);
+        src[0] = DeviceCloudRing::DeviceCloud{vg.ox(), vg.oy(), vg.oz(), vg.oi(), vg.n_out};
+        return true;
+    }
+    void keyframe_host(const std::vector<PtI>** clouds) override {
+        src_filter.materialize(stream, source);
+        clouds[0] = &source;
     }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
         MatchPlan m;
@@ -512,11 +248,10 @@ struct IcpMatcher final : fls_matcher {
         return run_job_groups<IcpMatcher>(n_jobs, s0, n0, stride, T, st, status, n_slots, GroupCounters{&batch_counters[1], &batch_counters[2], &batch_counters[3]},
                                           prepare, table, queue, finish);
     }
-    void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }  // function-static last_T of a fresh process (Q12)
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
-        return fitness_score_device(*this, map.grid, scan, final_T, max_range, score);
+        return fitness_score_device(*this, maps.map[0].grid, scan, final_T, max_range, score);
     }
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override {
         const size_t n = std::min(cap, scan.n);
@@ -532,10 +267,7 @@ struct IcpMatcher final : fls_matcher {
     size_t map_size(int slot) const override {
         if (slot == 105) return size_t(src_filter.device_runs);  // source filters run on the device / on the host
         if (slot == 106) return size_t(src_filter.host_runs);
-        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map.counter(slot);
-        if (slot >= 160 && slot <= 163) return image.counter(slot);
-        if (slot == 167) return size_t(push_declines);
-        return map.n;
+        return KdMatcher::map_size(slot);
     }
 };
 
@@ -585,11 +317,8 @@ struct FeatureDev {
     }
 };
 
-struct LoamFullMatcher final : fls_matcher {
-    KdLocalMap map_planar, map_corner;
-    const LoamFullMatcher* owner = nullptr;  // batch lane: reads the owner's two map grids
+struct LoamFullMatcher final : KdMatcher {  // maps.map[0]: planar, [1]: corner
     FeatureDev corner, planar;
-    hm::KeyframeGate gate;
     DevBuf<unsigned> d_loam_ticket;
 
     fls_status init() {
@@ -601,34 +330,12 @@ struct LoamFullMatcher final : fls_matcher {
         if (!(p.point_search_thres > 0.0) || !(p.corner_voxel_filter_size > 0.f) || !(p.planar_voxel_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
         init_tickets(d_loam_ticket);
-        map_planar.init();
-        map_corner.init();
-        map_corner.on_device = map_planar.on_device;  // one device-path decision per matcher, the planar map's (both read the same two switches)
-        return FLS_OK;
-    }
-    fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud, const std::vector<PtI>& corner_cloud) {  // :65-104
-        map_corner.push(corner_cloud, stream);  // both classes are pushed before either deque is trimmed
-        map_planar.push(planar_cloud, stream);
-        map_planar.trim(p.local_planar_size);
-        map_corner.trim(p.local_corner_size);
-        return rebuild_maps();
-    }
-    fls_status rebuild_maps() {  // (a keyframe update and an image import)
-        // half-gate cells + the two-stage kernel; the VoxelGrid only once the deque holds more than 5 frames (:92-100)
+        // AddCloudToLocalMap :65-104: half-gate cells + the two-stage kernel; the VoxelGrid only once the deque holds more than 5 frames (:92-100)
         const float cs = 0.5f * cell_for_gate(p.point_search_thres);
-        fls_status rc = map_planar.rebuild(map_planar.deque.size() > 5, p.planar_voxel_filter_size, cs, kGridRings, stream);
-        if (rc != FLS_OK) return rc;
-        rc = map_corner.rebuild(map_corner.deque.size() > 5, p.corner_voxel_filter_size, cs, kGridRings, stream);
-        have_map = rc == FLS_OK;  // (the corner rebuild's status alone)
-        return rc;
-    }
-    // ---- the maps as one flat image (include/fls_map_kd.h): planar first, then corner ----
-    void image_maps(KdLocalMap** m) { m[0] = &map_planar; m[1] = &map_corner; }
-    void map_replaced() {}
-    FLS_KD_IMAGE_OVERRIDES(LoamFullMatcher)
-    fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
-        if (c1 == nullptr && n1 != 0) return FLS_ERR_INVALID;  // CHECK_EQ(cloud_list.size(), 2) :66
-        return add_cloud_impl(cloud_from(c0, n0, stride), c1 ? cloud_from(c1, n1, stride) : std::vector<PtI>());
+        maps.init(kind, p, device, stream, {{false, p.planar_voxel_filter_size, cs, kGridRings, p.local_planar_size},
+                                            {false, p.corner_voxel_filter_size, cs, kGridRings, p.local_corner_size}});
+        xform_double = true;
+        return FLS_OK;
     }
     fls_status scan_upload(const float* s0, size_t n0, const float* s1, size_t n1, int stride) override {
         planar.scan.upload(cloud_from(s0, n0, stride), stream);
@@ -641,7 +348,7 @@ struct LoamFullMatcher final : fls_matcher {
         return FLS_OK;
     }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
-        if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
+        if (!map_ready()) return FLS_ERR_STATE;
         const size_t np = planar.scan.n, nc = corner.scan.n;
         const int nbp = int((np + 255) / 256), nbc = int((nc + 255) / 256);
         stats = fls_stats{};
@@ -651,7 +358,7 @@ struct LoamFullMatcher final : fls_matcher {
         corner.prepare();
         d_partials_a.reserve(size_t(std::max(nbc, 1)) * kPartialStride);
         d_partials_b.reserve(size_t(std::max(nbp, 1)) * kPartialStride);
-        const CellGridDev cgp = cell_dev(owner ? owner->map_planar.grid : map_planar.grid), cgc = cell_dev(owner ? owner->map_corner.grid : map_corner.grid);
+        const CellGridDev cgp = cell_dev(read_maps().map[0].grid), cgc = cell_dev(read_maps().map[1].grid);
         const float gate_f = float(p.point_search_thres);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
@@ -679,74 +386,30 @@ struct LoamFullMatcher final : fls_matcher {
         });
         const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
-        bool has_converge = true;
-        if (mb.n_valid < 50) has_converge = false;  // number_valid_planar_ < 50 :181
         stats.n_valid_corner = mb.n_valid2;
         stats.sum_res_corner = mb.sum_res2;
-        stats.converged = has_converge ? 1 : 0;
-        fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
-        if (update_map && !owner && has_converge && gate.need(mb.T, p.dist_thre_add_cloud, p.rot_thre_add_cloud)) {  // :185-193 (no localization switch)
-            fls_status arc;
-            if (push_keyframe_device(mb.T)) {  // add_cloud_impl, both pushes in one launch on the device
-                map_planar.trim(p.local_planar_size);
-                map_corner.trim(p.local_corner_size);
-                map_planar.rebuild_declined = map_corner.rebuild_declined = false;
-                arc = rebuild_maps();
-                if (map_planar.rebuild_declined || map_corner.rebuild_declined) ++push_declines;
-            } else {
-                planar.scan.fetch_host(stream);  // (attached scans are fetched only here)
-                corner.scan.fetch_host(stream);
-                arc = add_cloud_impl(hm::xform_cloud_d(planar.scan.host, mb.T), hm::xform_cloud_d(corner.scan.host, mb.T));
-            }
-            if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
-        }
-        if (out) *out = stats;
-        return rc;
+        return finish_match(mb.T, mb.n_valid >= 50, update_map, out);  // number_valid_planar_ < 50 :181
     }
-    // both feature scans, still on the device, into their rings at the pose the Match found.  Intensity: the fourth planes of attached
-    // scans (an empty scan needs none); of uploaded ones the host copies', sent up first (one plane for both).  false: the maps cannot
-    // take a device push -- nothing has changed
-    KdPushIntensity push_i;
-    unsigned long long push_declines = 0;  // keyframes after whose device push a device rebuild was declined (fls_map_size slot 167)
-    bool push_keyframe_device(const double* T) {
-        if (!map_planar.can_push_device() || !map_corner.can_push_device()) return false;
-        const DevScan &ps = planar.scan, &cs = corner.scan;
-        const float *in_p = nullptr, *in_c = nullptr;
-        if ((ps.dev_intensity || ps.n == 0) && (cs.dev_intensity || cs.n == 0) && (ps.dev_intensity || cs.dev_intensity)) {
-            if (ps.n) in_p = ps.xyz.p + 3 * ps.n;
-            if (cs.n) in_c = cs.xyz.p + 3 * cs.n;
-        } else {
-            if (ps.host.size() != ps.n || cs.host.size() != cs.n) return false;
-            const std::vector<PtI>* clouds[2] = {&ps.host, &cs.host};
-            in_p = push_i.upload(clouds, 2, stream);
-            in_c = in_p ? in_p + ps.n : nullptr;
-        }
-        const DeviceCloudRing::DeviceCloud src[2] = {{ps.x.p, ps.y.p, ps.z.p, in_p, ps.n}, {cs.x.p, cs.y.p, cs.z.p, in_c, cs.n}};
-        KdLocalMap* maps[2] = {&map_planar, &map_corner};
-        return KdLocalMap::push_device(maps, src, 2, kd_push_xform_d(T), stream);
+    // both feature scans, still on the device
+    bool keyframe_device(DeviceCloudRing::DeviceCloud* src) override {
+        const DevScan* scans[2] = {&planar.scan, &corner.scan};
+        return maps.scan_sources(scans, src);
     }
-    void reset_job_state() override { gate = hm::KeyframeGate(); }  // function-static last_T of a fresh process (Q12)
+    void keyframe_host(const std::vector<PtI>** clouds) override {
+        planar.scan.fetch_host(stream);  // (attached scans are fetched only here)
+        corner.scan.fetch_host(stream);
+        clouds[0] = &planar.scan.host; clouds[1] = &corner.scan.host;
+    }
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float, float* score) override { *score = std::numeric_limits<float>::max(); return FLS_OK; }  // FloatNaN :206-208
     int correspondences(int slot, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override {
         return (slot == 1 ? corner : planar).fetch(stream, ids, cnt, valid, cap);
     }
-    size_t map_size(int slot) const override {
-        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map_planar.counter(slot) + map_corner.counter(slot);  // (clouds: two per keyframe)
-        if (slot >= 160 && slot <= 163) return image.counter(slot);
-        if (slot == 167) return size_t(push_declines);
-        return slot == 1 ? map_corner.n : map_planar.n;
-    }
 };
 
 // ---------------------------------------------------------------------------------------------
-struct P2PlaneKdMatcher final : fls_matcher {
-    KdLocalMap map;
-    const P2PlaneKdMatcher* owner = nullptr;  // batch lane: reads the owner's map grid
+struct P2PlaneKdMatcher final : KdMatcher {
     FeatureDev planar;
-    hm::KeyframeGate gate;
-    double final_T[16]{};
-    bool have_final = false;
 
     fls_status init() {
         if (unset_d(p.point_to_planar_thres) || unset_d(p.position_converge_thres) || unset_d(p.rotation_converge_thres) ||
@@ -754,27 +417,9 @@ struct P2PlaneKdMatcher final : fls_matcher {
             return FLS_ERR_INVALID;  // CHECK_NE block loam_point_to_plane_kdtree.h:43-50
         if (!(p.map_cloud_filter_size > 0.f)) return FLS_ERR_INVALID;
         init_common();
-        map.init();
+        // AddCloudToLocalMap :56-79.  un-gated 5-NN: ring search with a cell of two map leaves (>= 1 point per leaf after VoxelGrid)
+        maps.init(kind, p, device, stream, {{true, p.map_cloud_filter_size, std::max(2.0f * p.map_cloud_filter_size, 0.5f), 1, p.local_map_size}});
         return FLS_OK;
-    }
-    fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud) {  // :56-79
-        if (p.is_localization_mode) map.reset_to(planar_cloud, stream);
-        else { map.push(planar_cloud, stream); map.trim(p.local_map_size); }
-        return rebuild_maps();
-    }
-    fls_status rebuild_maps() {  // (a keyframe update and an image import)
-        // un-gated 5-NN: ring search with a cell of two map leaves (>= 1 point per leaf after VoxelGrid)
-        const fls_status rc = map.rebuild(true, p.map_cloud_filter_size, std::max(2.0f * p.map_cloud_filter_size, 0.5f), 1, stream);
-        have_map = rc == FLS_OK;
-        return rc;
-    }
-    // ---- the map as one flat image (include/fls_map_kd.h) ----
-    void image_maps(KdLocalMap** m) { m[0] = &map; m[1] = nullptr; }
-    void map_replaced() { have_final = false; }
-    FLS_KD_IMAGE_OVERRIDES(P2PlaneKdMatcher)
-    fls_status add_cloud(const float* c0, size_t n0, const float* c1, size_t n1, int stride) override {
-        if (c1 != nullptr && n1 != 0) return FLS_ERR_INVALID;
-        return add_cloud_impl(cloud_from(c0, n0, stride));
     }
     fls_status scan_upload(const float* s0, size_t n0, const float*, size_t, int stride) override {
         planar.scan.upload(cloud_from(s0, n0, stride), stream);
@@ -785,14 +430,14 @@ struct P2PlaneKdMatcher final : fls_matcher {
         return FLS_OK;
     }
     fls_status match_resident(double* T, int update_map, fls_stats* out) override {
-        if (!(owner ? owner->have_map : have_map)) return FLS_ERR_STATE;
+        if (!map_ready()) return FLS_ERR_STATE;
         const size_t n = planar.scan.n;
         const int nblk = int((n + 255) / 256);
         stats = fls_stats{};
         stats.n_source = int(n);
         planar.prepare();
         d_partials_b.reserve(size_t(std::max(nblk, 1)) * kPartialStride);
-        const CellGridDev cg = cell_dev(owner ? owner->map.grid : map.grid);
+        const CellGridDev cg = cell_dev(read_maps().map[0].grid);
         Pose16 T0;
         std::memcpy(T0.m, T, sizeof(T0.m));
         const unsigned word = run_mailbox_loop(int(p.max_iterations), n, [&](int it, int first) {
@@ -806,53 +451,23 @@ struct P2PlaneKdMatcher final : fls_matcher {
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(final_T, mb.T, sizeof(final_T));
         have_final = true;
-        bool has_converge = true;
-        if (mb.n_valid < 50) has_converge = false;
-        stats.converged = has_converge ? 1 : 0;
-        fls_status rc = has_converge ? FLS_OK : FLS_NOT_CONVERGED;
-        if (update_map && !owner && has_converge && gate.need(final_T, p.dist_thre_add_cloud, p.rot_thre_add_cloud) && !p.is_localization_mode) {  // :145-149
-            fls_status arc;
-            if (push_keyframe_device()) {  // the mapping branch of add_cloud_impl, the push on the device
-                map.trim(p.local_map_size);
-                arc = rebuild_maps();
-                if (map.rebuild_declined) ++push_declines;
-            } else {
-                planar.scan.fetch_host(stream);  // (an attached scan is fetched only here)
-                arc = add_cloud_impl(hm::xform_cloud_f(planar.scan.host, final_T));
-            }
-            if (arc != FLS_OK) rc = arc; else stats.map_updated = 1;
-        }
-        if (out) *out = stats;
-        return rc;
+        return finish_match(final_T, mb.n_valid >= 50, update_map, out);
     }
-    // the scan, still on the device, into the ring at final_T.  Intensity: the fourth plane of an attached scan; of an uploaded one the
-    // host copy's, sent up here.  false: the map cannot take a device push -- nothing has changed
-    KdPushIntensity push_i;
-    unsigned long long push_declines = 0;  // device rebuilds declined after a device push (fls_map_size slot 167)
-    bool push_keyframe_device() {
-        if (!map.can_push_device()) return false;
-        const DevScan& sc = planar.scan;
-        const float* in = nullptr;
-        if (sc.dev_intensity) in = sc.xyz.p + 3 * sc.n;
-        else if (sc.host.size() == sc.n) { const std::vector<PtI>* clouds[1] = {&sc.host}; in = push_i.upload(clouds, 1, stream); }
-        else return false;
-        const DeviceCloudRing::DeviceCloud src{sc.x.p, sc.y.p, sc.z.p, in, sc.n};
-        KdLocalMap* maps[1] = {&map};
-        return KdLocalMap::push_device(maps, &src, 1, kd_push_xform_f(final_T), stream);
+    // the scan, still on the device
+    bool keyframe_device(DeviceCloudRing::DeviceCloud* src) override {
+        const DevScan* scans[1] = {&planar.scan};
+        return maps.scan_sources(scans, src);
     }
-    void reset_job_state() override { gate = hm::KeyframeGate(); have_final = false; }
+    void keyframe_host(const std::vector<PtI>** clouds) override {
+        planar.scan.fetch_host(stream);  // (an attached scan is fetched only here)
+        clouds[0] = &planar.scan.host;
+    }
     std::unique_ptr<fls_matcher> clone_for_lane() override { return make_owned_lane(*this); }
     fls_status fitness(float max_range, float* score) override {
         if (owner || !have_map || !have_final) return FLS_ERR_STATE;
-        return fitness_score_device(*this, map.grid, planar.scan, final_T, max_range, score);
+        return fitness_score_device(*this, maps.map[0].grid, planar.scan, final_T, max_range, score);
     }
     int correspondences(int, int32_t* ids, uint8_t* cnt, uint8_t* valid, size_t cap) override { return planar.fetch(stream, ids, cnt, valid, cap); }
-    size_t map_size(int slot) const override {
-        if ((slot >= 114 && slot <= 116) || (slot >= 164 && slot <= 166)) return map.counter(slot);
-        if (slot >= 160 && slot <= 163) return image.counter(slot);
-        if (slot == 167) return size_t(push_declines);
-        return map.n;
-    }
 };
 
 }  // namespace fls

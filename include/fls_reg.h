@@ -286,9 +286,9 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
  * device-built image (the first fls_map_export, host fallback or external non-first add_cloud after such a build).
  * iVox, the blob packed and built on the device (fls_map_ivox.h documents the slots): 168 / 169 = exports packed on the device / written by
  * the host, 170 / 171 = imports built on the device / declined to fls_map_import's path, 172-175 = declines by reason.
- * The kd-tree kinds, flat images (fls_map_kd.h; KdMapImage in csrc/matchers_kd.hpp): 160 = exports packed on the device, 161 = exports
+ * The kd-tree kinds, flat images (fls_map_kd.h; KdMapImage in csrc/kd_map.hpp): 160 = exports packed on the device, 161 = exports
  * written by the host from the deque, 162 = imports unpacked on the device, 163 = imports through the host deque alone.
- * The kd-tree kinds, keyframes (KdLocalMap in csrc/device_voxelgrid.hpp; LoamFull: both deques together, so two clouds per keyframe in
+ * The kd-tree kinds, keyframes (KdLocalMap, KdMaps in csrc/kd_map.hpp; LoamFull: both deques together, so two clouds per keyframe in
  * 164-166): 164 = clouds a Match pushed into the device deque on the device (the scan it just used, transformed there; FLS_KD_DEVICE_PUSH=0
  * restores the push through the host, FLS_DEVICE_VOXELGRID=0 / FLS_DEVICE_GRID_BUILD=0 imply it), 165 = clouds pushed through the host while
  * a device deque exists (fls_add_cloud_to_local_map, a host-filtered ICP source, the switch), 166 = clouds whose host copy was fetched from

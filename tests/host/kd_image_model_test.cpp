@@ -5,7 +5,7 @@
 // tests/test_kd_image_model.py with hipcc (the product headers include the HIP headers; no HIP runtime call is made), once plain and once
 // with AddressSanitizer and UBSan on the host side.
 // A batch lane (a matcher with `owner != nullptr`) never reaches this code: its export answers 0 bytes and its import FLS_ERR_INVALID
-// before anything is read (KdImageCalls in csrc/matchers_kd.hpp); no public call hands out a lane, so no test drives one.
+// before anything is read (KdMatcher in csrc/matchers_kd.hpp); no public call hands out a lane, so no test drives one.
 #include "../../funny_lidar_slam_amd/csrc/kd_image.hpp"
 #include <cmath>
 #include <cstdio>

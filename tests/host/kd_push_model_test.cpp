@@ -1,6 +1,6 @@
 // The bookkeeping of the kd-tree kinds' lazy host deque (csrc/kd_lazy_deque.hpp) without a device: 200 seeded random sequences of
 // push-device, push-host, trim, reset, fetch and import on a KdLazyDeque, with a plain std::deque of vectors kept beside it as the checker
-// and four host arrays standing in for the DeviceCloudRing's planes (clouds back to back from a head that advances with every pop and
+// and four host arrays standing in for the DeviceCloudRing's (csrc/kd_map.hpp) planes (clouds back to back from a head that advances with every pop and
 // returns to 0 with a re-pack).  After every step: count, sizes and point total equal the checker's, every cloud the host holds equals the
 // checker's bit for bit (NaN payloads and negative zeros among the values), the missing runs are maximal, cover exactly what is missing
 // and name the ring floats the clouds lie at; after a fetch nothing is missing and the whole deque equals the checker.  Built by

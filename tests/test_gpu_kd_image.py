@@ -193,7 +193,7 @@ def test_one_image_three_calls_two_paths(kind, monkeypatch):
 
 
 def test_ring_geometry(monkeypatch):
-    """DeviceCloudRing::make_room (csrc/device_voxelgrid.hpp): a ring starts at 65,536 floats per plane and appends at its tail.  With
+    """DeviceCloudRing::make_room (csrc/kd_map.hpp): a ring starts at 65,536 floats per plane and appends at its tail.  With
     local_map_size = 1 and clouds of 30,001 points: the first two lie at 0 and 30,001 (tail 60,002 <= 65,536) and the first is popped (head
     30,001); the third does not fit behind the tail (90,003 > 65,536) but fits the ring (30,001 live + 30,001 <= 65,536) and the live
     cloud's 30,001 floats do not overlap their destination (head >= live): the ring is re-packed IN PLACE, and after the pop its head is

@@ -1,5 +1,5 @@
 """Keyframes of the kd-tree kinds (IcpOptimized, LoamFull, LoamPointToPlaneKdtree) pushed into the device deque on the device
-(csrc/kernels_kd_push.hpp, DeviceCloudRing::push_back_device, KdLocalMap in csrc/device_voxelgrid.hpp) and the host deque that is filled
+(csrc/kernels_kd_push.hpp, DeviceCloudRing::push_back_device, KdLocalMap in csrc/kd_map.hpp) and the host deque that is filled
 only when something reads it (csrc/kd_lazy_deque.hpp).  Handle A is created with FLS_KD_DEVICE_PUSH=0 (the push through the host: download,
 host transform, upload), handle B with the default; both live in one process and get the same calls.  Every comparison is bit for bit.
 fls_map_size slots: 164 clouds pushed on the device, 165 pushed through the host while a ring exists, 166 fetched to the host lazily,
@@ -170,7 +170,7 @@ def test_pushed_rows_against_the_restated_transform(name):
 
 # ---- ring edges ----------------------------------------------------------------------------------------------------------------------------
 def ring_model(pushes, keep):
-    """DeviceCloudRing::make_room + pop_front restated (csrc/device_voxelgrid.hpp): `pushes` = [(points, pushed on the device)], a trim to
+    """DeviceCloudRing::make_room + pop_front restated (csrc/kd_map.hpp): `pushes` = [(points, pushed on the device)], a trim to
     `keep` clouds after every push.  Returns how often a DEVICE push re-packed the ring in place / moved it to new planes."""
     cap = head = tail = 0
     sizes, in_place, moved = [], 0, 0
