@@ -71,6 +71,9 @@ DEBUG_LOOP_SYMBOLS = ["fls_debug_loop_revision", "fls_debug_loop_ndt", "fls_debu
 # every symbol include/fls_debug_knn.h declares (FLS_DEBUG_KNN_REVISION 1): test hooks of the cooperative grid k-NN kernels of the kd-tree kinds
 DEBUG_KNN_SYMBOLS = ["fls_debug_knn_revision", "fls_debug_grid_knn5", "fls_debug_grid_knn5_dual", "fls_debug_icp_knn1"]
 
+# every symbol include/fls_debug_ivox_knn.h declares (FLS_DEBUG_IVOX_KNN_REVISION 1): the limits of the iVox kNN kernel's shared-run gate
+DEBUG_IVOX_KNN_SYMBOLS = ["fls_debug_ivox_knn_revision", "fls_debug_ivox_knn_limits"]
+
 # every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
 # fls_map_image_* and the replica sets of fls_reg.h
 NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
@@ -554,6 +557,11 @@ def lib():
                                                    C.c_float, C.c_int, dp, C.c_int, fp, bp, fp, ip, fp, bp, fp, ip]
             L.fls_debug_icp_knn1.restype = C.c_int
             L.fls_debug_icp_knn1.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_double, dp, C.c_int, ip, bp, ip]
+        if hasattr(L, "fls_debug_ivox_knn_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_debug_ivox_knn_revision.restype = C.c_int
+            L.fls_debug_ivox_knn_revision.argtypes = []
+            L.fls_debug_ivox_knn_limits.restype = C.c_int
+            L.fls_debug_ivox_knn_limits.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

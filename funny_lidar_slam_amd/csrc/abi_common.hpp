@@ -23,6 +23,7 @@
 #include "../../include/fls_debug_ndt.h"
 #include "../../include/fls_debug_loop.h"
 #include "../../include/fls_debug_knn.h"
+#include "../../include/fls_debug_ivox_knn.h"
 #include "../../include/fls_map_kd.h"
 #include <new>
 #include <type_traits>

@@ -63,6 +63,15 @@ extern "C" {
 
 int fls_debug_knn_revision(void) { return FLS_DEBUG_KNN_REVISION; }
 
+// include/fls_debug_ivox_knn.h: the limits of the iVox kNN kernel's shared-run gate, as compiled
+int fls_debug_ivox_knn_revision(void) { return FLS_DEBUG_IVOX_KNN_REVISION; }
+fls_status fls_debug_ivox_knn_limits(int* r_max, int* cap) {
+    if (!r_max || !cap) return FLS_ERR_INVALID;
+    *r_max = kIvoxKnnRunMax;
+    *cap = kIvoxKnnStageCap;
+    return FLS_OK;
+}
+
 fls_status fls_debug_grid_knn5(int device_id, const float* map, int nm, const float* query, int nq, int stride, float cell, int rings, float gate,
                                const double* T16, int host_grid, float* out_pts, uint8_t* out_cnt, float* out_kth, int32_t* out_has_window) {
     if (!debug_knn_common_ok(map, nm, query, nq, stride, cell, host_grid) || !T16 || !out_pts || !out_cnt || !out_kth || !out_has_window || (rings != 1 && rings != 2) ||

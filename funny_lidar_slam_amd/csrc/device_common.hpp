@@ -253,6 +253,7 @@ struct Pose16 { double m[16]; };
 
 struct TrafficCounters {
     unsigned long long probes, hits, cand;
+    unsigned long long shared;  // iVox kNN: waves (with at least one query) that took the shared-run path, summed over a Match's launches
 };
 
 __host__ __device__ __forceinline__ unsigned long long pack_key(int x, int y, int z) {

@@ -789,6 +789,7 @@ struct IvoxMap {
             case 173: return n_blob_decline_reason[int(BlobDecline::Range)];     // a key outside the key range or with reserved bits /
             case 174: return n_blob_decline_reason[int(BlobDecline::Budget)];    // a brick pool over its byte budget /
             case 175: return n_blob_decline_reason[int(BlobDecline::NotDense)];  // the hash-table form
+            // (176 is the matcher's, not the map's: kNN waves of the last counting Match that took the shared-run path, TrafficCounters::shared)
             default: return image_is_map() ? dev_n_points : ivox.n_points;
         }
     }

@@ -6,8 +6,10 @@
 //                        concatenated, cut into four equal contiguous ranges, one per lane (balanced split); every lane
 //                        scans its range four loads at a time into a private sorted top-5 of keys
 //                        {float-bits(d2) : map slot} held as IEEE doubles (v_min_f64 / v_max_f64 insertion), and the
-//                        four private lists are merged by five rounds of a DPP group-min.  48-62 VGPRs over the 16
-//                        instantiations (48 / 54 for the brick image's product forms, lean / GEN) and 12 KiB of LDS per
+//                        four private lists are merged by five rounds of a DPP group-min.  On the brick image's lean form a
+//                        wave whose 16 queries fall into <= 3 voxels first stages those voxels' neighbourhoods in LDS once and
+//                        scans them from there (shared runs, below).  48-60 VGPRs over the 16
+//                        instantiations (52 / 54 for the brick image's product forms, lean / GEN) and 16 KiB of LDS per
 //                        256-thread workgroup -> 8 waves/SIMD, four times as many waves as points/64: the dependent
 //                        gathers (cell -> voxel points) are hidden by thread-level parallelism instead of being
 //                        serialised in one lane (the first, fused kernel spent 117 us per launch that way).
@@ -110,13 +112,26 @@ __device__ __forceinline__ double group_min_dkey(const double v) { return dpp_mi
 //     difference (at |key| near 2^20 one ulp of a coordinate is res / 8); the selection keys then stay finite doubles as with the gate.
 //   - 64-bit candidate addresses.  With slots x 16 bytes < 2^32 the four loads of a trip take a 32-bit byte offset from the uniform base.
 // The body of workgroup blockIdx.x of ONE registration: ivox_knn_kernel is that registration alone, ivox_knn_jobs_kernel runs one per blockIdx.y.
-// The LDS is the calling kernel's (declared there under the names the single-job kernel has always used, as icp_knn_fit_body's is).
+// The LDS is the calling kernel's (one array, declared there through FLS_IVOX_KNN_SMEM_DECL, as icp_knn_fit_body's is).
+// Shared runs (brick image, !GEN): the 16 queries of a wave are 16 neighbouring azimuths of one ring of the ring-major scan and mostly fall into a
+// few voxels.  A RUN is a maximal stretch of consecutive queries of a wave with the same (kx, ky, kz, have).  A wave with at most kIvoxKnnRunMax runs
+// whose 19-voxel neighbourhoods hold at most kIvoxKnnStageCap map points together probes each run's 19 cells once (one lane per (run, probe): 3 x 19 = 57
+// lanes, one pass), copies the runs' points once into its LDS region as {x, y, z, map slot} -- one flat round trip, every load of the copy in flight
+// together, coalesced along the voxels' slot ranges -- and every query scans its run's staged range from LDS.  A query's candidate set stays exactly the
+// points of its 19 voxels and the distances are computed from the same float bits in the same order: the key set {d2 bits : slot} of every query, hence
+// its list, is the per-query code's.  Any other wave runs the per-query code.  (tools/knn_run_stats.py: what the gate admits on the headline scan.)
+constexpr int kIvoxKnnRunMax = 3;
+constexpr int kIvoxKnnStageCap = 256;
 constexpr int kIvoxKnnQueries = 256 / 4;  // queries per workgroup (four lanes each)
-#define FLS_IVOX_KNN_SMEM_PARAMS unsigned (&s_end)[kIvoxKnnQueries][24], unsigned (&s_off)[kIvoxKnnQueries][24]
-#define FLS_IVOX_KNN_SMEM_DECL                                                             \
-    __shared__ __attribute__((aligned(16))) unsigned s_end[kIvoxKnnQueries][24];           \
-    __shared__ __attribute__((aligned(16))) unsigned s_off[kIvoxKnnQueries][24]
-#define FLS_IVOX_KNN_SMEM_ARGS s_end, s_off
+// One LDS region per wave, used either as the per-query voxel tables (16 queries x 24 words of s_end, then 16 x 24 of s_off) or as the staging area.
+constexpr int kIvoxKnnWaveWords = kIvoxKnnStageCap * 4;
+static_assert(kIvoxKnnWaveWords >= 2 * 16 * 24, "the per-query tables of a wave fit its region");
+static_assert(4 * kIvoxKnnWaveWords * sizeof(unsigned) <= 20480, "eight workgroups per CU: the 1,800-workgroup launch stays one round");
+static_assert(kIvoxKnnRunMax * 19 <= 64 && kIvoxKnnStageCap <= 4 * 64, "one probe pass, four staged rows per lane");
+static_assert(kIvoxKnnRunMax == 3, "the leader and range selects of the shared path are written out for three runs");
+#define FLS_IVOX_KNN_SMEM_PARAMS unsigned (&s_knn)[256 / 64][kIvoxKnnWaveWords]
+#define FLS_IVOX_KNN_SMEM_DECL __shared__ __attribute__((aligned(16))) unsigned s_knn[256 / 64][kIvoxKnnWaveWords]
+#define FLS_IVOX_KNN_SMEM_ARGS s_knn
 template <bool COUNT, bool DENSE, bool FIRST, bool GEN, class P>
 __device__ __forceinline__ void
 ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int n,
@@ -142,6 +157,10 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     const int lb = ((seq / chunk) * 8 + xcd) * chunk + (seq % chunk);
     const int sub = threadIdx.x % G;
     const int q = lb * QPB + threadIdx.x / G;
+    // the wave's LDS region, and this query's rows of the per-query voxel tables in it
+    unsigned* const s_wave = &s_knn[threadIdx.x >> 6][0];
+    unsigned* const s_end = s_wave + 24 * ((threadIdx.x / G) & 15);
+    unsigned* const s_off = s_end + 16 * 24;
     const bool active = lb < nb && q < n;
     // issue the state / source loads before looking at the stop flag: one memory round trip instead of three
     // (source loads are unconditional on a clamped index: a guarded load costs a branch and a wait each).
@@ -196,7 +215,18 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
         cnt = hit ? ek.count : 0u;
         if (COUNT && pv) { c_probes++; if (hit) { c_hits++; c_cand += ek.count; } }
     };
-    unsigned b0 = 0, b1 = 0, b2 = 0, b3 = 0, b4 = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+    // scan a lane's candidates (the dependent-load latency is paid once per four candidates; the tail of a range re-reads its last point, masked out)
+    auto consider = [&](const float4 p, const unsigned s, const bool ok) {
+        const float dx = p.x - ptx, dy = p.y - pty, dz = p.z - ptz;
+        const float d2 = dx * dx + (dy * dy + dz * dz);  // Eigen Vector3f::squaredNorm order
+        top5_insert_dkey(t5, make_dkey(d2, s, GEN ? ok && d2 < 25.0f : ok));  // max_range 5.0 squared (!GEN: cannot bind, see above)
+    };
+    auto map_pt = [&](const unsigned s) -> float4 {
+        if (GEN) return grid.pts[s];
+        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(grid.pts) + (s << 4));  // (32-bit byte offset, as reduce_partials_trip)
+    };
+    bool have = false;     // brick image: the query's brick exists
+    unsigned cbase = 0u;   // ... and the query's own cell in its slab
     if (DENSE) {
         // brick image (device_common.hpp): ONE directory look-up per query -- the same 16-byte entry for the lanes of a group -- then
         // every probe is a slab offset from the query's own cell (the slab's halo mirrors the neighbouring bricks' boundary cells):
@@ -209,9 +239,103 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
             h = (h + 1) & bd.mask;
             be = bd.table[h];
         }
-        const bool have = in_range && be.key == bkey && be.begin < bd.n_cap;
-        const unsigned cbase = (have ? be.begin : 0u) * kBrickStride +
-                               brick_slab_index((kx & (kBrickSide - 1)) + 1, (ky & (kBrickSide - 1)) + 1, (kz & (kBrickSide - 1)) + 1);
+        have = in_range && be.key == bkey && be.begin < bd.n_cap;
+        cbase = (have ? be.begin : 0u) * kBrickStride +
+                brick_slab_index((kx & (kBrickSide - 1)) + 1, (ky & (kBrickSide - 1)) + 1, (kz & (kBrickSide - 1)) + 1);
+    }
+    bool shared = false;  // wave-uniform: this wave takes the shared-run path
+    if (DENSE && !GEN) {
+        const unsigned lane = threadIdx.x & 63u;
+        // Run detection: a query starts a run when (kx, ky, kz, have) differs from the query before it in the wave; query 0 always does.  (A query
+        // that is inactive or beyond the key range has key 0 and no brick: it belongs to a run without candidates.)  The four lanes of a query agree.
+        const int kxh = kx * 2 + (have ? 1 : 0);
+        const int pkx = __shfl_up(kxh, G, 64), pky = __shfl_up(ky, G, 64), pkz = __shfl_up(kz, G, 64);
+        const bool start = lane < (unsigned)G || pkx != kxh || pky != ky || pkz != kz;
+        const unsigned long long starts = __ballot(start) & 0x1111111111111111ull;  // bit 4 g: query g of the wave starts a run
+        const int nruns = __popcll(starts);
+        if (nruns <= kIvoxKnnRunMax) {
+            // the runs' leader lanes (wave-uniform) and what the probe lanes need of them: the leader's cell and whether its brick exists
+            const unsigned long long rest1 = starts & (starts - 1ull), rest2 = rest1 & (rest1 - 1ull), have_mask = __ballot(have);
+            const int l1 = rest1 ? __ffsll((long long)rest1) - 1 : 0, l2 = rest2 ? __ffsll((long long)rest2) - 1 : 0;
+            const unsigned cb0 = (unsigned)__builtin_amdgcn_readlane((int)cbase, 0), cb1 = (unsigned)__builtin_amdgcn_readlane((int)cbase, l1),
+                           cb2 = (unsigned)__builtin_amdgcn_readlane((int)cbase, l2);
+            const bool hv0 = (have_mask & 1ull) != 0ull, hv1 = rest1 != 0ull && ((have_mask >> l1) & 1ull) != 0ull,
+                       hv2 = rest2 != 0ull && ((have_mask >> l2) & 1ull) != 0ull;
+            // one lane per (run, probe): lane 19 r + k probes cell k of run r (lanes 57..63 and the lanes of a run the wave does not have load a cell
+            // of some run and count nothing); every load stays inside the leader's slab, as the per-query probes do
+            const unsigned pr = lane / 19u, pk = lane - 19u * pr;
+            int ox, oy, oz;
+            nearby18((int)pk, ox, oy, oz);
+            const int poff = (oz * kBrickStored + oy) * kBrickStored + ox;
+            const unsigned pcb = pr == 0u ? cb0 : pr == 1u ? cb1 : cb2;
+            const bool phv = pr == 0u ? hv0 : pr == 1u ? hv1 : pr == 2u ? hv2 : false;
+            const uint2 pe = bd.cells[pcb + (unsigned)poff];
+            const unsigned pbeg = pe.x, pcnt_all = phv ? pe.y : 0u;
+            // wave prefix over the probe lanes' counts: run r's points take the contiguous staging range [S_r, S_r+1).  (Counts enter clamped to
+            // CAP + 1, so that the sum cannot wrap; a clamped count fails the gate.)
+            const unsigned pcnt = pcnt_all < (unsigned)kIvoxKnnStageCap + 1u ? pcnt_all : (unsigned)kIvoxKnnStageCap + 1u;
+            unsigned inc = pcnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned t = __shfl_up(inc, o, 64);
+                if (lane >= (unsigned)o) inc += t;
+            }
+            const unsigned pex = inc - pcnt;
+            const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)inc, 63);
+            if (total <= (unsigned)kIvoxKnnStageCap) {
+                shared = true;
+                const unsigned S1 = (unsigned)__builtin_amdgcn_readlane((int)pex, 19), S2 = (unsigned)__builtin_amdgcn_readlane((int)pex, 38);
+                // this query's run: the runs that start at or before its lane
+                const int my_run = __popcll(starts & ((2ull << lane) - 1ull)) - 1;
+                const unsigned sh_beg = my_run == 0 ? 0u : my_run == 1 ? S1 : S2, sh_end = my_run == 0 ? S1 : my_run == 1 ? S2 : total;
+                if (COUNT) {  // every active query: its 19 probes, its run's hit voxels and candidates; the wave counts once as shared
+                    const unsigned long long hit_mask = __ballot(pcnt != 0u);
+                    const unsigned hits_run = (unsigned)__popcll((hit_mask >> (19 * my_run)) & 0x7FFFFull);
+                    if (active && sub == 0) { c_probes += 19u; c_hits += hits_run; c_cand += sh_end - sh_beg; }
+                    if (__ballot(active) != 0ull && lane == 0u) atomicAdd(&tc->shared, 1ull);
+                }
+                // Staging.  (1) every probe lane writes the slots of its voxel into the slot words of its entries, (2) lane l takes entries l, l + 64,
+                // l + 128, l + 192: slot from LDS, point from the map -- all loads of the copy issued before the first is used -- (3) the entry becomes
+                // {x, y, z, slot}.  Entries [0, total) only; total <= CAP keeps everything inside the wave's region.
+                for (unsigned i = 0u; i < pcnt; ++i) s_wave[4u * (pex + i) + 3u] = pbeg + i;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                uint4* const stage = reinterpret_cast<uint4*>(s_wave);
+                unsigned sl[4] = {0u, 0u, 0u, 0u};
+                float4 sp[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned en = lane + 64u * (unsigned)j;
+                    sp[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (en < total) { sl[j] = s_wave[4u * en + 3u]; sp[j] = map_pt(sl[j]); }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned en = lane + 64u * (unsigned)j;
+                    if (en < total) stage[en] = make_uint4(__float_as_uint(sp[j].x), __float_as_uint(sp[j].y), __float_as_uint(sp[j].z), sl[j]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                // Scan: the query's four lanes cut its run's range [0, C) into four equal contiguous parts, four entries per trip from LDS
+                const unsigned C = sh_end - sh_beg, Q = (C + 3u) >> 2, a = (unsigned)sub * Q, e = a + Q < C ? a + Q : C;
+                const uint4* const runp = stage + sh_beg;
+                for (unsigned idx = a; idx < e; idx += 4u) {
+                    const unsigned last = e - 1u, i1 = idx + 1u, i2 = idx + 2u, i3 = idx + 3u;
+                    const uint4 r0 = runp[idx], r1 = runp[i1 < last ? i1 : last], r2 = runp[i2 < last ? i2 : last], r3 = runp[i3 < last ? i3 : last];
+                    consider(make_float4(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), 0.f), r0.w, true);
+                    consider(make_float4(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), 0.f), r1.w, i1 <= last);
+                    consider(make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), 0.f), r2.w, i2 <= last);
+                    consider(make_float4(__uint_as_float(r3.x), __uint_as_float(r3.y), __uint_as_float(r3.z), 0.f), r3.w, i3 <= last);
+                }
+            }
+        }
+    }
+    unsigned b0 = 0, b1 = 0, b2 = 0, b3 = 0, b4 = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+    if (shared) {
+        // (the wave's candidates are in its top-5 lists already)
+    } else if (DENSE) {
         constexpr unsigned PK[5] = {nearby18_slab_pack4(0), nearby18_slab_pack4(1), nearby18_slab_pack4(2), nearby18_slab_pack4(3), nearby18_slab_pack4(4)};
         const unsigned sub8 = 8u * (unsigned)sub;
         auto cell = [&](const int r, const unsigned pk4, unsigned& beg, unsigned& cnt) {
@@ -248,24 +372,14 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
             for (int r = 0; r < R; ++r) c_probes += sub + G * r < 19 ? 1u : 0u;
         }
     }
-    // scan this lane's <= R voxels, 4 point loads in flight per trip (the dependent-load latency is paid
-    // once per four candidates; the tail of a voxel re-reads its last point, masked out)
-    auto consider = [&](const float4 p, const unsigned s, const bool ok) {
-        const float dx = p.x - ptx, dy = p.y - pty, dz = p.z - ptz;
-        const float d2 = dx * dx + (dy * dy + dz * dz);  // Eigen Vector3f::squaredNorm order
-        top5_insert_dkey(t5, make_dkey(d2, s, GEN ? ok && d2 < 25.0f : ok));  // max_range 5.0 squared (!GEN: cannot bind, see above)
-    };
-    auto map_pt = [&](const unsigned s) -> float4 {
-        if (GEN) return grid.pts[s];
-        return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(grid.pts) + (s << 4));  // (32-bit byte offset, as reduce_partials_trip)
-    };
+    if (!shared) {
+    // per-query scan of this lane's share of the query's voxels, 4 point loads in flight per trip
     const unsigned tot = c0 + c1 + c2 + c3 + c4;  // this lane's candidates
     // Balanced split: the group's candidates (all hit voxels of the query, concatenated) are cut into four equal
     // contiguous ranges, one per lane, instead of whole voxels per lane: a wave runs max-over-lanes trips of the
     // loop below, and voxels hold 1..20+ points (4.7 trips of four candidates per wave before, 2.8 after).
     // The hit voxels are compacted into a per-group LDS table {prefix end, begin - prefix start}; a lane walks
     // its range through a two-entry window of that table (see the loop).
-    const int g = threadIdx.x / G;
     const unsigned nz = (c0 ? 1u : 0u) + (c1 ? 1u : 0u) + (c2 ? 1u : 0u) + (c3 ? 1u : 0u) + (c4 ? 1u : 0u);
     const unsigned packed = tot * 32u + nz;  // candidates (< 2^27) and hit voxels (<= 19 per group) of this lane
     const unsigned t0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)packed, 0x00, 0xf, 0xf, true);  // quad broadcasts
@@ -278,7 +392,7 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     // every entry behind the last real one is a sentinel (the window looks one entry ahead, the start search
     // four): the whole row is filled first, the real entries overwrite (LDS operations of a wave are in order)
     {
-        uint2* const rowp = reinterpret_cast<uint2*>(&s_end[g][6 * sub]);
+        uint2* const rowp = reinterpret_cast<uint2*>(&s_end[6 * sub]);
         rowp[0] = make_uint2(~0u, ~0u); rowp[1] = make_uint2(~0u, ~0u); rowp[2] = make_uint2(~0u, ~0u);
     }
     // predicated, not branched: a missed probe writes its pair to a word of the lane's own behind the table (real entries: 0..18; the
@@ -286,9 +400,9 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     const unsigned dmy = 20u + (unsigned)sub;
     auto put = [&](const unsigned b, const unsigned c) {
         const unsigned at = c ? pos : dmy;
-        s_off[g][at] = b - run;
+        s_off[at] = b - run;
         run += c;
-        s_end[g][at] = run;
+        s_end[at] = run;
         pos += c ? 1u : 0u;
     };
     put(b0, c0);
@@ -296,7 +410,7 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     put(b2, c2);
     put(b3, c3);
     put(b4, c4);
-    s_end[g][dmy] = ~0u;
+    s_end[dmy] = ~0u;
     // a group lives inside one wave and the LDS serves a wave's operations in order: no workgroup barrier, only a
     // compiler-level ordering point between the table writes and the cross-lane reads
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -314,7 +428,7 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     ps = P3 <= A32 ? P3 : ps;
     unsigned k = ps & 31u;  // (<= 19: the five words read below stay inside the row)
     {
-        const unsigned* const w = &s_end[g][k];
+        const unsigned* const w = &s_end[k];
         const unsigned w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
         k += (w0 <= a ? 1u : 0u) + (w1 <= a ? 1u : 0u) + (w2 <= a ? 1u : 0u) + (w3 <= a ? 1u : 0u) + (w4 <= a ? 1u : 0u);
     }
@@ -323,8 +437,8 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
     // cutting them costs 0.8 % more trips and saves a five-entry select chain per candidate.  The candidates of [a, e) are still
     // taken once each, only grouped differently: the same top-5 set.  (Behind the last run E1 is the sentinel: the trip ends at e.)
     for (unsigned idx = a; idx < e;) {
-        const unsigned E0 = s_end[g][k], E1 = s_end[g][k + 1];
-        const unsigned O0 = s_off[g][k], O1 = s_off[g][k + 1];
+        const unsigned E0 = s_end[k], E1 = s_end[k + 1];
+        const unsigned O0 = s_off[k], O1 = s_off[k + 1];
         const unsigned last = (E1 < e ? E1 : e) - 1;
         const unsigned i1 = idx + 1, i2 = idx + 2, i3 = idx + 3;
         const unsigned j1 = i1 < last ? i1 : last, j2 = i2 < last ? i2 : last, j3 = i3 < last ? i3 : last;
@@ -340,6 +454,7 @@ ivox_knn_body(FLS_IVOX_KNN_SMEM_PARAMS, const float* __restrict__ sx, const floa
         idx = j3 + 1;  // min(idx + 4, end of the second run, e)
         k += (E0 <= idx ? 1u : 0u) + (E1 <= idx ? 1u : 0u);  // (runs are never empty: E1 == idx puts idx into run k + 2)
     }
+    }  // (!shared)
     // phase 2: merge the four private lists: five rounds of group-min + pop (keys are unique -- the slot is the low
     // word -- so exactly one lane pops per round); the neighbour count is the number of valid minima
     const double m0 = group_min_dkey(t5[0]);

@@ -41,7 +41,7 @@ struct fls_matcher {
     double prof_ms = 0.0;
     int64_t prof_launches = 0;
     uint64_t prof_point_iters = 0;
-    fls::TrafficCounters last_tc{0, 0, 0};
+    fls::TrafficCounters last_tc{0, 0, 0, 0};
 
     // iteration log of the last Match
     int log_n = 0;

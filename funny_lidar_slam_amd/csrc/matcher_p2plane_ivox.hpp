@@ -649,7 +649,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         }
         return int(n);
     }
-    size_t map_size(int slot) const override { return map.counter(slot); }
+    size_t map_size(int slot) const override { return slot == 176 ? size_t(last_tc.shared) : map.counter(slot); }  // (176: the last counting Match's kNN waves on the shared-run path)
 };
 
 }  // namespace fls

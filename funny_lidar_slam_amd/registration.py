@@ -368,6 +368,11 @@ class RegistrationInterface:
         _lib.lib().fls_get_traffic_counters(self._h, C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
+    def knn_shared_waves(self) -> int:
+        """PointToPlane_IVOX, after a counting Match (set_profiling(counters=True)): the iVox kNN waves with at least one query that took the
+        shared-run path, summed over the Match's launches (fls_map_size slot 176; 0 with the hash-table image, which never shares)."""
+        return self.map_size(176)
+
     def close(self) -> None:
         if getattr(self, "_h", None) and self._h.value:
             _lib.lib().fls_destroy(self._h)

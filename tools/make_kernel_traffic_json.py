@@ -1,5 +1,5 @@
-"""profiles/traffic_<name>.json for ANY kernel from the raw rocprofv3 --pmc CSVs of tools/prof_round5.sh (one counter group per pass) and the
-kernel trace of the same workload.  The round-3/4 generator (make_traffic_json.py) knows one kernel; this one takes the name.
+"""profiles/traffic_<name>.json for ANY kernel from raw rocprofv3 --pmc CSVs (one counter group per pass, as tools/prof_round5.sh left them, or
+--pmc alone without tracing) and the kernel trace of the same workload.  The round-3/4 generator (make_traffic_json.py) knows one kernel; this one takes the name.
 usage: python tools/make_kernel_traffic_json.py <dir with pmc*_counter_collection.csv + kernel_trace.csv> <kernel-name substring> <out name> "<workload>"
 Units as /opt/skills/guides/MI355X_MICROARCH.md prescribes: FETCH_SIZE / WRITE_SIZE in KB per dispatch, FETCH_SIZE doubled on gfx950."""
 import collections, csv, glob, json, os, sys
@@ -29,7 +29,7 @@ def active_mean(v):
 
 launch_us = active_mean(durs)
 fetch, write = active_mean(vals.get("FETCH_SIZE")), active_mean(vals.get("WRITE_SIZE"))
-out = {"kernel": sub, "workload": workload, "source": "rocprofv3 --kernel-trace --pmc <one group per pass> (tools/prof_round5.sh) -> tools/make_kernel_traffic_json.py, directory " + os.path.basename(os.path.normpath(d)), "launches_in_trace": len(durs), "trace_avg_launch_us": launch_us,
+out = {"kernel": sub, "workload": workload, "source": "rocprofv3 --kernel-trace --stats in a run of its own, --pmc <one group per pass> -> tools/make_kernel_traffic_json.py, directory " + os.path.basename(os.path.normpath(d)), "launches_in_trace": len(durs), "trace_avg_launch_us": launch_us,
        "fetch_size_kb_per_launch_raw": fetch, "write_size_kb_per_launch_raw": write, "fetch_correction": 2.0,
        "hbm_bytes_per_launch": (2.0 * fetch + write) * 1024.0 if fetch is not None and write is not None else None}
 if out["hbm_bytes_per_launch"] and launch_us:
@@ -54,6 +54,17 @@ if wc:
     if wa is not None: out["wave_wait_pct"] = 100.0 * wa / wc
     if wi is not None: out["wave_issue_stall_pct"] = 100.0 * wi / wc
     if ai is not None: out["wave_issuing_pct"] = 100.0 * ai / wc
+# the vector-memory and LDS side of a kernel, where the passes collected it (wave-instructions, TCP tag accesses, TCP->TCC read requests, TA busy cycles)
+for key, ctr in (("vmem_read_wave_instructions_per_launch", "SQ_INSTS_VMEM_RD"), ("lds_wave_instructions_per_launch", "SQ_INSTS_LDS"),
+                 ("lds_bank_conflict_cycles_per_launch", "SQ_LDS_BANK_CONFLICT"), ("tcp_cache_accesses_per_launch", "TCP_TOTAL_CACHE_ACCESSES_sum"),
+                 ("tcp_tcc_read_requests_per_launch", "TCP_TCC_READ_REQ_sum"), ("tcp_pending_stall_cycles_per_launch", "TCP_PENDING_STALL_CYCLES_sum"),
+                 ("ta_busy_cycles_avg_per_launch", "TA_BUSY_avr"), ("ta_busy_cycles_max_per_launch", "TA_BUSY_max"),
+                 ("ta_addr_stalled_by_tc_cycles_per_launch", "TA_ADDR_STALLED_BY_TC_CYCLES_sum"), ("ta_data_stalled_by_tc_cycles_per_launch", "TA_DATA_STALLED_BY_TC_CYCLES_sum")):
+    v = active_mean(vals.get(ctr))
+    if v is not None:
+        out[key] = v
+if "ta_busy_cycles_avg_per_launch" in out and launch_us:
+    out["ta_busy_pct_of_launch"] = 100.0 * out["ta_busy_cycles_avg_per_launch"] / (launch_us * 2.4e3)  # (2.4 GHz, the clock of instruction_floor_us)
 out["note"] = ("mean over the active launches (> half of the 90th percentile); FETCH_SIZE doubled per the gfx950 note in MI355X_MICROARCH.md, WRITE_SIZE uncorrected; "
                "l2_read_bytes assumes 128-B TCP->TCC read requests; instruction_floor = SQ_INSTS_VALU wave-instructions x 4 cycles / 1024 SIMDs at 2.4 GHz")
 with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "traffic_%s.json" % name), "w") as f:
