@@ -145,6 +145,10 @@ class IvoxBlobVoxel(C.Structure):
     _fields_ = [("key", C.c_uint64), ("count", C.c_uint32), ("pad", C.c_uint32)]
 
 
+# every symbol include/fls_knn_order.h declares (FLS_KNN_ORDER_REVISION 1): the neighbour order of the iVox point-to-plane kind
+KNN_ORDER_SYMBOLS = ["fls_knn_order_revision", "fls_set_knn_order", "fls_get_knn_order", "fls_knn_order_limits"]
+KNN_ORDER_DEFAULT, KNN_ORDER_REFERENCE = 0, 1
+
 FLS_OK, FLS_NOT_CONVERGED, FLS_SKIPPED = 0, 1, 2
 FLS_ERR_INVALID, FLS_ERR_DEVICE, FLS_ERR_RANGE, FLS_ERR_NOMEM, FLS_ERR_STATE = -1, -2, -3, -4, -5
 
@@ -570,6 +574,15 @@ def lib():
             L.fls_kd_image_revision.argtypes = []
             L.fls_replicas_match_batch_fused.restype = C.c_int
             L.fls_replicas_match_batch_fused.argtypes = L.fls_replicas_match_batch.argtypes
+        if hasattr(L, "fls_knn_order_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_knn_order_revision.restype = C.c_int
+            L.fls_knn_order_revision.argtypes = []
+            L.fls_set_knn_order.restype = C.c_int
+            L.fls_set_knn_order.argtypes = [hp, C.c_int]
+            L.fls_get_knn_order.restype = C.c_int
+            L.fls_get_knn_order.argtypes = [hp, C.POINTER(C.c_int)]
+            L.fls_knn_order_limits.restype = C.c_int
+            L.fls_knn_order_limits.argtypes = [C.POINTER(C.c_int)]
         L.fls_status_string.restype = C.c_char_p
         L.fls_status_string.argtypes = [C.c_int]
         L.fls_abi_version.restype = C.c_int
@@ -581,6 +594,15 @@ def lib():
 
 def status_string(s: int) -> str:
     return lib().fls_status_string(int(s)).decode()
+
+
+def knn_order_limit() -> int:
+    """fls_knn_order_limits: W, the records of one query's work array in the reference neighbour order (include/fls_knn_order.h)."""
+    w = C.c_int(0)
+    rc = lib().fls_knn_order_limits(C.byref(w))
+    if rc != FLS_OK:
+        raise FlsError(rc, "fls_knn_order_limits")
+    return int(w.value)
 
 
 def device_count() -> int:

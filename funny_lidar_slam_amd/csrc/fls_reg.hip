@@ -13,3 +13,5 @@
 #include "abi_debug_voxel.hpp"  // fls_debug_voxel_grid, _voxel_grid_timed, _exact_sort, _exact_sort_marks
 #include "abi_debug_loop.hpp"   // fls_debug_loop.h
 #include "abi_debug_knn.hpp"    // fls_debug_knn.h
+// The reference neighbour order of the iVox kind: its kernel is named here, behind every other one (see the header).
+#include "abi_knn_order.hpp"     // fls_knn_order.h

@@ -10,6 +10,7 @@
 #include <vector>
 #include <stdexcept>
 #include "../../include/fls_reg.h"
+#include "../../include/fls_knn_order.h"
 
 namespace fls {
 

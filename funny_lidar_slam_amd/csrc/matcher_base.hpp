@@ -117,6 +117,9 @@ struct fls_matcher {
     // the map image current and complete on the device, the owner's stream idle
     virtual fls_status prepare_batch() { FLS_HIP(hipStreamSynchronize(stream)); return have_map ? FLS_OK : FLS_ERR_STATE; }
     virtual void tune_lane(fls_matcher&) {}                                    // copy run-time switches to a lane
+    // fls_knn_order.h: only the iVox point-to-plane kind has a reference order to select
+    virtual fls_status set_knn_order(int mode) { return mode == FLS_KNN_ORDER_DEFAULT ? FLS_OK : FLS_ERR_STATE; }
+    virtual int knn_order() const { return FLS_KNN_ORDER_DEFAULT; }
     // at least `want` lane clones, if they can be set up; returns how many of `want` exist
     size_t ensure_lanes(size_t want) {
         while (lanes.size() < want) {

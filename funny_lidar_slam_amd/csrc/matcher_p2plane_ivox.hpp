@@ -64,6 +64,11 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     DeviceGridBuilder fitness_builder;
     std::vector<Pt4> h_nn;
     std::vector<unsigned char> h_cnt, h_flag;
+    // fls_knn_order.h: the kNN launches in the reference's neighbour order (kernels_ivox_knn_reforder.hpp), FLS_IVOX_KNN_ORDER=reference at creation
+    bool knn_reference = false;
+    size_t n_ref_launches = 0;                     // kNN launches run in reference order (fls_map_size slot 177, with the lanes')
+    DevBuf<unsigned long long> d_ref_fallbacks;    // queries that kept the default order because of the per-query limit W, since creation
+    size_t n_ref_fallbacks = 0;                    // ... as of the last reference-order Match (slot 178, with the lanes')
 
     ~P2PlaneIvoxMatcher() override { if (stream) (void)hipStreamSynchronize(stream); }
     fls_status init() {
@@ -73,8 +78,14 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         host_timing = host_timing_enabled();
         init_tickets(d_ticket);
         map.init(stream, unsigned(kind), p.is_localization_mode != 0);
+        if (const char* e = std::getenv("FLS_IVOX_KNN_ORDER")) knn_reference = std::strcmp(e, "reference") == 0;
+        d_ref_fallbacks.reserve(1);
+        FLS_HIP(hipMemsetAsync(d_ref_fallbacks.p, 0, sizeof(unsigned long long), stream));
         return FLS_OK;
     }
+    fls_status set_knn_order(const int mode) override { knn_reference = mode == FLS_KNN_ORDER_REFERENCE; return FLS_OK; }
+    int knn_order() const override { return knn_reference ? FLS_KNN_ORDER_REFERENCE : FLS_KNN_ORDER_DEFAULT; }
+    void tune_lane(fls_matcher& lane) override { static_cast<P2PlaneIvoxMatcher&>(lane).knn_reference = knn_reference; }
     // what earlier Matches left behind, forgotten (nearest_points_ of a fresh matcher is empty): per batch job, and whenever the map is replaced
     void reset_match_state() { nn_n = 0; have_final = false; nn_rows_current = true; spec_pending = false; }
     void reset_job_state() override { reset_match_state(); }
@@ -442,6 +453,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         m.go = true;
         return FLS_OK;
     }
+    void launch_knn_reforder(const MatchPlan& m, bool first, const float* src_x, const float* src_y, const float* src_z, float* dev_copy, hipEvent_t e0,
+                             hipEvent_t e1);  // kernels_ivox_knn_reforder.hpp
     unsigned match_launch(const MatchPlan& m) {
         const size_t n = m.n;
         auto after_chunk = [&](int) {
@@ -463,7 +476,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             const float* const src_y = from_host ? hx + n : (const float*)scan.y.p;
             const float* const src_z = from_host ? hx + 2 * n : (const float*)scan.z.p;
             float* const dev_copy = from_host ? scan.xyz.p : nullptr;
-            with_bools([&](auto COUNT, auto DENSE, auto FIRST, auto GEN) {  // (4 lanes per query: 64 queries per 256-thread workgroup)
+            if (knn_reference) launch_knn_reforder(m, first != 0, src_x, src_y, src_z, dev_copy, e0, e1);
+            else with_bools([&](auto COUNT, auto DENSE, auto FIRST, auto GEN) {  // (4 lanes per query: 64 queries per 256-thread workgroup)
                 hipExtLaunchKernelGGL((ivox_knn_kernel<COUNT.value, DENSE.value, FIRST.value, GEN.value>), dim3(m.knn_blocks), dim3(256), 0, stream, e0, e1, 0,
                                       src_x, src_y, src_z, int(n), (const GnState*)d_state.p, m.T0, m.v.g, m.v.win, m.v.inv_resolution, d_nn.p, d_nn_cnt.p,
                                       d_flag.p, d_tc.p, kIvoxXcdChunk, d_nn_ids.p, nn_prev, dev_copy);
@@ -480,6 +494,12 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     fls_status match_finish(double* T, unsigned word, int update_map, fls_stats* out) {
         scan_in_staging = false;  // (the first launch left the device copy)
         nn_rows_current = false;  // the lists of every point with candidates are slots of the current image now
+        if (knn_reference) {
+            unsigned long long fb = 0;
+            FLS_HIP(hipMemcpyAsync(&fb, d_ref_fallbacks.p, sizeof(fb), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            n_ref_fallbacks = size_t(fb);
+        }
         const Mailbox& mb = take_result(word);
         std::memcpy(T, mb.T, sizeof(double) * 16);
         std::memcpy(T_, mb.T, sizeof(T_));
@@ -516,6 +536,8 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     DevBuf<IvoxJob> d_jobs;
     fls_status match_batch_shared_ivox(size_t n_jobs, const float* const* s0, const size_t* n0, const float* const*, const size_t*, int stride, double* T,
                                        fls_stats* st, int32_t* status, int n_slots) override {
+        // (the shared launches are the default order's: a reference-order handle runs the jobs on its lanes, as a kind without a shared form does)
+        if (knn_reference) return fls_matcher::match_batch_shared_ivox(n_jobs, s0, n0, nullptr, nullptr, stride, T, st, status, n_slots);
         std::vector<MatchPlan> plan(size_t(2) * kMaxLanes);  // per slot
         size_t n_class[2] = {0, 0};                           // jobs of the 256- / 512-thread fit class in the current group
         unsigned knn_rows_max = 0, fit_rows_max[2] = {0, 0};
@@ -649,7 +671,14 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         }
         return int(n);
     }
-    size_t map_size(int slot) const override { return slot == 176 ? size_t(last_tc.shared) : map.counter(slot); }  // (176: the last counting Match's kNN waves on the shared-run path)
+    size_t map_size(int slot) const override {
+        if (slot == 177 || slot == 178) {  // reference-order kNN launches / queries that fell back to the default order: this handle's and its batch lanes'
+            size_t v = slot == 177 ? n_ref_launches : n_ref_fallbacks;
+            for (const auto& l : lanes) v += l->map_size(slot);
+            return v;
+        }
+        return slot == 176 ? size_t(last_tc.shared) : map.counter(slot);  // (176: the last counting Match's kNN waves on the shared-run path)
+    }
 };
 
 }  // namespace fls

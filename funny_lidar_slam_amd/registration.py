@@ -335,6 +335,26 @@ class RegistrationInterface:
     def map_size(self, slot: int = 0) -> int:
         return int(_lib.lib().fls_map_size(self._h, slot))
 
+    def SetKnnOrder(self, order: str) -> None:
+        """fls_set_knn_order (include/fls_knn_order.h): "default" = candidates ordered by (distance bits, map slot); "reference" = the reference's own
+        std::nth_element order, exact under distance ties (PointToPlane_IVOX only: every other kind raises FlsError with FLS_ERR_STATE and stays
+        usable).  A parity mode: a Match costs several times the default's.  map_size(177) counts the kNN launches run in reference order,
+        map_size(178) the queries that kept the default order because of the per-query limit (_lib.knn_order_limit())."""
+        modes = {"default": _lib.KNN_ORDER_DEFAULT, "reference": _lib.KNN_ORDER_REFERENCE}
+        if order not in modes:
+            raise ValueError(f"order must be one of {sorted(modes)}")
+        rc = _lib.lib().fls_set_knn_order(self._h, modes[order])
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_set_knn_order")
+
+    def KnnOrder(self) -> str:
+        """fls_get_knn_order: "default" or "reference"."""
+        mode = C.c_int(-1)
+        rc = _lib.lib().fls_get_knn_order(self._h, C.byref(mode))
+        if rc != _lib.FLS_OK:
+            raise FlsError(rc, "fls_get_knn_order")
+        return "reference" if mode.value == _lib.KNN_ORDER_REFERENCE else "default"
+
     def ndt_voxels(self) -> dict:
         """fls_debug_ndt_voxels (IncrementalNDT): every alive voxel in LRU order, most recently touched first, as a dict of arrays --
         keys (n, 3) int32, vid, num_points (n,) int32, estimated, pending (n,) uint8, mu (n, 3), sigma and info (n, 9) column-major."""

@@ -20,6 +20,7 @@
 #include "fls_reg.h"
 #include "fls_preprocess.h"
 #include "fls_features_device.h"
+#include "fls_knn_order.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -188,6 +189,14 @@ public:
         const fls_status rc = fls_get_fitness_score(handle_, max_range, &score);
         if (rc != FLS_OK) return std::numeric_limits<float>::max();
         return score;
+    }
+
+    // fls_knn_order.h: the reference's own std::nth_element neighbour order, exact under distance ties (PointToPlane_IVOX_HIP only; a parity
+    // mode for replaying a recording against the reference's output -- a Match costs several times the default's).  false: another kind.
+    bool SetReferenceKnnOrder(bool on) {
+        const fls_status rc = fls_set_knn_order(handle_, on ? FLS_KNN_ORDER_REFERENCE : FLS_KNN_ORDER_DEFAULT);
+        if (rc != FLS_OK) std::fprintf(stderr, "HipRegistration::SetReferenceKnnOrder: %s\n", fls_status_string(rc));
+        return rc == FLS_OK;
     }
 
     const fls_stats& stats() const { return stats_; }

@@ -293,7 +293,10 @@ int fls_get_correspondences(fls_handle h, int slot, int32_t* ids, uint8_t* cnt, 
  * restores the push through the host, FLS_DEVICE_VOXELGRID=0 / FLS_DEVICE_GRID_BUILD=0 imply it), 165 = clouds pushed through the host while
  * a device deque exists (fls_add_cloud_to_local_map, a host-filtered ICP source, the switch), 166 = clouds whose host copy was fetched from
  * the device deque because something read it (a rebuild the device declined, an export written by the host), 167 = keyframes pushed on
- * the device whose map rebuild the device then declined (the host rebuilt, on the fetched deque).                                          */
+ * the device whose map rebuild the device then declined (the host rebuilt, on the fetched deque).
+ * iVox, the reference neighbour order (fls_knn_order.h; the handle's own Matches and its batch lanes' together): 177 = kNN launches run in
+ * reference order since the handle was created, 178 = queries of those launches that kept the default order because a voxel they probe holds
+ * more points than the per-query limit admits (fls_knn_order_limits), as of the last reference-order Match.                                 */
 size_t fls_map_size(fls_handle h, int slot);
 
 /* ---- measurement hooks ----------------------------------------------------------------------------
