@@ -74,6 +74,9 @@ DEBUG_KNN_SYMBOLS = ["fls_debug_knn_revision", "fls_debug_grid_knn5", "fls_debug
 # every symbol include/fls_debug_ivox_knn.h declares (FLS_DEBUG_IVOX_KNN_REVISION 1): the limits of the iVox kNN kernel's shared-run gate
 DEBUG_IVOX_KNN_SYMBOLS = ["fls_debug_ivox_knn_revision", "fls_debug_ivox_knn_limits"]
 
+# every symbol include/fls_debug_ivox_update.h declares (FLS_DEBUG_IVOX_UPDATE_REVISION 1): one decided batch through the iVox map update
+DEBUG_IVOX_UPDATE_SYMBOLS = ["fls_debug_ivox_update_revision", "fls_debug_ivox_add_points"]
+
 # every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
 # fls_map_image_* and the replica sets of fls_reg.h
 NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
@@ -566,6 +569,11 @@ def lib():
             L.fls_debug_ivox_knn_revision.argtypes = []
             L.fls_debug_ivox_knn_limits.restype = C.c_int
             L.fls_debug_ivox_knn_limits.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "fls_debug_ivox_update_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_debug_ivox_update_revision.restype = C.c_int
+            L.fls_debug_ivox_update_revision.argtypes = []
+            L.fls_debug_ivox_add_points.restype = C.c_int
+            L.fls_debug_ivox_add_points.argtypes = [hp, fp, bp, C.c_size_t, C.POINTER(C.c_uint32)]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

@@ -8,10 +8,11 @@
 #include "abi_frontend.hpp"  // fls_features.h, fls_features_device.h, fls_preprocess.h, fls_ingest.h, the two attach calls
 #include "abi_stores.hpp"    // fls_keyframes.h, fls_localmap.h
 // What exists for the tests.  These hooks are the first host code to name some kernels, and the code object lists kernels in the order
-// of first naming: keep the order of these four lines, and of the hooks within each file.
+// of first naming: keep the order of these lines, and of the hooks within each file.
 #include "abi_debug_fit.hpp"    // fls_debug_linalg.h, fls_debug_fit.h, fls_debug_ndt.h; fls_debug_fullpiv_qr6, _ldlt6, _last_system
 #include "abi_debug_voxel.hpp"  // fls_debug_voxel_grid, _voxel_grid_timed, _exact_sort, _exact_sort_marks
 #include "abi_debug_loop.hpp"   // fls_debug_loop.h
 #include "abi_debug_knn.hpp"    // fls_debug_knn.h
+#include "abi_debug_ivox_update.hpp"  // fls_debug_ivox_update.h (names no kernel of its own)
 // The reference neighbour order of the iVox kind: its kernel is named here, behind every other one (see the header).
 #include "abi_knn_order.hpp"     // fls_knn_order.h

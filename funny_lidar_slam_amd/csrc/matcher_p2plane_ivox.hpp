@@ -227,8 +227,112 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         return c.lx != nullptr;
     }
 
-    fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud, const bool from_resident_scan = false, const bool pre_enqueued = false) {
+    // A decided batch into the map: insertion code + world point of n source points stand in d_code / d_pw (launch_decide, or the test hook
+    // fls_debug_ivox_add_points), `counted` says the codes are counted per block (IvoxMap::count_args), `enqueued` that the update chain is
+    // queued already (the speculative chain).  A Device map tries the device chain; a batch it refuses, and every batch of a map the host holds,
+    // is replayed on the mirror in the reference's order (code 1 in source order, then code 2).  on_mirror false: the device applied the batch,
+    // nothing is left to do.  on_mirror true: the mirror took the lists as far as `rc` says and the caller settles the image (settle_mirror).
+    // chain_status (may be null): the status word the chain's commit published, 0xFFFFFFFF when no chain ran.
+    fls_status apply_decided(const size_t n, const bool counted, const bool enqueued, const bool scan_intensities, const std::chrono::steady_clock::time_point tm0,
+                             bool& on_mirror, unsigned* chain_status) {
         using Verdict = IvoxMap::Verdict;
+        HostIvox& ivox = map.ivox;
+        std::vector<PtI> to_add, no_downsample;
+        on_mirror = true;
+        if (chain_status) *chain_status = 0xFFFFFFFFu;
+        if (n) {
+            if (!enqueued && map.on_device() && !map.enqueue_update(d_code.p, d_pw.p, n, counted)) map.fall_back(Verdict::Refused);  // (too large for the device path)
+            if (map.on_device()) {
+                Verdict v = map.await_update(n);
+                if (v == Verdict::Skipped) {
+                    // a speculative chain that judged "no update here" although the host wants one (cannot happen while host and device
+                    // read the same words; kept as a safe path): decide + apply the ordinary way
+                    nn_rows_current = false;  // (the skipped launch materialised nothing)
+                    const bool recounted = launch_decide(n, false);
+                    ensure_nn_rows();
+                    v = map.enqueue_update(d_code.p, d_pw.p, n, recounted) ? map.await_update(n) : Verdict::Refused;
+                }
+                if (chain_status) *chain_status = map.upd_mb_host->status;
+                if (v == Verdict::Applied) {
+                    if (host_timing)
+                        std::fprintf(stderr, "[fls host] device AddPoints: %u points into %u voxels, %.3f ms\n", map.upd_mb_host->added, map.upd_mb_host->touched,
+                                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count());
+                    on_mirror = false;
+                    return FLS_OK;
+                }
+                // refused (an eviction-order conflict, the point array or brick pool full): nothing was applied; the exact sequential
+                // path below replays the batch on the host mirror
+                map.fall_back(v);
+            }
+            map.to_mirror();   // (an ImageOnly map -- bulk-built, device update not allowed -- has no mirror yet)
+            h_code.resize(n);  // (host copies only on this path: the device applied nothing)
+            h_pw.resize(n);
+            FLS_HIP(hipMemcpyAsync(h_code.data(), d_code.p, n, hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipMemcpyAsync(h_pw.data(), d_pw.p, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
+            FLS_HIP(hipStreamSynchronize(stream));
+            if (scan_intensities) scan.fetch_stage(stream);  // (an attached scan's intensities are still on the device)
+            for (size_t i = 0; i < n; ++i) {
+                if (h_code[i] == 0) continue;
+                const PtI pw{h_pw[i].x, h_pw[i].y, h_pw[i].z, scan_intensities ? scan.staged_intensity(i) : 0.0f};
+                (h_code[i] == 1 ? to_add : no_downsample).push_back(pw);
+            }
+        }
+        const auto tm1 = std::chrono::steady_clock::now();
+        // (each list is all-or-nothing -- HostIvox::add_points checks every key first -- so a key beyond the limit among the code-2 points
+        // leaves the code-1 points inserted: the caller settles the image whatever `rc` says)
+        fls_status rc = ivox.add_points(to_add.data(), to_add.size());
+        if (rc != FLS_OK) return rc;
+        rc = ivox.add_points(no_downsample.data(), no_downsample.size());
+        if (rc != FLS_OK) return rc;
+        if (host_timing) {
+            const auto tm2 = std::chrono::steady_clock::now();
+            std::fprintf(stderr, "[fls host] decide+lists %.3f ms (%zu + %zu pts), AddPoints %.3f ms\n",
+                         std::chrono::duration<double, std::milli>(tm1 - tm0).count(), to_add.size(), no_downsample.size(),
+                         std::chrono::duration<double, std::milli>(tm2 - tm1).count());
+        }
+        return FLS_OK;
+    }
+    // the image behind a mirror that took insertions: the journal scattered (or the image re-flattened), the map back on the device where allowed
+    void settle_mirror() {
+        map.mirror_changed();
+        const auto tr0 = std::chrono::steady_clock::now();
+        map.refresh();
+        if (host_timing)
+            std::fprintf(stderr, "[fls host] refresh_image %.3f ms (%zu pt updates, %zu cell updates)\n",
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), map.image.pt_upd.size(),
+                         map.image.cell_upd.size());
+    }
+    // fls_debug_ivox_add_points (include/fls_debug_ivox_update.h): one decided batch, given by the caller instead of launch_decide
+    fls_status debug_add_points(const float* world_xyz, const unsigned char* code, const size_t n, unsigned* chain_status) {
+        *chain_status = 0xFFFFFFFFu;
+        const auto tm0 = std::chrono::steady_clock::now();
+        bool counted = false;
+        if (n) {
+            ensure_nn_rows();  // (the update moves map slots)
+            d_code.reserve(n);
+            d_pw.reserve(n);
+            h_pw.resize(n);
+            for (size_t i = 0; i < n; ++i) h_pw[i] = Pt4{world_xyz[3 * i], world_xyz[3 * i + 1], world_xyz[3 * i + 2], 0};  // (w = 0.f, as the decision launch writes it)
+            FLS_HIP(hipMemcpyAsync(d_code.p, code, n, hipMemcpyHostToDevice, stream));
+            FLS_HIP(hipMemcpyAsync(d_pw.p, h_pw.data(), n * sizeof(float4), hipMemcpyHostToDevice, stream));
+            FLS_HIP(hipStreamSynchronize(stream));  // (pageable sources: both may change once the call returns)
+            const IvoxMap::CountArgs c = map.count_args(n);
+            if (c.lx) {  // what the decision launch does besides deciding: block-local counts, raw block totals, the two status words reset
+                const IvoxUpdBatch b{d_code.p, d_pw.p, int(n), c.lx, c.bt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+                hipLaunchKernelGGL(ivox_upd_count, dim3(unsigned(IvoxMap::update_blocks(n))), dim3(kUpdBlock), 0, stream, b);
+                FLS_HIP(hipGetLastError());
+                FLS_HIP(hipMemsetAsync(c.status, 0, sizeof(unsigned), stream));  // kUpdOk
+                FLS_HIP(hipMemsetAsync(c.apply, 0, sizeof(unsigned), stream));
+                counted = true;
+            }
+        }
+        bool on_mirror = false;
+        const fls_status rc = apply_decided(n, counted, /*enqueued=*/false, /*scan_intensities=*/false, tm0, on_mirror, chain_status);
+        if (on_mirror) settle_mirror();
+        return rc;
+    }
+
+    fls_status add_cloud_impl(const std::vector<PtI>& planar_cloud, const bool from_resident_scan = false, const bool pre_enqueued = false) {
         HostIvox& ivox = map.ivox;
         if (map.is_replica()) return FLS_ERR_STATE;
         if (p.is_localization_mode) { map.become_empty(); map.is_first = true; }
@@ -245,59 +349,17 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
         } else if (from_resident_scan) {
             // :79-131 on the device (the cloud is the scan just matched, still resident): decision code + world point
             // per source point; the host only walks the codes to build the two insertion lists in index order.
-            std::vector<PtI> to_add, no_downsample;
             const size_t n = std::min(number_planar_point, scan.n);
             const auto tm0 = std::chrono::steady_clock::now();
-            if (n) {
-                if (!pre_enqueued) {
-                    const bool counted = launch_decide(n, /*speculative=*/false);
-                    ensure_nn_rows();
-                    if (map.on_device() && !map.enqueue_update(d_code.p, d_pw.p, n, counted)) map.fall_back(Verdict::Refused);  // (too large for the device path)
-                }
-                if (map.on_device()) {
-                    Verdict v = map.await_update(n);
-                    if (v == Verdict::Skipped) {
-                        // a speculative chain that judged "no update here" although the host wants one (cannot happen while host and device
-                        // read the same words; kept as a safe path): decide + apply the ordinary way
-                        nn_rows_current = false;  // (the skipped launch materialised nothing)
-                        const bool counted = launch_decide(n, false);
-                        ensure_nn_rows();
-                        v = map.enqueue_update(d_code.p, d_pw.p, n, counted) ? map.await_update(n) : Verdict::Refused;
-                    }
-                    if (v == Verdict::Applied) {
-                        if (host_timing)
-                            std::fprintf(stderr, "[fls host] device AddPoints: %u points into %u voxels, %.3f ms\n", map.upd_mb_host->added, map.upd_mb_host->touched,
-                                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count());
-                        return FLS_OK;
-                    }
-                    // refused (an eviction-order conflict, the point array or brick pool full): nothing was applied; the exact sequential
-                    // path below replays the batch on the host mirror
-                    map.fall_back(v);
-                }
-                map.to_mirror();   // (an ImageOnly map -- bulk-built, device update not allowed -- has no mirror yet)
-                h_code.resize(n);  // (host copies only on this path: the device applied nothing)
-                h_pw.resize(n);
-                FLS_HIP(hipMemcpyAsync(h_code.data(), d_code.p, n, hipMemcpyDeviceToHost, stream));
-                FLS_HIP(hipMemcpyAsync(h_pw.data(), d_pw.p, n * sizeof(float4), hipMemcpyDeviceToHost, stream));
-                FLS_HIP(hipStreamSynchronize(stream));
-                scan.fetch_stage(stream);  // (an attached scan's intensities are still on the device)
-                for (size_t i = 0; i < n; ++i) {
-                    if (h_code[i] == 0) continue;
-                    const PtI pw{h_pw[i].x, h_pw[i].y, h_pw[i].z, scan.staged_intensity(i)};
-                    (h_code[i] == 1 ? to_add : no_downsample).push_back(pw);
-                }
+            bool counted = false;
+            if (n && !pre_enqueued) {
+                counted = launch_decide(n, /*speculative=*/false);
+                ensure_nn_rows();
             }
-            const auto tm1 = std::chrono::steady_clock::now();
-            rc = ivox.add_points(to_add.data(), to_add.size());
-            if (rc != FLS_OK) return rc;
-            rc = ivox.add_points(no_downsample.data(), no_downsample.size());
-            if (rc != FLS_OK) return rc;
-            if (host_timing) {
-                const auto tm2 = std::chrono::steady_clock::now();
-                std::fprintf(stderr, "[fls host] decide+lists %.3f ms (%zu + %zu pts), AddPoints %.3f ms\n",
-                             std::chrono::duration<double, std::milli>(tm1 - tm0).count(), to_add.size(), no_downsample.size(),
-                             std::chrono::duration<double, std::milli>(tm2 - tm1).count());
-            }
+            bool on_mirror = false;
+            rc = apply_decided(n, counted, pre_enqueued, /*scan_intensities=*/true, tm0, on_mirror, nullptr);
+            if (!on_mirror) return rc;  // (the device applied the batch)
+            if (rc != FLS_OK) { settle_mirror(); return rc; }
         } else {
             // external non-first call with an arbitrary cloud: same rule on the host (:79-131)
             download_nn();
@@ -335,15 +397,7 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             rc = ivox.add_points(no_downsample.data(), no_downsample.size());
             if (rc != FLS_OK) return rc;
         }
-        map.mirror_changed();
-        {
-            const auto tr0 = std::chrono::steady_clock::now();
-            map.refresh();
-            if (host_timing)
-                std::fprintf(stderr, "[fls host] refresh_image %.3f ms (%zu pt updates, %zu cell updates)\n",
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), map.image.pt_upd.size(),
-                             map.image.cell_upd.size());
-        }
+        settle_mirror();
         if (p.is_localization_mode) {  // :134-138 kd-tree for GetFitnessScore
             const auto tf0 = std::chrono::steady_clock::now();
             rc = fitness_grid.build(planar_cloud, 1.0f, stream);

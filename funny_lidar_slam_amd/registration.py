@@ -375,6 +375,20 @@ class RegistrationInterface:
                 raise FlsError(rc, "fls_debug_ndt_voxels")
         return out
 
+    def DebugAddPoints(self, points, codes):
+        """fls_debug_ivox_add_points (include/fls_debug_ivox_update.h; PointToPlane_IVOX in mapping mode): one decided batch -- world points (n, 3)
+        and their insertion codes (n,) 0 drop / 1 points_to_add / 2 point_no_need_downsample -- through the product's map update.  Returns
+        (status, device_status): the call's status (FLS_OK, or an error: nothing is raised) and the status word of the batch's device chain,
+        0xFFFFFFFF when none ran."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+        code = np.ascontiguousarray(np.asarray(codes, dtype=np.uint8).reshape(-1))
+        if len(pts) != len(code):
+            raise ValueError("one code per point")
+        st = C.c_uint32(0)
+        rc = _lib.lib().fls_debug_ivox_add_points(self._h, pts.ctypes.data_as(C.POINTER(C.c_float)), code.ctypes.data_as(C.POINTER(C.c_uint8)), len(code),
+                                                  C.byref(st))
+        return int(rc), int(st.value)
+
     def set_profiling(self, events: bool, counters: bool = False) -> None:
         _lib.lib().fls_set_profiling(self._h, (1 if events else 0) | (2 if counters else 0))
 
