@@ -68,6 +68,14 @@ DEBUG_NDT_SYMBOLS = ["fls_debug_ndt_revision", "fls_debug_ndt_voxels"]
 DEBUG_LOOP_SYMBOLS = ["fls_debug_loop_revision", "fls_debug_loop_ndt", "fls_debug_loop_gicp_cov", "fls_debug_loop_gicp_corr", "fls_debug_loop_gicp_fdf",
                       "fls_debug_loop_fitness"]
 
+# every symbol include/fls_loop_device.h declares (FLS_LOOP_DEVICE_REVISION 1): the loop-closure Match from clouds on the device
+LOOP_DEVICE_SYMBOLS = ["fls_loop_device_revision", "fls_loop_match_device", "fls_keyframes_loop_match_device", "fls_loop_device_stat"]
+LOOP_DEVICE_STAT_SLOTS = ("matches", "filters_device", "filters_host", "leaves_device", "leaves_host", "input_bytes_downloaded",
+                          "filtered_bytes_downloaded")
+
+# every symbol include/fls_debug_loop_leaves.h declares (FLS_DEBUG_LOOP_LEAVES_REVISION 1): test hooks of the device leaf-Gaussian build
+DEBUG_LOOP_LEAVES_SYMBOLS = ["fls_debug_loop_leaves_revision", "fls_debug_loop_leaves", "fls_debug_loop_ndt_device"]
+
 # every symbol include/fls_debug_knn.h declares (FLS_DEBUG_KNN_REVISION 1): test hooks of the cooperative grid k-NN kernels of the kd-tree kinds
 DEBUG_KNN_SYMBOLS = ["fls_debug_knn_revision", "fls_debug_grid_knn5", "fls_debug_grid_knn5_dual", "fls_debug_icp_knn1"]
 
@@ -554,6 +562,23 @@ def lib():
             L.fls_debug_loop_gicp_fdf.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, dp, ip, dp, C.c_int, dp]
             L.fls_debug_loop_fitness.restype = C.c_int
             L.fls_debug_loop_fitness.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, dp, i64p]
+        if hasattr(L, "fls_loop_device_revision"):  # (as fls_batch_ivox_revision above)
+            i64p = C.POINTER(C.c_int64)
+            vp = C.c_void_p  # device pointers
+            L.fls_loop_device_revision.restype = C.c_int
+            L.fls_loop_device_revision.argtypes = []
+            L.fls_loop_match_device.restype = C.c_int
+            L.fls_loop_match_device.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t, dp, fp, C.c_void_p]
+            L.fls_keyframes_loop_match_device.restype = C.c_int
+            L.fls_keyframes_loop_match_device.argtypes = L.fls_keyframes_loop_match.argtypes
+            L.fls_loop_device_stat.restype = C.c_size_t
+            L.fls_loop_device_stat.argtypes = [C.c_int, C.c_int]
+            L.fls_debug_loop_leaves_revision.restype = C.c_int
+            L.fls_debug_loop_leaves_revision.argtypes = []
+            L.fls_debug_loop_leaves.restype = C.c_int
+            L.fls_debug_loop_leaves.argtypes = [C.c_int, fp, C.c_int, C.c_int, C.c_float, C.c_int, ip, ip, dp, dp, fp, C.c_int, ip, ip]
+            L.fls_debug_loop_ndt_device.restype = C.c_int
+            L.fls_debug_loop_ndt_device.argtypes = [C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_float, dp, C.c_int, dp, dp, dp, i64p, ip, ip]
         if hasattr(L, "fls_debug_knn_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_debug_knn_revision.restype = C.c_int
             L.fls_debug_knn_revision.argtypes = []

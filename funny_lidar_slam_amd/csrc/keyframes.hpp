@@ -58,6 +58,12 @@ struct fls_keyframes {
     fls::DevBuf<float> d_planes;      // merge output for the final filter
     fls::DevBuf<unsigned char> d_table;
     fls::PinnedBuf<unsigned char> h_table;
+    // fls_keyframes_loop_match_device: the two sub-maps as planes, each with a segment table of its own (the second merge is queued while
+    // the first one's table is still on its way), and the event the matcher's stream waits for
+    fls::DevBuf<float> d_sub[2];
+    fls::DevBuf<unsigned char> d_sub_table[2];
+    fls::PinnedBuf<unsigned char> h_sub_table[2];
+    hipEvent_t ev_sub = nullptr;
     std::vector<float> tmp;
     size_t n_points = 0, n_cached = 0, n_filters = 0, n_hits = 0, n_declined = 0, n_merges = 0, n_bytes = 0;
 
@@ -65,6 +71,7 @@ struct fls_keyframes {
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         if (ev_t0) (void)hipEventDestroy(ev_t0);
         if (ev_t1) (void)hipEventDestroy(ev_t1);
+        if (ev_sub) (void)hipEventDestroy(ev_sub);
     }
 
     void init() {
@@ -72,6 +79,7 @@ struct fls_keyframes {
         FLS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         FLS_HIP(hipEventCreate(&ev_t0));
         FLS_HIP(hipEventCreate(&ev_t1));
+        FLS_HIP(hipEventCreateWithFlags(&ev_sub, hipEventDisableTiming));
     }
 
     bool valid_id(int32_t id) const { return id >= 0 && size_t(id) < kf.size(); }
@@ -192,9 +200,10 @@ struct fls_keyframes {
     }
 
     // ---- the sub-map ---------------------------------------------------------------------------------------------------------------
-    // out / cap, or `grow`: a vector that takes whatever size the result has (fls_keyframes_loop_match)
+    // out / cap, or `grow`: a vector that takes whatever size the result has (fls_keyframes_loop_match), or sub = 0 / 1: the merged cloud
+    // stays on the device as x | y | z | intensity planes of *n_out floats each in d_sub[sub] -- queued, not waited for, no final filter
     fls_status merge(const int32_t* ids, const double* poses, size_t n_ids, float leaf_each, float leaf_final, float* out, size_t cap, size_t* n_out,
-                     std::vector<float>* grow = nullptr) {
+                     std::vector<float>* grow = nullptr, int sub = -1) {
         *n_out = 0;
         if (grow) grow->clear();
         if (n_ids == 0) return FLS_OK;
@@ -211,13 +220,17 @@ struct fls_keyframes {
             if (grow) { grow->resize(4 * n); out = grow->data(); return true; }
             return n <= cap;
         };
-        const bool rows = !(leaf_final > 0.f);
+        const bool rows = sub < 0 && !(leaf_final > 0.f);
+        if (sub >= 0) *n_out = total;
         if (rows && !room(total)) return FLS_ERR_INVALID;
         if (total == 0) return FLS_OK;
 
         // the table: one entry per selected keyframe, then the first segment of every tile
         const size_t n_tiles = (total + fls::kKfTile - 1) / fls::kKfTile;
         const size_t table_bytes = n_ids * sizeof(fls::KfSegment) + n_tiles * sizeof(unsigned);
+        fls::PinnedBuf<unsigned char>& h_table = sub >= 0 ? h_sub_table[sub] : this->h_table;
+        fls::DevBuf<unsigned char>& d_table = sub >= 0 ? d_sub_table[sub] : this->d_table;
+        fls::DevBuf<float>& d_planes = sub >= 0 ? d_sub[sub] : this->d_planes;
         h_table.reserve(table_bytes);
         d_table.reserve(table_bytes);
         fls::KfSegment* seg = reinterpret_cast<fls::KfSegment*>(h_table.p);
@@ -251,6 +264,7 @@ struct fls_keyframes {
         FLS_HIP(hipEventRecord(ev_t1, stream));
         timed = true;
         ++n_merges;
+        if (sub >= 0) return FLS_OK;
         if (rows) {
             FLS_HIP(hipMemcpyAsync(out, d_rows.p, total * sizeof(float4), hipMemcpyDeviceToHost, stream));
             FLS_HIP(hipStreamSynchronize(stream));

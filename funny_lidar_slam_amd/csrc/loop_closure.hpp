@@ -59,6 +59,7 @@ struct LoopMatcher {
         FLS_HIP(hipHostMalloc((void**)&mail_host, sizeof(LoopMail), hipHostMallocMapped));
         std::memset(mail_host, 0, sizeof(LoopMail));
         FLS_HIP(hipHostGetDevicePointer((void**)&mail_dev, mail_host, 0));
+        if (const char* e = std::getenv("FLS_LOOP_DEVICE_LEAVES")) device_leaves = std::atoi(e) != 0;
         read_env();
     }
     void read_env() {  // per Match: one matcher per device is kept alive across calls (fls_reg.hip)
@@ -125,10 +126,23 @@ struct LoopMatcher {
         DevBuf<float> xyz;
         PinnedBuf<float> stage;
         size_t n = 0;
-        const float* x() const { return xyz.p; }
-        const float* y() const { return xyz.p + n; }
-        const float* z() const { return xyz.p + 2 * n; }
+        const float* ext[3] = {nullptr, nullptr, nullptr};  // attach(): planes that lie elsewhere on the device (a filter's output), not owned
+        const float* x() const { return ext[0] ? ext[0] : xyz.p; }
+        const float* y() const { return ext[0] ? ext[1] : xyz.p + n; }
+        const float* z() const { return ext[0] ? ext[2] : xyz.p + 2 * n; }
+        void attach(const float* px, const float* py, const float* pz, size_t count) { ext[0] = px; ext[1] = py; ext[2] = pz; n = count; }
+        // the same planes copied into this cloud's own buffer, device to device on `s` (no wait)
+        void copy_from(const float* px, const float* py, const float* pz, size_t count, hipStream_t s) {
+            ext[0] = ext[1] = ext[2] = nullptr;
+            n = count;
+            if (!n) return;
+            xyz.reserve(3 * n);
+            FLS_HIP(hipMemcpyAsync(xyz.p, px, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            FLS_HIP(hipMemcpyAsync(xyz.p + n, py, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            FLS_HIP(hipMemcpyAsync(xyz.p + 2 * n, pz, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
         void upload(const std::vector<PtI>& c, hipStream_t s) {
+            ext[0] = ext[1] = ext[2] = nullptr;
             n = c.size();
             if (!n) return;
             stage.reserve(3 * n);
@@ -161,8 +175,10 @@ struct LoopMatcher {
         std::vector<int> leaf_row;
         std::vector<double> mean, icov;
         std::vector<float> centroid;
+        std::vector<int> row_cell, row_n;  // per row: the leaf's cell index and number of points (fls_debug_loop_leaves)
         size_t rows = 0;
         DevBuf<int> d_leaf_row;
+        DevBuf<int> d_row_cell, d_row_n;   // the same, written by the device build
         DevBuf<double> d_mean, d_icov;
         DevBuf<float> d_centroid;
         // sparse form (grid volume above kMaxDenseLeafCells: a stray far point must not cost gigabytes): cell -> row through an
@@ -186,7 +202,7 @@ struct LoopMatcher {
     std::vector<LeafAcc> accs;
 
     // symmetric 3x3 eigen-decomposition, ascending (SelfAdjointEigenSolver stand-in: Jacobi via hm::svd3)
-    static void sym_eig3(const double* A, double* ev, double* evec) {
+    __host__ __device__ static void sym_eig3(const double* A, double* ev, double* evec) {
         double U[9], S[3], V[9];
         hm::svd3(A, U, S, V);
         for (int k = 0; k < 3; ++k) {
@@ -197,7 +213,34 @@ struct LoopMatcher {
         }
         for (int a = 0; a < 3; ++a)
             for (int b = a + 1; b < 3; ++b)
-                if (ev[b] < ev[a]) { std::swap(ev[a], ev[b]); for (int i = 0; i < 3; ++i) std::swap(evec[i + 3 * a], evec[i + 3 * b]); }
+                if (ev[b] < ev[a]) {
+                    { const double t = ev[a]; ev[a] = ev[b]; ev[b] = t; }
+                    for (int i = 0; i < 3; ++i) { const double t = evec[i + 3 * a]; evec[i + 3 * a] = evec[i + 3 * b]; evec[i + 3 * b] = t; }
+                }
+    }
+    // The Gaussian of a leaf of n >= 6 points from its sums (VoxelGridCovariance::applyFilter): the mean, the covariance with the 0.01 * ev[2]
+    // eigenvalue floor, its inverse -- zero for a leaf with a negative eigenvalue, which stays searchable as in PCL.  One function for
+    // build_target and the device build (kernels_loop_leaves.hpp): the same IEEE operation sequence on both sides (-ffp-contract=off).
+    __host__ __device__ static void leaf_gaussian(const int n, const double* sum, const double* xx, double* mean, double* icov) {
+        double cov[9];
+        for (int a = 0; a < 9; ++a) icov[a] = 0.0;
+        for (int a = 0; a < 3; ++a) mean[a] = sum[a] / n;
+        for (int c = 0; c < 3; ++c)
+            for (int r = 0; r < 3; ++r) cov[r + 3 * c] = (xx[r + 3 * c] - 2.0 * (sum[r] * mean[c])) / n + mean[r] * mean[c];
+        for (int i = 0; i < 9; ++i) cov[i] *= (n - 1.0) / n;
+        double ev[3], evec[9];
+        sym_eig3(cov, ev, evec);
+        if (ev[0] < 0 || ev[1] < 0 || ev[2] <= 0) return;
+        const double floor_ev = 0.01 * ev[2];
+        if (ev[0] < floor_ev) {
+            ev[0] = floor_ev;
+            if (ev[1] < floor_ev) ev[1] = floor_ev;
+            double vinv[9], tmp[9];
+            hm::inv3(evec, vinv);
+            for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) tmp[r + 3 * c] = evec[r + 3 * c] * ev[c];
+            hm::mul3(tmp, vinv, cov);
+        }
+        hm::inv3(cov, icov);
     }
 
     bool build_target(const std::vector<PtI>& in, float resolution, TargetLeaves& tl) {
@@ -277,31 +320,14 @@ struct LoopMatcher {
             tl.hash_mask = unsigned(hs - 1);
             tl.leaf_hash.assign(hs, make_int2(-1, -1));
         }
-        tl.mean.clear(); tl.icov.clear(); tl.centroid.clear();
+        tl.mean.clear(); tl.icov.clear(); tl.centroid.clear(); tl.row_cell.clear(); tl.row_n.clear();
         for (const std::pair<int, int>& oc : order) {
             const size_t cell_i = size_t(oc.first);
             const LeafAcc& l = accs[size_t(oc.second)];
             const int n = l.n;
             if (n < 6) continue;
-            double mean[3], cov[9], icov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int a = 0; a < 3; ++a) mean[a] = l.sum[a] / n;
-            for (int c = 0; c < 3; ++c)
-                for (int r = 0; r < 3; ++r) cov[r + 3 * c] = (l.xx[r + 3 * c] - 2.0 * (l.sum[r] * mean[c])) / n + mean[r] * mean[c];
-            for (int i = 0; i < 9; ++i) cov[i] *= (n - 1.0) / n;
-            double ev[3], evec[9];
-            sym_eig3(cov, ev, evec);
-            if (!(ev[0] < 0 || ev[1] < 0 || ev[2] <= 0)) {  // (else: the leaf stays searchable with a zero inverse covariance, as in PCL)
-                const double floor_ev = 0.01 * ev[2];
-                if (ev[0] < floor_ev) {
-                    ev[0] = floor_ev;
-                    if (ev[1] < floor_ev) ev[1] = floor_ev;
-                    double vinv[9], tmp[9];
-                    hm::inv3(evec, vinv);
-                    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) tmp[r + 3 * c] = evec[r + 3 * c] * ev[c];
-                    hm::mul3(tmp, vinv, cov);
-                }
-                hm::inv3(cov, icov);
-            }
+            double mean[3], icov[9];
+            leaf_gaussian(n, l.sum, l.xx, mean, icov);
             if (!tl.sparse) tl.leaf_row[cell_i] = int(tl.rows);
             else {
                 unsigned h = leaf_hash_of(int(cell_i)) & tl.hash_mask;
@@ -310,6 +336,7 @@ struct LoopMatcher {
             }
             for (int a = 0; a < 3; ++a) { tl.mean.push_back(mean[a]); tl.centroid.push_back(l.csum[a] / float(n)); }
             for (int a = 0; a < 9; ++a) tl.icov.push_back(icov[a]);
+            tl.row_cell.push_back(int(cell_i)); tl.row_n.push_back(n);
             ++tl.rows;
         }
         if (tl.rows == 0) return false;
@@ -901,6 +928,21 @@ struct LoopMatcher {
         }
         if (timing) FLS_HIP(hipStreamSynchronize(stream));
         lap(t_gicp_setup);
+        const LoopMat4f fin = gicp_outer(int(src.size()), guess, T);
+        lap(t_gicp);
+        fitness_score(int(src.size()), fin, fitness);
+        lap(t_fit);
+        if (timing) print_timing(t_filter, t_leaves, t_ndt, t_gicp_setup, t_gicp, t_fit);
+        return FLS_OK;
+    }
+
+    void print_timing(double t_filter, double t_leaves, double t_ndt, double t_gicp_setup, double t_gicp, double t_fit) const {
+        std::fprintf(stderr, "[fls loop] ms: 10 filters %.2f, leaf Gaussians + uploads %.2f, NDT align (%d evaluations) %.2f, GICP grids + covariances %.2f, GICP loop (%d evaluations) %.2f, fitness %.2f\n",
+                     t_filter, t_leaves, st.ndt_evaluations[0] + st.ndt_evaluations[1] + st.ndt_evaluations[2] + st.ndt_evaluations[3], t_ndt, t_gicp_setup, st.gicp_evaluations, t_gicp, t_fit);
+    }
+
+    // the outer GICP iterations over g.moved / g.tgt_grid / the covariances (n = source points): T = the final transformation, which is returned
+    LoopMat4f gicp_outer(const int n, const LoopMat4f& guess, double* T) {
         LoopMat4f transformation = ident(), previous = ident();
         const double corr_dist = 2.0, dist_threshold = corr_dist * corr_dist, rotation_epsilon = 2e-3, transformation_epsilon = 5e-4;
         const CellGridDev cg_tgt = cell_dev(g.tgt_grid);
@@ -913,7 +955,6 @@ struct LoopMatcher {
                     for (int k = 0; k < 4; ++k) sum += double(transformation.m[i + 4 * k]) * double(guess.m[k + 4 * j]);
                     rot.R[i + 3 * j] = sum;
                 }
-            const int n = int(src.size());
             hipLaunchKernelGGL(gicp_corr_kernel, dim3(unsigned((n + 63) / 64)), dim3(64), 0, stream, g.moved.x(), g.moved.y(), g.moved.z(), n, transformation, cg_tgt,
                                float(dist_threshold), dist_threshold, rot, (const double*)g.cov_src.p, (const double*)g.cov_tgt.p, g.corr.p, g.mahal.p);
             FLS_HIP(hipGetLastError());
@@ -938,25 +979,44 @@ struct LoopMatcher {
                                     double(transformation.m[12]), double(transformation.m[13]), double(transformation.m[14]));
             if (nr >= 30 || delta < 1) { converged = true; previous = transformation; }
         }
-        lap(t_gicp);
         const LoopMat4f fin = mul(previous, guess);
         for (int i = 0; i < 16; ++i) T[i] = double(fin.m[i]);
         st.gicp_iterations = nr; st.gicp_inner_iterations = g.inner_total; st.gicp_evaluations = g.evaluations; st.gicp_correspondences = g.n_corr;
-        // ---- getFitnessScore ------------------------------------------------------------------------------------------------
-        {
-            const int n = int(src.size()), nb = (n + kLoopBlock - 1) / kLoopBlock;
-            const double* v = reduce(nb, [&](const LoopOut rows) {
-                hipLaunchKernelGGL(loop_fitness_kernel, dim3(unsigned(nb)), dim3(kLoopBlock), 0, stream, src_own.x(), src_own.y(), src_own.z(), n, fin, cg_tgt, rows);
-            });
-            if (v[1] > 0) *fitness = float(v[0] / v[1]);
-        }
-        FLS_HIP(hipStreamSynchronize(stream));
-        lap(t_fit);
-        if (timing)
-            std::fprintf(stderr, "[fls loop] ms: 10 filters %.2f, leaf Gaussians + uploads %.2f, NDT align (%d evaluations) %.2f, GICP grids + covariances %.2f, GICP loop (%d evaluations) %.2f, fitness %.2f\n",
-                         t_filter, t_leaves, st.ndt_evaluations[0] + st.ndt_evaluations[1] + st.ndt_evaluations[2] + st.ndt_evaluations[3], t_ndt, t_gicp_setup, st.gicp_evaluations, t_gicp, t_fit);
-        return FLS_OK;
+        return fin;
     }
+
+    // getFitnessScore of src_own (n points) under `fin` against g.tgt_grid; ends with the stream drained
+    void fitness_score(const int n, const LoopMat4f& fin, float* fitness) {
+        const CellGridDev cg_tgt = cell_dev(g.tgt_grid);
+        const int nb = (n + kLoopBlock - 1) / kLoopBlock;
+        const double* v = reduce(nb, [&](const LoopOut rows) {
+            hipLaunchKernelGGL(loop_fitness_kernel, dim3(unsigned(nb)), dim3(kLoopBlock), 0, stream, src_own.x(), src_own.y(), src_own.z(), n, fin, cg_tgt, rows);
+        });
+        if (v[1] > 0) *fitness = float(v[0] / v[1]);
+        FLS_HIP(hipStreamSynchronize(stream));
+    }
+
+    // ======================================================================================================================
+    // The same Match from clouds that lie on this device (include/fls_loop_device.h).  Defined in kernels_loop_leaves.hpp (the leaf
+    // build) and loop_device.hpp (run_device), which fls_reg.hip includes last: the code object keeps the order of the kernels in front.
+    // ======================================================================================================================
+    struct DevInput {  // x | y | z | intensity planes of n floats each, any 4-byte alignment; in == nullptr: intensity 0
+        const float *x = nullptr, *y = nullptr, *z = nullptr, *in = nullptr;
+        size_t n = 0;
+    };
+    enum { kStatMatches = 0, kStatFiltersDevice, kStatFiltersHost, kStatLeavesDevice, kStatLeavesHost, kStatInputBytes, kStatFilteredBytes, kStatSlots };
+    unsigned long long dstat[kStatSlots] = {0, 0, 0, 0, 0, 0, 0};
+    bool device_leaves = true;  // FLS_LOOP_DEVICE_LEAVES=0 (read by init()): every leaf grid through build_target
+    enum LeafBuild { kLeavesNone, kLeavesBuilt, kLeavesDeclined };
+    DevicePairSort leaf_sort;
+    DevBuf<VgHeader> d_leaf_hdr;
+    PinnedBuf<VgHeader> h_leaf_hdr;
+    DevBuf<unsigned> d_leaf_lx, d_leaf_bt;
+    DevBuf<float> d_zero;             // the intensity plane of a cloud that has none
+    DevCloud tgt_filtered;           // a declined target filter's result, uploaded
+    LeafBuild build_target_device(const float* x, const float* y, const float* z, size_t n, float resolution, TargetLeaves& tl);
+    void download_leaves(TargetLeaves& tl);
+    fls_status run_device(const DevInput& source, const DevInput& target, double* T, float* fitness);
 };
 
 }  // namespace fls

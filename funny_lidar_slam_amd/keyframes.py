@@ -112,19 +112,21 @@ class KeyframeStore:
         ids, sel = self.submap_selection(keyframe_id, left, right, use_local_pose, poses)
         return self.merge(ids, sel, 0.2, 0.0)
 
-    def loop_match(self, src_ids, src_poses, tgt_ids, tgt_poses, pose: np.ndarray):
+    def loop_match(self, src_ids, src_poses, tgt_ids, tgt_poses, pose: np.ndarray, on_device: bool = False):
         """GetSubMap twice + LoopClosure::Match on the selections; `pose` (4, 4) is in/out like the reference's Mat4d&.  Returns
-        (fitness, LoopStats), equal to registration.LoopClosureMatch on the two merge() results."""
+        (fitness, LoopStats), equal to registration.LoopClosureMatch on the two merge() results.  on_device: the sub-maps stay on the
+        device and the Match starts from them there (fls_keyframes_loop_match_device): the same results, bit for bit."""
         from .registration import LoopStats
         si, sp = _ids_poses(src_ids, src_poses)
         ti, tp = _ids_poses(tgt_ids, tgt_poses)
         Tf = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(4, 4).T).reshape(-1).copy()
         fit = C.c_float()
         st = LoopStats()
-        rc = _lib.lib().fls_keyframes_loop_match(self._h, si.ctypes.data_as(_IP), sp.ctypes.data_as(_DP), si.shape[0], ti.ctypes.data_as(_IP),
-                                                 tp.ctypes.data_as(_DP), ti.shape[0], Tf.ctypes.data_as(_DP), C.byref(fit), C.byref(st))
+        call = _lib.lib().fls_keyframes_loop_match_device if on_device else _lib.lib().fls_keyframes_loop_match
+        rc = call(self._h, si.ctypes.data_as(_IP), sp.ctypes.data_as(_DP), si.shape[0], ti.ctypes.data_as(_IP), tp.ctypes.data_as(_DP), ti.shape[0],
+                  Tf.ctypes.data_as(_DP), C.byref(fit), C.byref(st))
         if rc != _lib.FLS_OK:
-            raise FlsError(rc, "fls_keyframes_loop_match")
+            raise FlsError(rc, "fls_keyframes_loop_match_device" if on_device else "fls_keyframes_loop_match")
         pose[...] = Tf.reshape(4, 4).T
         return float(fit.value), st
 

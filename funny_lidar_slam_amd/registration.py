@@ -529,6 +529,34 @@ def LoopClosureMatch(source_cloud: np.ndarray, target_cloud: np.ndarray, pose: n
     return float(fit.value), st
 
 
+def LoopClosureMatchDevice(source_planes, n_source: int, target_planes, n_target: int, pose: np.ndarray, device_id: int = 0):
+    """LoopClosureMatch from clouds that lie on the device (fls_loop_match_device): source_planes / target_planes are the four device
+    addresses (ints) of a cloud's x, y, z and intensity planes of n floats each; the intensity address may be None or 0 (intensity 0).
+    The data must be complete when the call is made.  The same results as LoopClosureMatch on the same points, bit for bit."""
+    def planes(p, n):
+        p = [int(a or 0) for a in p]
+        if len(p) != 4:
+            raise ValueError("a cloud is four plane addresses: x, y, z, intensity")
+        if n < 0 or (n and not all(p[:3])):
+            raise ValueError("a cloud of n > 0 points needs its x, y and z planes")
+        return [C.c_void_p(a) for a in p]
+    Tf = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(4, 4).T).reshape(-1).copy()
+    fit = C.c_float()
+    st = LoopStats()
+    rc = _lib.lib().fls_loop_match_device(device_id, *planes(source_planes, n_source), int(n_source), *planes(target_planes, n_target), int(n_target),
+                                          Tf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(fit), C.byref(st))
+    if rc != _lib.FLS_OK:
+        raise FlsError(rc, "fls_loop_match_device")
+    pose[...] = Tf.reshape(4, 4).T
+    return float(fit.value), st
+
+
+def loop_device_stats(device_id: int = 0) -> dict:
+    """fls_loop_device_stat: the counters of the device's loop-closure matcher (include/fls_loop_device.h)."""
+    L = _lib.lib()
+    return {name: int(L.fls_loop_device_stat(device_id, k)) for k, name in enumerate(_lib.LOOP_DEVICE_STAT_SLOTS)}
+
+
 def VoxelGridCloud(cloud: np.ndarray, voxel_size: float = 0.1, on_device: bool = False, device_id: int = 0) -> np.ndarray:
     """include/common/pointcloud_utility.h:216-271 (pcl::VoxelGrid<PointXYZI>::filter): the stand-alone filter of the preprocessing
     thread (preprocessing.cpp:224-237) and of loop closure.  (n, 3|4|8) float32 -> (m, 4) {x, y, z, intensity}.

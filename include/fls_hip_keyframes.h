@@ -11,6 +11,7 @@
 #pragma once
 #include "fls_hip_preprocess.h"
 #include "fls_keyframes.h"
+#include "fls_loop_device.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -126,6 +127,16 @@ public:
         float fitness = std::numeric_limits<float>::max();
         (void)Check(fls_keyframes_loop_match(h_, source.ids.data(), source.poses.data(), source.ids.size(), target.ids.data(), target.poses.data(),
                                              target.ids.size(), pose.data(), &fitness, stats), "Match");
+        return fitness;
+    }
+
+    // The same with both sub-maps left on the device and the Match started from them there (include/fls_loop_device.h): the same pose,
+    // fitness and stats, bit for bit, without the two downloads, the ten host filters and the host leaf builds
+    template <class Mat4>
+    float LoopMatchOnDevice(const Selection& source, const Selection& target, Mat4& pose, fls_loop_stats* stats = nullptr) {
+        float fitness = std::numeric_limits<float>::max();
+        (void)Check(fls_keyframes_loop_match_device(h_, source.ids.data(), source.poses.data(), source.ids.size(), target.ids.data(), target.poses.data(),
+                                                    target.ids.size(), pose.data(), &fitness, stats), "LoopMatchOnDevice");
         return fitness;
     }
 

@@ -70,8 +70,8 @@ fls_status fls_keyframes_merge(fls_keyframes_handle h, const int32_t* ids, const
 /* GetSubMap twice (leaf 0.2, no final filter) + LoopClosure::Match: the result equals fls_loop_match on the two clouds
  * fls_keyframes_merge returns.  T_colmajor is the initial guess on entry, as in fls_loop_match; stats may be NULL.
  * Both sub-maps are assembled on the device and downloaded once each; the matcher is fls_loop_match's own (one per device, calls on a
- * device serialised).  That matcher starts from host clouds: its first filters are the exact host ones.  Starting it from the device
- * sub-maps is not part of revision 1. */
+ * device serialised).  Here that matcher starts from host clouds: its first filters are the exact host ones.  The same Match started
+ * from the device sub-maps, without the two downloads, is fls_keyframes_loop_match_device (include/fls_loop_device.h). */
 fls_status fls_keyframes_loop_match(fls_keyframes_handle h, const int32_t* src_ids, const double* src_poses, size_t n_src, const int32_t* tgt_ids,
                                     const double* tgt_poses, size_t n_tgt, double T_colmajor[16], float* fitness, fls_loop_stats* stats);
 
