@@ -85,6 +85,18 @@ DEBUG_IVOX_KNN_SYMBOLS = ["fls_debug_ivox_knn_revision", "fls_debug_ivox_knn_lim
 # every symbol include/fls_debug_ivox_update.h declares (FLS_DEBUG_IVOX_UPDATE_REVISION 1): one decided batch through the iVox map update
 DEBUG_IVOX_UPDATE_SYMBOLS = ["fls_debug_ivox_update_revision", "fls_debug_ivox_add_points"]
 
+# every symbol include/fls_debug_ivox_decide.h declares (FLS_DEBUG_IVOX_DECIDE_REVISION 1): the iVox map-update decision launch, the list
+# materialization and the host rule on caller-supplied arrays
+DEBUG_IVOX_DECIDE_SYMBOLS = ["fls_debug_ivox_decide_revision", "fls_debug_ivox_decide", "fls_debug_ivox_nn_materialize", "fls_debug_ivox_decide_host"]
+DEBUG_IVOX_DECIDE_FILL, DEBUG_IVOX_DECIDE_MAP_PAD = 0xA5, 64  # FLS_DEBUG_IVOX_DECIDE_FILL, FLS_DEBUG_IVOX_DECIDE_MAP_PAD
+
+
+class DebugIvoxGate(C.Structure):
+    """fls_debug_ivox_gate (include/fls_debug_ivox_decide.h)."""
+
+    _fields_ = [("done", C.c_int32), ("iter", C.c_int32), ("n_valid", C.c_int32), ("max_iterations", C.c_int32), ("T", C.c_double * 16)]
+
+
 # every symbol include/fls_map_ndt.h declares (FLS_NDT_IMAGE_REVISION 1): the flat image of the NDT voxel map, moved by fls_map_export / _import,
 # fls_map_image_* and the replica sets of fls_reg.h
 NDT_IMAGE_SYMBOLS = ["fls_ndt_image_revision"]
@@ -599,6 +611,17 @@ def lib():
             L.fls_debug_ivox_update_revision.argtypes = []
             L.fls_debug_ivox_add_points.restype = C.c_int
             L.fls_debug_ivox_add_points.argtypes = [hp, fp, bp, C.c_size_t, C.POINTER(C.c_uint32)]
+        if hasattr(L, "fls_debug_ivox_decide_revision"):  # (as fls_batch_ivox_revision above)
+            u32p = C.POINTER(C.c_uint32)
+            L.fls_debug_ivox_decide_revision.restype = C.c_int
+            L.fls_debug_ivox_decide_revision.argtypes = []
+            L.fls_debug_ivox_decide.restype = C.c_int
+            L.fls_debug_ivox_decide.argtypes = [C.c_int, fp, C.c_int, dp, C.c_double, fp, bp, C.c_int, u32p, fp, C.c_int, fp, C.c_int, C.c_int,
+                                                C.POINTER(DebugIvoxGate), bp, fp, u32p, u32p, u32p]
+            L.fls_debug_ivox_nn_materialize.restype = C.c_int
+            L.fls_debug_ivox_nn_materialize.argtypes = [C.c_int, u32p, bp, C.c_int, fp, C.c_int, fp, fp]
+            L.fls_debug_ivox_decide_host.restype = C.c_int
+            L.fls_debug_ivox_decide_host.argtypes = [fp, dp, C.c_double, fp, bp, C.c_int, bp, fp]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

@@ -14,6 +14,7 @@
 #include "abi_debug_loop.hpp"   // fls_debug_loop.h
 #include "abi_debug_knn.hpp"    // fls_debug_knn.h
 #include "abi_debug_ivox_update.hpp"  // fls_debug_ivox_update.h (names no kernel of its own)
+#include "abi_debug_ivox_decide.hpp"  // fls_debug_ivox_decide.h (names no kernel of its own)
 // The reference neighbour order of the iVox kind: its kernel is named here, behind every one above (see the header).
 #include "abi_knn_order.hpp"     // fls_knn_order.h
 // The loop-closure Match from device clouds: its leaf-build kernels are named here, behind every other one, for the same reason.

@@ -26,6 +26,84 @@ namespace fls {
 
 constexpr int kIvoxXcdChunk = 8;  // workgroups per XCD chunk of the kNN block re-map (ivox_knn_kernel's `chunk`)
 
+// The two launches around the map-update decision, each written once: the matcher below and the test hooks of include/fls_debug_ivox_decide.h
+// (abi_debug_ivox_decide.hpp) launch through these, so the grid rule and the argument order cannot drift apart.
+inline void launch_nn_materialize(const unsigned* nn_ids, unsigned char* nn_cnt, const size_t nn_n, const float4* map_pts, const unsigned n_slots, float4* nn_pts,
+                                  hipStream_t stream) {
+    hipLaunchKernelGGL(ivox_nn_materialize_kernel, dim3(unsigned((nn_n + 255) / 256)), dim3(256), 0, stream, nn_ids, nn_cnt, int(nn_n), map_pts, n_slots, nn_pts);
+}
+struct DecideLaunch {
+    const float *sx, *sy, *sz;  // the source points, n of them
+    size_t n;
+    const double* T;            // the pose as a launch argument (a speculative launch takes GnState::T instead)
+    float4* nn_pts;             // [nn_n][5] neighbour rows
+    unsigned char* nn_cnt;      // [nn_n]
+    size_t nn_n;
+    double fs;                  // filter_size_map_min
+    unsigned char* code;        // [n]
+    float4* pw;                 // [n]
+    const unsigned* nn_ids;     // [nn_n][8], may be null
+    const float4* map_pts;
+    unsigned n_slots;
+    uint2 *lx, *bt;             // lx null: no counting
+    unsigned *status, *apply;
+    const GnState* gn;          // non-null: the speculative form
+    int max_it;
+    bool rows_too;              // the MATERIALIZE form: the grid covers max(n, nn_n) points
+};
+inline void launch_add_decide(const DecideLaunch& a, hipStream_t stream) {
+    Pose16 Tw;
+    std::memcpy(Tw.m, a.T, sizeof(Tw.m));
+    const size_t m = a.rows_too ? std::max(a.n, a.nn_n) : a.n;
+    with_bools([&](auto ROWS) {
+        hipLaunchKernelGGL(ivox_add_decide_kernel<ROWS.value>, dim3(unsigned((m + 255) / 256)), dim3(256), 0, stream, a.sx, a.sy, a.sz, int(a.n), Tw, a.nn_pts,
+                           a.nn_cnt, int(a.nn_n), a.fs, a.code, a.pw, a.nn_ids, a.map_pts, a.n_slots, a.lx, a.bt, a.status, a.apply, a.gn, a.max_it);
+    }, a.rows_too);
+}
+
+// pcl::transformPoint with Affine3d(T_): double evaluation, float result
+inline PtI ivox_xform_d(const PtI& p, const double* T) {
+    PtI r = p;
+    const double x = p.x, y = p.y, z = p.z;
+    r.x = float(((T[0] * x + T[4] * y) + T[8] * z) + T[12]);
+    r.y = float(((T[1] * x + T[5] * y) + T[9] * z) + T[13]);
+    r.z = float(((T[2] * x + T[6] * y) + T[10] * z) + T[14]);
+    return r;
+}
+// AddCloudToLocalMap's rule (:79-131) on the host, over arrays: point i is src[i * src_stride ..+3], its list near[(i * 5 + k) * near_stride ..+3] with
+// cnt[i] entries (no list at all from nn_n on) -> code[i] (0 drop, 1 points_to_add, 2 point_no_need_downsample), pw[3 * i ..+3] the world point.
+// What add_cloud_impl runs for a cloud that is not the resident scan, and fls_debug_ivox_decide_host.
+inline void ivox_decide_host(const float* src, const size_t src_stride, const size_t n, const double* T, const double fs, const float* near_rows,
+                             const size_t near_stride, const unsigned char* cnt_of, const size_t nn_n, unsigned char* code, float* pw_out) {
+    const double half = 0.5 * fs;
+    for (size_t i = 0; i < n; ++i) {
+        const PtI pw = ivox_xform_d(PtI{src[i * src_stride], src[i * src_stride + 1], src[i * src_stride + 2], 0.0f}, T);
+        pw_out[3 * i] = pw.x; pw_out[3 * i + 1] = pw.y; pw_out[3 * i + 2] = pw.z;
+        const int cnt = i < nn_n ? cnt_of[i] : 0;
+        code[i] = 1;
+        if (cnt > 0) {
+            const auto near = [&](const int k, const int a) { return double(near_rows[(i * 5 + size_t(k)) * near_stride + size_t(a)]); };
+            const double c[3] = {(std::floor(double(pw.x) / fs) + 0.5) * fs, (std::floor(double(pw.y) / fs) + 0.5) * fs,
+                                 (std::floor(double(pw.z) / fs) + 0.5) * fs};
+            const double d0[3] = {near(0, 0) - c[0], near(0, 1) - c[1], near(0, 2) - c[2]};
+            if (std::fabs(d0[0]) > half && std::fabs(d0[1]) > half && std::fabs(d0[2]) > half) {
+                code[i] = 2;
+                continue;
+            }
+            bool need_add = true;
+            const double e[3] = {double(pw.x) - c[0], double(pw.y) - c[1], double(pw.z) - c[2]};
+            const double dist = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+            if (cnt >= 5) {
+                for (int k = 0; k < 5; ++k) {
+                    const double f[3] = {near(k, 0) - c[0], near(k, 1) - c[1], near(k, 2) - c[2]};
+                    if ((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] < dist + 1.0e-6) { need_add = false; break; }
+                }
+            }
+            code[i] = need_add ? 1 : 0;
+        }
+    }
+}
+
 struct P2PlaneIvoxMatcher final : fls_matcher {
     IvoxMap map;
     // a batch lane (fls_match_batch) reads its owner's map; its own stays empty and idle
@@ -90,22 +168,12 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     void reset_match_state() { nn_n = 0; have_final = false; nn_rows_current = true; spec_pending = false; }
     void reset_job_state() override { reset_match_state(); }
 
-    // pcl::transformPoint with Affine3d(T_): double evaluation, float result
-    static PtI xform_d(const PtI& p, const double* T) {
-        PtI r = p;
-        const double x = p.x, y = p.y, z = p.z;
-        r.x = float(((T[0] * x + T[4] * y) + T[8] * z) + T[12]);
-        r.y = float(((T[1] * x + T[5] * y) + T[9] * z) + T[13]);
-        r.z = float(((T[2] * x + T[6] * y) + T[10] * z) + T[14]);
-        return r;
-    }
-
     // ids form -> rows form for every point (the ids are slots of the image as it is NOW: call before anything moves slots)
     void ensure_nn_rows() {
         if (nn_rows_current || nn_n == 0) { nn_rows_current = true; return; }
         const IvoxImage& im = read_map().image;
-        hipLaunchKernelGGL(ivox_nn_materialize_kernel, dim3(unsigned((nn_n + 255) / 256)), dim3(256), 0, stream, (const unsigned*)d_nn_ids.p, d_nn_cnt.p, int(nn_n),
-                           (const float4*)im.d_pts.p, unsigned(im.d_pts.cap), d_nn.p);  // (slot bound = the allocation: in device mode the host's `used` is stale)
+        // (slot bound = the allocation: in device mode the host's `used` is stale)
+        launch_nn_materialize(d_nn_ids.p, d_nn_cnt.p, nn_n, im.d_pts.p, unsigned(im.d_pts.cap), d_nn.p, stream);
         FLS_HIP(hipGetLastError());
         nn_rows_current = true;
     }
@@ -209,19 +277,13 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
     bool launch_decide(const size_t n, const bool speculative) {
         d_code.reserve(n);
         d_pw.reserve(n);
-        Pose16 Tw;
-        std::memcpy(Tw.m, T_, sizeof(Tw.m));
         const GnState* const gn = speculative ? (const GnState*)d_state.p : nullptr;
-        const int max_it = int(p.max_iterations);
         const IvoxMap::CountArgs c = map.count_args(n);
         // (the update moves map slots: lists still in ids form become rows in the same launch)
         const bool rows_too = (speculative || !nn_rows_current) && nn_n > 0;
-        const size_t m = rows_too ? std::max(n, nn_n) : n;
-        with_bools([&](auto ROWS) {
-            hipLaunchKernelGGL(ivox_add_decide_kernel<ROWS.value>, dim3(unsigned((m + 255) / 256)), dim3(256), 0, stream, scan.x.p, scan.y.p, scan.z.p,
-                               int(n), Tw, d_nn.p, d_nn_cnt.p, int(nn_n), filter_size_map_min, d_code.p, d_pw.p, (const unsigned*)d_nn_ids.p,
-                               (const float4*)map.image.d_pts.p, unsigned(map.image.d_pts.cap), c.lx, c.bt, c.status, c.apply, gn, max_it);
-        }, rows_too);
+        launch_add_decide(DecideLaunch{scan.x.p, scan.y.p, scan.z.p, n, T_, d_nn.p, d_nn_cnt.p, nn_n, filter_size_map_min, d_code.p, d_pw.p, d_nn_ids.p,
+                                       map.image.d_pts.p, unsigned(map.image.d_pts.cap), c.lx, c.bt, c.status, c.apply, gn, int(p.max_iterations), rows_too},
+                          stream);
         if (rows_too && !speculative) nn_rows_current = true;
         FLS_HIP(hipGetLastError());
         return c.lx != nullptr;
@@ -364,33 +426,15 @@ struct P2PlaneIvoxMatcher final : fls_matcher {
             // external non-first call with an arbitrary cloud: same rule on the host (:79-131)
             download_nn();
             std::vector<PtI> to_add, no_downsample;
-            const double fs = filter_size_map_min, half = 0.5 * filter_size_map_min;
             const size_t n = std::min(number_planar_point, planar_cloud.size());
+            static_assert(sizeof(PtI) == 4 * sizeof(float) && sizeof(Pt4) == 4 * sizeof(float), "ivox_decide_host strides");
+            std::vector<unsigned char> code(n);
+            std::vector<float> pw(3 * n);
+            ivox_decide_host(reinterpret_cast<const float*>(planar_cloud.data()), 4, n, T_, filter_size_map_min, reinterpret_cast<const float*>(h_nn.data()), 4,
+                             h_cnt.data(), nn_n, code.data(), pw.data());
             for (size_t i = 0; i < n; ++i) {
-                const PtI pw = xform_d(planar_cloud[i], T_);
-                const int cnt = i < nn_n ? h_cnt[i] : 0;
-                if (cnt > 0) {
-                    const Pt4* near = &h_nn[i * 5];
-                    const double c[3] = {(std::floor(double(pw.x) / fs) + 0.5) * fs, (std::floor(double(pw.y) / fs) + 0.5) * fs,
-                                         (std::floor(double(pw.z) / fs) + 0.5) * fs};
-                    const double d0[3] = {double(near[0].x) - c[0], double(near[0].y) - c[1], double(near[0].z) - c[2]};
-                    if (std::fabs(d0[0]) > half && std::fabs(d0[1]) > half && std::fabs(d0[2]) > half) {
-                        no_downsample.push_back(pw);
-                        continue;
-                    }
-                    bool need_add = true;
-                    const double e[3] = {double(pw.x) - c[0], double(pw.y) - c[1], double(pw.z) - c[2]};
-                    const double dist = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-                    if (cnt >= 5) {
-                        for (int k = 0; k < 5; ++k) {
-                            const double f[3] = {double(near[k].x) - c[0], double(near[k].y) - c[1], double(near[k].z) - c[2]};
-                            if ((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] < dist + 1.0e-6) { need_add = false; break; }
-                        }
-                    }
-                    if (need_add) to_add.push_back(pw);
-                } else {
-                    to_add.push_back(pw);
-                }
+                if (code[i] == 0) continue;
+                (code[i] == 1 ? to_add : no_downsample).push_back(PtI{pw[3 * i], pw[3 * i + 1], pw[3 * i + 2], planar_cloud[i].i});
             }
             rc = ivox.add_points(to_add.data(), to_add.size());
             if (rc != FLS_OK) return rc;

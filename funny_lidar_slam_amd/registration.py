@@ -557,6 +557,82 @@ def loop_device_stats(device_id: int = 0) -> dict:
     return {name: int(L.fls_loop_device_stat(device_id, k)) for k, name in enumerate(_lib.LOOP_DEVICE_STAT_SLOTS)}
 
 
+def _debug_ivox_map(map_rows, sentinel):
+    fp = C.POINTER(C.c_float)
+    rows = np.zeros((0, 4), np.float32) if map_rows is None else np.ascontiguousarray(np.asarray(map_rows, dtype=np.float32).reshape(-1, 4))
+    sen = np.ascontiguousarray(np.asarray(sentinel, dtype=np.float32).reshape(4))
+    return rows, sen, (rows.ctypes.data_as(fp) if len(rows) else None), sen.ctypes.data_as(fp)
+
+
+def DebugIvoxDecide(src_xyz, T, fs, nn_rows, nn_cnt, nn_ids=None, map_rows=None, sentinel=(0, 0, 0, 0), materialize=False, count=True, gate=None,
+                    device_id: int = 0) -> dict:
+    """fls_debug_ivox_decide (include/fls_debug_ivox_decide.h): one launch of the iVox map-update decision kernel on caller-supplied arrays.
+    src_xyz (n, 3); T 4x4 or (16,) column-major; nn_rows (nn_n, 5, 4) float32 (the id bits in column 3); nn_cnt (nn_n,) uint8 (bit 7: rows form);
+    nn_ids (nn_n, 8) uint32 or None; map_rows (n_slots, 4) or None; gate = dict(done, iter, n_valid, max_iterations, T) or None.  Returns a dict:
+    status (the call's, nothing is raised), code (n,), pw (n, 4), rows, cnt (the lists after the launch), lx (n, 2), bt (blocks, 2), st (2,);
+    every output starts as bytes of _lib.DEBUG_IVOX_DECIDE_FILL on the device."""
+    fp, bp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    src = np.ascontiguousarray(np.asarray(src_xyz, dtype=np.float32).reshape(-1, 3))
+    Tm = np.asarray(T, dtype=np.float64)
+    Tv = np.ascontiguousarray(Tm.reshape(-1, order="F") if Tm.ndim == 2 else Tm.reshape(16))
+    rows = np.array(np.asarray(nn_rows, dtype=np.float32).reshape(-1, 5, 4), order="C")
+    cnt = np.array(np.asarray(nn_cnt, dtype=np.uint8).reshape(-1), order="C")
+    ids = None if nn_ids is None else np.ascontiguousarray(np.asarray(nn_ids, dtype=np.uint32).reshape(-1, 8))
+    n, nn_n = len(src), len(cnt)
+    if len(rows) != nn_n or (ids is not None and len(ids) != nn_n):
+        raise ValueError("one row block, one count and one ids row per list")
+    mrows, sen, pm, psen = _debug_ivox_map(map_rows, sentinel)
+    m = max(n, nn_n) if materialize else n
+    out = {"code": np.full(n, 0x3C, np.uint8), "pw": np.full((n, 4), 0x3C3C3C3C, np.uint32).view(np.float32), "lx": np.full((n, 2), 0x3C3C3C3C, np.uint32),
+           "bt": np.full(((m + 255) // 256, 2), 0x3C3C3C3C, np.uint32), "st": np.full(2, 0x3C3C3C3C, np.uint32)}
+    g = None
+    if gate is not None:
+        gT = np.asarray(gate["T"], dtype=np.float64)
+        gT = gT.reshape(-1, order="F") if gT.ndim == 2 else gT.reshape(16)
+        g = _lib.DebugIvoxGate(int(gate["done"]), int(gate["iter"]), int(gate["n_valid"]), int(gate["max_iterations"]), (C.c_double * 16)(*gT))
+    rc = _lib.lib().fls_debug_ivox_decide(device_id, src.ctypes.data_as(fp), n, Tv.ctypes.data_as(C.POINTER(C.c_double)), float(fs), rows.ctypes.data_as(fp),
+                                          cnt.ctypes.data_as(bp), nn_n, None if ids is None else ids.ctypes.data_as(u32p), pm, len(mrows), psen,
+                                          1 if materialize else 0, 1 if count else 0, None if g is None else C.byref(g), out["code"].ctypes.data_as(bp),
+                                          out["pw"].ctypes.data_as(fp), out["lx"].ctypes.data_as(u32p), out["bt"].ctypes.data_as(u32p),
+                                          out["st"].ctypes.data_as(u32p))
+    out.update(status=int(rc), rows=rows, cnt=cnt)
+    return out
+
+
+def DebugIvoxNnMaterialize(nn_ids, nn_cnt, map_rows, nn_rows, sentinel=(0, 0, 0, 0), device_id: int = 0):
+    """fls_debug_ivox_nn_materialize (include/fls_debug_ivox_decide.h): one launch of the kernel that turns ids-form neighbour lists into rows.
+    Returns (status, rows (nn_n, 5, 4), cnt (nn_n,)) after the launch."""
+    fp, bp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    ids = np.ascontiguousarray(np.asarray(nn_ids, dtype=np.uint32).reshape(-1, 8))
+    rows = np.array(np.asarray(nn_rows, dtype=np.float32).reshape(-1, 5, 4), order="C")
+    cnt = np.array(np.asarray(nn_cnt, dtype=np.uint8).reshape(-1), order="C")
+    if not len(ids) == len(rows) == len(cnt):
+        raise ValueError("one row block, one count and one ids row per list")
+    mrows, sen, pm, psen = _debug_ivox_map(map_rows, sentinel)
+    rc = _lib.lib().fls_debug_ivox_nn_materialize(device_id, ids.ctypes.data_as(u32p), cnt.ctypes.data_as(bp), len(cnt), pm, len(mrows), psen,
+                                                  rows.ctypes.data_as(fp))
+    return int(rc), rows, cnt
+
+
+def DebugIvoxDecideHost(src_xyz, T, fs, nn_xyz, cnt):
+    """fls_debug_ivox_decide_host (include/fls_debug_ivox_decide.h; needs no device): the host form of the map-update rule, the loop
+    AddCloudToLocalMap runs for a later cloud that is not the resident scan.  src_xyz (n, 3), nn_xyz (n, 5, 3), cnt (n,) plain counts ->
+    (status, code (n,), pw (n, 3))."""
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+    src = np.ascontiguousarray(np.asarray(src_xyz, dtype=np.float32).reshape(-1, 3))
+    nn = np.ascontiguousarray(np.asarray(nn_xyz, dtype=np.float32).reshape(-1, 5, 3))
+    c = np.ascontiguousarray(np.asarray(cnt, dtype=np.uint8).reshape(-1))
+    if not len(src) == len(nn) == len(c):
+        raise ValueError("one list and one count per point")
+    Tm = np.asarray(T, dtype=np.float64)
+    Tv = np.ascontiguousarray(Tm.reshape(-1, order="F") if Tm.ndim == 2 else Tm.reshape(16))
+    code = np.full(len(src), 0x3C, np.uint8)
+    pw = np.full((len(src), 3), 0x3C3C3C3C, np.uint32).view(np.float32)
+    rc = _lib.lib().fls_debug_ivox_decide_host(src.ctypes.data_as(fp), Tv.ctypes.data_as(C.POINTER(C.c_double)), float(fs), nn.ctypes.data_as(fp),
+                                               c.ctypes.data_as(bp), len(src), code.ctypes.data_as(bp), pw.ctypes.data_as(fp))
+    return int(rc), code, pw
+
+
 def VoxelGridCloud(cloud: np.ndarray, voxel_size: float = 0.1, on_device: bool = False, device_id: int = 0) -> np.ndarray:
     """include/common/pointcloud_utility.h:216-271 (pcl::VoxelGrid<PointXYZI>::filter): the stand-alone filter of the preprocessing
     thread (preprocessing.cpp:224-237) and of loop closure.  (n, 3|4|8) float32 -> (m, 4) {x, y, z, intensity}.

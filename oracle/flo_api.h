@@ -180,6 +180,10 @@ void flo_svd3(const double A[9], double U[9], double S[3], double V[9]);
  * pt[n][3] (transformed point), T[n][16], gate[n] (plane threshold / line ratio) -> valid[n], J[n][6], d[n] (left alone where the lambda returns early) */
 void flo_plane_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d);
 void flo_line_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d);
+/* LoamPointToPlaneIVOX::AddCloudToLocalMap's per-point rule for a non-first cloud (loam_point_to_plane_ivox.h:79-131), the function P2PlaneIvox::AddCloud
+ * itself calls, on caller-supplied neighbour lists: src[n][3], T[16] column-major, fs = filter_size_map_min, nn[n][5][3] (nn[s][0] the nearest; rows beyond
+ * cnt[s] do not enter the decision), cnt[s] = nearest_points[s].size() -> code[n] (0 dropped, 1 points_to_add, 2 point_no_need_downsample), pw[n][3] = transformPoint(src, T) */
+void flo_ivox_add_decide(const float* src, const double* T, double fs, const float* nn, const uint8_t* cnt, size_t n, uint8_t* code, float* pw);
 int flo_knn_bruteforce(const float* map_xyz, size_t m, const float* q, int k, int32_t* idx, float* d2);
 int flo_kdtree_knn(const float* map_xyz, size_t m, const float* queries, size_t nq, int k, int32_t* idx, float* d2);
 

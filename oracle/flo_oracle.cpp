@@ -190,6 +190,29 @@ static std::vector<float> flat_xyz(const Cloud& c) {
 // =============================================================================================
 // LoamPointToPlaneIVOX<double>
 // =============================================================================================
+// AddCloudToLocalMap's rule for one source point of a non-first cloud (:79-131): pw = pcl::transformPoint(p, T_); n_near = nearest_points[i].size(),
+// near[k] its first min(n_near, 5) points.  0: dropped, 1: points_to_add, 2: point_no_need_downsample.
+static int ivox_add_decide(const P4& p, const double* T, const double filter_size_map_min, const P4* near, const size_t n_near, P4& pw) {
+    const double half = 0.5 * filter_size_map_min;
+    pw = transform_point_d(p, T);
+    if (n_near == 0) return 1;
+    const double c[3] = {(std::floor(double(pw.x) / filter_size_map_min) + 0.5) * filter_size_map_min,
+                         (std::floor(double(pw.y) / filter_size_map_min) + 0.5) * filter_size_map_min,
+                         (std::floor(double(pw.z) / filter_size_map_min) + 0.5) * filter_size_map_min};
+    const double d2c[3] = {double(near[0].x) - c[0], double(near[0].y) - c[1], double(near[0].z) - c[2]};
+    if (std::fabs(d2c[0]) > half && std::fabs(d2c[1]) > half && std::fabs(d2c[2]) > half) return 2;
+    bool need_add = true;
+    const double e[3] = {double(pw.x) - c[0], double(pw.y) - c[1], double(pw.z) - c[2]};
+    const double dist = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    if (n_near >= 5u) {
+        for (int k = 0; k < 5; ++k) {
+            const double f[3] = {double(near[k].x) - c[0], double(near[k].y) - c[1], double(near[k].z) - c[2]};
+            if ((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] < dist + 1.0e-6) { need_add = false; break; }
+        }
+    }
+    return need_add ? 1 : 0;
+}
+
 struct P2PlaneIvox final : MatcherBase {
     std::unique_ptr<IVoxMap> ivox;
     bool is_first = true;  // loam_point_to_plane_ivox.h:62 (static there)
@@ -213,32 +236,13 @@ struct P2PlaneIvox final : MatcherBase {
             is_first = false;
         } else {
             Cloud points_to_add, no_downsample;
-            const double half = 0.5 * filter_size_map_min;
             for (size_t i = 0; i < number_planar_point && i < planar_cloud.size(); ++i) {
-                const P4 pw = transform_point_d(planar_cloud[i], T_);
-                if (!nearest_points[i].empty()) {
-                    const auto& near = nearest_points[i];
-                    const double c[3] = {(std::floor(double(pw.x) / filter_size_map_min) + 0.5) * filter_size_map_min,
-                                         (std::floor(double(pw.y) / filter_size_map_min) + 0.5) * filter_size_map_min,
-                                         (std::floor(double(pw.z) / filter_size_map_min) + 0.5) * filter_size_map_min};
-                    const double d2c[3] = {double(near[0].pt.x) - c[0], double(near[0].pt.y) - c[1], double(near[0].pt.z) - c[2]};
-                    if (std::fabs(d2c[0]) > half && std::fabs(d2c[1]) > half && std::fabs(d2c[2]) > half) {
-                        no_downsample.push_back(pw);
-                        continue;
-                    }
-                    bool need_add = true;
-                    const double e[3] = {double(pw.x) - c[0], double(pw.y) - c[1], double(pw.z) - c[2]};
-                    const double dist = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-                    if (near.size() >= 5u) {
-                        for (int k = 0; k < 5; ++k) {
-                            const double f[3] = {double(near[k].pt.x) - c[0], double(near[k].pt.y) - c[1], double(near[k].pt.z) - c[2]};
-                            if ((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2] < dist + 1.0e-6) { need_add = false; break; }
-                        }
-                    }
-                    if (need_add) points_to_add.push_back(pw);
-                } else {
-                    points_to_add.push_back(pw);
-                }
+                const auto& near = nearest_points[i];
+                P4 near5[5] = {}, pw;
+                for (size_t k = 0; k < near.size() && k < 5u; ++k) near5[k] = near[k].pt;
+                const int code = ivox_add_decide(planar_cloud[i], T_, filter_size_map_min, near5, near.size(), pw);
+                if (code == 1) points_to_add.push_back(pw);
+                else if (code == 2) no_downsample.push_back(pw);
             }
             ivox->AddPoints(points_to_add);
             ivox->AddPoints(no_downsample);
@@ -1388,7 +1392,15 @@ void flo_plane_residual(const float* nn, const float* ps, const float* pt, const
         valid[s] = plane_residual(q, P4{ps[s * 3], ps[s * 3 + 1], ps[s * 3 + 2], 0.f}, P4{pt[s * 3], pt[s * 3 + 1], pt[s * 3 + 2], 0.f}, T + s * 16, gate[s], J + s * 6, d[s]) ? 1 : 0;
     }
 }
-void flo_line_residual(const float* nn, const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d) {
+void flo_ivox_add_decide(const float* src, const double* T, double fs, const float* nn, const uint8_t* cnt, size_t n, uint8_t* code, float* pw) {
+    for (size_t s = 0; s < n; ++s) {
+        P4 q[5], w;
+        for (int j = 0; j < 5; ++j) q[j] = P4{nn[s * 15 + j * 3], nn[s * 15 + j * 3 + 1], nn[s * 15 + j * 3 + 2], 0.f};
+        code[s] = uint8_t(ivox_add_decide(P4{src[s * 3], src[s * 3 + 1], src[s * 3 + 2], 0.f}, T, fs, q, cnt[s], w));
+        pw[s * 3] = w.x; pw[s * 3 + 1] = w.y; pw[s * 3 + 2] = w.z;
+    }
+}
+void flo_line_residual(const float* nn,const float* ps, const float* pt, const double* T, const double* gate, size_t n, uint8_t* valid, double* J, double* d) {
     for (size_t s = 0; s < n; ++s) {
         P4 q[5];
         for (int j = 0; j < 5; ++j) q[j] = P4{nn[s * 15 + j * 3], nn[s * 15 + j * 3 + 1], nn[s * 15 + j * 3 + 2], 0.f};

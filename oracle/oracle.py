@@ -182,6 +182,8 @@ def lib():
         L.flo_plane_residual.argtypes = [fp, fp, fp, dp, dp, C.c_size_t, bp, dp, dp]
         L.flo_line_residual.restype = None
         L.flo_line_residual.argtypes = [fp, fp, fp, dp, dp, C.c_size_t, bp, dp, dp]
+        L.flo_ivox_add_decide.restype = None
+        L.flo_ivox_add_decide.argtypes = [fp, dp, C.c_double, fp, bp, C.c_size_t, bp, fp]
         L.flo_map_size.restype = C.c_size_t
         L.flo_map_size.argtypes = [C.c_void_p, C.c_int]
         L.flo_map_voxels.restype = C.c_size_t
@@ -509,6 +511,19 @@ def plane_residual(nn, ps, pt, T, thres):
 def line_residual(nn, ps, pt, T, ratio):
     """the point-to-line lambda, same shapes: -> valid, J, dist"""
     return _residual(lib().flo_line_residual, nn, ps, pt, T, ratio)
+
+
+def ivox_add_decide(src, T, fs, nn, cnt):
+    """AddCloudToLocalMap's per-point rule of the iVox kind (the function P2PlaneIvox::AddCloud calls): src (n, 3), T (16,) column-major, fs,
+    nn (n, 5, 3), cnt (n,) -> code (n,) uint8 (0 dropped, 1 points_to_add, 2 point_no_need_downsample), pw (n, 3) float32"""
+    s_, ps = _f32(src); T_, pT = _f64(np.asarray(T, np.float64).reshape(16)); nn_, pn = _f32(np.asarray(nn).reshape(-1, 15))
+    c_ = np.ascontiguousarray(cnt, dtype=np.uint8)
+    n = s_.shape[0]
+    assert s_.shape == (n, 3) and nn_.shape == (n, 15) and c_.shape == (n,)
+    code = np.full(n, 0xEE, np.uint8); pw = np.full((n, 3), 7.0, np.float32)
+    bp = C.POINTER(C.c_uint8)
+    lib().flo_ivox_add_decide(ps, pT, float(fs), pn, c_.ctypes.data_as(bp), n, code.ctypes.data_as(bp), pw.ctypes.data_as(C.POINTER(C.c_float)))
+    return code, pw
 
 
 def inverse3(A):
