@@ -90,6 +90,26 @@ DEBUG_IVOX_UPDATE_SYMBOLS = ["fls_debug_ivox_update_revision", "fls_debug_ivox_a
 DEBUG_IVOX_DECIDE_SYMBOLS = ["fls_debug_ivox_decide_revision", "fls_debug_ivox_decide", "fls_debug_ivox_nn_materialize", "fls_debug_ivox_decide_host"]
 DEBUG_IVOX_DECIDE_FILL, DEBUG_IVOX_DECIDE_MAP_PAD = 0xA5, 64  # FLS_DEBUG_IVOX_DECIDE_FILL, FLS_DEBUG_IVOX_DECIDE_MAP_PAD
 
+# every symbol include/fls_debug_tail.h declares (FLS_DEBUG_TAIL_REVISION 1): one launch of a Gauss-Newton tail on caller-supplied rows and state
+DEBUG_TAIL_SYMBOLS = ["fls_debug_tail_revision", "fls_debug_loam_tail", "fls_debug_lu_tail"]
+DEBUG_TAIL_MAX_ITER, DEBUG_TAIL_MAX_ROWS = 64, 2048  # FLS_DEBUG_TAIL_MAX_ITER, FLS_DEBUG_TAIL_MAX_ROWS
+
+
+class DebugGnState(C.Structure):
+    """fls_debug_gn_state (include/fls_debug_tail.h): GnState of csrc/device_common.hpp."""
+
+    _fields_ = [("T", C.c_double * 16), ("last_rot", C.c_double), ("last_pos", C.c_double), ("sum_res", C.c_double), ("sum_res2", C.c_double),
+                ("last_dx", C.c_double * 6), ("H", C.c_double * 36), ("g", C.c_double * 6), ("iter", C.c_int32), ("done", C.c_int32),
+                ("converged", C.c_int32), ("n_valid", C.c_int32), ("n_valid2", C.c_int32), ("pad", C.c_int32), ("dbg", C.c_int64 * 16),
+                ("log_T", C.c_double * (16 * DEBUG_TAIL_MAX_ITER)), ("log_res", C.c_double * DEBUG_TAIL_MAX_ITER), ("log_nv", C.c_int32 * DEBUG_TAIL_MAX_ITER)]
+
+
+class DebugMailbox(C.Structure):
+    """fls_debug_mailbox (include/fls_debug_tail.h): Mailbox of csrc/device_common.hpp."""
+
+    _fields_ = [("T", C.c_double * 16), ("sum_res", C.c_double), ("sum_res2", C.c_double), ("last_dx", C.c_double * 6), ("iter", C.c_int32),
+                ("done", C.c_int32), ("converged", C.c_int32), ("n_valid", C.c_int32), ("n_valid2", C.c_int32), ("seq", C.c_uint32)]
+
 
 class DebugIvoxGate(C.Structure):
     """fls_debug_ivox_gate (include/fls_debug_ivox_decide.h)."""
@@ -622,6 +642,13 @@ def lib():
             L.fls_debug_ivox_nn_materialize.argtypes = [C.c_int, u32p, bp, C.c_int, fp, C.c_int, fp, fp]
             L.fls_debug_ivox_decide_host.restype = C.c_int
             L.fls_debug_ivox_decide_host.argtypes = [fp, dp, C.c_double, fp, bp, C.c_int, bp, fp]
+        if hasattr(L, "fls_debug_tail_revision"):  # (as fls_batch_ivox_revision above)
+            L.fls_debug_tail_revision.restype = C.c_int
+            L.fls_debug_tail_revision.argtypes = []
+            L.fls_debug_loam_tail.restype = C.c_int
+            L.fls_debug_loam_tail.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_void_p, dp, C.c_int, dp, C.c_int, C.c_double, C.c_double, C.c_uint32, C.c_void_p]
+            L.fls_debug_lu_tail.restype = C.c_int
+            L.fls_debug_lu_tail.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_void_p, dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_void_p]
         if hasattr(L, "fls_ndt_image_revision"):  # (as fls_batch_ivox_revision above)
             L.fls_ndt_image_revision.restype = C.c_int
             L.fls_ndt_image_revision.argtypes = []

@@ -19,3 +19,5 @@
 #include "abi_knn_order.hpp"     // fls_knn_order.h
 // The loop-closure Match from device clouds: its leaf-build kernels are named here, behind every other one, for the same reason.
 #include "abi_loop_device.hpp"   // fls_loop_device.h, fls_debug_loop_leaves.h
+// The Gauss-Newton tails on caller-supplied rows: the test kernels are named here, behind every other one, for the same reason.
+#include "abi_debug_tail.hpp"    // fls_debug_tail.h
