@@ -1,5 +1,5 @@
-// abi_debug_loop.hpp -- test hooks of the stages of the loop-closure matcher (include/fls_debug_loop.h): each launches the product kernel on
-// the device's own LoopMatcher (loop_matcher_for, abi_matcher.hpp).
+// abi_debug_loop.hpp -- test hooks of the stages of the loop-closure matcher (include/fls_debug_loop.h): each stages the buffers the test supplies
+// on the device's own LoopMatcher (loop_matcher_for, abi_matcher.hpp) and calls the stage function the Match calls.
 #pragma once
 #include "abi_matcher.hpp"
 
@@ -19,15 +19,45 @@ fls_status debug_loop_run(int device_id, F&& body) {
     });
 }
 
-// a cloud's cell grid as LoopMatcher::run builds it: on the device, else (or with host_grid) on the host
-fls_status debug_loop_grid(LoopMatcher& m, CellGridImage& g, const LoopMatcher::DevCloud& dev, const std::vector<PtI>& c, float cell, bool by_id, bool host_grid) {
-    if (!host_grid && m.builder.run(g, dev.x(), dev.y(), dev.z(), c.size(), cell, 1, by_id, m.stream)) return FLS_OK;
-    return g.build(c, cell, m.stream, 1, by_id);
+// a hook's cloud: the rows the test supplies, uploaded into `dev`
+LoopMatcher::Filtered debug_loop_cloud(LoopMatcher& m, LoopMatcher::DevCloud& dev, const float* pts, int n, int stride) {
+    LoopMatcher::Filtered c;
+    c.dev = &dev;
+    c.set_rows(cloud_from(pts, size_t(n), stride));
+    m.planes(c);
+    return c;
 }
 
 LoopMat4f debug_loop_mat(const float* T) { LoopMat4f r; for (int i = 0; i < 16; ++i) r.m[i] = T[i]; return r; }
 
-constexpr float kDebugLoopCell = 1.5f;  // LoopMatcher::run's GICP cell
+// fls_debug_loop_ndt (the leaves by build_target) and fls_debug_loop_ndt_device (on the device, counted): the target's leaves, then ONE ndt_eval
+fls_status debug_loop_ndt(int device_id, const float* src, int ns, const float* tgt, int nt, int stride, float resolution, const double* p, int want_hessian,
+                          double* score, double* grad, double* hess, int64_t* pairs, int32_t* leaves, int32_t* sparse, bool on_device) {
+    if (!src || !tgt || !p || !score || !grad || !hess || !pairs || !leaves || !sparse || ns < 0 || nt < 0 || stride < 3 || !(resolution > 0.f) ||
+        !std::isfinite(resolution))
+        return FLS_ERR_INVALID;
+    *score = 0.0; *pairs = 0; *leaves = 0; *sparse = 0;
+    for (int i = 0; i < 6; ++i) grad[i] = 0.0;
+    if (want_hessian) for (int i = 0; i < 36; ++i) hess[i] = 0.0;
+    if (ns == 0 || nt == 0) return FLS_OK;
+    return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
+        LoopMatcher::Filtered t;
+        t.dev = &m.tgt_filtered;
+        t.set_rows(cloud_from(tgt, size_t(nt), stride));
+        if (!m.target_leaves(t, resolution, m.leaves, on_device, on_device)) return FLS_OK;
+        *leaves = int32_t(m.leaves.rows);
+        *sparse = m.leaves.sparse ? 1 : 0;
+        LoopMatcher::NdtRun run;
+        run.resolution = resolution;
+        loop::ndt_gauss(run);
+        debug_loop_cloud(m, m.src_dev, src, ns, stride);
+        run.src = &m.src_dev;
+        run.tl = &m.leaves;
+        *score = m.ndt_eval(run, loop::pose_xyz(p), p, want_hessian != 0, grad, hess);
+        *pairs = int64_t(m.mail_host->v[want_hessian ? 43 : 7]);
+        return FLS_OK;
+    });
+}
 
 }  // namespace
 
@@ -37,46 +67,17 @@ int fls_debug_loop_revision(void) { return FLS_DEBUG_LOOP_REVISION; }
 
 fls_status fls_debug_loop_ndt(int device_id, const float* src, int ns, const float* tgt, int nt, int stride, float resolution, const double* p,
                               int want_hessian, double* score, double* grad, double* hess, int64_t* pairs, int32_t* leaves, int32_t* sparse) {
-    if (!src || !tgt || !p || !score || !grad || !hess || !pairs || !leaves || !sparse || ns < 0 || nt < 0 || stride < 3 || !(resolution > 0.f) ||
-        !std::isfinite(resolution))
-        return FLS_ERR_INVALID;
-    auto zero = [&] {
-        *score = 0.0; *pairs = 0; *leaves = 0; *sparse = 0;
-        for (int i = 0; i < 6; ++i) grad[i] = 0.0;
-        if (want_hessian) for (int i = 0; i < 36; ++i) hess[i] = 0.0;
-    };
-    if (ns == 0 || nt == 0) { zero(); return FLS_OK; }
-    return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> s = cloud_from(src, size_t(ns), stride), t = cloud_from(tgt, size_t(nt), stride);
-        zero();
-        if (!m.build_target(t, resolution, m.leaves)) return FLS_OK;
-        *leaves = int32_t(m.leaves.rows);
-        *sparse = m.leaves.sparse ? 1 : 0;
-        LoopMatcher::NdtRun run;
-        run.resolution = resolution;
-        const double c1 = 10.0 * (1.0 - run.outlier_ratio), c2 = run.outlier_ratio / std::pow(double(resolution), 3), d3 = -std::log(c2);  // (ndt_align)
-        run.pose.gauss_d1 = -std::log(c1 + c2) - d3;
-        run.pose.gauss_d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / run.pose.gauss_d1);
-        m.src_dev.upload(s, m.stream);
-        run.src = &m.src_dev;
-        run.tl = &m.leaves;
-        *score = m.ndt_eval(run, LoopMatcher::pose_xyz(p), p, want_hessian != 0, grad, hess);
-        *pairs = int64_t(m.mail_host->v[want_hessian ? 43 : 7]);
-        return FLS_OK;
-    });
+    return debug_loop_ndt(device_id, src, ns, tgt, nt, stride, resolution, p, want_hessian, score, grad, hess, pairs, leaves, sparse, false);
 }
 
 fls_status fls_debug_loop_gicp_cov(int device_id, const float* cloud, int n, int stride, float cell, double epsilon, int host_grid, double* cov) {
     if (!cloud || !cov || n < 20 || stride < 3 || !(cell > 0.f) || !std::isfinite(cell) || !(epsilon > 0.0) || (host_grid != 0 && host_grid != 1)) return FLS_ERR_INVALID;
     return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> c = cloud_from(cloud, size_t(n), stride);
-        m.src_own.upload(c, m.stream);
-        const fls_status rc = debug_loop_grid(m, m.src_grid, m.src_own, c, cell, false, host_grid != 0);
+        LoopMatcher::Filtered c = debug_loop_cloud(m, m.src_own, cloud, n, stride);
+        const fls_status rc = m.cell_grid(m.src_grid, c, cell, false, host_grid != 0);
         if (rc != FLS_OK) return rc;
         m.g.cov_src.reserve(size_t(n) * 9);
-        hipLaunchKernelGGL(gicp_cov_kernel, dim3(unsigned((size_t(n) + kCovWaves - 1) / kCovWaves)), dim3(64 * kCovWaves), 0, m.stream, m.src_own.x(), m.src_own.y(), m.src_own.z(), n,
-                           cell_dev(m.src_grid), epsilon, m.g.cov_src.p);
-        FLS_HIP(hipGetLastError());
+        m.gicp_cov(m.src_own, m.src_grid, epsilon, m.g.cov_src.p);
         FLS_HIP(hipMemcpyAsync(cov, m.g.cov_src.p, size_t(n) * 9 * sizeof(double), hipMemcpyDeviceToHost, m.stream));
         FLS_HIP(hipStreamSynchronize(m.stream));
         return FLS_OK;
@@ -96,10 +97,9 @@ fls_status fls_debug_loop_gicp_corr(int device_id, const float* moved, int ns, c
         return FLS_OK;
     }
     return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> s = cloud_from(moved, size_t(ns), stride), t = cloud_from(tgt, size_t(nt), stride);
-        m.g.moved.upload(s, m.stream);
-        m.tgt_dev.upload(t, m.stream);
-        const fls_status rc = debug_loop_grid(m, m.g.tgt_grid, m.tgt_dev, t, kDebugLoopCell, true, host_grid != 0);
+        debug_loop_cloud(m, m.g.moved, moved, ns, stride);
+        LoopMatcher::Filtered t = debug_loop_cloud(m, m.tgt_dev, tgt, nt, stride);
+        const fls_status rc = m.cell_grid(m.g.tgt_grid, t, LoopMatcher::kGicpCell, true, host_grid != 0);
         if (rc != FLS_OK) return rc;
         m.g.cov_src.reserve(size_t(ns) * 9); m.g.cov_tgt.reserve(size_t(nt) * 9); m.g.mahal.reserve(size_t(ns) * 9); m.g.corr.reserve(size_t(ns));
         std::fill(mahal, mahal + size_t(ns) * 9, nan);
@@ -108,10 +108,7 @@ fls_status fls_debug_loop_gicp_corr(int device_id, const float* moved, int ns, c
         FLS_HIP(hipMemcpyAsync(m.g.mahal.p, mahal, size_t(ns) * 9 * sizeof(double), hipMemcpyHostToDevice, m.stream));
         GicpRot rot;
         for (int i = 0; i < 9; ++i) rot.R[i] = R[i];
-        const double dist_threshold = corr_dist * corr_dist;
-        hipLaunchKernelGGL(gicp_corr_kernel, dim3(unsigned((ns + 63) / 64)), dim3(64), 0, m.stream, m.g.moved.x(), m.g.moved.y(), m.g.moved.z(), ns, debug_loop_mat(T),
-                           cell_dev(m.g.tgt_grid), float(dist_threshold), dist_threshold, rot, (const double*)m.g.cov_src.p, (const double*)m.g.cov_tgt.p, m.g.corr.p, m.g.mahal.p);
-        FLS_HIP(hipGetLastError());
+        m.gicp_corr(ns, debug_loop_mat(T), corr_dist * corr_dist, rot);
         FLS_HIP(hipMemcpyAsync(corr, m.g.corr.p, size_t(ns) * sizeof(int), hipMemcpyDeviceToHost, m.stream));
         FLS_HIP(hipMemcpyAsync(mahal, m.g.mahal.p, size_t(ns) * 9 * sizeof(double), hipMemcpyDeviceToHost, m.stream));
         FLS_HIP(hipStreamSynchronize(m.stream));
@@ -126,8 +123,7 @@ fls_status fls_debug_loop_gicp_fdf(int device_id, const float* moved, int ns, co
     const int nv = want_grad ? 14 : 2;
     if (ns == 0) { for (int i = 0; i < nv; ++i) v[i] = 0.0; return FLS_OK; }
     return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> s = cloud_from(moved, size_t(ns), stride);
-        m.g.moved.upload(s, m.stream);
+        debug_loop_cloud(m, m.g.moved, moved, ns, stride);
         std::vector<Pt4> by_id(size_t(std::max(nt, 1)), Pt4{0.f, 0.f, 0.f, 0});
         for (int i = 0; i < nt; ++i) by_id[size_t(i)] = Pt4{tgt[size_t(i) * stride], tgt[size_t(i) * stride + 1], tgt[size_t(i) * stride + 2], i};
         m.g.tgt_grid.d_by_id.reserve(by_id.size());
@@ -149,17 +145,11 @@ fls_status fls_debug_loop_fitness(int device_id, const float* src, int ns, const
     if (!src || !tgt || !T || !sum_d2 || !count || ns < 0 || nt < 0 || stride < 3 || (host_grid != 0 && host_grid != 1)) return FLS_ERR_INVALID;
     if (ns == 0 || nt == 0) { *sum_d2 = 0.0; *count = 0; return FLS_OK; }
     return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> s = cloud_from(src, size_t(ns), stride), t = cloud_from(tgt, size_t(nt), stride);
-        m.src_own.upload(s, m.stream);
-        m.tgt_dev.upload(t, m.stream);
-        const fls_status rc = debug_loop_grid(m, m.g.tgt_grid, m.tgt_dev, t, kDebugLoopCell, true, host_grid != 0);
+        debug_loop_cloud(m, m.src_own, src, ns, stride);
+        LoopMatcher::Filtered t = debug_loop_cloud(m, m.tgt_dev, tgt, nt, stride);
+        const fls_status rc = m.cell_grid(m.g.tgt_grid, t, LoopMatcher::kGicpCell, true, host_grid != 0);
         if (rc != FLS_OK) return rc;
-        const LoopMat4f fin = debug_loop_mat(T);
-        const CellGridDev cg_tgt = cell_dev(m.g.tgt_grid);
-        const int nb = (ns + kLoopBlock - 1) / kLoopBlock;
-        const double* v = m.reduce(nb, [&](const LoopOut rows) {
-            hipLaunchKernelGGL(loop_fitness_kernel, dim3(unsigned(nb)), dim3(kLoopBlock), 0, m.stream, m.src_own.x(), m.src_own.y(), m.src_own.z(), ns, fin, cg_tgt, rows);
-        });
+        const double* v = m.fitness_sums(ns, debug_loop_mat(T));
         *sum_d2 = v[0];
         *count = int64_t(v[1]);
         FLS_HIP(hipStreamSynchronize(m.stream));

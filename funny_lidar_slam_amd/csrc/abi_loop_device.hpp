@@ -1,5 +1,5 @@
 // abi_loop_device.hpp -- include/fls_loop_device.h (the loop-closure Match from device clouds) and include/fls_debug_loop_leaves.h (the test
-// hooks of its leaf build).  Includes the leaf-build kernels and LoopMatcher::run_device (loop_device.hpp), which this translation unit
+// hooks of its leaf build).  Includes the leaf-build kernels and LoopMatcher::match with its two entries (loop_device.hpp), which this translation unit
 // names last: the code object keeps the order of every kernel in front of them.
 #pragma once
 #include "abi_matcher.hpp"
@@ -103,24 +103,12 @@ fls_status fls_debug_loop_leaves(int device_id, const float* tgt, int nt, int st
     *sparse = 0;
     if (nt == 0) return FLS_OK;
     return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> t = cloud_from(tgt, size_t(nt), stride);
+        LoopMatcher::Filtered t;
+        t.dev = &m.tgt_filtered;
+        t.set_rows(cloud_from(tgt, size_t(nt), stride));
         LoopMatcher::TargetLeaves& tl = m.leaves;
-        bool have = false, built = false;
-        if (on_device) {
-            m.tgt_filtered.upload(t, m.stream);
-            const LoopMatcher::LeafBuild rc = m.build_target_device(m.tgt_filtered.x(), m.tgt_filtered.y(), m.tgt_filtered.z(), t.size(), resolution, tl);
-            if (rc != LoopMatcher::kLeavesDeclined) {
-                ++m.dstat[LoopMatcher::kStatLeavesDevice];
-                built = true;
-                have = rc == LoopMatcher::kLeavesBuilt;
-                if (have) m.download_leaves(tl);
-            }
-        }
-        if (!built) {
-            if (on_device) ++m.dstat[LoopMatcher::kStatLeavesHost];
-            have = m.build_target(t, resolution, tl);
-        }
-        if (!have) return FLS_OK;
+        if (!m.target_leaves(t, resolution, tl, on_device != 0, on_device != 0)) return FLS_OK;
+        m.download_leaves(tl);
         *n_leaves = int32_t(tl.rows);
         *sparse = tl.sparse ? 1 : 0;
         if (tl.rows > size_t(cap)) return FLS_ERR_INVALID;
@@ -134,39 +122,7 @@ fls_status fls_debug_loop_leaves(int device_id, const float* tgt, int nt, int st
 
 fls_status fls_debug_loop_ndt_device(int device_id, const float* src, int ns, const float* tgt, int nt, int stride, float resolution, const double* p,
                                      int want_hessian, double* score, double* grad, double* hess, int64_t* pairs, int32_t* leaves, int32_t* sparse) {
-    if (!src || !tgt || !p || !score || !grad || !hess || !pairs || !leaves || !sparse || ns < 0 || nt < 0 || stride < 3 || !(resolution > 0.f) ||
-        !std::isfinite(resolution))
-        return FLS_ERR_INVALID;
-    auto zero = [&] {
-        *score = 0.0; *pairs = 0; *leaves = 0; *sparse = 0;
-        for (int i = 0; i < 6; ++i) grad[i] = 0.0;
-        if (want_hessian) for (int i = 0; i < 36; ++i) hess[i] = 0.0;
-    };
-    if (ns == 0 || nt == 0) { zero(); return FLS_OK; }
-    return debug_loop_run(device_id, [&](LoopMatcher& m) -> fls_status {
-        const std::vector<PtI> s = cloud_from(src, size_t(ns), stride), t = cloud_from(tgt, size_t(nt), stride);
-        zero();
-        m.tgt_filtered.upload(t, m.stream);
-        LoopMatcher::LeafBuild rc = m.build_target_device(m.tgt_filtered.x(), m.tgt_filtered.y(), m.tgt_filtered.z(), t.size(), resolution, m.leaves);
-        if (rc == LoopMatcher::kLeavesDeclined) {
-            ++m.dstat[LoopMatcher::kStatLeavesHost];
-            rc = m.build_target(t, resolution, m.leaves) ? LoopMatcher::kLeavesBuilt : LoopMatcher::kLeavesNone;
-        } else ++m.dstat[LoopMatcher::kStatLeavesDevice];
-        if (rc != LoopMatcher::kLeavesBuilt) return FLS_OK;
-        *leaves = int32_t(m.leaves.rows);
-        *sparse = m.leaves.sparse ? 1 : 0;
-        LoopMatcher::NdtRun run;
-        run.resolution = resolution;
-        const double c1 = 10.0 * (1.0 - run.outlier_ratio), c2 = run.outlier_ratio / std::pow(double(resolution), 3), d3 = -std::log(c2);  // (ndt_align)
-        run.pose.gauss_d1 = -std::log(c1 + c2) - d3;
-        run.pose.gauss_d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / run.pose.gauss_d1);
-        m.src_dev.upload(s, m.stream);
-        run.src = &m.src_dev;
-        run.tl = &m.leaves;
-        *score = m.ndt_eval(run, LoopMatcher::pose_xyz(p), p, want_hessian != 0, grad, hess);
-        *pairs = int64_t(m.mail_host->v[want_hessian ? 43 : 7]);
-        return FLS_OK;
-    });
+    return debug_loop_ndt(device_id, src, ns, tgt, nt, stride, resolution, p, want_hessian, score, grad, hess, pairs, leaves, sparse, true);
 }
 
 }  // extern "C"

@@ -18,13 +18,13 @@
 #pragma once
 #include "kernels_knn.hpp"
 #include "host_math.hpp"
+#include "loop_types.hpp"
 
 namespace fls {
 
 constexpr int kLoopBlock = 256;
 constexpr int kLoopMaxV = 48;  // doubles per partial row (score + 6 + 36 + count = 44 used)
 
-struct LoopMat4f { float m[16]; };  // column-major
 // pcl::transformPointCloud, float (SSE form): c0 * x + (c1 * y + (c2 * z + c3))
 __host__ __device__ __forceinline__ void loop_xform(const LoopMat4f& t, const float x, const float y, const float z, float (&o)[3]) {
 #pragma unroll
@@ -112,12 +112,6 @@ __device__ __forceinline__ int ndt_leaf_row(const NdtP2dTarget& tg, const int ce
         if (e.x < 0) return -1;
     }
 }
-struct NdtP2dPose {
-    LoopMat4f T;
-    double gauss_d1, gauss_d2;
-    double j_ang[8][3];
-    double h_ang[15][3];
-};
 
 template <bool HESS>
 __global__ void __launch_bounds__(kLoopBlock)

@@ -11,7 +11,7 @@
 //               scan of those counts (block-local here, the block totals through vg_scan) is the row = the rank among the leaves of
 //               >= 6 points in ascending cell index: build_target's emission order
 //   leaf_stats  one lane per counted head walks its segment: double sum[3], xx[9], float csum[3] in cloud order as build_target's
-//               accumulate does, then LoopMatcher::leaf_gaussian -- the function build_target calls -- and the rows of mean / icov /
+//               accumulate does, then loop::leaf_gaussian (loop_optim.hpp) -- the function build_target calls -- and the rows of mean / icov /
 //               centroid, the cell and the point count; leaf_row[cell] = row (dense), or the open-addressing {cell, row} table (sparse)
 // ORDER: every floating-point sum is one lane's sequential chain over a stably sorted segment: no floating-point atomics anywhere, the
 // result does not depend on the launch geometry.  The sparse table is filled with integer compare-and-swap: a cell's SLOT depends on the
@@ -108,7 +108,7 @@ leaf_stats(const unsigned* __restrict__ key, const unsigned* __restrict__ val, c
         ++cnt;
     }
     double mean[3], icov[9];
-    LoopMatcher::leaf_gaussian(cnt, sum, xx, mean, icov);
+    loop::leaf_gaussian(cnt, sum, xx, mean, icov);
 #pragma unroll
     for (int a = 0; a < 3; ++a) { o.mean[3 * (size_t)row + a] = mean[a]; o.centroid[3 * (size_t)row + a] = csum[a] / (float)cnt; }
 #pragma unroll
@@ -121,7 +121,7 @@ leaf_stats(const unsigned* __restrict__ key, const unsigned* __restrict__ val, c
     }
 }
 
-// GICP's `output`: the filtered source moved by the guess, with the function LoopMatcher::run's host loop calls
+// GICP's `output`: the filtered source moved by the guess, with the function the host entry's loop calls
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK)
 loop_moved_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const int n, const LoopMat4f T,
@@ -136,6 +136,7 @@ loop_moved_kernel(const float* __restrict__ x, const float* __restrict__ y, cons
 inline LoopMatcher::LeafBuild LoopMatcher::build_target_device(const float* x, const float* y, const float* z, const size_t n, const float resolution,
                                                                TargetLeaves& tl) {
     tl.rows = 0;
+    tl.rows_on_host = false;
     tl.inv = 1.0f / resolution;
     const float inv = tl.inv;
     if (n == 0) return kLeavesNone;
@@ -211,6 +212,8 @@ inline LoopMatcher::LeafBuild LoopMatcher::build_target_device(const float* x, c
 // the rows of a device build on the host (fls_debug_loop_leaves; the Match itself never reads them)
 inline void LoopMatcher::download_leaves(TargetLeaves& tl) {
     const size_t r = tl.rows;
+    if (tl.rows_on_host) return;
+    tl.rows_on_host = true;
     tl.mean.resize(3 * r); tl.icov.resize(9 * r); tl.centroid.resize(3 * r); tl.row_cell.resize(r); tl.row_n.resize(r);
     if (!r) return;
     FLS_HIP(hipMemcpyAsync(tl.mean.data(), tl.d_mean.p, 3 * r * sizeof(double), hipMemcpyDeviceToHost, stream));
